@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: molecules/sec at 64 diffusion steps (QM9-shaped inverse model) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is one full QMDiffusion.sample() call over one batch: BASELINE.json configs[1] = inverse model
 channels=64, pred_dim=16, max_len=64, cond_len=12, batch 1024 per GPU, 64 timesteps (126 U-Net
 evaluations + 63 ADPM2 updates), fp32, cond_scale=1.0, synthetic weights/conditioning, inputs resident in
 HBM, on-device counter-based noise.  `--batch 8192` is the per-GPU shard of configs[3] (65,536 over 8 GPUs).
+Weights, conditioning and noise are seeded: the same arguments give the same inputs in every run.
+
+A plain run sets up, warms up, times K steps and prints the headline line.  `--dump-outputs DIR` then also writes the
+samples the last timed step returned as DIR/samples.npy (float32; above 64 MB, a fixed seeded sample of its rows), so that
+two builds can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  Either the driver launches the ranks itself (torch.distributed.run sets
 RANK / WORLD_SIZE) or this script does: `python bench.py --gpus N` without RANK in the environment starts
@@ -14,11 +19,14 @@ RANK / WORLD_SIZE) or this script does: `python bench.py --gpus N` without RANK 
 GPU, relays rank 0's JSON line and exits with the child's return code.  Every rank samples its own batch (weak
 scaling, no collective in the step loop) and the generated samples are all-gathered once per call over RCCL.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields.  `--full` adds everything beyond the headline (the
+`--no-*` options drop single legs of it):
   "roofline":     the dominant kernel class of one U-Net evaluation, HIP-event timed per launch
+  "unet_eval":    HIP-event time of every U-Net evaluation of the timed steps; "power": socket power over them
   "exact_f32":    the same workload and the same fused program with exact fp32 MFMA products (MDT_GEMM=f32), 5 steps, with
                   its own roofline block against the fp32 MFMA peak                                      (N = 1)
   "cpu_baseline": the CPU oracle (PyTorch restatement pinned to the reference) on a bounded sample       (N = 1)
+  "other_configs": the other single-GPU configurations of BASELINE.json, a few steps each                 (N = 1)
   "multi_gpu":    ranks seen by the all-gather and the bitwise shard-invariance check                    (N > 1)
 """
 import argparse
@@ -38,6 +46,7 @@ BF16_MFMA_PEAK_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense bf16 MFMA (not t
 HBM_PEAK_GBS = 8000.0
 REF_FLOPS_PER_SAMPLE_EVAL = 455.3e6   # reference op graph (incl. per-eval cross-attn K/V + time mapping)
 REF_OPGRAPH_BYTES_PER_SAMPLE_EVAL = 13.21e6
+DUMP_LIMIT_BYTES = 64_000_000
 
 WORKLOADS = {
     "cfg1": "QMDiffusion inverse sample(): channels=64 pred_dim=16 max_len=64 cond_len=12, ",
@@ -67,7 +76,17 @@ def parse():
     ap.add_argument("--no-exact-f32", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--master-port", type=int, default=29511, help="rendezvous port when this script launches its own ranks")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the samples of the last one as DIR/samples.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beyond the headline: per-evaluation times, roofline, power, exact fp32, the "
+                         "other configurations, the CPU baseline and parity, the multi-GPU details (the --no-* options drop legs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)     # self-launched ranks run from the repository root
+    return a
 
 
 def self_launch(a) -> int:
@@ -75,6 +94,8 @@ def self_launch(a) -> int:
     imported torch or touched a GPU), stream the child's output through, return its exit code."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(a.master_port), os.path.abspath(__file__)] + sys.argv[1:]
+    if a.dump_outputs:
+        cmd += ["--dump-outputs", a.dump_outputs]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL across processes on this driver
     env.setdefault("OMP_NUM_THREADS", "8")
@@ -84,6 +105,18 @@ def self_launch(a) -> int:
     except KeyboardInterrupt:
         child.terminate()
         return child.wait()
+
+
+def dump_outputs(out, d):
+    """--dump-outputs: the samples a caller of the timed path received from its last step, as d/samples.npy (float32).  Over
+    DUMP_LIMIT_BYTES, a fixed sample of rows (numpy seed 0, in row order) is written instead of the whole tensor."""
+    import numpy as np
+    x = out.detach().float().cpu().numpy()
+    if x.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (x.nbytes // x.shape[0])
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], keep, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "samples.npy"), np.ascontiguousarray(x))
 
 
 def op_flops(op, rt, B):
@@ -356,13 +389,17 @@ def main():
     seq = seq_of(rank).to(device)
     if a.workload != "cfg1" or a.cond_scale != 1.0:
         a.no_cpu_baseline = a.no_exact_f32 = a.no_other_configs = True
+    if not a.full:         # a plain run: the headline alone
+        a.no_breakdown = a.no_cpu_baseline = a.no_exact_f32 = a.no_other_configs = True
     evals = 2 * (T - 1)
-    eval_timer = rt.EventTimer(evals * (a.steps + a.warmup) + 8)
+    # --full: every U-Net evaluation of the timed steps HIP-event timed (sample() then calls its loop directly instead of through
+    # torch.ops.mdt.sample: same kernels, same bits)
+    eval_timer = rt.EventTimer(evals * (a.steps + a.warmup) + 8) if a.full else None
 
     phase_ev = []          # N > 1: (sample start, sample end = gather start, gather end) HIP events of every timed step, this rank
 
     def one_step(step_idx, timed):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if (grouped and timed) else None
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if (grouped and timed and a.full) else None
         if ev:
             ev[0].record()
         out = model.sample(seq, device, cond_scale=a.cond_scale, timesteps=T, clamp=False,
@@ -387,7 +424,7 @@ def main():
             torch.cuda.synchronize(device)
 
     fence()
-    sampler = PowerSampler(device.index if device.index is not None else 0) if rank == 0 else None
+    sampler = PowerSampler(device.index if device.index is not None else 0) if (rank == 0 and a.full) else None
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
@@ -397,7 +434,7 @@ def main():
     elapsed = time.perf_counter() - t0
     power = sampler.summary() if sampler else None
     per_rank = None
-    if grouped:
+    if grouped and a.full:
         # per rank: wall time of its K steps, GPU time inside sample() (compute, no collective) and inside the all-gather (which
         # includes waiting for the slowest rank), gathered to every rank (a K-independent 3 x N table; outside the timed region)
         smp = sum(e[0].elapsed_time(e[1]) for e in phase_ev) * 1e-3
@@ -406,96 +443,21 @@ def main():
         table = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(table, mine)
         per_rank = [[float(v) for v in t_] for t_ in table]
+    if grouped:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(out, a.dump_outputs)
 
-    eval_ms = eval_timer.collect()
     result = None
     if rank == 0:
         eng = model._engine                               # the engine the timed calls ran on (kernel choice by batch)
         mols = world * B * a.steps
         value = mols / elapsed
-        flops_exec = eng.c.flops_per_sample_eval           # executed per sample per eval (K/V + time mapping hoisted)
-        avg_eval_ms = sum(eval_ms) / len(eval_ms)
         split = eng.c.gemm_mode == "bf16x3"
         plain = eng.c.gemm_mode == "bf16"
-        # split-bf16 path: every fp32 product is 3 bf16 MFMAs, so the executed matrix-core work is 3x the
-        # algorithmic FLOPs and the roof is the dense bf16 MFMA peak; plain bf16: one MFMA per product, same roof;
-        # exact path: fp32 MFMA peak.
-        peak = BF16_MFMA_PEAK_TFLOPS if (split or plain) else FP32_MFMA_PEAK_TFLOPS
-        mult = 3.0 if split else 1.0
-        roof = {"bound": "mfma", "unit": "TFLOP/s", "peak": peak, "traffic": None,
-                "mfma_dtype": "bf16 (3 MFMAs per fp32 product, fp32 accumulate)" if split else
-                              ("bf16 (one MFMA per product, fp32 accumulate)" if plain else "f32")}
-        extra = {}
-        if not a.no_breakdown:
-            bd = kernel_breakdown(eng, rt, B)
-            dom = max((k for k in bd if bd[k][2] > 0), key=lambda k: bd[k][1])
-            n_dom, ms_dom, fl_dom = bd[dom]
-            alg = fl_dom / (ms_dom * 1e-3) / 1e12
-            roof.update({"kernel": dom + (" = fused transformer kernels k_tblock32 / k_tf128 / k_tf256" if dom == "k_tblock" else "")
-                                   + " (all launches of the dominant kernel class in one U-Net eval)",
-                         "achieved": round(alg * mult, 2), "frac": round(alg * mult / peak, 4),
-                         "algorithmic_tflops_fp32_equiv": round(alg, 2), "launches_per_eval": n_dom,
-                         "avg_launch_us": round(1e3 * ms_dom / n_dom, 2), "flops_per_launch_avg": fl_dom / n_dom})
-            if dom == "k_tblock":
-                # the contract's roofline is the MFMA fraction; what binds this kernel class is not a memory level
-                roof["binding_resource"] = "the weight stream where it enters the CU, then the in-launch hand-off: LDS-DMA runs through the 64 B/clk/CU " \
-                                           "vector-memory path (a 32 KB sub-tile = 512 cycles at best, 555 measured with nothing else running) and a " \
-                                           "32-row workgroup of the 256-channel level consumes one in 650-700 cycles (384 of them MFMA); round-3 ablations " \
-                                           "of a pair-split launch (DESIGN.md 3.5): no wait for tiles to land -9 %, no workgroup barriers at all -18 %, " \
-                                           "no waits on fragment reads -3.6 %, broadcast fragment reads -4.4 % of the class, a deeper ring +4.5 % (slower); " \
-                                           "in-kernel stamps: 74 % streamed phases, 15 % hand-off between the two workgroups of a row block (2.35 us per " \
-                                           "round), 5 % LayerNorm, 4 % wave-pair LDS exchange; the shader clock is stretched to 1.75-1.95 GHz in the streamed " \
-                                           "phases; HBM ~23 % of peak over the whole evaluation"
-            if a.workload == "cfg1" and B == 1024:     # the committed PMC summary is of exactly this workload
-                roof["traffic"], roof["traffic_source"] = pmc_traffic(dom)
-            extra["eval_breakdown_ms"] = {k: {"launches": n, "ms": round(t, 4),
-                                              "algorithmic_tflops": round(f / (t * 1e-3) / 1e12, 2) if f else None}
-                                          for k, (n, t, f) in sorted(bd.items())}
-        else:
-            alg = flops_exec * B / (avg_eval_ms * 1e-3) / 1e12
-            roof.update({"kernel": "whole U-Net eval", "achieved": round(alg * mult, 2),
-                         "frac": round(alg * mult / peak, 4)})
-        med_eval = sorted(eval_ms)[len(eval_ms) // 2]
-        slow = [(i, t) for i, t in enumerate(eval_ms) if t > 1.25 * med_eval]
-        ue = {"ms_avg_graph_replay": round(avg_eval_ms, 4), "ms_min_graph_replay": round(min(eval_ms), 4),
-              "ms_max_graph_replay": round(max(eval_ms), 4), "ms_median_graph_replay": round(med_eval, 4),
-              # evaluations more than 25 % over the median, as (index in the timed run, evaluation of its call 0..evals-1, ms):
-              # an index that repeats at the same evaluation of every call is the path's own; a scattered one is the box's
-              "outliers_over_1p25_median": {"count": len(slow), "first": [(i, i % evals, round(t, 3)) for i, t in slow[:8]]},
-              "evals_timed": len(eval_ms),
-              "launches": len(eng.c.programs["eval"]),
-              "flops_per_sample_executed": flops_exec,
-              "tflops_executed_fp32_equiv": round(flops_exec * B / (avg_eval_ms * 1e-3) / 1e12, 2)}
-        if split or plain:
-            ue["bf16_mfma_fraction_executed"] = round(mult * flops_exec * B / (avg_eval_ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)
-        else:
-            ue["fp32_mfma_fraction_executed"] = round(flops_exec * B / (avg_eval_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4)
-        if a.workload == "cfg1":
-            # NOT a roofline: the byte count of the reference's UNFUSED op graph (SURVEY §8d, 13.21 MB / sample / eval)
-            # divided by this path's time, as a fraction of the HBM peak.  The fused kernels move far fewer bytes.
-            ue["reference_unfused_opgraph_bytes_per_s_over_hbm_peak"] = round(
-                REF_OPGRAPH_BYTES_PER_SAMPLE_EVAL * B / (avg_eval_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-            if B == 1024:
-                fname, rows = pmc_summary()
-                # kernels of the EVAL program only (not the hoisted time / context programs' k_gemm_as / k_gemm / k_time_embed,
-                # the sampler's own kernels or torch's fills), evaluations counted from a kernel that runs once per evaluation
-                eval_kernels = ("mdt::k_tf128", "mdt::k_tf256", "mdt::k_tblock", "mdt::k_tb_reduce", "mdt::k_rconv", "mdt::k_gemm3",
-                                "mdt::k_resblock", "mdt::k_attn", "mdt::k_gn_", "mdt::k_concat", "mdt::k_patch")
-                evals_profiled = sum(n for nm, n, mb in rows if nm.startswith("mdt::k_resblock<16, 64>")) or None
-                if rows and evals_profiled and pmc_is_current(fname)[0]:
-                    unet_mb = sum(n * mb for nm, n, mb in rows if nm.startswith(eval_kernels))
-                    per_eval = unet_mb / evals_profiled
-                    ue["hbm_measured_mb_per_eval"] = round(per_eval, 1)
-                    ue["hbm_measured_frac"] = round(per_eval * 1e6 / (avg_eval_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                    ue["hbm_measured_source"] = f"profiles/{fname}: PMC bytes (FETCH_SIZE x2 + WRITE_SIZE) of the eval program's kernels " \
-                                                f"over the {evals_profiled} evaluations of the profiled run (counted from k_resblock<16, 64>, " \
-                                                f"one launch per evaluation), over THIS run's evaluation time"
-        extra["unet_eval"] = ue
-        extra["power"] = power
         result = {
             "metric": "molecules/sec @64 diffusion steps (QM9 max_len=64)" if a.workload == "cfg1"
                       else f"molecules/sec @{T} diffusion steps ({a.workload})", "value": round(value, 2),
@@ -508,11 +470,90 @@ def main():
             "config": {"workload": WORKLOADS[a.workload]
                                    + f"batch={B}/GPU, {T} timesteps ({evals} U-Net evals), cond_scale={a.cond_scale}, " + ("bf16 products" if plain else "fp32"),
                        "global_batch": world * B, "timesteps": T, "parallelism": f"batch-shard x{world}"},
-            "roofline": roof,
         }
-        result.update(extra)
+        if a.full:
+            eval_ms = eval_timer.collect()
+            flops_exec = eng.c.flops_per_sample_eval           # executed per sample per eval (K/V + time mapping hoisted)
+            avg_eval_ms = sum(eval_ms) / len(eval_ms)
+            # split-bf16 path: every fp32 product is 3 bf16 MFMAs, so the executed matrix-core work is 3x the
+            # algorithmic FLOPs and the roof is the dense bf16 MFMA peak; plain bf16: one MFMA per product, same roof;
+            # exact path: fp32 MFMA peak.
+            peak = BF16_MFMA_PEAK_TFLOPS if (split or plain) else FP32_MFMA_PEAK_TFLOPS
+            mult = 3.0 if split else 1.0
+            roof = {"bound": "mfma", "unit": "TFLOP/s", "peak": peak, "traffic": None,
+                    "mfma_dtype": "bf16 (3 MFMAs per fp32 product, fp32 accumulate)" if split else
+                                  ("bf16 (one MFMA per product, fp32 accumulate)" if plain else "f32")}
+            extra = {}
+            if not a.no_breakdown:
+                bd = kernel_breakdown(eng, rt, B)
+                dom = max((k for k in bd if bd[k][2] > 0), key=lambda k: bd[k][1])
+                n_dom, ms_dom, fl_dom = bd[dom]
+                alg = fl_dom / (ms_dom * 1e-3) / 1e12
+                roof.update({"kernel": dom + (" = fused transformer kernels k_tblock32 / k_tf128 / k_tf256" if dom == "k_tblock" else "")
+                                       + " (all launches of the dominant kernel class in one U-Net eval)",
+                             "achieved": round(alg * mult, 2), "frac": round(alg * mult / peak, 4),
+                             "algorithmic_tflops_fp32_equiv": round(alg, 2), "launches_per_eval": n_dom,
+                             "avg_launch_us": round(1e3 * ms_dom / n_dom, 2), "flops_per_launch_avg": fl_dom / n_dom})
+                if dom == "k_tblock":
+                    # the contract's roofline is the MFMA fraction; what binds this kernel class is not a memory level
+                    roof["binding_resource"] = "the weight stream where it enters the CU, then the in-launch hand-off: LDS-DMA runs through the 64 B/clk/CU " \
+                                               "vector-memory path (a 32 KB sub-tile = 512 cycles at best, 555 measured with nothing else running) and a " \
+                                               "32-row workgroup of the 256-channel level consumes one in 650-700 cycles (384 of them MFMA); round-3 ablations " \
+                                               "of a pair-split launch (DESIGN.md 3.5): no wait for tiles to land -9 %, no workgroup barriers at all -18 %, " \
+                                               "no waits on fragment reads -3.6 %, broadcast fragment reads -4.4 % of the class, a deeper ring +4.5 % (slower); " \
+                                               "in-kernel stamps: 74 % streamed phases, 15 % hand-off between the two workgroups of a row block (2.35 us per " \
+                                               "round), 5 % LayerNorm, 4 % wave-pair LDS exchange; the shader clock is stretched to 1.75-1.95 GHz in the streamed " \
+                                               "phases; HBM ~23 % of peak over the whole evaluation"
+                if a.workload == "cfg1" and B == 1024:     # the committed PMC summary is of exactly this workload
+                    roof["traffic"], roof["traffic_source"] = pmc_traffic(dom)
+                extra["eval_breakdown_ms"] = {k: {"launches": n, "ms": round(t, 4),
+                                                  "algorithmic_tflops": round(f / (t * 1e-3) / 1e12, 2) if f else None}
+                                              for k, (n, t, f) in sorted(bd.items())}
+            else:
+                alg = flops_exec * B / (avg_eval_ms * 1e-3) / 1e12
+                roof.update({"kernel": "whole U-Net eval", "achieved": round(alg * mult, 2),
+                             "frac": round(alg * mult / peak, 4)})
+            med_eval = sorted(eval_ms)[len(eval_ms) // 2]
+            slow = [(i, t) for i, t in enumerate(eval_ms) if t > 1.25 * med_eval]
+            ue = {"ms_avg_graph_replay": round(avg_eval_ms, 4), "ms_min_graph_replay": round(min(eval_ms), 4),
+                  "ms_max_graph_replay": round(max(eval_ms), 4), "ms_median_graph_replay": round(med_eval, 4),
+                  # evaluations more than 25 % over the median, as (index in the timed run, evaluation of its call 0..evals-1, ms):
+                  # an index that repeats at the same evaluation of every call is the path's own; a scattered one is the box's
+                  "outliers_over_1p25_median": {"count": len(slow), "first": [(i, i % evals, round(t, 3)) for i, t in slow[:8]]},
+                  "evals_timed": len(eval_ms),
+                  "launches": len(eng.c.programs["eval"]),
+                  "flops_per_sample_executed": flops_exec,
+                  "tflops_executed_fp32_equiv": round(flops_exec * B / (avg_eval_ms * 1e-3) / 1e12, 2)}
+            if split or plain:
+                ue["bf16_mfma_fraction_executed"] = round(mult * flops_exec * B / (avg_eval_ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4)
+            else:
+                ue["fp32_mfma_fraction_executed"] = round(flops_exec * B / (avg_eval_ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4)
+            if a.workload == "cfg1":
+                # NOT a roofline: the byte count of the reference's UNFUSED op graph (SURVEY §8d, 13.21 MB / sample / eval)
+                # divided by this path's time, as a fraction of the HBM peak.  The fused kernels move far fewer bytes.
+                ue["reference_unfused_opgraph_bytes_per_s_over_hbm_peak"] = round(
+                    REF_OPGRAPH_BYTES_PER_SAMPLE_EVAL * B / (avg_eval_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                if B == 1024:
+                    fname, rows = pmc_summary()
+                    # kernels of the EVAL program only (not the hoisted time / context programs' k_gemm_as / k_gemm / k_time_embed,
+                    # the sampler's own kernels or torch's fills), evaluations counted from a kernel that runs once per evaluation
+                    eval_kernels = ("mdt::k_tf128", "mdt::k_tf256", "mdt::k_tblock", "mdt::k_tb_reduce", "mdt::k_rconv", "mdt::k_gemm3",
+                                    "mdt::k_resblock", "mdt::k_attn", "mdt::k_gn_", "mdt::k_concat", "mdt::k_patch")
+                    evals_profiled = sum(n for nm, n, mb in rows if nm.startswith("mdt::k_resblock<16, 64>")) or None
+                    if rows and evals_profiled and pmc_is_current(fname)[0]:
+                        unet_mb = sum(n * mb for nm, n, mb in rows if nm.startswith(eval_kernels))
+                        per_eval = unet_mb / evals_profiled
+                        ue["hbm_measured_mb_per_eval"] = round(per_eval, 1)
+                        ue["hbm_measured_frac"] = round(per_eval * 1e6 / (avg_eval_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                        ue["hbm_measured_source"] = f"profiles/{fname}: PMC bytes (FETCH_SIZE x2 + WRITE_SIZE) of the eval program's kernels " \
+                                                    f"over the {evals_profiled} evaluations of the profiled run (counted from k_resblock<16, 64>, " \
+                                                    f"one launch per evaluation), over THIS run's evaluation time"
+            extra["unet_eval"] = ue
+            extra["power"] = power
+            result["roofline"] = roof
+            result.update(extra)
 
-        if grouped:
+        if grouped and a.full:
             # the gathered tensor holds every rank's rows; counter-based noise is keyed by the GLOBAL sample index, so the
             # last rank's first rows must equal, bit for bit, a 1-rank run of those global indices with the same seed
             probe = min(64, B)

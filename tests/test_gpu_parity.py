@@ -334,6 +334,42 @@ def test_edge_batches_single_and_empty():
     assert empty.shape == (0, 16, 64)
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline alone (no roofline, no other legs) for exactly --steps timed steps, and
+    --dump-outputs writes the samples of the last timed step.  The same arguments with --full (every evaluation HIP-event
+    timed, then the extra legs) dump the same bits: the inputs are seeded and both runs compute the same thing."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("RANK", None)
+    lines = {}
+    for leg in ("plain", "full"):
+        args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--timesteps", "4",
+                "--dump-outputs", str(tmp_path / leg)]
+        if leg == "full":
+            args += ["--full", "--no-breakdown", "--no-cpu-baseline", "--no-exact-f32", "--no-other-configs"]
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args],
+                           capture_output=True, text=True, timeout=900, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[leg] = json.loads(out[0])
+    d = lines["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 64) < 0.5             # molecules/s x s per step = molecules per step
+    assert not {"roofline", "unet_eval", "power", "exact_f32", "other_configs", "cpu_baseline"} & set(d)
+    assert {"roofline", "unet_eval"} <= set(lines["full"]) and lines["full"]["unet_eval"]["evals_timed"] == 2 * 6
+    a, b = np.load(tmp_path / "plain" / "samples.npy"), np.load(tmp_path / "full" / "samples.npy")
+    assert a.shape == (64, 16, 64) and a.dtype == np.float32 and np.isfinite(a).all()
+    assert np.array_equal(a, b)
+
+
 def test_bench_two_rank_logic_on_one_gpu():
     """bench.py's N > 1 path as the driver invokes it (`python bench.py --gpus 2`, no torchrun around it): the script
     launches its own ranks as a child process, barriers, one all-gather per call, max-over-ranks timing, ONE JSON line from
@@ -347,7 +383,7 @@ def test_bench_two_rank_logic_on_one_gpu():
     env = dict(os.environ, MDT_BENCH_SHARE_GPU="1")
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--batch", "64", "--timesteps", "4", "--no-breakdown", "--master-port", "29533"],
+                        "--batch", "64", "--timesteps", "4", "--no-breakdown", "--full", "--master-port", "29533"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -376,7 +412,7 @@ def test_bench_eight_rank_logic_on_one_gpu():
     env = dict(os.environ, MDT_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="2")
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-                        "--batch", "32", "--timesteps", "3", "--no-breakdown", "--master-port", "29541"],
+                        "--batch", "32", "--timesteps", "3", "--no-breakdown", "--full", "--master-port", "29541"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -403,7 +439,7 @@ def test_bench_eight_ranks_at_the_configs3_shard_size_on_one_gpu():
     env = dict(os.environ, MDT_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="4")
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-                        "--batch", "8192", "--no-breakdown", "--master-port", "29547"],
+                        "--batch", "8192", "--no-breakdown", "--full", "--master-port", "29547"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -454,7 +490,7 @@ dist.barrier(); torch.cuda.synchronize(); dist.destroy_process_group(); print('R
     assert r.returncode == 0 and "RCCL_OK" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
     env.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_PORT="29542")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "64",
-                        "--timesteps", "4", "--no-breakdown", "--no-cpu-baseline", "--no-exact-f32", "--no-other-configs"],
+                        "--timesteps", "4", "--full", "--no-breakdown", "--no-cpu-baseline", "--no-exact-f32", "--no-other-configs"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -511,6 +511,26 @@ def test_bench_power_sampler_is_optional():
     assert s.summary() is None
 
 
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a tensor within the budget is written whole as float32; a larger one as a fixed sample of its
+    rows, in row order, the same in every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    x = torch.randn(40, 4, 8)
+    mod.dump_outputs(x, str(tmp_path / "whole"))
+    got = np.load(tmp_path / "whole" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(mod, "DUMP_LIMIT_BYTES", 10 * 4 * 8 * 4 + 100)       # room for 10 rows
+    mod.dump_outputs(x, str(tmp_path / "a"))
+    mod.dump_outputs(x.clone(), str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "samples.npy"), np.load(tmp_path / "b" / "samples.npy")
+    assert a.shape == (10, 4, 8) and a.dtype == np.float32 and np.array_equal(a, b)
+    rows = [int(np.flatnonzero((x.numpy() == r).all(axis=(1, 2)))[0]) for r in a]
+    assert rows == sorted(rows) and len(set(rows)) == 10
+
+
 def test_torch_library_ops_are_registered_and_refuse_cpu_tensors():
     """SURVEY section 8(b), last row: the native boundary as a torch.library namespace.  Every op of torch.ops.mdt has a
     schema and shape inference (meta tensors, no GPU needed) and raises RuntimeError for non-HIP tensors (TORCH_CHECK

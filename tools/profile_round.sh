@@ -2,7 +2,7 @@
 # Round profile recipe (run on the GPU box from the repo root):
 #   bash tools/profile_round.sh r3                                   # the headline workload (BASELINE configs[1], B = 1024)
 #   BENCH_ARGS="--workload cfg3 --batch 4096" TRACE_TS=100 bash tools/profile_round.sh r3_cfg3      # another configuration
-# 1. plain bench.py (headline only: with the CPU baseline leg)         -> gpurun_out/prof_<tag>/bench.json
+# 1. bench.py --full (the headline with every leg, CPU baseline included) -> $out/bench.json
 # 2. rocprofv3 --output-format csv --kernel-trace --stats of the same command   -> .../trace (kernel_stats.csv, domain_stats.csv)
 # 3. PMC passes, kernel-trace only, on a 4-timestep run: FETCH_SIZE, WRITE_SIZE (HBM traffic), SQ wave-state /
 #    MFMA-busy / LDS-conflict counters -> .../pmc_fetch, .../pmc_write, .../pmc_sq
@@ -14,10 +14,10 @@ root=$(pwd)
 out=$root/gpurun_out/prof_$tag
 rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-quiet="--no-cpu-baseline --no-exact-f32 --no-other-configs"
+quiet="--full --no-cpu-baseline --no-exact-f32 --no-other-configs"
 echo "bench.py $args (kernel trace: --timesteps $trace_ts; PMC passes: --timesteps 4 --steps 1 --warmup 1)" > "$out/args.txt"
 if [ -z "$args" ]; then
-  python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+  python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 fi
 cd /tmp
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/trace" -o runc -- python3 "$root/bench.py" $args --timesteps $trace_ts $quiet \

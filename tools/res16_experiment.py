@@ -2,8 +2,9 @@
 residual stream of the transformer blocks ("tf") or of transformer and ResNet blocks ("both") rounded to bf16 after every residual
 add, everything else fp32 -- max-abs deviation of the final sample from the fp32 oracle on identical noise.  DESIGN.md section 9 (#3)
 quotes the result.   python tools/res16_experiment.py"""
-import sys, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import torch, torch.nn.functional as F
 from helpers import oracle_cfg, synth_sd
 from moleculediffusiontransformer_amd.synth import synth_normal
