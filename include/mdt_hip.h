@@ -454,6 +454,33 @@ int mdt_adpm2_next(float *x, const float *x_mid, const float *pred, const float 
 int mdt_adpm2_euler(const float *x_base, const float *x_from, const float *denoised, const float *noise,
                     float *out, float sigma, float dt, float sigma_up, int32_t noise_mode, uint64_t seed,
                     uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L, void *stream);
+/* The whole AEulerSampler.step after its one evaluation (diffusion.py:465-474), fused with the denoise output:
+ *   D = clip(c_skip*x + c_out*pred); d = (x - D) / sigma; x = x + d * dt;  x = x + noise * sigma_up   (in place on x),
+ *   dt = fp32(sigma_down - sigma),
+ * and xin_next = c_in_next * x.  noise == NULL, tokens and dyn_scale as for mdt_adpm2_next.  An addition inside ABI version 5. */
+int mdt_aeuler_next(float *x, const float *pred, const float *noise, float *xin_next, float c_skip, float c_out,
+                    float sigma, float dt, float sigma_up, float c_in_next, uint64_t seed, uint32_t step,
+                    int64_t sample0, int32_t B, int32_t C, int32_t L, int32_t Cp, int32_t *tokens,
+                    const float *dyn_scale, void *stream);
+/* KarrasSampler.step (diffusion.py:417-435) in three stages around its two evaluations; additions inside ABI version 5.
+ * Churn (:424-425):   x_hat = x + noise_scale * (s_noise * noise),  noise_scale = fp32(sqrt(sigma_hat^2 - sigma^2)),
+ *                     xin = c_in_hat * x_hat (token-major, padded).  x_hat may be x.  noise == NULL: counter-based generator. */
+int mdt_karras_hat(const float *x, const float *noise, float *x_hat, float *xin, float noise_scale, float s_noise,
+                   float c_in_hat, uint64_t seed, uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L,
+                   int32_t Cp, void *stream);
+/* Euler move (:427-429): D = clip(c_skip*x_hat + c_out*pred); d = (x_hat - D) / sigma_hat; x_next = x_hat + dt * d,
+ *                     dt = sigma_next - sigma_hat; d is kept for the correction; xin_next = c_in_next * x_next.
+ * xin_next == NULL when sigma_next == 0 (no second evaluation: x_next is the step's result); tokens only then. */
+int mdt_karras_mid(const float *x_hat, const float *pred, float *d, float *x_next, float *xin_next, float c_skip,
+                   float c_out, float sigma_hat, float dt, float c_in_next, int32_t B, int32_t C, int32_t L,
+                   int32_t Cp, int32_t *tokens, const float *dyn_scale, void *stream);
+/* Correction (:432-434), the reference's line as it stands:
+ *                     D = clip(c_skip*x_next + c_out*pred); d' = (x_next - D) / sigma_next; x = x_hat + half * (d + d'),
+ *                     half = 0.5 * (sigma - sigma_hat) -- zero without churn, the step then returns x_hat.
+ * x may be x_hat.  tokens != NULL: the fused decode of the final x. */
+int mdt_karras_next(const float *x_hat, const float *x_next, const float *d, const float *pred, float *x,
+                    float c_skip, float c_out, float sigma_next, float half, int32_t B, int32_t C, int32_t L,
+                    int32_t Cp, int32_t *tokens, const float *dyn_scale, void *stream);
 /* x = sigma0 * noise (diffusion.py:520); noise == NULL: counter-based generator as above. */
 int mdt_init_noise(float *x, const float *noise, float sigma0, uint64_t seed, uint32_t step,
                    int64_t sample0, int32_t B, int32_t C, int32_t L, void *stream);

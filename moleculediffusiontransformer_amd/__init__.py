@@ -7,8 +7,8 @@ Drop-in classes (same names and call signatures as the reference's MoleculeDiffu
 The sampling hot path (QMDiffusion.sample -> ADPM2 sampler -> 1-D conditional U-Net) runs in
 hand-written gfx950 kernels (csrc/, C ABI in include/mdt_hip.h).
 """
-from .diffusion import (ADPM2Sampler, DiffusionInpainter, DiffusionSampler, KarrasSchedule,  # noqa: F401
-                        LogNormalDistribution, NoiseSource, Sampler)
+from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler,  # noqa: F401
+                        KarrasSchedule, LogNormalDistribution, NoiseSource, Sampler)
 from .generative import (KDiffusion_mod, QMDiffusion, QMDiffusionForward, XDiffusion_x,  # noqa: F401
                          generate_and_validate, predict_properties_from_tokens, tokens_to_forward_input)
 from .graphmodel import AnalogDiffusionFull, AnalogDiffusionSparse  # noqa: F401

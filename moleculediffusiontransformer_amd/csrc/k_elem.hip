@@ -1,8 +1,8 @@
-// HBM-bound kernels of the sampling path on gfx950: k-diffusion preconditioning, the ADPM2 sampler update,
+// HBM-bound kernels of the sampling path on gfx950: k-diffusion preconditioning, the ADPM2 / AEuler / Karras sampler updates,
 // noise generation, conditioning/time embeddings and the layout shuffles around the U-Net.
 //
 // Built with -ffp-contract=off: the sampler arithmetic keeps the reference's separate fp32 multiplies and
-// adds (diffusion.py:502-515, :810-814) instead of fused multiply-adds.
+// adds (diffusion.py:417-435, :465-474, :502-515, :810-814) instead of fused multiply-adds.
 //
 // Sampler state, noise and results are (B, C, L) channel-major as in the reference; the U-Net consumes and
 // produces token-major (B, L, Cp) tiles.  One workgroup handles one sample: the (L x Cp) tile is transposed
@@ -250,6 +250,175 @@ __global__ __launch_bounds__(256) void k_adpm2_next(float* x, const float* x_mid
       }
       tokens[(int64_t)b * L + l] = arg;
     }
+  }
+}
+
+// tokens[b,l] = argmax_c tile[l][c] (first maximum, NaN wins, as torch.argmax) of a tile that carries the final x
+__device__ __forceinline__ void tile_argmax(const float* tile, int32_t* tokens, int b, int C, int L, int Cp) {
+  for (int l = threadIdx.x; l < L; l += blockDim.x) {
+    const float* t = tile + l * (Cp + 1);
+    float best = t[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = t[c];
+      if (v > best || (v != v && best == best)) { best = v; arg = c; }
+    }
+    tokens[(int64_t)b * L + l] = arg;
+  }
+}
+
+// The whole AEulerSampler.step after its one evaluation                   (diffusion.py:465-474, :811-814)
+//   den = clip(c_skip x + c_out pred); d = (x - den) / sigma; x' = x + d * dt; x' = x' + noise * sigma_up
+// k_adpm2_next without the x_mid stream: the derivative is taken at x itself.  xin_next / tokens as there.
+__global__ __launch_bounds__(256) void k_aeuler_next(float* x, const float* pred, const float* noise, float* xin_next,
+                                                      float c_skip, float c_out, float sigma, float dt, float sigma_up,
+                                                      float c_in_next, uint64_t seed, uint32_t step, int64_t sample0,
+                                                      int C, int L, int Cp, int32_t* tokens, const float* dscale) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const float ds = dscale ? dscale[b] : 0.f;
+  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
+  __syncthreads();
+  const int l4n = L / 4;
+  const bool keep_x = tokens && !xin_next;       // the tile then carries x itself (not c_in_next * x) for the argmax
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 v = *reinterpret_cast<const float4*>(x + o);
+    float4 nz;
+    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
+    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
+    const float xv[4] = {v.x, v.y, v.z, v.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
+    float xn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float* t = tile + (l + q) * (Cp + 1) + c;
+      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), ds);
+      const float d = (xv[q] - den) / sigma;
+      float xx = xv[q] + d * dt;
+      xx = xx + nv[q] * sigma_up;
+      xn[q] = xx;
+      *t = keep_x ? xx : c_in_next * xx;
+    }
+    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  }
+  if (xin_next) {
+    tile_zero_pad(tile, C, L, Cp);
+    __syncthreads();
+    tile_store(tile, xin_next + (int64_t)b * L * Cp, L, Cp);
+  } else if (tokens) {
+    __syncthreads();
+    tile_argmax(tile, tokens, b, C, L, Cp);
+  }
+}
+
+// KarrasSampler.step, the churn stage                                      (diffusion.py:424-425, :810)
+//   x_hat = x + ns * (s_noise * noise), ns = fp32(sqrt(sigma_hat^2 - sigma^2));   xin = c_in_hat * x_hat
+// x_hat may be x (every element is read and written by one thread).
+__global__ __launch_bounds__(256) void k_karras_hat(const float* x, const float* noise, float* x_hat, float* xin, float ns,
+                                                     float s_noise, float c_in_hat, uint64_t seed, uint32_t step,
+                                                     int64_t sample0, int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 v = *reinterpret_cast<const float4*>(x + o);
+    float4 nz;
+    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
+    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
+    const float xv[4] = {v.x, v.y, v.z, v.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
+    float xh[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float eps = s_noise * nv[q];
+      xh[q] = xv[q] + ns * eps;
+      tile[(l + q) * (Cp + 1) + c] = c_in_hat * xh[q];
+    }
+    *reinterpret_cast<float4*>(x_hat + o) = make_float4(xh[0], xh[1], xh[2], xh[3]);
+  }
+  tile_zero_pad(tile, C, L, Cp);
+  __syncthreads();
+  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+}
+
+// KarrasSampler.step, the Euler move from sigma_hat to sigma_next          (diffusion.py:427-429, :811-814)
+//   den = clip(c_skip x_hat + c_out pred); d = (x_hat - den) / sigma_hat; x_next = x_hat + dt * d
+// d is kept for the correction; xin_next = c_in_next * x_next for the second evaluation, or (sigma_next == 0: no
+// correction, x_next is the step's result) NULL, then with the optional fused decode of k_adpm2_next.
+__global__ __launch_bounds__(256) void k_karras_mid(const float* x_hat, const float* pred, float* d_out, float* x_next,
+                                                     float* xin_next, float c_skip, float c_out, float sigma_hat, float dt,
+                                                     float c_in_next, int C, int L, int Cp, int32_t* tokens,
+                                                     const float* dscale) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const float ds = dscale ? dscale[b] : 0.f;
+  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
+  __syncthreads();
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 v = *reinterpret_cast<const float4*>(x_hat + o);
+    const float xv[4] = {v.x, v.y, v.z, v.w};
+    float dv[4], xn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float* t = tile + (l + q) * (Cp + 1) + c;
+      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), ds);
+      dv[q] = (xv[q] - den) / sigma_hat;
+      xn[q] = xv[q] + dt * dv[q];
+      *t = xin_next ? c_in_next * xn[q] : xn[q];
+    }
+    *reinterpret_cast<float4*>(d_out + o) = make_float4(dv[0], dv[1], dv[2], dv[3]);
+    *reinterpret_cast<float4*>(x_next + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  }
+  if (xin_next) {
+    tile_zero_pad(tile, C, L, Cp);
+    __syncthreads();
+    tile_store(tile, xin_next + (int64_t)b * L * Cp, L, Cp);
+  } else if (tokens) {
+    __syncthreads();
+    tile_argmax(tile, tokens, b, C, L, Cp);
+  }
+}
+
+// KarrasSampler.step, the second-order correction AS THE REFERENCE WRITES IT (diffusion.py:432-434, :811-814)
+//   den = clip(c_skip x_next + c_out pred); d' = (x_next - den) / sigma_next; x = x_hat + half * (d + d'),
+//   half = 0.5 * (sigma - sigma_hat)        (zero without churn: the step then returns x_hat)
+// x may be x_hat (one thread per element).  tokens != nullptr: the fused decode of the final x.
+__global__ __launch_bounds__(256) void k_karras_next(const float* x_hat, const float* x_next, const float* d_in,
+                                                      const float* pred, float* x, float c_skip, float c_out,
+                                                      float sigma_next, float half, int C, int L, int Cp, int32_t* tokens,
+                                                      const float* dscale) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const float ds = dscale ? dscale[b] : 0.f;
+  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
+  __syncthreads();
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 h = *reinterpret_cast<const float4*>(x_hat + o);
+    const float4 m = *reinterpret_cast<const float4*>(x_next + o);
+    const float4 dd = *reinterpret_cast<const float4*>(d_in + o);
+    const float hv[4] = {h.x, h.y, h.z, h.w}, mv[4] = {m.x, m.y, m.z, m.w}, dv[4] = {dd.x, dd.y, dd.z, dd.w};
+    float xn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float* t = tile + (l + q) * (Cp + 1) + c;
+      const float den = clip_dyn(c_skip * mv[q] + c_out * (*t), ds);
+      const float dp = (mv[q] - den) / sigma_next;
+      xn[q] = hv[q] + half * (dv[q] + dp);
+      *t = xn[q];
+    }
+    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  }
+  if (tokens) {
+    __syncthreads();
+    tile_argmax(tile, tokens, b, C, L, Cp);
   }
 }
 
@@ -584,6 +753,55 @@ int mdt_adpm2_next(float* x, const float* x_mid, const float* pred, const float*
                      noise, xin_next, c_skip, c_out, sigma_mid, dt_down, sigma_up, c_in_next, seed, step, sample0, C, L,
                      Cp, tokens, dyn_scale);
   return finish("mdt_adpm2_next");
+}
+
+int mdt_aeuler_next(float* x, const float* pred, const float* noise, float* xin_next, float c_skip, float c_out, float sigma,
+                    float dt, float sigma_up, float c_in_next, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
+                    int32_t C, int32_t L, int32_t Cp, int32_t* tokens, const float* dyn_scale, void* stream) {
+  MDT_CHECK_TILE("mdt_aeuler_next")
+  if (!x || !pred) return bad("mdt_aeuler_next: null pointer");
+  if (tokens && xin_next) return bad("mdt_aeuler_next: tokens are decoded on the LAST update of a call (xin_next == NULL)");
+  MDT_BIG_LDS(mdt::k_aeuler_next);
+  hipLaunchKernelGGL(mdt::k_aeuler_next, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, pred, noise,
+                     xin_next, c_skip, c_out, sigma, dt, sigma_up, c_in_next, seed, step, sample0, C, L, Cp, tokens,
+                     dyn_scale);
+  return finish("mdt_aeuler_next");
+}
+
+int mdt_karras_hat(const float* x, const float* noise, float* x_hat, float* xin, float noise_scale, float s_noise,
+                   float c_in_hat, uint64_t seed, uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L,
+                   int32_t Cp, void* stream) {
+  MDT_CHECK_TILE("mdt_karras_hat")
+  if (!x || !x_hat || !xin) return bad("mdt_karras_hat: null pointer");
+  MDT_BIG_LDS(mdt::k_karras_hat);
+  hipLaunchKernelGGL(mdt::k_karras_hat, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, noise, x_hat, xin,
+                     noise_scale, s_noise, c_in_hat, seed, step, sample0, C, L, Cp);
+  return finish("mdt_karras_hat");
+}
+
+int mdt_karras_mid(const float* x_hat, const float* pred, float* d, float* x_next, float* xin_next, float c_skip,
+                   float c_out, float sigma_hat, float dt, float c_in_next, int32_t B, int32_t C, int32_t L, int32_t Cp,
+                   int32_t* tokens, const float* dyn_scale, void* stream) {
+  MDT_CHECK_TILE("mdt_karras_mid")
+  if (!x_hat || !pred || !d || !x_next) return bad("mdt_karras_mid: null pointer");
+  if (x_next == x_hat || d == x_hat || d == x_next) return bad("mdt_karras_mid: x_hat, d and x_next are three buffers");
+  if (tokens && xin_next) return bad("mdt_karras_mid: tokens are decoded when the Euler move ends the call (xin_next == NULL)");
+  MDT_BIG_LDS(mdt::k_karras_mid);
+  hipLaunchKernelGGL(mdt::k_karras_mid, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x_hat, pred, d, x_next,
+                     xin_next, c_skip, c_out, sigma_hat, dt, c_in_next, C, L, Cp, tokens, dyn_scale);
+  return finish("mdt_karras_mid");
+}
+
+int mdt_karras_next(const float* x_hat, const float* x_next, const float* d, const float* pred, float* x, float c_skip,
+                    float c_out, float sigma_next, float half, int32_t B, int32_t C, int32_t L, int32_t Cp,
+                    int32_t* tokens, const float* dyn_scale, void* stream) {
+  MDT_CHECK_TILE("mdt_karras_next")
+  if (!x_hat || !x_next || !d || !pred || !x) return bad("mdt_karras_next: null pointer");
+  if (sigma_next == 0.0f) return bad("mdt_karras_next: sigma_next == 0 has no correction (the Euler move is the step)");
+  MDT_BIG_LDS(mdt::k_karras_next);
+  hipLaunchKernelGGL(mdt::k_karras_next, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x_hat, x_next, d, pred,
+                     x, c_skip, c_out, sigma_next, half, C, L, Cp, tokens, dyn_scale);
+  return finish("mdt_karras_next");
 }
 
 int mdt_init_noise(float* x, const float* noise, float sigma0, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,

@@ -15,8 +15,9 @@ import torch.nn as nn
 
 from . import ops, runtime as rt
 from .compiler import compile_unet
-from .diffusion import (ADPM2Sampler, DiffusionInpainter, DiffusionSampler, KarrasSchedule, LogNormalDistribution,
-                        NoiseSource, run_adpm2, run_adpm2_inpaint, scale_weights)
+from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler, KarrasSchedule,
+                        LogNormalDistribution, NoiseSource, fused_sampler_kind, run_adpm2, run_adpm2_inpaint, run_aeuler,
+                        run_karras, scale_weights)
 from .engine import UNetEngine, _require_gpu
 from .modules import PositionalEncoding1D, UNetCFG1d
 from .netspec import forward_unet_config, inverse_unet_config
@@ -93,8 +94,9 @@ class XDiffusion_x(nn.Module):
 
 
 class _FusedLoop:
-    """What ADPM2Sampler.forward / inpaint call when the denoiser belongs to a QMDiffusion* model: the whole loop on
-    the fused path (run_adpm2 / run_adpm2_inpaint) instead of one callback per evaluation."""
+    """What ADPM2Sampler.forward / inpaint and AEulerSampler / KarrasSampler.forward call when the denoiser belongs to a
+    QMDiffusion* model: the whole loop on the fused path (run_adpm2 / run_aeuler / run_karras / run_adpm2_inpaint) instead of
+    one callback per evaluation."""
 
     def __init__(self, owner, kwargs: dict, extra: dict):
         unknown = set(kwargs) - {"embedding", "embedding_scale"}
@@ -123,8 +125,24 @@ class _FusedLoop:
             if tok is not None:
                 tok.copy_(t)
             return out
-        return run_adpm2(eng, emb, o.pred_dim, num_steps, ns, sigmas, sampler, sigma_data, scale, bool(x.get("clamp", False)),
-                         x.get("trace"), x.get("timer"), x.get("tokens"), float(o.diffusion.diffusion.dynamic_threshold))
+        kind = fused_sampler_kind(sampler)
+        if kind is None:
+            raise TypeError(f"{type(sampler).__name__} has no fused loop")
+        if ns.steps is None and x.get("trace") is None and x.get("timer") is None and type(sampler) in (AEulerSampler, KarrasSampler):
+            # the plain call with one of the other samplers: ONE custom op too (mdt::sample stays ADPM2's)
+            tok = x.get("tokens")
+            init = None if ns.init is None else ns.init.to(device=emb.device, dtype=torch.float32)
+            skind, sparams = ops.sampler_spec(sampler)
+            out, t = torch.ops.mdt.sample_with(emb, init, None, torch.as_tensor(sigmas, dtype=torch.float32).cpu(),
+                                               ops.register_engine(eng), o.pred_dim, skind, sparams, float(sigma_data),
+                                               float(scale), bool(x.get("clamp", False)), int(ns.seed or 0), int(ns.sample0),
+                                               tok is not None, float(o.diffusion.diffusion.dynamic_threshold))
+            if tok is not None:
+                tok.copy_(t)
+            return out
+        run = {"adpm2": run_adpm2, "aeuler": run_aeuler, "karras": run_karras}[kind]
+        return run(eng, emb, o.pred_dim, num_steps, ns, sigmas, sampler, sigma_data, scale, bool(x.get("clamp", False)),
+                   x.get("trace"), x.get("timer"), x.get("tokens"), float(o.diffusion.diffusion.dynamic_threshold))
 
     def inpaint(self, source, mask, sampler, sigmas, num_steps, num_resamples):
         o, emb = self.owner, self.kw["embedding"]
@@ -332,15 +350,20 @@ class _QMBase(nn.Module):
         x = conditioning_embedding(self, sequences)
         return self.diffusion(output, embedding=x)
 
-    def _do_sample(self, sequences, device, cond_scale, timesteps, clamp, noise=None, trace=None, timer=None, tokens=None):
+    def _do_sample(self, sequences, device, cond_scale, timesteps, clamp, noise=None, trace=None, timer=None, tokens=None,
+                   sampler=None, sigma_schedule=None):
+        """``sampler`` / ``sigma_schedule`` None: the objects every sample() of the reference hard-codes (generative.py:855-858)."""
         emb = self._embed(sequences, device)
-        return self.diffusion.sample(num_steps=timesteps, sampler=ADPM2Sampler(rho=1),
-                                     sigma_schedule=KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0),
+        if sampler is None:
+            sampler = ADPM2Sampler(rho=1)
+        if sigma_schedule is None:
+            sigma_schedule = KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0)
+        return self.diffusion.sample(num_steps=timesteps, sampler=sampler, sigma_schedule=sigma_schedule,
                                      clamp=clamp, noise=noise, embedding=emb, embedding_scale=cond_scale,
                                      trace=trace, timer=timer, tokens=tokens)
 
     def sample_tokens(self, sequences, device, cond_scale=None, timesteps=100, clamp=False, *, noise=None,
-                      return_sample: bool = False):
+                      return_sample: bool = False, sampler=None, sigma_schedule=None):
         """sample() followed by the decode step of the reference's callers (sample_loop_generative / generate_from_conditioning,
         generative.py:1212-1213, :1690-1691: ``permute(0, 2, 1)`` then ``argmax(dim=2)``), with the argmax taken inside the
         last sampler update: returns (B, max_length) int64 token ids on ``device`` (and the fp32 sample if asked)."""
@@ -348,7 +371,8 @@ class _QMBase(nn.Module):
             cond_scale = 7.5 if self._inverse else 1.0
         B = sequences.shape[0]
         tok = torch.zeros(B, self.max_length, dtype=torch.int32, device=device)
-        x = self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, tokens=tok if B else None)
+        x = self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, tokens=tok if B else None,
+                            sampler=sampler, sigma_schedule=sigma_schedule)
         tok = tok.long()
         return (tok, x) if return_sample else tok
 
@@ -375,8 +399,12 @@ class QMDiffusion(_QMBase):
                           pos_emb_fourier, pos_emb_fourier_add, text_embed_dim, embed_dim_position)
 
     def sample(self, sequences, device, cond_scale=7.5, timesteps=100, clamp=False, *, noise=None, trace=None,
-               timer=None):
-        return self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, trace, timer)
+               timer=None, sampler=None, sigma_schedule=None):
+        """``sampler``: ADPM2Sampler(rho=1) (None, the reference's choice), AEulerSampler() -- one U-Net evaluation per
+        timestep instead of two -- KarrasSampler(...) or any Sampler; ``sigma_schedule``: KarrasSchedule(0.001, 9.0, 3.0) (None)
+        or any callable (num_steps, device) -> sigmas."""
+        return self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, trace, timer, sampler=sampler,
+                               sigma_schedule=sigma_schedule)
 
 
 class QMDiffusionForward(_QMBase):
@@ -392,8 +420,12 @@ class QMDiffusionForward(_QMBase):
                           pos_emb_fourier, pos_emb_fourier_add, text_embed_dim, embed_dim_position)
 
     def sample(self, sequences, device, cond_scale=1.0, timesteps=100, clamp=False, *, noise=None, trace=None,
-               timer=None):
-        return self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, trace, timer)
+               timer=None, sampler=None, sigma_schedule=None):
+        """``sampler``: ADPM2Sampler(rho=1) (None, the reference's choice), AEulerSampler() -- one U-Net evaluation per
+        timestep instead of two -- KarrasSampler(...) or any Sampler; ``sigma_schedule``: KarrasSchedule(0.001, 9.0, 3.0) (None)
+        or any callable (num_steps, device) -> sigmas."""
+        return self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, trace, timer, sampler=sampler,
+                               sigma_schedule=sigma_schedule)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -420,23 +452,27 @@ def tokens_to_forward_input(tokens: Tensor, max_length: int, X_norm_factor: floa
 
 def predict_properties_from_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, device, cond_scale: float = 1.0,
                                    timesteps: int = 100, clamp: bool = False, X_norm_factor: float = 1.0,
-                                   context_embedding_max_length: int = 12, noise=None) -> Tensor:
+                                   context_embedding_max_length: int = 12, noise=None, *, sampler=None,
+                                   sigma_schedule=None) -> Tensor:
     """predict_properties_from_SMILES (generative.py:404-451) for molecules given as token ids on the device: the forward
     model's sample() on the re-tokenised ids, first ``context_embedding_max_length`` positions = the (scaled) properties.
     Returns (B, context_embedding_max_length) on ``device`` (the caller applies scaler.inverse_transform)."""
     data = tokens_to_forward_input(tokens.to(device), model_forward.max_length, X_norm_factor)
-    result = model_forward.sample(data, device, cond_scale=cond_scale, timesteps=timesteps, clamp=clamp, noise=noise)
+    result = model_forward.sample(data, device, cond_scale=cond_scale, timesteps=timesteps, clamp=clamp, noise=noise,
+                                  sampler=sampler, sigma_schedule=sigma_schedule)
     return result[:, 0, :context_embedding_max_length]
 
 
 def generate_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForward", conditioning: Tensor, device,
                           cond_scale: float = 1.0, timesteps: int = 100, forward_timesteps: int = 100,
-                          X_norm_factor: float = 1.0, noise=None, forward_noise=None):
+                          X_norm_factor: float = 1.0, noise=None, forward_noise=None, *, sampler=None, sigma_schedule=None):
     """generate_from_conditioning's core (generative.py:1685-1713) without leaving the GPU: sample molecules for the
     conditioning, decode them inside the last sampler update, re-predict their properties with the forward model.
     Returns (tokens (B, L) int64, predicted properties (B, n_cond))."""
-    tokens = model.sample_tokens(conditioning, device, cond_scale=cond_scale, timesteps=timesteps, noise=noise)
+    tokens = model.sample_tokens(conditioning, device, cond_scale=cond_scale, timesteps=timesteps, noise=noise,
+                                 sampler=sampler, sigma_schedule=sigma_schedule)
     props = predict_properties_from_tokens(model_forward, tokens, device, cond_scale=1.0, timesteps=forward_timesteps,
                                            X_norm_factor=X_norm_factor,
-                                           context_embedding_max_length=conditioning.shape[1], noise=forward_noise)
+                                           context_embedding_max_length=conditioning.shape[1], noise=forward_noise,
+                                           sampler=sampler, sigma_schedule=sigma_schedule)
     return tokens, props

@@ -53,8 +53,10 @@ class _AnalogBase(_QMBase):
             xyz = torch.cat((xyz, pad_sequence(output[:, 4:4 + max_neighbors, :], self.max_length)), 1)
         return self.diffusion(xyz, embedding=conditioning_embedding(self, sequences))
 
-    def sample(self, sequences, device, cond_scale=7.5, timesteps=100, clamp=False, *, noise=None, trace=None, timer=None):
-        return self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, trace, timer)
+    def sample(self, sequences, device, cond_scale=7.5, timesteps=100, clamp=False, *, noise=None, trace=None, timer=None,
+               sampler=None, sigma_schedule=None):
+        return self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, trace, timer, sampler=sampler,
+                               sigma_schedule=sigma_schedule)
 
 
 class AnalogDiffusionSparse(_AnalogBase):

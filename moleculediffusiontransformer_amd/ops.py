@@ -13,13 +13,16 @@ fake / meta tensors).
     adpm2_euler         one Euler move of the step for a caller-supplied denoiser
     argmax_tokens       decode step after the path (generative.py:1212-1213)
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
+    aeuler_next         the whole AEulerSampler.step after its evaluation (diffusion.py:465-474)
+    karras_hat / _mid / _next   the three stages of KarrasSampler.step (diffusion.py:417-435)
     sample              DiffusionSampler.forward + ADPM2Sampler.forward, the whole loop (diffusion.py:577-591, :517-524)
+    sample_with         the same with the sampler chosen: ADPM2Sampler, AEulerSampler (:476-483) or KarrasSampler (:437-453)
     all_gather_samples  the one collective of a sharded call (RCCL all_gather_into_tensor)
 """
 from __future__ import annotations
 
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch.library import custom_op
@@ -247,6 +250,106 @@ def _(x_base, x_from, denoised, noise, sigma, dt, sigma_up):
     return x_base.new_empty(x_base.shape, dtype=torch.float32)
 
 
+@custom_op("mdt::aeuler_next", mutates_args=())
+def aeuler_next(x: Tensor, pred: Tensor, noise: Optional[Tensor], c_skip: float, c_out: float, sigma: float, dt: float,
+                sigma_up: float, c_in_next: float, seed: int, step: int, sample0: int,
+                dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """The whole AEulerSampler.step after its evaluation.  Returns (x_next, xin_next); noise None = counter-based generator."""
+    dev = _hip(x, pred, noise)
+    lib = rt.load_library()
+    xn, pred = _f32c(x).clone(), _f32c(pred)
+    nz = None if noise is None else _f32c(noise)
+    B, C, L = xn.shape
+    Cp = pred.shape[2]
+    xin = torch.zeros(B, L, Cp, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            ds = _dyn_scale(lib, xn, pred, c_skip, c_out, dynamic_threshold)
+            rt.check(lib.mdt_aeuler_next(rt.ptr(xn), rt.ptr(pred), rt.ptr(nz), rt.ptr(xin), float(c_skip), float(c_out),
+                                         float(sigma), float(dt), float(sigma_up), float(c_in_next), int(seed), int(step),
+                                         int(sample0), B, C, L, Cp, 0, rt.ptr(ds), rt.current_stream()))
+    return xn, xin
+
+
+@aeuler_next.register_fake
+def _(x, pred, noise, c_skip, c_out, sigma, dt, sigma_up, c_in_next, seed, step, sample0, dynamic_threshold=0.0):
+    return x.new_empty(x.shape, dtype=torch.float32), pred.new_empty(pred.shape, dtype=torch.float32)
+
+
+@custom_op("mdt::karras_hat", mutates_args=())
+def karras_hat(x: Tensor, noise: Optional[Tensor], noise_scale: float, s_noise: float, c_in_hat: float, Cp: int, seed: int,
+               step: int, sample0: int) -> Tuple[Tensor, Tensor]:
+    """Churn stage of KarrasSampler.step.  Returns (x_hat, xin_hat)."""
+    dev = _hip(x, noise)
+    lib = rt.load_library()
+    x = _f32c(x)
+    nz = None if noise is None else _f32c(noise)
+    B, C, L = x.shape
+    if Cp < C or Cp % 16:
+        raise RuntimeError(f"mdt::karras_hat: Cp={Cp} must be a multiple of 16 and >= C={C}")
+    x_hat = torch.empty_like(x)
+    xin = torch.zeros(B, L, Cp, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_karras_hat(rt.ptr(x), rt.ptr(nz), rt.ptr(x_hat), rt.ptr(xin), float(noise_scale), float(s_noise),
+                                        float(c_in_hat), int(seed), int(step), int(sample0), B, C, L, Cp, rt.current_stream()))
+    return x_hat, xin
+
+
+@karras_hat.register_fake
+def _(x, noise, noise_scale, s_noise, c_in_hat, Cp, seed, step, sample0):
+    return x.new_empty(x.shape, dtype=torch.float32), x.new_empty(x.shape[0], x.shape[2], Cp, dtype=torch.float32)
+
+
+@custom_op("mdt::karras_mid", mutates_args=())
+def karras_mid(x_hat: Tensor, pred: Tensor, c_skip: float, c_out: float, sigma_hat: float, dt: float, c_in_next: float,
+               dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """Euler move of KarrasSampler.step.  Returns (d, x_next, xin_next)."""
+    dev = _hip(x_hat, pred)
+    lib = rt.load_library()
+    x_hat, pred = _f32c(x_hat), _f32c(pred)
+    B, C, L = x_hat.shape
+    Cp = pred.shape[2]
+    d, x_next = torch.empty_like(x_hat), torch.empty_like(x_hat)
+    xin = torch.zeros(B, L, Cp, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            ds = _dyn_scale(lib, x_hat, pred, c_skip, c_out, dynamic_threshold)
+            rt.check(lib.mdt_karras_mid(rt.ptr(x_hat), rt.ptr(pred), rt.ptr(d), rt.ptr(x_next), rt.ptr(xin), float(c_skip),
+                                        float(c_out), float(sigma_hat), float(dt), float(c_in_next), B, C, L, Cp, 0, rt.ptr(ds),
+                                        rt.current_stream()))
+    return d, x_next, xin
+
+
+@karras_mid.register_fake
+def _(x_hat, pred, c_skip, c_out, sigma_hat, dt, c_in_next, dynamic_threshold=0.0):
+    e = x_hat.new_empty(x_hat.shape, dtype=torch.float32)
+    return e, x_hat.new_empty(x_hat.shape, dtype=torch.float32), pred.new_empty(pred.shape, dtype=torch.float32)
+
+
+@custom_op("mdt::karras_next", mutates_args=())
+def karras_next(x_hat: Tensor, x_next: Tensor, d: Tensor, pred: Tensor, c_skip: float, c_out: float, sigma_next: float,
+                half: float, dynamic_threshold: float = 0.0) -> Tensor:
+    """Correction of KarrasSampler.step as the reference writes it: x_hat + half * (d + d')."""
+    dev = _hip(x_hat, x_next, d, pred)
+    lib = rt.load_library()
+    x_hat, x_next, d, pred = _f32c(x_hat), _f32c(x_next), _f32c(d), _f32c(pred)
+    B, C, L = x_hat.shape
+    out = torch.empty_like(x_hat)
+    if B:
+        with torch.cuda.device(dev):
+            ds = _dyn_scale(lib, x_next, pred, c_skip, c_out, dynamic_threshold)
+            rt.check(lib.mdt_karras_next(rt.ptr(x_hat), rt.ptr(x_next), rt.ptr(d), rt.ptr(pred), rt.ptr(out), float(c_skip),
+                                         float(c_out), float(sigma_next), float(half), B, C, L, pred.shape[2], 0, rt.ptr(ds),
+                                         rt.current_stream()))
+    return out
+
+
+@karras_next.register_fake
+def _(x_hat, x_next, d, pred, c_skip, c_out, sigma_next, half, dynamic_threshold=0.0):
+    return x_hat.new_empty(x_hat.shape, dtype=torch.float32)
+
+
 @custom_op("mdt::argmax_tokens", mutates_args=())
 def argmax_tokens(x: Tensor) -> Tensor:
     dev = _hip(x)
@@ -334,6 +437,70 @@ def sample(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Optional
 @sample.register_fake
 def _(embedding, init_noise, step_noise, sigmas, handle, pred_dim, rho, sigma_data, embedding_scale, clamp, seed, sample0,
       want_tokens, dynamic_threshold=0.0):
+    eng = _engine(handle)
+    B = embedding.shape[0]
+    return (embedding.new_empty(B, pred_dim, eng.c.length, dtype=torch.float32),
+            embedding.new_empty((B, eng.c.length) if want_tokens else (0,), dtype=torch.int32))
+
+
+SAMPLER_KINDS = {"adpm2": 0, "aeuler": 1, "karras": 2}      # sampler_kind of mdt::sample_with
+
+
+def sampler_spec(sampler) -> Tuple[int, list]:
+    """(sampler_kind, sampler_params) of mdt::sample_with for a sampler object that may take the fused loop."""
+    from .diffusion import fused_sampler_kind
+    kind = fused_sampler_kind(sampler)
+    if kind is None:
+        raise TypeError(f"{type(sampler).__name__} has no fused loop")
+    params = {"adpm2": lambda s: [s.rho], "aeuler": lambda s: [],
+              "karras": lambda s: [s.s_tmin, s.s_tmax, s.s_churn, s.s_noise]}[kind](sampler)
+    return SAMPLER_KINDS[kind], [float(p) for p in params]
+
+
+def _make_sampler(kind: int, params):
+    from .diffusion import ADPM2Sampler, AEulerSampler, KarrasSampler, run_adpm2, run_aeuler, run_karras
+    want = {0: 1, 1: 0, 2: 4}.get(int(kind))
+    if want is None or len(params) != want:
+        raise RuntimeError(f"mdt::sample_with: sampler_kind {kind} with {len(params)} parameters (0 = ADPM2 [rho], 1 = AEuler [], "
+                           "2 = Karras [s_tmin, s_tmax, s_churn, s_noise])")
+    if kind == 0:
+        return ADPM2Sampler(rho=params[0]), run_adpm2
+    if kind == 1:
+        return AEulerSampler(), run_aeuler
+    return KarrasSampler(*params), run_karras
+
+
+@custom_op("mdt::sample_with", mutates_args=())
+def sample_with(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Optional[Tensor], sigmas: Tensor, handle: int,
+                pred_dim: int, sampler_kind: int, sampler_params: Sequence[float], sigma_data: float, embedding_scale: float,
+                clamp: bool, seed: int, sample0: int, want_tokens: bool, dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """mdt::sample with the sampler chosen by the caller: sampler_kind 0 = ADPM2Sampler (sampler_params [rho]), 1 =
+    AEulerSampler ([]), 2 = KarrasSampler ([s_tmin, s_tmax, s_churn, s_noise]).  Every other argument and both results as
+    mdt::sample; each sampler makes one draw per step, so step_noise holds num_steps - 1 draws for all of them."""
+    from .diffusion import NoiseSource
+    dev = _hip(embedding, step_noise)
+    eng = _engine(handle)
+    if eng.device != dev:
+        raise RuntimeError(f"mdt::sample_with: engine lives on {eng.device}, tensors on {dev}")
+    sampler, run = _make_sampler(sampler_kind, list(sampler_params))
+    B = embedding.shape[0]
+    num_steps = sigmas.numel() - 1
+    ns = NoiseSource(seed=int(seed), sample0=int(sample0))
+    if init_noise is not None:
+        ns.init = init_noise
+    if step_noise is not None:
+        if step_noise.shape[0] != max(num_steps - 1, 0):
+            raise RuntimeError(f"mdt::sample_with: step_noise holds {step_noise.shape[0]} draws, the loop makes {num_steps - 1}")
+        ns.steps = lambda i: step_noise[i]
+    tok = torch.zeros(B, eng.c.length, dtype=torch.int32, device=dev) if want_tokens else None
+    x = run(eng, embedding, pred_dim, num_steps, ns, sigmas, sampler, float(sigma_data), float(embedding_scale), bool(clamp),
+            None, None, tok if B else None, float(dynamic_threshold))
+    return x, (tok if want_tokens else torch.empty(0, dtype=torch.int32, device=dev))
+
+
+@sample_with.register_fake
+def _(embedding, init_noise, step_noise, sigmas, handle, pred_dim, sampler_kind, sampler_params, sigma_data, embedding_scale,
+      clamp, seed, sample0, want_tokens, dynamic_threshold=0.0):
     eng = _engine(handle)
     B = embedding.shape[0]
     return (embedding.new_empty(B, pred_dim, eng.c.length, dtype=torch.float32),

@@ -84,6 +84,10 @@ SYMBOLS = {
     "mdt_adpm2_mid": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P]),
     "mdt_adpm2_next": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P, _P, _P]),
     "mdt_adpm2_euler": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _I, _U64, _U32, _L, _I, _I, _I, _P]),
+    "mdt_aeuler_next": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P, _P, _P]),
+    "mdt_karras_hat": (_I, [_P, _P, _P, _P, _F, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P]),
+    "mdt_karras_mid": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P]),
+    "mdt_karras_next": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P, _P]),
     "mdt_init_noise": (_I, [_P, _P, _F, _U64, _U32, _L, _I, _I, _I, _P]),
     "mdt_clamp": (_I, [_P, _F, _F, _L, _P]),
     "mdt_copy_f32": (_I, [_P, _P, _L, _P]),
