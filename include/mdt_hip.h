@@ -86,7 +86,8 @@ enum mdt_op_kind {
   MDT_OP_TIME_EMBED = 6, /* LearnedPositionalEmbedding.forward (modules.py:554-559)              */
   MDT_OP_GN_ACT = 8,   /* nn.GroupNorm + FiLM + SiLU applied in one pass: out = silu(gn(a) * (scale + 1) + shift)
                           (ConvBlock1d.forward before its convolution, modules.py:117-121); a -> out, p0 = gain,
-                          p1 = bias, p3 = [scale | shift] or none; ints as MDT_OP_GN_STATS plus MDT_N_SILU        */
+                          p1 = bias, p3 = [scale | shift] or none (one row, or one per sample: mdt_op.film_bstride);
+                          ints as MDT_OP_GN_STATS plus MDT_N_SILU                                                */
   MDT_OP_RCONV = 9,    /* row-stationary Conv1d (k = 1 | 3, C -> C channels, C in {128, 256}) with the ConvBlock1d prologue
                           computed in the kernel: out = bias + conv(silu(gn(s * a) * (scale + 1) + shift)) (+ res);
                           with a2 the input is cat([s * a, s2 * a2]) (2C channels, GroupNorm groups inside a half; the second
@@ -360,7 +361,11 @@ enum mdt_tf128_f { MDT_FF_EPS_LN = 0, MDT_FF_SCALE = 1, MDT_FF_EPS_GN = 2, MDT_F
 
 typedef struct mdt_op {
   int32_t kind;
-  int32_t reserved;
+  int32_t film_bstride; /* floats between the FiLM rows (p3) of consecutive samples: sample b reads p3 + b * film_bstride.  0 = ONE row
+                           shared by the batch (sigma is a scalar: every sampling program).  Non-zero (a multiple of 4): one noise
+                           level per sample (the "eval_rows" programs, KDiffusion_mod.forward); taken by MDT_OP_GN_ACT,
+                           MDT_OP_RCONV (single source, GroupNorm prologue), MDT_OP_RESBLOCK and the GroupNorm prologue of MDT_OP_GEMM
+                           (WFMT 0, M_MODE 0); refused on every other op (the chains of MDT_OP_TF128 / MDT_OP_RES256 stage one row).  Was `reserved` (always 0): an addition inside ABI version 5. */
   mdt_ref a;    /* GEMM A / GN input / ATTN q / CONCAT a / PATCH in / TIME c_noise values        */
   mdt_ref a2;   /* ATTN k (v = k + heads*64 floats) / CONCAT b / GEMM: bf16 lo plane of split weights:
                    when set, w is the bf16 hi plane [N][K] and the product is formed as hi*hi + hi*lo + lo*hi
@@ -426,6 +431,26 @@ int mdt_precond_out(const float *x, const float *pred, float *D, float c_skip, f
  * 0 < q <= 1, linear interpolation between the neighbouring order statistics as torch.quantile; C * L <= 32768. */
 int mdt_dyn_scale(const float *x, const float *pred, float *scale, float c_skip, float c_out, float q, int32_t B,
                   int32_t C, int32_t L, int32_t Cp, void *stream);
+/* ---- per-sample noise levels: KDiffusion_mod.forward (diffusion.py:820-844) and denoise_fn(sigmas=(B,)) (:798-814) as a batch.
+ * sigma / c_in / c_skip / c_out / weight are DEVICE vectors of B floats (get_scale_weights / loss_weight, :789-796, :816-818, computed
+ * by the host in the reference's fp32 tensor expressions).  Additions inside ABI version 5. ---- */
+/* x_noisy = x0 + sigma[b] * noise (:828-829); xin = c_in[b] * x_noisy (:810), token-major, padded.  noise == NULL: the counter-based
+ * generator of mdt_init_noise, keyed by (seed, step, sample0 + b): independent of how a batch is split. */
+int mdt_noise_in_rows(const float *x0, const float *noise, const float *sigma, const float *c_in, float *x_noisy, float *xin,
+                      uint64_t seed, uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L, int32_t Cp, void *stream);
+/* mdt_precond_in / mdt_precond_out / mdt_dyn_scale with one coefficient per sample. */
+int mdt_precond_in_rows(const float *x, float *xin, const float *c_in, int32_t B, int32_t C, int32_t L, int32_t Cp, void *stream);
+int mdt_precond_out_rows(const float *x, const float *pred, float *D, const float *c_skip, const float *c_out, int32_t B,
+                         int32_t C, int32_t L, int32_t Cp, const float *dyn_scale, void *stream);
+int mdt_dyn_scale_rows(const float *x, const float *pred, float *scale, const float *c_skip, const float *c_out, float q,
+                       int32_t B, int32_t C, int32_t L, int32_t Cp, void *stream);
+/* The objective's value in one pass (:838-844), the denoised tensor never written:
+ *   loss[b] = weight[b] * mean_{c,l}((clip(c_skip[b] x_noisy + c_out[b] pred) - x0)^2),
+ * clip as mdt_precond_out (dyn_scale NULL: clamp to [-1, 1]).  Fixed summation order: bitwise repeatable, and a sample's value does
+ * not depend on its position in the batch.  C * L <= 32768. */
+int mdt_loss_rows(const float *x0, const float *x_noisy, const float *pred, const float *c_skip, const float *c_out,
+                  const float *weight, const float *dyn_scale, float *loss, int32_t B, int32_t C, int32_t L, int32_t Cp,
+                  void *stream);
 /* UNetCFG1d.forward guidance mix (modules.py:1253): out = um + (cond - um) * scale, token-major. */
 int mdt_cfg_mix(const float *cond, const float *uncond, float *out, float scale, int64_t n, void *stream);
 /* First half of ADPM2Sampler.step (diffusion.py:506-508) fused with the denoise output:

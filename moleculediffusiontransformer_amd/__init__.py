@@ -5,7 +5,8 @@ Drop-in classes (same names and call signatures as the reference's MoleculeDiffu
     from moleculediffusiontransformer_amd import QMDiffusion, QMDiffusionForward
 
 The sampling hot path (QMDiffusion.sample -> ADPM2 sampler -> 1-D conditional U-Net) runs in
-hand-written gfx950 kernels (csrc/, C ABI in include/mdt_hip.h).
+hand-written gfx950 kernels (csrc/, C ABI in include/mdt_hip.h).  So does the VALUE of the training objective,
+``model.eval_loss(sequences, output, device)`` (one noise level per sample, no gradients); ``forward()`` itself stays PyTorch.
 """
 from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler,  # noqa: F401
                         KarrasSchedule, LogNormalDistribution, NoiseSource, Sampler)

@@ -29,6 +29,7 @@ from .netspec import UNetConfig
 
 EXT_XIN, EXT_CTX, EXT_OUT = 0, 1, 2      # bindings.ext slots used by the programs
 EXT_XFLAGS, EXT_XBUF = 3, 4              # pair-split MDT_OP_TF256: hand-off flags / blocks (engine.py sizes them per batch)
+EXT_FILM = 5                             # per-row programs: the (B, ss_total) table of per-sample (scale | shift) rows
 
 
 def pad16(c: int) -> int:
@@ -139,6 +140,11 @@ class CompiledUNet:
     dual_multiple: int = 1
     tf256: bool = False              # compiled with the whole-transformer form of the 256-channel level (generative._wide)
     xchg_tokens: int = 0             # > 0: pair-split MDT_OP_TF256 ops present; tokens per sample of the largest (engine.py)
+    # the per-row form (compile_unet(rows=True)): programs "time_rows" / "eval_rows" / "eval_rows_fixed" instead of "time" / "eval" /
+    # "eval_fixed" / "eval_dual" -- one time-mapping row and one (scale | shift) row PER SAMPLE (KDiffusion_mod.forward's one sigma
+    # per sample); `act_named`: per-sample arena offsets of the time program's tensors
+    rows: bool = False
+    act_named: Dict[str, int] = field(default_factory=dict)
 
 
 class UNetCompiler:
@@ -210,6 +216,7 @@ class UNetCompiler:
         # program of rounds 1-3 (k_gemm + k_attn + k_gn_act), kept as the second exact implementation the tests compare with.
         self.wf32 = gemm_mode == "f32" and os.environ.get("MDT_F32_FUSED", "1") == "1"
         self.ring_mode = gemm_mode == "bf16x3" or self.wf32        # may the ring kernels be used at all?
+        self.rows = False                    # the per-row form (use_rows())
         self._packed: Dict = {}
         self._zeros_off, self._zeros_len = 0, 0
         if cfg.channels % 16:
@@ -234,6 +241,21 @@ class UNetCompiler:
         self.ss_total = 0
         self.shr_top = 0
         self.shr: Dict[str, int] = {}
+
+    def use_rows(self) -> "UNetCompiler":
+        """Switch to the per-row form before build(): every FiLM consumer reads the row of ITS sample (mdt_op.film_bstride), which
+        MDT_OP_GN_ACT, MDT_OP_RCONV, MDT_OP_RESBLOCK and the GroupNorm prologue of MDT_OP_GEMM take.  So the ResNet blocks are
+        lowered one by one -- k_resblock on the 64-token level, k_rconv launches at 128 / 256 channels, GroupNorm-apply passes +
+        convolution GEMMs elsewhere -- never through the chains inside k_tf128 / k_res256, which stage ONE row per block for the
+        8 / 2 samples of a workgroup by LDS-DMA; every Transformer1d keeps the kernel it has in the shared-row program (a
+        transformer-only launch where the shared-row program puts the level's ResNet blocks in front of it).  Compiler state, not
+        environment: the shared-row programs of the same process keep their fused forms."""
+        if self.gemm_mode == "bf16":
+            raise ValueError("the per-row evaluation (batched=True, eval_loss) is built and pinned for gemm_mode 'bf16x3' and 'f32'; "
+                             "in the plain-bf16 mode the FiLM rows also enter MDT_OP_PREP16, which reads one shared row")
+        self.rows = True
+        self.res128, self.res256_mode = False, "0"
+        return self
 
     # ------------------------------------------------------------------ helpers
     def _shr_alloc(self, name: str, n: int) -> int:
@@ -1986,7 +2008,7 @@ class UNetCompiler:
             act_floats += (self.n_ctx * cfg.ctx_features + 63) // 64 * 64
 
         # ---- shared arena layout ----
-        rows = self.max_time_rows
+        rows = 0 if self.rows else self.max_time_rows      # (the per-row form keeps its time tensors in batch-scaled memory)
         mapf = cfg.mapping_features
         ldt = pad16(cfg.channels + 1)
         cn = self._shr_alloc("c_noise", rows)
@@ -2007,7 +2029,18 @@ class UNetCompiler:
                 o = rt.MdtOp()
                 C_memmove(o, op)
                 if op.kind in (rt.OP_GEMM, rt.OP_GN_ACT, rt.OP_RCONV, rt.OP_RESBLOCK, rt.OP_PREP16, rt.OP_TF128, rt.OP_RES256) and isinstance(getattr(op, "_film", None), tuple):
-                    o.p3 = _ref(rt.SP_SHR, ss_cur + op._film[1])
+                    if self.rows:
+                        # the sample's own row of the (B, ss_total) table; only kernels that address FiLM by sample may read it
+                        if not (op.kind in (rt.OP_GN_ACT, rt.OP_RCONV, rt.OP_RESBLOCK)
+                                or (op.kind == rt.OP_GEMM and op.i[rt.G_PRO] == rt.PRO_GROUPNORM and op.i[rt.G_WFMT] == 0
+                                    and op.i[rt.G_M_MODE] == 0)):
+                            raise NotImplementedError(f"per-row evaluation: the FiLM rows reach op kind {op.kind} "
+                                                      f"({rt.OP_NAMES.get(op.kind)}), which reads one shared row: this U-Net shape is "
+                                                      "outside the per-row envelope")
+                        o.p3 = _ref(rt.SP_EXT0 + EXT_FILM, op._film[1])
+                        o.film_bstride = self.ss_total
+                    else:
+                        o.p3 = _ref(rt.SP_SHR, ss_cur + op._film[1])
                 if op.kind == rt.OP_ATTN_CTX:
                     if fixed:
                         o.a2 = _ref(rt.SP_SHR, chat_fixed)
@@ -2026,7 +2059,10 @@ class UNetCompiler:
                 out.append(o)
             return out
 
-        programs = {"eval": resolve(eval_ops, False), "eval_fixed": resolve(eval_ops, True)}
+        if self.rows:
+            programs = {"eval_rows": resolve(eval_ops, False), "eval_rows_fixed": resolve(eval_ops, True)}
+        else:
+            programs = {"eval": resolve(eval_ops, False), "eval_fixed": resolve(eval_ops, True)}
         # Both passes of classifier-free guidance as ONE evaluation of a batch of 2B (UNetCFG1d.forward, modules.py:1248-1253:
         # the masked pass sees the same x and time, only the context differs): the first half of the samples attends to its
         # hoisted K/V, the second half to the FixedEmbedding's.  Needs every cross-attention block on a ring kernel (the
@@ -2037,7 +2073,7 @@ class UNetCompiler:
                                                                          and (16 // op.i[rt.B_T]) * op.i[rt.B_TK] <= 16)))
                    for op in cross)
         dual_multiple = 1
-        if cross and ring and os.environ.get("MDT_CFG_DUAL", "1") == "1":
+        if cross and ring and not self.rows and os.environ.get("MDT_CFG_DUAL", "1") == "1":
             dual_multiple = max(64 // op.i[rt.F_T] if op.kind == rt.OP_TF128 else 32 // op.i[rt.F_T] if op.kind == rt.OP_TF256
                                 else (32 if op.i[rt.B_VARIANT] >= 2 else 64) // op.i[rt.B_T] for op in cross)
             dual = resolve(eval_ops, False)
@@ -2047,22 +2083,36 @@ class UNetCompiler:
                     o.i[rt.F_KV2 if op.kind in (rt.OP_TF128, rt.OP_TF256) else rt.B_KV2] = 1
             programs["eval_dual"] = dual
 
-        # ---- time program (m_mode 1) ----
+        # ---- time program (m_mode 1; per-row form: m_mode 0, one row per SAMPLE in the per-sample arena, the (scale | shift) rows
+        #      into the (B, ss_total) table bound as EXT_FILM -- B may exceed max_time_rows) ----
         self.ops, self.flops = [], 0
-        t_cn = Ten(rt.SP_SHR, cn, 1, 1)
-        t_emb = Ten(rt.SP_SHR, temb, 1, ldt)
+        act_named: Dict[str, int] = {}
+        tm = 0 if self.rows else 1
+        if self.rows:
+            def act_alloc(name: str, n: int) -> int:
+                nonlocal act_floats
+                off = act_named[name] = act_floats
+                act_floats += (n + 63) // 64 * 64
+                return off
+            sp = rt.SP_ACT
+            cn, temb = act_alloc("c_noise", 1), act_alloc("time_embed", ldt)
+            m1, m2, m3 = act_alloc("map1", mapf), act_alloc("map2", mapf), act_alloc("map3", mapf)
+        else:
+            sp = rt.SP_SHR
+        t_cn = Ten(sp, cn, 1, 1)
+        t_emb = Ten(sp, temb, 1, ldt)
         op = rt.MdtOp()
         op.kind = rt.OP_TIME_EMBED
         op.a, op.w, op.out = t_cn.ref(), _ref(rt.SP_WEIGHT, self.W.add("to_time.0.0.weights", self.sd["to_time.0.0.weights"])), t_emb.ref()
         op.i[rt.T_HALF], op.i[rt.T_LD] = cfg.channels // 2, ldt
         self._emit(op)
-        t1, t2, t3 = Ten(rt.SP_SHR, m1, 1, mapf), Ten(rt.SP_SHR, m2, 1, mapf), Ten(rt.SP_SHR, m3, 1, mapf)
+        t1, t2, t3 = Ten(sp, m1, 1, mapf), Ten(sp, m2, 1, mapf), Ten(sp, m3, 1, mapf)
         self.gemm(t_emb, self._lin_w("to_time.0.1.weight", mapf, ldt), mapf, t1, cin=ldt,
-                  bias_off=self._vec("to_time.0.1.bias", mapf), act=1, m_mode=1)
+                  bias_off=self._vec("to_time.0.1.bias", mapf), act=1, m_mode=tm)
         self.gemm(t1, self._lin_w("to_mapping.0.weight"), mapf, t2, cin=mapf,
-                  bias_off=self._vec("to_mapping.0.bias", mapf), act=1, m_mode=1)
+                  bias_off=self._vec("to_mapping.0.bias", mapf), act=1, m_mode=tm)
         self.gemm(t2, self._lin_w("to_mapping.2.weight"), mapf, t3, cin=mapf,
-                  bias_off=self._vec("to_mapping.2.bias", mapf), act=1, m_mode=1)
+                  bias_off=self._vec("to_mapping.2.bias", mapf), act=1, m_mode=tm)
         # all MappingToScaleShift linears as one GEMM: rows laid out [scale(Cp) | shift(Cp)] per block
         w_all = torch.zeros(self.ss_total, mapf)
         b_all = torch.zeros(self.ss_total)
@@ -2075,10 +2125,10 @@ class UNetCompiler:
             w_all[off + cp: off + cp + c] = w[c:]
             b_all[off: off + c] = b[:c]
             b_all[off + cp: off + cp + c] = b[c:]
-        t_ss = Ten(rt.SP_SHR, ss_all, 1, self.ss_total)
+        t_ss = Ten(rt.SP_EXT0 + EXT_FILM, 0, 1, self.ss_total) if self.rows else Ten(rt.SP_SHR, ss_all, 1, self.ss_total)
         self.gemm(t3, ("scale_shift_all.weight", w_all), self.ss_total, t_ss, cin=mapf,
-                  bias_off=self.W.add("scale_shift_all.bias", b_all), pro=rt.PRO_SILU, m_mode=1)
-        programs["time"] = self.ops
+                  bias_off=self.W.add("scale_shift_all.bias", b_all), pro=rt.PRO_SILU, m_mode=tm)
+        programs["time_rows" if self.rows else "time"] = self.ops
 
         # ---- context programs ----
         self.ops, self.flops = [], 0
@@ -2117,7 +2167,7 @@ class UNetCompiler:
                             max_time_rows=rows, shr=dict(self.shr), ss_total=self.ss_total, n_cross=n_cross,
                             flops_per_sample_eval=flops_eval, flops_ctx_per_sample=flops_ctx, gemm_mode=self.gemm_mode,
                             weight_index=dict(self.W.index), dual_multiple=dual_multiple, tf256=self.tf256,
-                            xchg_tokens=self.xchg_tokens)
+                            xchg_tokens=self.xchg_tokens, rows=self.rows, act_named=act_named)
 
 
 def C_memmove(dst: rt.MdtOp, src: rt.MdtOp) -> None:
@@ -2134,7 +2184,9 @@ def _prod(xs) -> int:
 
 def compile_unet(cfg: UNetConfig, length: int, cond_len: int, sd: Dict[str, torch.Tensor],
                  max_time_rows: int = 1024, gemm_mode: str = "bf16x3", fuse_blocks: bool = True,
-                 tf256: bool = False) -> CompiledUNet:
-    """tf256: the 256-channel transformers as whole-transformer launches without the head split (k_tf256.hip; the better
+                 tf256: bool = False, rows: bool = False) -> CompiledUNet:
+    """rows: the per-row form -- programs "time_rows" / "eval_rows" / "eval_rows_fixed" with one time value per SAMPLE (CompiledUNet.rows).
+    tf256: the 256-channel transformers as whole-transformer launches without the head split (k_tf256.hip; the better
     form once the batch fills the chip by itself) instead of one head-split launch per sub-block (k_tblock32.hip)."""
-    return UNetCompiler(cfg, length, cond_len, sd, max_time_rows, gemm_mode, fuse_blocks, tf256).build()
+    comp = UNetCompiler(cfg, length, cond_len, sd, max_time_rows, gemm_mode, fuse_blocks, tf256)
+    return (comp.use_rows() if rows else comp).build()

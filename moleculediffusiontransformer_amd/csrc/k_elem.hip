@@ -127,9 +127,8 @@ __global__ __launch_bounds__(256) void k_precond_out(const float* x, const float
 // quantile is torch's linear interpolation between the two neighbouring order statistics: rank = q (N - 1) in fp32,
 // lerp(v[floor], v[ceil], rank - floor) with ATen's two-sided formula.  The consumers (k_precond_out / k_adpm2_mid / k_adpm2_next)
 // then clamp to [-scale, scale] and divide.  Rarely used (every class of the reference passes 0.0): simple, not tuned.
-__global__ __launch_bounds__(256) void k_dyn_scale(const float* x, const float* pred, float* scale, float c_skip, float c_out,
-                                                    float q, int C, int L, int Cp, int npad) {
-  extern __shared__ float tile[];
+__device__ __forceinline__ void dyn_scale_sample(float* tile, const float* x, const float* pred, float* scale, float c_skip,
+                                                 float c_out, float q, int C, int L, int Cp, int npad) {
   const int b = blockIdx.x, N = C * L;
   const float* xb = x + (int64_t)b * N;
   const float* pb = pred + (int64_t)b * L * Cp;
@@ -163,6 +162,17 @@ __global__ __launch_bounds__(256) void k_dyn_scale(const float* x, const float* 
     const float qv = fabsf(w) < 0.5f ? v0 + w * diff : v1 - diff * (1.0f - w);
     scale[b] = fmaxf(qv, 1.0f);
   }
+}
+__global__ __launch_bounds__(256) void k_dyn_scale(const float* x, const float* pred, float* scale, float c_skip, float c_out,
+                                                    float q, int C, int L, int Cp, int npad) {
+  extern __shared__ float tile[];
+  dyn_scale_sample(tile, x, pred, scale, c_skip, c_out, q, C, L, Cp, npad);
+}
+// ... with one (c_skip, c_out) pair per sample (KDiffusion_mod.forward: one sigma per sample, diffusion.py:820-844)
+__global__ __launch_bounds__(256) void k_dyn_scale_rows(const float* x, const float* pred, float* scale, const float* c_skip,
+                                                         const float* c_out, float q, int C, int L, int Cp, int npad) {
+  extern __shared__ float tile[];
+  dyn_scale_sample(tile, x, pred, scale, c_skip[blockIdx.x], c_out[blockIdx.x], q, C, L, Cp, npad);
 }
 
 // First half of ADPM2Sampler.step fused with denoise_fn's output stage   (diffusion.py:506-508, :811-814)
@@ -614,6 +624,118 @@ __global__ __launch_bounds__(256) void k_patch(const float* in, float* out, int 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// One noise level PER SAMPLE (KDiffusion_mod.forward / denoise_fn(sigmas=(B,)), diffusion.py:798-844): the kernels above with
+// their coefficients read from device vectors of B entries, and the training objective's value as one fused pass.
+// ------------------------------------------------------------------------------------------------
+// x_noisy = x0 + sigma[b] * noise (diffusion.py:828-829), xin = c_in[b] * x_noisy (:810).  noise == nullptr: the counter-based
+// generator keyed by (seed, step, global sample index), as k_init_noise.
+__global__ __launch_bounds__(256) void k_noise_in_rows(const float* x0, const float* noise, const float* sigma, const float* c_in,
+                                                        float* x_noisy, float* xin, uint64_t seed, uint32_t step, int64_t sample0,
+                                                        int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const float sg = sigma[b], ci = c_in[b];
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 v = *reinterpret_cast<const float4*>(x0 + o);
+    float4 nz;
+    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
+    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
+    const float xv[4] = {v.x, v.y, v.z, v.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
+    float xn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      xn[q] = xv[q] + sg * nv[q];
+      tile[(l + q) * (Cp + 1) + c] = ci * xn[q];
+    }
+    *reinterpret_cast<float4*>(x_noisy + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  }
+  tile_zero_pad(tile, C, L, Cp);
+  __syncthreads();
+  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+}
+
+// xin[b,l,c] = c_in[b] * x[b,c,l]
+__global__ __launch_bounds__(256) void k_precond_in_rows(const float* x, float* xin, const float* c_in, int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const float ci = c_in[b];
+  const float* xb = x + (int64_t)b * C * L;
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const float4 v = *reinterpret_cast<const float4*>(xb + c * L + l);
+    tile[(l + 0) * (Cp + 1) + c] = ci * v.x;
+    tile[(l + 1) * (Cp + 1) + c] = ci * v.y;
+    tile[(l + 2) * (Cp + 1) + c] = ci * v.z;
+    tile[(l + 3) * (Cp + 1) + c] = ci * v.w;
+  }
+  tile_zero_pad(tile, C, L, Cp);
+  __syncthreads();
+  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+}
+
+// D = clip(c_skip[b] * x + c_out[b] * pred)
+__global__ __launch_bounds__(256) void k_precond_out_rows(const float* x, const float* pred, float* D, const float* c_skip,
+                                                           const float* c_out, int C, int L, int Cp, const float* dscale) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const float ds = dscale ? dscale[b] : 0.f, cs = c_skip[b], co = c_out[b];
+  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
+  __syncthreads();
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 v = *reinterpret_cast<const float4*>(x + o);
+    float4 d;
+    d.x = clip_dyn(cs * v.x + co * tile[(l + 0) * (Cp + 1) + c], ds);
+    d.y = clip_dyn(cs * v.y + co * tile[(l + 1) * (Cp + 1) + c], ds);
+    d.z = clip_dyn(cs * v.z + co * tile[(l + 2) * (Cp + 1) + c], ds);
+    d.w = clip_dyn(cs * v.w + co * tile[(l + 3) * (Cp + 1) + c], ds);
+    *reinterpret_cast<float4*>(D + o) = d;
+  }
+}
+
+// loss[b] = weight[b] * mean_{c,l} ((clip(c_skip[b] x_noisy + c_out[b] pred) - x0)^2)   (diffusion.py:838-844), the denoised
+// tensor never written.  The sum runs in a fixed order: every thread over its own elements in ascending order, the 64 lanes of a
+// wave by a butterfly, the four waves' partials as (w0 + w1) + (w2 + w3) -- two calls give the same bits, and a sample's value
+// does not depend on its position in the batch.
+__global__ __launch_bounds__(256) void k_loss_rows(const float* x0, const float* x_noisy, const float* pred, const float* c_skip,
+                                                    const float* c_out, const float* weight, const float* dscale, float* loss,
+                                                    int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  float* red = tile;                                 // the waves' partial sums reuse the tile once every thread is done with it
+  const int b = blockIdx.x;
+  const float ds = dscale ? dscale[b] : 0.f, cs = c_skip[b], co = c_out[b];
+  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
+  __syncthreads();
+  const int l4n = L / 4;
+  float acc = 0.f;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l;
+    const float4 v = *reinterpret_cast<const float4*>(x_noisy + o);
+    const float4 t = *reinterpret_cast<const float4*>(x0 + o);
+    const float xv[4] = {v.x, v.y, v.z, v.w}, tv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float den = clip_dyn(cs * xv[q] + co * tile[(l + q) * (Cp + 1) + c], ds);
+      const float r = den - tv[q];
+      acc = acc + r * r;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[b] = weight[b] * (((red[0] + red[1]) + (red[2] + red[3])) / (float)(C * L));
+}
+
 static inline unsigned grid_for(int64_t n, int block = 256, int cap = 256 * 8) {
   int64_t g = (n + block - 1) / block;
   if (g > cap) g = cap;
@@ -730,6 +852,62 @@ int mdt_dyn_scale(const float* x, const float* pred, float* scale, float c_skip,
   hipLaunchKernelGGL(mdt::k_dyn_scale, dim3(B), dim3(256), (size_t)npad * sizeof(float), (hipStream_t)stream, x, pred, scale,
                      c_skip, c_out, q, C, L, Cp, npad);
   return finish("mdt_dyn_scale");
+}
+
+/* ---- one noise level per sample (include/mdt_hip.h: "per-sample noise levels") ---- */
+int mdt_noise_in_rows(const float* x0, const float* noise, const float* sigma, const float* c_in, float* x_noisy, float* xin,
+                      uint64_t seed, uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L, int32_t Cp, void* stream) {
+  MDT_CHECK_TILE("mdt_noise_in_rows")
+  if (!x0 || !sigma || !c_in || !x_noisy || !xin) return bad("mdt_noise_in_rows: null pointer");
+  MDT_BIG_LDS(mdt::k_noise_in_rows);
+  hipLaunchKernelGGL(mdt::k_noise_in_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x0, noise, sigma, c_in,
+                     x_noisy, xin, seed, step, sample0, C, L, Cp);
+  return finish("mdt_noise_in_rows");
+}
+
+int mdt_precond_in_rows(const float* x, float* xin, const float* c_in, int32_t B, int32_t C, int32_t L, int32_t Cp, void* stream) {
+  MDT_CHECK_TILE("mdt_precond_in_rows")
+  if (!x || !xin || !c_in) return bad("mdt_precond_in_rows: null pointer");
+  MDT_BIG_LDS(mdt::k_precond_in_rows);
+  hipLaunchKernelGGL(mdt::k_precond_in_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, c_in, C, L, Cp);
+  return finish("mdt_precond_in_rows");
+}
+
+int mdt_precond_out_rows(const float* x, const float* pred, float* D, const float* c_skip, const float* c_out, int32_t B, int32_t C,
+                         int32_t L, int32_t Cp, const float* dyn_scale, void* stream) {
+  MDT_CHECK_TILE("mdt_precond_out_rows")
+  if (!x || !pred || !D || !c_skip || !c_out) return bad("mdt_precond_out_rows: null pointer");
+  MDT_BIG_LDS(mdt::k_precond_out_rows);
+  hipLaunchKernelGGL(mdt::k_precond_out_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, pred, D, c_skip,
+                     c_out, C, L, Cp, dyn_scale);
+  return finish("mdt_precond_out_rows");
+}
+
+int mdt_dyn_scale_rows(const float* x, const float* pred, float* scale, const float* c_skip, const float* c_out, float q, int32_t B,
+                       int32_t C, int32_t L, int32_t Cp, void* stream) {
+  if (B <= 0) return 0;
+  if (!x || !pred || !scale || !c_skip || !c_out) return bad("mdt_dyn_scale_rows: null pointer");
+  if (!(q > 0.0f && q <= 1.0f)) return bad("mdt_dyn_scale_rows: the quantile must lie in (0, 1]");
+  if (C <= 0 || L <= 0 || Cp < C) return bad("mdt_dyn_scale_rows: bad dims");
+  int npad = 1;
+  while (npad < C * L) npad <<= 1;
+  if ((size_t)npad * sizeof(float) > 160 * 1024) return bad("mdt_dyn_scale_rows: C * L exceeds 32768 values (the sort runs in one compute unit's LDS)");
+  MDT_BIG_LDS(mdt::k_dyn_scale_rows);
+  hipLaunchKernelGGL(mdt::k_dyn_scale_rows, dim3(B), dim3(256), (size_t)npad * sizeof(float), (hipStream_t)stream, x, pred, scale,
+                     c_skip, c_out, q, C, L, Cp, npad);
+  return finish("mdt_dyn_scale_rows");
+}
+
+int mdt_loss_rows(const float* x0, const float* x_noisy, const float* pred, const float* c_skip, const float* c_out,
+                  const float* weight, const float* dyn_scale, float* loss, int32_t B, int32_t C, int32_t L, int32_t Cp,
+                  void* stream) {
+  MDT_CHECK_TILE("mdt_loss_rows")
+  if (!x0 || !x_noisy || !pred || !c_skip || !c_out || !weight || !loss) return bad("mdt_loss_rows: null pointer");
+  if ((int64_t)C * L > 32768) return bad("mdt_loss_rows: C * L exceeds 32768 values");
+  MDT_BIG_LDS(mdt::k_loss_rows);
+  hipLaunchKernelGGL(mdt::k_loss_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x0, x_noisy, pred, c_skip,
+                     c_out, weight, dyn_scale, loss, C, L, Cp);
+  return finish("mdt_loss_rows");
 }
 
 int mdt_adpm2_mid(const float* x, const float* pred, float* x_mid, float* xin_mid, float c_skip, float c_out,

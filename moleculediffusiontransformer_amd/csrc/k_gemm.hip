@@ -203,7 +203,13 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
             x[e] = x[e] * sc + (be[e] - sc * mean);
           }
           if (g.p3) {
-            const float a[4] = {fsc.x, fsc.y, fsc.z, fsc.w}, s[4] = {fsh.x, fsh.y, fsh.z, fsh.w};
+            float4 fr = fsc, fh = fsh;
+            if (g.film_bs) {                           // one noise level per sample: the row of this A row's sample
+              const float* fp = g.p3 + (int64_t)rb[i] * g.film_bs + ci;
+              fr = *reinterpret_cast<const float4*>(fp);
+              fh = *reinterpret_cast<const float4*>(fp + g.cin);
+            }
+            const float a[4] = {fr.x, fr.y, fr.z, fr.w}, s[4] = {fh.x, fh.y, fh.z, fh.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[e] = x[e] * (a[e] + 1.0f) + s[e];
           }

@@ -193,12 +193,19 @@ __global__ __launch_bounds__(256) void k_gemm3(GemmArgs g) {
         for (int e = 0; e < 4; ++e) x[e] = (x[e] - mean) * rstd * ga[e] + be[e];
       } else if constexpr (PRO == 2) {
         const float* st = g.p2 + (int64_t)rb[i] * g.groups * 2;
+        float fr[4] = {fa[0], fa[1], fa[2], fa[3]}, fh[4] = {fs[0], fs[1], fs[2], fs[3]};
+        if (g.film_bs) {                               // one noise level per sample: the row of this A row's sample (rb is clamped)
+          const float* fp = g.p3 + (int64_t)rb[i] * g.film_bs + ci;
+          const float4 rsc = *reinterpret_cast<const float4*>(fp), rsh = *reinterpret_cast<const float4*>(fp + g.cin);
+          fr[0] = rsc.x + 1.0f; fr[1] = rsc.y + 1.0f; fr[2] = rsc.z + 1.0f; fr[3] = rsc.w + 1.0f;
+          fh[0] = rsh.x; fh[1] = rsh.y; fh[2] = rsh.z; fh[3] = rsh.w;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float mean = st[grp[e] * 2], rstd = st[grp[e] * 2 + 1];
           const float sc = rstd * ga[e];
           x[e] = x[e] * sc + (be[e] - sc * mean);
-          x[e] = x[e] * fa[e] + fs[e];
+          x[e] = x[e] * fr[e] + fh[e];
         }
         if (g.pro_silu) {
 #pragma unroll

@@ -142,8 +142,10 @@ __global__ __launch_bounds__(TB) void k_gn_act(GnActArgs a) {
       const float g4[4] = {ga.x, ga.y, ga.z, ga.w}, b4[4] = {be.x, be.y, be.z, be.w};
       float f4[4] = {1.f, 1.f, 1.f, 1.f}, h4[4] = {0.f, 0.f, 0.f, 0.f};
       if (a.film) {
-        const float4 fs = *reinterpret_cast<const float4*>(a.film + c);
-        const float4 fh = *reinterpret_cast<const float4*>(a.film + a.ld + c);
+        // film_bs: floats between the rows of consecutive samples (0: one row shared by the batch -- sigma is a scalar)
+        const float* film = a.film + (int64_t)b * a.film_bs;
+        const float4 fs = *reinterpret_cast<const float4*>(film + c);
+        const float4 fh = *reinterpret_cast<const float4*>(film + a.ld + c);
         f4[0] = fs.x + 1.0f; f4[1] = fs.y + 1.0f; f4[2] = fs.z + 1.0f; f4[3] = fs.w + 1.0f;
         h4[0] = fh.x; h4[1] = fh.y; h4[2] = fh.z; h4[3] = fh.w;
       }
@@ -178,6 +180,7 @@ bool gn_act_eligible(int rows, int ld, int groups, int gsize) {
 hipError_t launch_gn_act(const GnActArgs& a, hipStream_t s) {
   if (a.batch <= 0) return hipSuccess;
   if (!gn_act_eligible(a.rows, a.ld, a.groups, a.gsize)) return hipErrorInvalidValue;
+  if (a.film_bs < 0 || a.film_bs % 4) return hipErrorInvalidValue;      // float4 loads of the per-sample FiLM rows
   if (a.x2 && (a.ca <= 0 || a.ca >= a.ld || a.ca % a.gsize || a.ca % 4 || (a.ld - a.ca) % 4)) return hipErrorInvalidValue;
   const int tpg = 256 / a.groups, per = (a.rows * (a.gsize / 4) + tpg - 1) / tpg;
   const int nf4 = a.rows * (a.gsize / 4);

@@ -310,13 +310,16 @@ __global__ __launch_bounds__(512) void k_rconv(RConvArgs a) {
           be[st][hf] = *reinterpret_cast<const float4*>(beta + c);
         }
       if (PRO == 2 && a.film) {
+        // film_bs: floats between the FiLM rows of consecutive samples (0: one row for the batch).  Lane i owns row mc, i.e. sample
+        // mc / T, and T divides 16: a shift
+        const float* film = a.film + (int64_t)(mc >> __builtin_ctz(a.T)) * a.film_bs;
 #pragma unroll
         for (int st = 0; st < NSTW; ++st)
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
             const int c = 32 * (st0 + st) + 8 * g + 4 * hf;
-            fs[st][hf] = *reinterpret_cast<const float4*>(a.film + c);
-            fsh[st][hf] = *reinterpret_cast<const float4*>(a.film + a.film_ld + c);
+            fs[st][hf] = *reinterpret_cast<const float4*>(film + c);
+            fsh[st][hf] = *reinterpret_cast<const float4*>(film + a.film_ld + c);
           }
       }
     }

@@ -249,6 +249,21 @@ __global__ __launch_bounds__(512) void k_resblock(ResBlockArgs a) {
   for (int it = 0; it < niter; ++it) {
     const int b = 2 * blockIdx.x + it * step + half;
     const bool live = b < a.B;
+    if (a.film && a.film_bs) {
+      // one noise level per sample (film_bs: floats between the samples' FiLM rows; 0 = the one row folded above, once per
+      // workgroup): this sample's row, folded into GroupNorm 2's gain / bias as there; the loads land under conv1
+      const float* film = a.film + (int64_t)(live ? b : a.B - 1) * a.film_bs;
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        const int c = 16 * rt + 4 * g;
+        const float4 g2 = *reinterpret_cast<const float4*>(a.vec + 2 * CIN + COUT + c);
+        const float4 be2 = *reinterpret_cast<const float4*>(a.vec + 2 * CIN + 2 * COUT + c);
+        const float4 fs = *reinterpret_cast<const float4*>(film + c), fh = *reinterpret_cast<const float4*>(film + a.film_ld + c);
+        fa[rt] = make_float4(g2.x * (fs.x + 1.0f), g2.y * (fs.y + 1.0f), g2.z * (fs.z + 1.0f), g2.w * (fs.w + 1.0f));
+        fb[rt] = make_float4(be2.x * (fs.x + 1.0f) + fh.x, be2.y * (fs.y + 1.0f) + fh.y, be2.z * (fs.z + 1.0f) + fh.z,
+                             be2.w * (fs.w + 1.0f) + fh.w);
+      }
+    }
     // ---- input rows (requested during the previous pass), GroupNorm 1 (one group: the whole sample), SiLU, split ----
     float xv[NV][4];
 #pragma unroll

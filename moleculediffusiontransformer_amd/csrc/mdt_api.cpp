@@ -96,6 +96,15 @@ static const char* validate(const mdt_op& o, int idx, char* buf, size_t nbuf) {
   auto space_ok = [](const mdt_ref& r) { return r.space >= 0 && r.space < MDT_SP_EXT0 + MDT_N_EXT; };
   for (const mdt_ref* r : {&o.a, &o.a2, &o.w, &o.bias, &o.out, &o.res, &o.p0, &o.p1, &o.p2, &o.p3})
     if (!space_ok(*r) || r->off < 0) return bad("bad operand reference");
+  // per-sample FiLM rows: only the kernels that address them by sample take a batch stride
+  if (o.film_bstride && (o.film_bstride < 0 || o.film_bstride % 4 || !o.p3.space ||
+                         !(o.kind == MDT_OP_GN_ACT || o.kind == MDT_OP_RESBLOCK ||
+                           (o.kind == MDT_OP_RCONV && !o.a2.space && o.i[MDT_R_GSIZE] > 0 && o.i[MDT_R_KSRC] <= 1 && !o.i[MDT_R_HALF_OUT] && o.i[MDT_R_NB] <= 1) ||
+                           (o.kind == MDT_OP_GEMM && o.i[MDT_G_PRO] == MDT_PRO_GROUPNORM && o.i[MDT_G_WFMT] == 0 &&
+                                                       o.i[MDT_G_M_MODE] == 0))))
+    return bad("film_bstride: a FiLM batch stride (a positive multiple of 4 floats, with p3 bound) is taken by MDT_OP_GN_ACT, "
+               "MDT_OP_RESBLOCK, a single-source MDT_OP_RCONV with its GroupNorm prologue and the GroupNorm prologue of an fp32 / split-bf16 "
+               "MDT_OP_GEMM over the batch (WFMT 0, M_MODE 0) only");
   switch (o.kind) {
     case MDT_OP_GEMM: {
       const int32_t* i = o.i;
@@ -392,7 +401,7 @@ int mdt_program_run(const mdt_program* p, const mdt_bindings* bd, int32_t B, int
         const int32_t* i = o.i;
         mdt::GemmArgs g;
         g.A = ptr(o.a); g.W = ptr(o.w); g.W_lo = ptr(o.a2); g.bias = ptr(o.bias); g.out = ptr(o.out); g.res = ptr(o.res);
-        g.p0 = ptr(o.p0); g.p1 = ptr(o.p1); g.p2 = ptr(o.p2); g.p3 = ptr(o.p3);
+        g.p0 = ptr(o.p0); g.p1 = ptr(o.p1); g.p2 = ptr(o.p2); g.p3 = ptr(o.p3); g.film_bs = o.film_bstride;
         const int batches = i[MDT_G_M_MODE] == 0 ? B : (i[MDT_G_M_MODE] == 1 ? n_shared_rows : 1);
         g.M = batches * i[MDT_G_R_OUT];
         g.r_out = i[MDT_G_R_OUT]; g.r_in = i[MDT_G_R_IN]; g.lda = i[MDT_G_LDA]; g.cin = i[MDT_G_CIN];
@@ -445,7 +454,7 @@ int mdt_program_run(const mdt_program* p, const mdt_bindings* bd, int32_t B, int
       }
       case MDT_OP_GN_ACT: {
         mdt::GnActArgs a;
-        a.x = ptr(o.a); a.y = ptr(o.out); a.gamma = ptr(o.p0); a.beta = ptr(o.p1); a.film = ptr(o.p3);
+        a.x = ptr(o.a); a.y = ptr(o.out); a.gamma = ptr(o.p0); a.beta = ptr(o.p1); a.film = ptr(o.p3); a.film_bs = o.film_bstride;
         a.batch = B; a.rows = o.i[MDT_N_ROWS]; a.ld = o.i[MDT_N_LD]; a.groups = o.i[MDT_N_GROUPS];
         a.gsize = o.i[MDT_N_GSIZE]; a.silu = o.i[MDT_N_SILU]; a.eps = o.f[MDT_NF_EPS]; a.out16 = o.i[MDT_N_OUT16];
         a.x2 = ptr(o.a2); a.ca = o.i[MDT_N_CA]; a.scale2 = o.f[MDT_NF_SCALE2]; a.raw16 = reinterpret_cast<unsigned short*>(ptr(o.p2));
@@ -455,7 +464,7 @@ int mdt_program_run(const mdt_program* p, const mdt_bindings* bd, int32_t B, int
       case MDT_OP_RCONV: {
         mdt::RConvArgs a;
         a.x = ptr(o.a); a.x2 = ptr(o.a2); a.w = ptr(o.w); a.bias = ptr(o.bias); a.res = ptr(o.res); a.out = ptr(o.out);
-        a.gamma = ptr(o.p0); a.beta = ptr(o.p1); a.film = ptr(o.p3); a.dbgbuf = ptr(o.p2);
+        a.gamma = ptr(o.p0); a.beta = ptr(o.p1); a.film = ptr(o.p3); a.film_bs = o.film_bstride; a.dbgbuf = ptr(o.p2);
         a.T = o.i[MDT_R_T]; a.M = B * a.T; a.C = o.i[MDT_R_C]; a.lda = o.i[MDT_R_LDA]; a.ldc = o.i[MDT_R_LDC];
         a.ldr = o.i[MDT_R_LDR]; a.taps = o.i[MDT_R_TAPS]; a.gsize = o.i[MDT_R_GSIZE]; a.silu = o.i[MDT_R_SILU];
         a.film_ld = o.i[MDT_R_FILM_LD]; a.eps = o.f[MDT_RF_EPS]; a.in_scale = o.f[MDT_RF_IN_SCALE];
@@ -466,7 +475,7 @@ int mdt_program_run(const mdt_program* p, const mdt_bindings* bd, int32_t B, int
       }
       case MDT_OP_RESBLOCK: {
         mdt::ResBlockArgs a;
-        a.x = ptr(o.a); a.out = ptr(o.out); a.w = ptr(o.w); a.vec = ptr(o.bias); a.film = ptr(o.p3);
+        a.x = ptr(o.a); a.out = ptr(o.out); a.w = ptr(o.w); a.vec = ptr(o.bias); a.film = ptr(o.p3); a.film_bs = o.film_bstride;
         a.B = B; a.T = o.i[MDT_K_T]; a.cin = o.i[MDT_K_CIN]; a.cout = o.i[MDT_K_COUT]; a.film_ld = o.i[MDT_K_FILM_LD];
         a.eps = o.f[MDT_KF_EPS]; a.wf32 = o.i[MDT_K_WF32];
         a.cin_real = o.i[MDT_K_CIN_REAL] > 0 ? o.i[MDT_K_CIN_REAL] : a.cin;

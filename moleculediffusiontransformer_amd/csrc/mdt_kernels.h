@@ -47,6 +47,7 @@ struct GemmArgs {
   const float* p1;  // bias of the norm
   const float* p2;  // GroupNorm stats [batch][G][2] = (mean, rstd)
   const float* p3;  // FiLM [scale(cin) | shift(cin)]
+  int film_bs = 0;  // GroupNorm prologue: floats between the FiLM rows of consecutive samples, 0 = one shared row (mdt_op.film_bstride)
   int M, r_out, r_in, lda, cin, taps, t_stride, t_dj, t_off;
   int N, ldc, o_rows, o_stride, o_off, ldr;
   int pro, groups, gsize, pro_silu, act, a_col, o_col;
@@ -157,6 +158,7 @@ struct GnActArgs {
   const float* gamma;
   const float* beta;
   const float* film;   // [scale(ld) | shift(ld)] or nullptr
+  int film_bs = 0;     // floats between the FiLM rows of consecutive samples; 0 = one row for the whole batch (mdt_op.film_bstride)
   int batch, rows, ld, groups, gsize, silu;
   float eps;
   int out16;   // 1: y is bf16 [rows][ld] (the A operand of a bf16 x bf16 GEMM)
@@ -181,6 +183,7 @@ struct RConvArgs {
   const float* gamma;  // GroupNorm gain / bias of the C input channels (gsize > 0)
   const float* beta;
   const float* film;   // [scale | shift] rows film_ld apart, or nullptr
+  int film_bs = 0;     // floats between the FiLM rows of consecutive samples, 0 = one shared row (mdt_op.film_bstride)
   const float* dbgbuf; // diagnostic stamps (tuning builds), normally nullptr
   int M, T, C, lda, lda2, ldc, ldr, taps, gsize, silu, film_ld;
   float eps, in_scale, in_scale2;
@@ -219,6 +222,7 @@ struct ResBlockArgs {
   const float* w;      // bf16 hi/lo MFMA fragments [step][row tile][hi | lo][64 lanes][8], steps: conv1 | conv2 | to_out
   const float* vec;    // gamma1[cin] | beta1[cin] | b1[cout] | gamma2[cout] | beta2[cout] | b2 + to_out bias [cout]
   const float* film;   // [scale | shift] rows film_ld apart, or nullptr
+  int film_bs = 0;     // floats between the FiLM rows of consecutive samples, 0 = one shared row (mdt_op.film_bstride)
   int B, T, cin, cout, film_ld;
   float eps;
   int wf32;            // 1: w = fp32 MFMA fragments [step][row tile][half][64 lanes][4], exact fp32 products (MDT_K_WF32)

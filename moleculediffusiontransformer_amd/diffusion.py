@@ -300,6 +300,39 @@ def scale_weights(sigma: Tensor, sigma_data: float) -> ScaleWeights:
 
 
 @dataclass(frozen=True)
+class RowWeights:
+    """get_scale_weights + loss_weight (diffusion.py:789-796, :816-818) for one sigma PER SAMPLE: fp32 CPU vectors of B entries."""
+    sigmas: Tensor
+    c_skip: Tensor
+    c_out: Tensor
+    c_in: Tensor
+    c_noise: Tensor
+    loss_weight: Tensor
+
+    def packed(self) -> Tensor:
+        """(6, B): sigma | c_in | c_skip | c_out | c_noise | loss_weight -- one upload per call."""
+        return torch.stack((self.sigmas, self.c_in, self.c_skip, self.c_out, self.c_noise, self.loss_weight))
+
+
+def scale_weights_rows(sigmas: Tensor, sigma_data: float) -> RowWeights:
+    """The per-sample form of scale_weights: the reference's fp32 tensor expressions on the whole sigma vector
+    (KDiffusion_mod.forward, diffusion.py:820-844).  Element i equals scale_weights(sigmas[i]) bit for bit: the vector is padded to
+    a multiple of 16 entries, so every element takes the vectorised path that scale_weights' 16-entry vector takes."""
+    sig = torch.as_tensor(sigmas, dtype=torch.float32).flatten().cpu()
+    n = sig.numel()
+    pad = torch.ones((n + 15) // 16 * 16, dtype=torch.float32)
+    pad[:n] = sig
+    c_noise = torch.log(pad) * 0.25
+    s = pad.view(-1, 1, 1)
+    c_skip = (sigma_data ** 2) / (s ** 2 + sigma_data ** 2)
+    c_out = s * sigma_data * (sigma_data ** 2 + s ** 2) ** -0.5
+    c_in = (s ** 2 + sigma_data ** 2) ** -0.5
+    weight = (pad ** 2 + sigma_data ** 2) * (pad * sigma_data) ** -2
+    return RowWeights(sig, c_skip.flatten()[:n].clone(), c_out.flatten()[:n].clone(), c_in.flatten()[:n].clone(),
+                      c_noise[:n].clone(), weight[:n].clone())
+
+
+@dataclass(frozen=True)
 class StepScalars:
     """Everything one ADPM2 step needs, as fp32-exact Python floats."""
     sigma: float

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from . import runtime as rt
-from .compiler import EXT_CTX, EXT_OUT, EXT_XBUF, EXT_XFLAGS, EXT_XIN, CompiledUNet
+from .compiler import EXT_CTX, EXT_FILM, EXT_OUT, EXT_XBUF, EXT_XFLAGS, EXT_XIN, CompiledUNet
 
 
 def _require_gpu(device: torch.device) -> None:
@@ -24,7 +24,8 @@ def _require_gpu(device: torch.device) -> None:
 
 
 class UNetEngine:
-    """Runs the `time`, `ctx`, `eval` and `eval_fixed` programs of a CompiledUNet for a batch."""
+    """Runs the `time`, `ctx`, `eval` and `eval_fixed` programs of a CompiledUNet for a batch -- or, for the per-row form
+    (CompiledUNet.rows: one noise level per sample), `time_rows`, `ctx`, `eval_rows` and `eval_rows_fixed`."""
 
     def __init__(self, compiled: CompiledUNet, device, use_graph: Optional[bool] = None):
         device = torch.device(device)
@@ -59,6 +60,7 @@ class UNetEngine:
         self.pred = None          # (B, L, Cp) token-major U-Net output
         self.pred_fixed = None
         self.xflags = self.xbuf = None
+        self.film = None          # per-row form: (B, ss_total) per-sample (scale | shift) rows
         self._graphs: Dict[str, torch.cuda.CUDAGraph] = {}
         self._time_rows = 0
         self._fixed_ready = False
@@ -76,6 +78,7 @@ class UNetEngine:
         self.pred = torch.zeros(B, c.length, c.in_pad, device=self.device)
         self.pred_fixed = torch.zeros(B, c.length, c.in_pad, device=self.device)
         self.xflags = self.xbuf = None
+        self.film = torch.empty(B, c.ss_total, device=self.device) if c.rows else None
         if c.xchg_tokens:
             # pair-split MDT_OP_TF256 (k_tf256.hip): per 32-row block two hand-off blocks of 32 x 256 fp32 in two parities, and
             # one 128-byte flag line per (row block, half) behind 64 diagnostic words.  The flags count hand-offs monotonically
@@ -91,6 +94,7 @@ class UNetEngine:
         b.weights, b.act, b.shr = rt.ptr(self.weights), rt.ptr(self.act), rt.ptr(self.shr)
         b.ext[EXT_XIN], b.ext[EXT_CTX], b.ext[EXT_OUT] = rt.ptr(xin), rt.ptr(ctx), rt.ptr(out)
         b.ext[EXT_XFLAGS], b.ext[EXT_XBUF] = rt.ptr(getattr(self, "xflags", None)), rt.ptr(getattr(self, "xbuf", None))
+        b.ext[EXT_FILM] = rt.ptr(getattr(self, "film", None))
         return b
 
     # A pair hand-off that runs into its time-out (a partner workgroup was never scheduled: the two workgroups of a pair must be
@@ -164,6 +168,8 @@ class UNetEngine:
         """Time mapping + all FiLM (scale, shift) rows for every U-Net call of a sampling run at once
         (rows are identical across the batch: sigma is a scalar broadcast by to_batch, diffusion.py:91-102)."""
         n = c_noise.numel()
+        if self.c.rows:
+            raise RuntimeError("this engine holds the per-row programs (one time value per sample): use prepare_time_rows / eval_rows")
         if n > self.c.max_time_rows:
             raise ValueError(f"{n} U-Net evaluations per call (timesteps = {n // 2 + 1}) exceed the time table of "
                              f"{self.c.max_time_rows} rows this engine was compiled with (at most "
@@ -183,6 +189,18 @@ class UNetEngine:
         # in the kernel trace, between the evaluation graphs; measured gain ~0.2 ms per 64-step call)
         base = self.shr.data_ptr()
         rt.check(rt.load_library().mdt_copy_f32(base + 4 * dst, base + 4 * src, c.ss_total, rt.current_stream()))
+
+    def prepare_time_rows(self, c_noise_rows: torch.Tensor) -> None:
+        """Per-row form: time mapping + all FiLM (scale, shift) rows for ONE evaluation with one c_noise value per sample of the
+        reserved batch (KDiffusion_mod.forward / denoise_fn(sigmas=(B,)), diffusion.py:798-844).  The table has B rows in
+        batch-scaled memory, so B is not limited by max_time_rows."""
+        if not self.c.rows:
+            raise RuntimeError("this engine holds the shared-row programs: compile_unet(rows=True) builds the per-row form")
+        if c_noise_rows.numel() != self.B:
+            raise ValueError(f"{c_noise_rows.numel()} time values for a reserved batch of {self.B}: the per-row form takes one per sample")
+        off = self.c.act_named["c_noise"] * self.B
+        self.act[off: off + self.B].copy_(c_noise_rows.to(device=self.device, dtype=torch.float32).flatten(), non_blocking=True)
+        self.programs["time_rows"].run(self._bind(), self.B, self.B)
 
     def prepare_context(self, embedding: torch.Tensor) -> None:
         """Hoisted cross-attention K/V of every layer for this batch's conditioning embedding."""
@@ -213,6 +231,16 @@ class UNetEngine:
         if dual and (self.B % 2 or (self.B // 2) % self.c.dual_multiple):
             raise ValueError(f"the dual guidance batch needs 2 x (a multiple of {self.c.dual_multiple}) samples: a cross-attention "
                              "workgroup must not straddle the conditional and the unconditional half")
+        return self._run_eval(name, out)
+
+    def eval_rows(self, fixed: bool = False) -> torch.Tensor:
+        """Per-row form: one U-Net evaluation of self.xin with the FiLM rows of prepare_time_rows -> self.pred (or
+        self.pred_fixed, against the fixed embedding).  Same HIP-graph policy and hand-off handling as eval()."""
+        if fixed:
+            self.prepare_fixed()
+        return self._run_eval("eval_rows_fixed" if fixed else "eval_rows", self.pred_fixed if fixed else self.pred)
+
+    def _run_eval(self, name: str, out: torch.Tensor) -> torch.Tensor:
         if not self.use_graph:
             self.programs[name].run(self._bind(xin=self.xin, out=out), self.B)
             return out

@@ -17,7 +17,7 @@ from . import ops, runtime as rt
 from .compiler import compile_unet
 from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler, KarrasSchedule,
                         LogNormalDistribution, NoiseSource, fused_sampler_kind, run_adpm2, run_adpm2_inpaint, run_aeuler,
-                        run_karras, scale_weights)
+                        run_karras, scale_weights, scale_weights_rows)
 from .engine import UNetEngine, _require_gpu
 from .modules import PositionalEncoding1D, UNetCFG1d
 from .netspec import forward_unet_config, inverse_unet_config
@@ -41,9 +41,11 @@ class KDiffusion_mod(nn.Module):
         self._owner = None
 
     def denoise_fn(self, x_noisy: Tensor, sigmas: Optional[Tensor] = None, sigma=None, *, embedding: Tensor,
-                   embedding_scale: float = 1.0) -> Tensor:
+                   embedding_scale: float = 1.0, batched: bool = False) -> Tensor:
         """diffusion.py:798-814: a scalar ``sigma`` (the sampling case) or one sigma per sample (``sigmas``, the
-        training-time form; samples sharing a sigma are evaluated together)."""
+        training-time form; samples sharing a sigma are evaluated together).  ``batched=True`` (with ``sigmas``): ONE evaluation
+        of the per-row program for the whole batch, whatever the number of distinct values -- equal to the default to rounding
+        (1e-6 class: the ResNet blocks run through other kernels), not bit for bit."""
         if sigma is None and sigmas is None:
             raise AssertionError("Either sigma or sigmas must be provided")       # to_batch, diffusion.py:97
         if sigma is not None:
@@ -51,6 +53,8 @@ class KDiffusion_mod(nn.Module):
         sig = torch.as_tensor(sigmas, dtype=torch.float32).flatten().cpu()
         if sig.numel() != x_noisy.shape[0]:
             raise AssertionError("sigmas must hold one value per sample")
+        if batched:
+            return self._owner._denoise_rows(x_noisy, sig, embedding, embedding_scale)
         out = torch.empty_like(x_noisy, dtype=torch.float32)
         for v in torch.unique(sig):
             rows = (sig == v).nonzero().flatten().to(x_noisy.device)
@@ -262,9 +266,11 @@ class _QMBase(nn.Module):
             self.kernel_choice = "wide" if self._wide(batch) else "narrow"
         return self.kernel_choice
 
-    def engine(self, device, n_ctx: Optional[int] = None, batch: Optional[int] = None) -> UNetEngine:
+    def engine(self, device, n_ctx: Optional[int] = None, batch: Optional[int] = None, rows: bool = False) -> UNetEngine:
         """Compiled-program engine for the current parameter values on `device` (rebuilt after an optimiser step or
-        load_state_dict), `n_ctx` conditioning tokens and the kernel choice that fits `batch` U-Net rows (see _wide)."""
+        load_state_dict), `n_ctx` conditioning tokens and the kernel choice that fits `batch` U-Net rows (see _wide).
+        ``rows``: the engine of the per-row programs (one noise level per sample: batched=True, eval_loss), compiled on first
+        use and kept next to the sampling engine -- a second copy of the packed weights that sampling-only users never pay."""
         device = torch.device(device)
         _require_gpu(device)
         n_ctx = self.unet.config.ctx_max_length if n_ctx is None else n_ctx
@@ -275,13 +281,16 @@ class _QMBase(nn.Module):
         if self._engine_key != key:                  # parameters changed: every cached engine is stale
             self._engines = {}
             self._engine_key = key
-        if wide not in self._engines:
+        slot = (wide, "rows") if rows else wide
+        if slot not in self._engines:
             sd = {k: v.detach().float().cpu() for k, v in self.unet.state_dict().items()}
-            compiled = compile_unet(self.unet.config, self.max_length, n_ctx, sd, gemm_mode=self.gemm_mode, tf256=wide)
-            self._engines[wide] = UNetEngine(compiled, device)
-        self._engine = self._engines[wide]
-        self._engine.sync_handoff_check = not self.defer_handoff_check
-        return self._engine
+            compiled = compile_unet(self.unet.config, self.max_length, n_ctx, sd, gemm_mode=self.gemm_mode, tf256=wide, rows=rows)
+            self._engines[slot] = UNetEngine(compiled, device)
+        eng = self._engines[slot]
+        eng.sync_handoff_check = not self.defer_handoff_check
+        if not rows:
+            self._engine = eng
+        return eng
 
     # ------------------------------------------------------------------ conditioning prelude
     def _embed(self, sequences: Tensor, device) -> Tensor:
@@ -308,13 +317,23 @@ class _QMBase(nn.Module):
     def _fused_adapter(self, kwargs: dict, extra: dict) -> _FusedLoop:
         return _FusedLoop(self, kwargs, extra)
 
-    def _unet_call(self, x: Tensor, time, embedding: Tensor, embedding_scale: float = 1.0) -> Tensor:
+    def _unet_call(self, x: Tensor, time, embedding: Tensor, embedding_scale: float = 1.0, batched: bool = False) -> Tensor:
         """net(x, time, embedding=..., embedding_scale=...) (modules.py:1228-1255); x is (B, C, L) as in the reference,
-        ``time`` a scalar or one value per row (rows sharing a time value are evaluated together)."""
+        ``time`` a scalar or one value per row (rows sharing a time value are evaluated together; ``batched=True``: all rows in
+        ONE evaluation of the per-row program)."""
         t = torch.as_tensor(time, dtype=torch.float32).flatten().cpu()
         B = x.shape[0]
         if t.numel() not in (1, B):
             raise ValueError(f"time must be a scalar or hold one value per sample (got {t.numel()} for batch {B})")
+        if batched:
+            device = x.device
+            _require_gpu(device)
+            eng = self.engine(device, embedding.shape[1], B, rows=True)
+            with torch.no_grad():
+                xin = torch.ops.mdt.precond_in(x, 1.0, eng.c.in_pad)
+                pred = torch.ops.mdt.unet_eval_rows(xin, embedding, t.expand(B).to(device), float(embedding_scale),
+                                                    ops.register_engine(eng))
+                return pred[:, :, :x.shape[1]].transpose(1, 2).contiguous()
         if t.numel() > 1 and not bool((t == t[0]).all()):
             out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
             for v in torch.unique(t):
@@ -341,6 +360,58 @@ class _QMBase(nn.Module):
             xin = torch.ops.mdt.precond_in(x_noisy, w.c_in, eng.c.in_pad)
             pred = torch.ops.mdt.unet_eval(xin, embedding, w.c_noise, float(embedding_scale), ops.register_engine(eng))
             return torch.ops.mdt.precond_out(x_noisy, pred, w.c_skip, w.c_out, float(self.diffusion.diffusion.dynamic_threshold))
+
+    def _denoise_rows(self, x_noisy: Tensor, sigmas: Tensor, embedding: Tensor, embedding_scale: float = 1.0) -> Tensor:
+        """KDiffusion_mod.denoise_fn with one sigma per sample (diffusion.py:798-814) as ONE per-row evaluation: the per-sample
+        coefficients are computed on the host in the reference's fp32 expressions and uploaded once."""
+        device = x_noisy.device
+        _require_gpu(device)
+        B = x_noisy.shape[0]
+        eng = self.engine(device, embedding.shape[1], B, rows=True)
+        w = scale_weights_rows(sigmas, self.diffusion.diffusion.sigma_data).packed().to(device)
+        with torch.no_grad():
+            xin = torch.ops.mdt.precond_in_rows(x_noisy, w[1], eng.c.in_pad)
+            pred = torch.ops.mdt.unet_eval_rows(xin, embedding, w[4], float(embedding_scale), ops.register_engine(eng))
+            return torch.ops.mdt.precond_out_rows(x_noisy, pred, w[2], w[3], float(self.diffusion.diffusion.dynamic_threshold))
+
+    def _loss_target(self, output: Tensor) -> Tensor:
+        """What forward() hands to the diffusion as the clean sample (the Analog* wrappers slice and pad `output`)."""
+        return output
+
+    def eval_loss(self, sequences, output, device, *, sigmas: Optional[Tensor] = None, noise: Optional[Tensor] = None,
+                  seed: Optional[int] = None, per_sample: bool = False) -> Tensor:
+        """The value of ``forward(sequences, output)`` -- conditioning prelude + KDiffusion_mod.forward (diffusion.py:820-844) at
+        embedding_scale 1, honouring ``dynamic_threshold`` -- computed under no_grad on the MI355X kernels: noising, ONE per-row
+        U-Net evaluation, fused clip + weighted MSE.  Returns a 0-dim tensor on ``device``, or with ``per_sample`` the (B,)
+        weighted losses whose mean it is.
+
+        ``sigmas`` (B,) / ``noise`` (B, C, L): given, or drawn from torch's global CPU generator in the reference's order (sigmas,
+        diffusion.py:824, then noise, :828), so that under one torch.manual_seed the value is forward()'s of a CPU copy of the
+        model.  ``seed`` (without ``noise``): the counter-based device generator keyed by (seed, sample index) instead.
+        An empty batch raises ValueError (the reference's mean over no samples is nan).  There is no CPU fallback."""
+        device = torch.device(device)
+        _require_gpu(device)
+        kd = self.diffusion.diffusion
+        with torch.no_grad():
+            x0 = self._loss_target(output.detach()).float()
+            B = x0.shape[0]
+            if B == 0:
+                raise ValueError("eval_loss needs at least one sample")
+            if tuple(x0.shape[1:]) != (self.pred_dim, self.max_length):
+                raise ValueError(f"output is {tuple(x0.shape)}, the model diffuses (B, {self.pred_dim}, {self.max_length})")
+            if sigmas is None:
+                sigmas = kd.sigma_distribution(num_samples=B)
+            if noise is None and seed is None:
+                noise = torch.randn(x0.shape, dtype=torch.float32)
+            w = scale_weights_rows(sigmas, kd.sigma_data)
+            if w.sigmas.numel() != B:
+                raise AssertionError("sigmas must hold one value per sample")
+            emb = self._embed(sequences, device)
+            eng = self.engine(device, emb.shape[1], B, rows=True)
+            nz = None if noise is None else noise.detach().to(device=device, dtype=torch.float32)
+            losses = torch.ops.mdt.eval_loss(x0.to(device), nz, emb, w.packed().to(device), ops.register_engine(eng),
+                                             float(kd.dynamic_threshold), int(seed or 0), 0)
+            return losses if per_sample else losses.mean()
 
     # ------------------------------------------------------------------ public API (reference signatures)
     def forward(self, sequences, output):

@@ -44,14 +44,19 @@ class _AnalogBase(_QMBase):
         return sparse_unet_config(pred_dim, channels, ctx_features, ctx_max_length, patch_size=self._patch,
                                   num_blocks=self._blocks)
 
+    def _loss_target(self, output):
+        """The clean sample of forward() (and of eval_loss(), generative.py): xyz rows (and the max_neighbors neighbour rows with
+        predict_neighbors) padded to max_length."""
+        xyz = pad_sequence(output[:, 1:4, :], self.max_length)
+        if self.predict_neighbors:
+            xyz = torch.cat((xyz, pad_sequence(output[:, 4:4 + max_neighbors, :], self.max_length)), 1)
+        return xyz
+
     def forward(self, sequences, output):
         """AnalogDiffusionSparse.forward (graphmodel.py:316-353): xyz rows (and the max_neighbors neighbour rows with
         predict_neighbors) padded to max_length, then the diffusion loss on the conditioning embedding."""
         from .train import conditioning_embedding
-        xyz = pad_sequence(output[:, 1:4, :], self.max_length)
-        if self.predict_neighbors:
-            xyz = torch.cat((xyz, pad_sequence(output[:, 4:4 + max_neighbors, :], self.max_length)), 1)
-        return self.diffusion(xyz, embedding=conditioning_embedding(self, sequences))
+        return self.diffusion(self._loss_target(output), embedding=conditioning_embedding(self, sequences))
 
     def sample(self, sequences, device, cond_scale=7.5, timesteps=100, clamp=False, *, noise=None, trace=None, timer=None,
                sampler=None, sigma_schedule=None):
@@ -80,6 +85,9 @@ class AnalogDiffusionFull(_AnalogBase):
         cat(xyz rows, neighbour rows), without it the packed `output` goes to the diffusion as it is (node-number row
         included), exactly as the reference does."""
         from .train import conditioning_embedding
+        return self.diffusion(self._loss_target(output), embedding=conditioning_embedding(self, sequences))
+
+    def _loss_target(self, output):
         if self.predict_neighbors:
             output = torch.cat((output[:, 1:4, :], output[:, 4:4 + self.max_length, :]), 1)
-        return self.diffusion(output, embedding=conditioning_embedding(self, sequences))
+        return output

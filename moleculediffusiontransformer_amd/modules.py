@@ -77,11 +77,14 @@ class UNetCFG1d(ParamNode):
         attach_parameters(self, unet_manifest(config))
         self._evaluator = None      # set by the owning QMDiffusion*/KDiffusion_mod
 
-    def forward(self, x, time, *, embedding, embedding_scale: float = 1.0, **kwargs):
+    def forward(self, x, time, *, embedding, embedding_scale: float = 1.0, batched: bool = False, **kwargs):
+        """``batched=True`` with one time value per row: ONE evaluation of the per-row program instead of one per distinct value."""
         if kwargs:
             raise TypeError(f"unsupported arguments: {sorted(kwargs)}")
         if self._evaluator is None:
             raise RuntimeError("this U-Net is not attached to a QMDiffusion / QMDiffusionForward model")
+        if batched:
+            return self._evaluator(x, time, embedding, embedding_scale, batched=True)
         return self._evaluator(x, time, embedding, embedding_scale)
 
 

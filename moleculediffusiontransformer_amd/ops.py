@@ -18,6 +18,9 @@ fake / meta tensors).
     sample              DiffusionSampler.forward + ADPM2Sampler.forward, the whole loop (diffusion.py:577-591, :517-524)
     sample_with         the same with the sampler chosen: ADPM2Sampler, AEulerSampler (:476-483) or KarrasSampler (:437-453)
     all_gather_samples  the one collective of a sharded call (RCCL all_gather_into_tensor)
+    precond_in_rows / precond_out_rows   the denoise scaling with ONE coefficient per sample (denoise_fn(sigmas=(B,)))
+    unet_eval_rows      net(x, time=(B,), ...) as ONE evaluation: one time-mapping / FiLM row per sample
+    eval_loss           KDiffusion_mod.forward's value per sample (diffusion.py:820-844): noising, one per-row evaluation, fused loss
 """
 from __future__ import annotations
 
@@ -405,6 +408,149 @@ def unet_eval(xin: Tensor, embedding: Tensor, c_noise: float, embedding_scale: f
 @unet_eval.register_fake
 def _(xin, embedding, c_noise, embedding_scale, handle):
     return xin.new_empty(xin.shape, dtype=torch.float32)
+
+
+def _rows_engine(handle: int, dev, what: str):
+    eng = _engine(handle)
+    if eng.device != dev:
+        raise RuntimeError(f"{what}: engine lives on {eng.device}, tensors on {dev}")
+    if not eng.c.rows:
+        raise RuntimeError(f"{what}: the handle names an engine of the shared-row programs; the per-row form is compiled with "
+                           "compile_unet(rows=True) (model.engine(device, n_ctx, batch, rows=True))")
+    return eng
+
+
+def _eval_rows(lib, eng, embedding: Tensor, c_noise: Tensor, embedding_scale: float) -> Tensor:
+    """eng.xin holds the network input of the reserved batch: context, per-sample time rows, one evaluation (two + the guidance
+    mix for embedding_scale != 1) -> eng.pred."""
+    eng.prepare_context(embedding)
+    eng.prepare_time_rows(c_noise)
+    eng.handoff_check()
+    pred = eng.eval_rows(False)
+    if embedding_scale != 1.0:
+        um = eng.eval_rows(True)
+        rt.check(lib.mdt_cfg_mix(rt.ptr(pred), rt.ptr(um), rt.ptr(pred), float(embedding_scale), pred.numel(), rt.current_stream()))
+    return pred
+
+
+@custom_op("mdt::precond_in_rows", mutates_args=())
+def precond_in_rows(x: Tensor, c_in: Tensor, Cp: int) -> Tensor:
+    """xin[b] = c_in[b] * x[b], token-major and padded (diffusion.py:810 with one sigma per sample)."""
+    dev = _hip(x, c_in)
+    lib = rt.load_library()
+    x, c_in = _f32c(x), _f32c(c_in).flatten()
+    B, C, L = x.shape
+    if Cp < C or Cp % 16 or c_in.numel() != B:
+        raise RuntimeError(f"mdt::precond_in_rows: Cp={Cp} must be a multiple of 16 and >= C={C}, c_in must hold B={B} values")
+    out = torch.zeros(B, L, Cp, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_precond_in_rows(rt.ptr(x), rt.ptr(out), rt.ptr(c_in), B, C, L, Cp, rt.current_stream()))
+    return out
+
+
+@precond_in_rows.register_fake
+def _(x, c_in, Cp):
+    return x.new_empty(x.shape[0], x.shape[2], Cp, dtype=torch.float32)
+
+
+@custom_op("mdt::precond_out_rows", mutates_args=())
+def precond_out_rows(x: Tensor, pred: Tensor, c_skip: Tensor, c_out: Tensor, dynamic_threshold: float = 0.0) -> Tensor:
+    """D[b] = clip(c_skip[b] x[b] + c_out[b] pred[b], dynamic_threshold) (diffusion.py:811-814 with one sigma per sample)."""
+    dev = _hip(x, pred, c_skip, c_out)
+    lib = rt.load_library()
+    x, pred, c_skip, c_out = _f32c(x), _f32c(pred), _f32c(c_skip).flatten(), _f32c(c_out).flatten()
+    B, C, L = x.shape
+    if pred.dim() != 3 or pred.shape[0] != B or pred.shape[1] != L or pred.shape[2] < C:
+        raise RuntimeError(f"mdt::precond_out_rows: pred {tuple(pred.shape)} is not token-major (B, L, Cp) for x {tuple(x.shape)}")
+    if c_skip.numel() != B or c_out.numel() != B:
+        raise RuntimeError(f"mdt::precond_out_rows: c_skip / c_out must hold B={B} values")
+    out = torch.empty_like(x)
+    if B:
+        with torch.cuda.device(dev):
+            ds = None
+            if dynamic_threshold:
+                ds = torch.empty(B, device=dev)
+                rt.check(lib.mdt_dyn_scale_rows(rt.ptr(x), rt.ptr(pred), rt.ptr(ds), rt.ptr(c_skip), rt.ptr(c_out),
+                                                float(dynamic_threshold), B, C, L, pred.shape[2], rt.current_stream()))
+            rt.check(lib.mdt_precond_out_rows(rt.ptr(x), rt.ptr(pred), rt.ptr(out), rt.ptr(c_skip), rt.ptr(c_out), B, C, L,
+                                              pred.shape[2], rt.ptr(ds), rt.current_stream()))
+    return out
+
+
+@precond_out_rows.register_fake
+def _(x, pred, c_skip, c_out, dynamic_threshold=0.0):
+    return x.new_empty(x.shape, dtype=torch.float32)
+
+
+@custom_op("mdt::unet_eval_rows", mutates_args=())
+def unet_eval_rows(xin: Tensor, embedding: Tensor, c_noise: Tensor, embedding_scale: float, handle: int) -> Tensor:
+    """mdt::unet_eval with one time value per sample: xin (B, L, Cp), embedding (B, n, F), c_noise (B,); ONE evaluation of the
+    per-row program whatever the number of distinct values.  `handle` names an engine of the per-row form."""
+    dev = _hip(xin, embedding, c_noise)
+    lib = rt.load_library()
+    eng = _rows_engine(handle, dev, "mdt::unet_eval_rows")
+    xin = _f32c(xin)
+    B = xin.shape[0]
+    if tuple(xin.shape[1:]) != (eng.c.length, eng.c.in_pad):
+        raise RuntimeError(f"mdt::unet_eval_rows: xin {tuple(xin.shape)} is not (B, {eng.c.length}, {eng.c.in_pad})")
+    if c_noise.numel() != B:
+        raise RuntimeError(f"mdt::unet_eval_rows: c_noise holds {c_noise.numel()} values for a batch of {B}")
+    if B == 0:
+        return torch.empty_like(xin)
+    with torch.no_grad(), torch.cuda.device(dev):
+        eng.reserve(B)
+        eng.xin.copy_(xin)
+        out = _eval_rows(lib, eng, embedding, c_noise, float(embedding_scale)).clone()
+        eng.note_handoff()
+        return out
+
+
+@unet_eval_rows.register_fake
+def _(xin, embedding, c_noise, embedding_scale, handle):
+    return xin.new_empty(xin.shape, dtype=torch.float32)
+
+
+@custom_op("mdt::eval_loss", mutates_args=())
+def eval_loss(x0: Tensor, noise: Optional[Tensor], embedding: Tensor, coef: Tensor, handle: int, dynamic_threshold: float,
+              seed: int, sample0: int) -> Tensor:
+    """KDiffusion_mod.forward's per-sample weighted losses (diffusion.py:820-844) on the kernels: x0 (B, C, L) the clean target,
+    noise (B, C, L) or None (counter-based generator keyed by (seed, sample0 + b)), embedding (B, n, F), coef (6, B) = sigma | c_in |
+    c_skip | c_out | c_noise | loss_weight (diffusion.RowWeights.packed()).  Returns (B,) = loss_weight * mean((D - x0)^2)."""
+    dev = _hip(x0, noise, embedding, coef)
+    lib = rt.load_library()
+    eng = _rows_engine(handle, dev, "mdt::eval_loss")
+    x0, coef = _f32c(x0), _f32c(coef)
+    nz = None if noise is None else _f32c(noise)
+    B, C, L = x0.shape
+    Cp = eng.c.in_pad
+    if L != eng.c.length or C > Cp or tuple(coef.shape) != (6, B) or (nz is not None and nz.shape != x0.shape):
+        raise RuntimeError(f"mdt::eval_loss: x0 {tuple(x0.shape)} / noise / coef {tuple(coef.shape)} do not fit (B, C <= {Cp}, "
+                           f"{eng.c.length}) and (6, B)")
+    loss = torch.empty(B, device=dev)
+    if B == 0:
+        return loss
+    sigma, c_in, c_skip, c_out, c_noise, weight = (coef[k] for k in range(6))
+    with torch.no_grad(), torch.cuda.device(dev):
+        eng.reserve(B)
+        x_noisy = torch.empty_like(x0)
+        rt.check(lib.mdt_noise_in_rows(rt.ptr(x0), rt.ptr(nz), rt.ptr(sigma), rt.ptr(c_in), rt.ptr(x_noisy), rt.ptr(eng.xin),
+                                       int(seed), 0, int(sample0), B, C, L, Cp, rt.current_stream()))
+        pred = _eval_rows(lib, eng, embedding, c_noise, 1.0)
+        ds = None
+        if dynamic_threshold:
+            ds = torch.empty(B, device=dev)
+            rt.check(lib.mdt_dyn_scale_rows(rt.ptr(x_noisy), rt.ptr(pred), rt.ptr(ds), rt.ptr(c_skip), rt.ptr(c_out),
+                                            float(dynamic_threshold), B, C, L, Cp, rt.current_stream()))
+        rt.check(lib.mdt_loss_rows(rt.ptr(x0), rt.ptr(x_noisy), rt.ptr(pred), rt.ptr(c_skip), rt.ptr(c_out), rt.ptr(weight),
+                                   rt.ptr(ds), rt.ptr(loss), B, C, L, Cp, rt.current_stream()))
+        eng.note_handoff()
+    return loss
+
+
+@eval_loss.register_fake
+def _(x0, noise, embedding, coef, handle, dynamic_threshold, seed, sample0):
+    return x0.new_empty(x0.shape[0], dtype=torch.float32)
 
 
 @custom_op("mdt::sample", mutates_args=())

@@ -52,7 +52,7 @@ class MdtRef(C.Structure):
 
 
 class MdtOp(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32),
+    _fields_ = [("kind", C.c_int32), ("film_bstride", C.c_int32),      # (floats between per-sample FiLM rows; 0 = one shared row)
                 ("a", MdtRef), ("a2", MdtRef), ("w", MdtRef), ("bias", MdtRef), ("out", MdtRef),
                 ("res", MdtRef), ("p0", MdtRef), ("p1", MdtRef), ("p2", MdtRef), ("p3", MdtRef),
                 ("i", C.c_int32 * 24), ("f", C.c_float * 8)]
@@ -80,6 +80,11 @@ SYMBOLS = {
     "mdt_precond_in": (_I, [_P, _P, _F, _I, _I, _I, _I, _P]),
     "mdt_precond_out": (_I, [_P, _P, _P, _F, _F, _I, _I, _I, _I, _P, _P]),
     "mdt_dyn_scale": (_I, [_P, _P, _P, _F, _F, _F, _I, _I, _I, _I, _P]),
+    "mdt_noise_in_rows": (_I, [_P, _P, _P, _P, _P, _P, _U64, _U32, _L, _I, _I, _I, _I, _P]),
+    "mdt_precond_in_rows": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "mdt_precond_out_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "mdt_dyn_scale_rows": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
+    "mdt_loss_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "mdt_cfg_mix": (_I, [_P, _P, _P, _F, _L, _P]),
     "mdt_adpm2_mid": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P]),
     "mdt_adpm2_next": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P, _P, _P]),

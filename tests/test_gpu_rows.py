@@ -1,0 +1,486 @@
+"""-m gpu: the per-row evaluation form (one noise level per sample) -- net(batched=True), denoise_fn(sigmas=, batched=True) and
+eval_loss() against the reference's golden vectors and against train.py on the CPU, in both product modes.
+
+Tolerances are the project's own: 5e-5 on single evaluations, 1e-4 on what the sampler / the objective consumes
+(tests/test_gpu_parity.py); the bounds on the loss are derived from the 1e-4 contract on the denoised tensor D (see each test).
+"""
+import pytest
+import torch
+
+from conftest import load_golden
+from gpu_util import DEV, make_model, ref, rnd
+from helpers import to_t
+from moleculediffusiontransformer_amd import runtime as rt
+from moleculediffusiontransformer_amd.diffusion import scale_weights_rows
+from moleculediffusiontransformer_amd.engine import UNetEngine
+from moleculediffusiontransformer_amd.synth import make_synth_model
+
+pytestmark = pytest.mark.gpu
+W, A, S = rt.SP_WEIGHT, rt.SP_ACT, rt.SP_SHR
+CASES7 = ["tiny", "pd22", "cfg3", "cfg1", "nb", "sparse", "full"]
+
+
+@pytest.fixture(scope="module", params=["bf16x3", "f32"])
+def models(request):
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            cache[case] = make_model(case)
+            cache[case].gemm_mode = request.param
+        return cache[case]
+    get.mode = request.param
+    return get
+
+
+def _cpu_denoise(m_cpu, x_noisy, sigmas, emb):
+    """KDiffusion_mod.denoise_fn with one sigma per sample as train.py states it (diffusion.py:798-814), on the CPU."""
+    from moleculediffusiontransformer_amd.train import _clip, unet_cfg_forward
+    kd = m_cpu.diffusion.diffusion
+    sd = kd.sigma_data
+    sp = sigmas.view(-1, 1, 1)
+    c_noise = torch.log(sigmas) * 0.25
+    c_skip = (sd ** 2) / (sp ** 2 + sd ** 2)
+    c_out = sp * sd * (sd ** 2 + sp ** 2) ** -0.5
+    c_in = (sp ** 2 + sd ** 2) ** -0.5
+    with torch.no_grad():
+        pred = unet_cfg_forward(m_cpu.unet, c_in * x_noisy, c_noise, emb)
+        return _clip(c_skip * x_noisy + c_out * pred, float(kd.dynamic_threshold))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5, 6
+@pytest.mark.parametrize("case", CASES7)
+def test_batched_net_and_denoise_match_reference(models, case):
+    g = load_golden(f"{case}_unet.npz")
+    m = models(case)
+    emb = m._embed(to_t(g["seq"]), DEV)
+    x, t = to_t(g["x"]).to(DEV), to_t(g["t"])
+    B = x.shape[0]
+    assert len(set(t.tolist())) == B                                # the golden batch holds a different time per row
+    y = m.unet(x, t, embedding=emb, embedding_scale=1.0, batched=True)
+    err = (y.cpu() - to_t(g["y_scale1"])).abs().max()
+    print(f"{case} {models.mode} net(batched) scale 1: {err:.3e}")
+    assert err < 5e-5
+    y = m.unet(x, t, embedding=emb, embedding_scale=7.5, batched=True)
+    err = (y.cpu() - to_t(g["y_scale7p5"])).abs().max()
+    print(f"{case} {models.mode} net(batched) scale 7.5: {err:.3e}")
+    assert err < (1e-4 if models.mode == "f32" else 4e-4)          # the bounds of test_gpu_parity.py for the one-row calls
+    kd = m.diffusion.diffusion
+    d = kd.denoise_fn(x * 2.5, sigmas=torch.full((B,), 2.5), embedding=emb, embedding_scale=1.0, batched=True)
+    err = (d.cpu() - to_t(g["denoise_sigma2p5"])).abs().max()
+    print(f"{case} {models.mode} denoise(batched) sigma 2.5: {err:.3e}")
+    assert err < 5e-5
+    d = kd.denoise_fn(x * 2.5, sigmas=torch.full((B,), 2.5), embedding=emb, embedding_scale=7.5, batched=True)
+    gd = load_golden("guided_denoise.npz")[f"{case}_denoise_sigma2p5_scale7p5"]
+    err = (d.cpu() - to_t(gd)).abs().max()
+    print(f"{case} {models.mode} guided denoise(batched): {err:.3e}")
+    assert err < 1e-4
+    if models.mode == "f32":                                        # exact fp32 on every ring op of the per-row program too
+        wf = {rt.OP_TF128: rt.F_WF32, rt.OP_TF256: rt.F_WF32, rt.OP_RCONV: rt.R_WF32, rt.OP_TBLOCK: rt.B_WF32}
+        eng = m.engine(DEV, emb.shape[1], B, rows=True)
+        assert all(op.i[wf[op.kind]] == 1 for op in eng.c.programs["eval_rows"] if op.kind in wf)
+
+
+@pytest.mark.parametrize("case", ["tiny", "cfg1"])
+def test_batched_denoise_with_distinct_sigmas(models, case):
+    g = load_golden(f"{case}_unet.npz")
+    m = models(case)
+    emb = m._embed(to_t(g["seq"]), DEV)
+    x = to_t(g["x"]).to(DEV)
+    B = x.shape[0]
+    sig = torch.tensor([2.5, 0.7, 0.05, 1.3][:B])
+    kd = m.diffusion.diffusion
+    one = kd.denoise_fn(x, sigmas=sig, embedding=emb, batched=True)
+    many = kd.denoise_fn(x, sigmas=sig, embedding=emb)
+    # NOT bit-equal: the per-row program runs the ResNet blocks as GroupNorm passes + convolution GEMMs, the default program
+    # through its fused block kernels (other summation orders); both are within 5e-5 of the reference arithmetic
+    assert (one - many).abs().max() < 1e-4
+    want = _cpu_denoise(make_synth_model(case), x.cpu(), sig, emb.cpu())
+    e1, e2 = (one.cpu() - want).abs().max(), (many.cpu() - want).abs().max()
+    print(f"{case} {models.mode} distinct sigmas: batched {e1:.3e} serial {e2:.3e} apart {(one - many).abs().max():.3e}")
+    assert e1 < 5e-5 and e2 < 5e-5
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7
+def test_eval_loss_matches_the_reference_loss(models):
+    """tests/golden/train_loss.npz: the REAL reference's loss of the tiny model on fixed sigmas / noise, dynamic_threshold 0.0 and
+    0.9.  Bound: the contract on D is 1e-4; a worst-case perturbation of D by 1e-4 aligned with the residual moves these two losses
+    by 1.43e-4 / 1.53e-4 relative; 2e-4 is that with a 1.3x margin for the reduction order."""
+    g = load_golden("train_loss.npz")
+    m = models("tiny")
+    seq, x0 = to_t(g["seq"]), to_t(g["x0"])
+    got = {}
+    try:
+        for q in (0.0, 0.9):
+            m.diffusion.diffusion.dynamic_threshold = q
+            loss = m.eval_loss(seq, x0, DEV, sigmas=to_t(g["sigmas"]), noise=to_t(g["noise"]))
+            assert loss.dim() == 0 and loss.device.type == "cuda" and not loss.requires_grad
+            got[q] = float(loss)
+            want = float(g[f"loss_q{q}"])
+            print(f"eval_loss {models.mode} q={q}: {got[q]:.7g} reference {want:.7g} relative {abs(got[q] - want) / abs(want):.3e}")
+            assert abs(got[q] - want) < 2e-4 * abs(want), (q, got[q], want)
+            per = m.eval_loss(seq, x0, DEV, sigmas=to_t(g["sigmas"]), noise=to_t(g["noise"]), per_sample=True)
+            assert tuple(per.shape) == (3,) and torch.equal(per.mean(), loss)
+    finally:
+        m.diffusion.diffusion.dynamic_threshold = 0.0
+    assert abs(got[0.9] - got[0.0]) > 1                    # the quantile branch is really taken
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8
+def test_eval_loss_per_sample_against_train_py_at_cfg1(models):
+    """cfg1, B = 64, log-normal sigmas: every per-sample loss against train.py on the CPU.  With D' = D + e, |e| <= delta = 1e-4 (the
+    project's contract on D): |mean((D' - x0)^2) - mean((D - x0)^2)| <= 2 delta rms + delta^2 by Cauchy-Schwarz, rms the CPU's
+    root-mean-square residual of the sample; times the sample's loss weight."""
+    from moleculediffusiontransformer_amd.train import conditioning_embedding
+    m = models("cfg1")
+    mc = make_synth_model("cfg1")
+    B = 64
+    gen = torch.Generator().manual_seed(20240)
+    seq = torch.randn(B, 12, generator=gen)
+    x0 = (0.5 * torch.randn(B, 16, 64, generator=gen)).clamp(-1, 1)
+    sig = (-1.2 + 1.2 * torch.randn(B, generator=gen)).exp()
+    noise = torch.randn(B, 16, 64, generator=gen)
+    got = m.eval_loss(seq, x0, DEV, sigmas=sig, noise=noise, per_sample=True).cpu()
+    with torch.no_grad():
+        D = _cpu_denoise(mc, x0 + sig.view(-1, 1, 1) * noise, sig, conditioning_embedding(mc, seq))
+    mse = ((D - x0) ** 2).flatten(1).mean(1)
+    weight = (sig ** 2 + 0.1 ** 2) * (sig * 0.1) ** -2
+    want = mse * weight
+    delta = 1e-4
+    bound = weight * (2 * delta * mse.sqrt() + delta ** 2)
+    ratio = ((got - want).abs() / bound)
+    print(f"cfg1 per-sample {models.mode}: worst |delta| / bound {ratio.max():.3f} (sample {int(ratio.argmax())}), mean loss relative "
+          f"{abs(got.mean() - want.mean()) / want.mean():.3e}")
+    assert got.shape == want.shape and bool(((got - want).abs() <= bound).all()), ratio      # all 64 samples
+    assert abs(got.mean() - want.mean()) < 2e-4 * want.mean()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 9
+def test_eval_loss_draws_like_forward(models):
+    """sigmas then noise from torch's global CPU generator, in the reference's order and distributions: under one seed the value is
+    forward()'s of a CPU copy of the model."""
+    g = load_golden("train_loss.npz")
+    m, mc = models("tiny"), make_synth_model("tiny")
+    seq, x0 = to_t(g["seq"]), to_t(g["x0"])
+    for seed in (7, 1234):
+        torch.manual_seed(seed)
+        got = float(m.eval_loss(seq, x0, DEV))
+        torch.manual_seed(seed)
+        with torch.no_grad():
+            want = float(mc(seq, x0))
+        print(f"eval_loss vs forward {models.mode} seed {seed}: {got:.7g} {want:.7g}")
+        assert abs(got - want) < 2e-4 * abs(want)
+    # seed=: the counter-based device noise -- repeatable, and another stream than another seed's
+    sig = to_t(g["sigmas"])
+    a, b = m.eval_loss(seq, x0, DEV, sigmas=sig, seed=5, per_sample=True), m.eval_loss(seq, x0, DEV, sigmas=sig, seed=5, per_sample=True)
+    c = m.eval_loss(seq, x0, DEV, sigmas=sig, seed=6, per_sample=True)
+    assert torch.equal(a, b) and not torch.equal(a, c)
+    with pytest.raises(ValueError):
+        m.eval_loss(seq[:0], x0[:0], DEV)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 10
+def test_one_per_row_evaluation_for_any_number_of_sigmas(models, monkeypatch):
+    m = models("tiny")
+    B = 9
+    x = rnd(B, 16, 32, seed=3).to(DEV)
+    emb = m._embed(rnd(B, 12, seed=4), DEV)
+    sig = torch.linspace(0.05, 3.0, B)
+    calls = {"rows": 0, "shared": 0}
+    eval_rows, eval_ = UNetEngine.eval_rows, UNetEngine.eval
+
+    def count_rows(self, *a, **k):
+        calls["rows"] += 1
+        return eval_rows(self, *a, **k)
+
+    def count_shared(self, *a, **k):
+        calls["shared"] += 1
+        return eval_(self, *a, **k)
+    monkeypatch.setattr(UNetEngine, "eval_rows", count_rows)
+    monkeypatch.setattr(UNetEngine, "eval", count_shared)
+    kd = m.diffusion.diffusion
+    one = kd.denoise_fn(x, sigmas=sig, embedding=emb, batched=True)
+    assert calls == {"rows": 1, "shared": 0}
+    many = kd.denoise_fn(x, sigmas=sig, embedding=emb, batched=False)
+    assert calls == {"rows": 1, "shared": B}
+    assert (one - many).abs().max() < 1e-4
+    m.eval_loss(rnd(B, 12, seed=4), x.cpu().clamp(-1, 1), DEV)
+    assert calls == {"rows": 2, "shared": B}
+
+
+# ---------------------------------------------------------------------------------------------------------------- 11
+def test_more_rows_than_the_shared_time_table(models):
+    """B = 1030 > max_time_rows (1024): the per-row FiLM table lives in batch-scaled memory."""
+    m = models("tiny")
+    B = 1030
+    x = rnd(B, 16, 32, seed=5).to(DEV)
+    emb = m._embed(rnd(B, 12, seed=6), DEV)
+    sig = (-1.2 + 1.2 * rnd(B, seed=7)).exp()
+    kd = m.diffusion.diffusion
+    d = kd.denoise_fn(x, sigmas=sig, embedding=emb, batched=True)
+    alone = kd.denoise_fn(x[1024:], sigmas=sig[1024:], embedding=emb[1024:])
+    assert (d[1024:] - alone).abs().max() < 1e-4
+    assert torch.equal(d, kd.denoise_fn(x, sigmas=sig, embedding=emb, batched=True))        # two identical calls
+
+
+@pytest.mark.parametrize("case", ["tiny", "cfg1"])
+def test_per_sample_losses_do_not_depend_on_the_split(models, case):
+    """With the kernel choice pinned, the per-sample losses of a batch of 37 equal bit for bit those of its parts of 20 and 17 --
+    the shard invariance of the sampling programs holds for the per-row program and the loss kernel."""
+    m = models(case)
+    C, L = m.pred_dim, m.max_length
+    B = 37
+    seq, x0 = rnd(B, 12, seed=8), rnd(B, C, L, seed=9, scale=0.5).clamp(-1, 1)
+    sig, noise = (-1.2 + 1.2 * rnd(B, seed=10)).exp(), rnd(B, C, L, seed=11)
+    old = m.kernel_choice
+    m.pin_kernel_choice(B)
+    try:
+        whole = m.eval_loss(seq, x0, DEV, sigmas=sig, noise=noise, per_sample=True)
+        parts = torch.cat([m.eval_loss(seq[s], x0[s], DEV, sigmas=sig[s], noise=noise[s], per_sample=True)
+                           for s in (slice(0, 20), slice(20, 37))])
+        again = m.eval_loss(seq, x0, DEV, sigmas=sig, noise=noise, per_sample=True)
+    finally:
+        m.kernel_choice = old
+    print(f"{case} {models.mode} split: max |whole - parts| {(whole - parts).abs().max():.3e}")
+    assert torch.equal(whole, again)
+    assert torch.equal(whole, parts)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 12
+def _run_gpu(ops, weights, act, shr, B):
+    gw, ga, gs = weights.to(DEV), act.to(DEV), shr.to(DEV)
+    b = rt.MdtBindings()
+    b.weights, b.act, b.shr = rt.ptr(gw), rt.ptr(ga), rt.ptr(gs)
+    with torch.cuda.device(DEV):
+        rt.Program(ops).run(b, B, 0)
+        torch.cuda.synchronize()
+    return ga.cpu()
+
+
+@pytest.mark.parametrize("R,C,G,silu,eps", [(16, 128, 8, True, 1e-5), (4, 512, 8, True, 1e-5), (64, 16, 1, True, 1e-5),
+                                            (32, 512, 8, True, 1e-5),          # one workgroup per (sample, group)
+                                            (32, 1024, 8, False, 1e-5)])       # the 1024-thread form
+def test_gn_act_with_one_film_row_per_sample(R, C, G, silu, eps):
+    B = 5
+    weights = torch.cat([1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3)])
+    film = 0.3 * rnd(B, 2 * C, seed=9)
+    act = torch.cat([rnd(B * R * C, seed=4) * 1.5 + 0.3, torch.zeros(B * R * C)])
+
+    def op(stride):
+        o = rt.MdtOp()
+        o.kind = rt.OP_GN_ACT
+        o.a, o.out, o.p0, o.p1, o.p3 = ref(A, 0), ref(A, R * C), ref(W, 0), ref(W, C), ref(S, 0)
+        o.i[rt.N_ROWS], o.i[rt.N_LD], o.i[rt.N_GROUPS], o.i[rt.N_GSIZE], o.i[rt.N_SILU] = R, C, G, C // G, int(silu)
+        o.f[0] = eps
+        o.film_bstride = stride
+        return o
+    x = act[: B * R * C].view(B, R, C).transpose(1, 2)
+    gn = torch.nn.functional.group_norm(x, G, weights[:C], weights[C:], eps)
+
+    def want(f):                                     # f: (B, 2C) FiLM rows
+        h = gn * (f[:, :C].unsqueeze(-1) + 1) + f[:, C:].unsqueeze(-1)
+        return (torch.nn.functional.silu(h) if silu else h).transpose(1, 2)
+    got = _run_gpu([op(2 * C)], weights, act, film.flatten(), B)[B * R * C:].view(B, R, C)
+    assert (got - want(film)).abs().max() < 2e-5                       # test_gpu_ops.py's tolerance for this op
+    # stride 0 = the op as it was: every sample reads row 0 -- and equals, bit for bit, the strided op on five copies of row 0
+    shared = _run_gpu([op(0)], weights, act, film.flatten(), B)[B * R * C:].view(B, R, C)
+    assert (shared - want(film[:1].expand(B, -1))).abs().max() < 2e-5
+    copies = _run_gpu([op(2 * C)], weights, act, film[:1].expand(B, -1).contiguous().flatten(), B)[B * R * C:].view(B, R, C)
+    assert torch.equal(shared, copies)
+
+
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("R,C,G,N,real", [(16, 128, 8, 128, 128), (64, 32, 1, 32, 22), (5, 64, 4, 96, 64)])
+def test_groupnorm_prologue_with_one_film_row_per_sample(R, C, G, N, real, split):
+    """The GroupNorm + FiLM + SiLU prologue of MDT_OP_GEMM (exact fp32: k_gemm; split-bf16: k_gemm3) with a FiLM batch stride:
+    the blocks whose channel count is padded (`real` < C channels: gain / bias / weights zero on the padding) take it."""
+    from test_gpu_ops import _split_planes, gemm_op
+    B, taps, eps = 5, 3, 1e-5
+    K = taps * C
+    gs = real // G
+    w = rnd(N, K, seed=1, scale=K ** -0.5)
+    gain, bias = 1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3)
+    gain[real:], bias[real:] = 0.0, 0.0
+    w.view(N, taps, C)[:, :, real:] = 0.0
+    if split:
+        hi, lo = _split_planes(w)
+        wv = (hi.view(torch.bfloat16).float() + lo.view(torch.bfloat16).float()).view(N, K)
+        weights = torch.cat([hi, lo, gain, bias])
+        o_lo, o_g = hi.numel(), 2 * hi.numel()
+    else:
+        wv, weights, o_lo, o_g = w, torch.cat([w.view(-1), gain, bias]), None, N * K
+    film = 0.3 * rnd(B, 2 * C, seed=9)
+    xoff, stoff, ooff = 0, R * C, R * C + 64
+    act = torch.zeros(B * (R * C + 64 + R * N))
+    xin = rnd(B, R, C, seed=4) * 1.5 + 0.3
+    xin[:, :, real:] = 0.0
+    act[: B * R * C] = xin.flatten()
+
+    def ops(stride):
+        st = rt.MdtOp()
+        st.kind = rt.OP_GN_STATS
+        st.a, st.out = ref(A, xoff), ref(A, stoff)
+        st.i[rt.N_ROWS], st.i[rt.N_LD], st.i[rt.N_GROUPS], st.i[rt.N_GSIZE] = R, C, G, gs
+        st.f[0] = eps
+        g = gemm_op(a=ref(A, xoff), w=ref(W, 0), out=ref(A, ooff), p0=ref(W, o_g), p1=ref(W, o_g + C), p2=ref(A, stoff), p3=ref(S, 0),
+                    r_out=R, r_in=R, lda=C, cin=C, taps=taps, t_dj=1, t_off=-1, n=N, ldc=N, o_rows=R, pro=rt.PRO_GROUPNORM,
+                    groups=G, gsize=gs, pro_silu=1, eps=eps)
+        if split:
+            g.a2 = ref(W, o_lo)
+        g.film_bstride = stride
+        return [st, g]
+    x = xin[:, :, :real].transpose(1, 2)
+    gn = torch.nn.functional.group_norm(x, G, gain[:real], bias[:real], eps)
+
+    def want(f):
+        h = torch.nn.functional.silu(gn * (f[:, :real].unsqueeze(-1) + 1) + f[:, C: C + real].unsqueeze(-1))
+        return torch.nn.functional.conv1d(h, wv.view(N, taps, C)[:, :, :real].permute(0, 2, 1), padding=1).transpose(1, 2)
+    got = _run_gpu(ops(2 * C), weights, act, film.flatten(), B)[B * ooff:].view(B, R, N)
+    assert (got - want(film)).abs().max() < 5e-5                       # test_gpu_ops.py's tolerance for this prologue
+    shared = _run_gpu(ops(0), weights, act, film.flatten(), B)[B * ooff:].view(B, R, N)
+    assert (shared - want(film[:1].expand(B, -1))).abs().max() < 5e-5
+    copies = _run_gpu(ops(2 * C), weights, act, film[:1].expand(B, -1).contiguous().flatten(), B)[B * ooff:].view(B, R, N)
+    assert torch.equal(shared, copies)
+
+
+def test_per_sample_preconditioning_and_loss_kernels():
+    """mdt_noise_in_rows / mdt_precond_in_rows / mdt_precond_out_rows / mdt_dyn_scale_rows / mdt_loss_rows against the reference's
+    expressions in torch (train.py), B = 5 different noise levels; the counter-based noise does not depend on the split."""
+    from moleculediffusiontransformer_amd.train import _clip
+    lib = rt.load_library()
+    B, C, L, Cp = 5, 22, 32, 32
+    x0, noise = rnd(B, C, L, seed=1, scale=0.5).clamp(-1, 1), rnd(B, C, L, seed=2)
+    pred_cl = rnd(B, C, L, seed=3)
+    w = scale_weights_rows(torch.tensor([9.0, 1.0, 0.3, 0.05, 0.001]), 0.1)
+    sp = w.sigmas.view(-1, 1, 1)
+    x_noisy = x0 + sp * noise
+    cf = w.packed().to(DEV)
+    x0d, nzd = x0.to(DEV), noise.to(DEV)
+    pred = torch.zeros(B, L, Cp, device=DEV)
+    pred[:, :, :C] = pred_cl.transpose(1, 2).to(DEV)
+    with torch.cuda.device(DEV):
+        st = rt.current_stream()
+        xn, xin = torch.empty(B, C, L, device=DEV), torch.full((B, L, Cp), 7.0, device=DEV)
+        rt.check(lib.mdt_noise_in_rows(rt.ptr(x0d), rt.ptr(nzd), rt.ptr(cf[0]), rt.ptr(cf[1]), rt.ptr(xn), rt.ptr(xin),
+                                       0, 0, 0, B, C, L, Cp, st))
+        assert torch.equal(xn.cpu(), x_noisy)
+        assert torch.equal(xin[:, :, :C].cpu(), (w.c_in.view(-1, 1, 1) * x_noisy).transpose(1, 2)) and float(xin[:, :, C:].abs().max()) == 0
+        xin2 = torch.ops.mdt.precond_in_rows(xn, cf[1], Cp)
+        assert torch.equal(xin2, xin)
+        for q in (0.0, 0.9):
+            D = torch.ops.mdt.precond_out_rows(xn, pred, cf[2], cf[3], q)
+            want = _clip(w.c_skip.view(-1, 1, 1) * x_noisy + w.c_out.view(-1, 1, 1) * pred_cl, q)
+            assert (D.cpu() - want).abs().max() < 1e-6
+            ds = None
+            if q:
+                ds = torch.empty(B, device=DEV)
+                rt.check(lib.mdt_dyn_scale_rows(rt.ptr(xn), rt.ptr(pred), rt.ptr(ds), rt.ptr(cf[2]), rt.ptr(cf[3]), q, B, C, L, Cp, st))
+            loss = torch.empty(B, device=DEV)
+            rt.check(lib.mdt_loss_rows(rt.ptr(x0d), rt.ptr(xn), rt.ptr(pred), rt.ptr(cf[2]), rt.ptr(cf[3]), rt.ptr(cf[5]),
+                                       rt.ptr(ds), rt.ptr(loss), B, C, L, Cp, st))
+            lw = ((want - x0) ** 2).flatten(1).mean(1) * w.loss_weight
+            assert ((loss.cpu() - lw).abs() <= 1e-5 * lw.abs() + 1e-12).all(), (q, loss.cpu(), lw)
+        # counter-based noise: sample b of a batch starting at sample0 sees the stream of global sample sample0 + b
+        full, xi = torch.empty(B, C, L, device=DEV), torch.empty(B, L, Cp, device=DEV)
+        rt.check(lib.mdt_noise_in_rows(rt.ptr(x0d), 0, rt.ptr(cf[0]), rt.ptr(cf[1]), rt.ptr(full), rt.ptr(xi), 77, 0, 0, B, C, L, Cp, st))
+        tail, x0t, sgt, cit = torch.empty(2, C, L, device=DEV), x0d[3:].contiguous(), cf[0][3:].contiguous(), cf[1][3:].contiguous()
+        rt.check(lib.mdt_noise_in_rows(rt.ptr(x0t), 0, rt.ptr(sgt), rt.ptr(cit),
+                                       rt.ptr(tail), rt.ptr(xi), 77, 0, 3, 2, C, L, Cp, st))
+        torch.cuda.synchronize()
+        assert torch.equal(full[3:], tail)
+        z = ((full.cpu() - x0) / sp).double()
+        assert abs(z.mean()) < 0.1 and abs(z.var() - 1) < 0.1
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "f32"])
+@pytest.mark.parametrize("C,T,B,gsize", [(128, 16, 5, 16), (256, 4, 5, 32), (256, 4, 37, 32), (256, 1, 70, 32), (128, 2, 5, 4)])
+def test_row_stationary_conv_with_one_film_row_per_sample(C, T, B, gsize, mode):
+    """k_rconv: lane i owns a row, i.e. sample row / T -- a workgroup's 32 / 64 rows hold 2 .. 64 samples with their own FiLM rows.
+    Against torch's group_norm / conv1d at test_gpu_ops.py's tolerance for this op; stride 0 equals the strided op on copies of
+    row 0 bit for bit."""
+    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
+    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
+    comp = UNetCompiler(inverse_unet_config(16, 64, 128, 12), 64, 12, {}, gemm_mode=mode)
+    taps, eps = 3, 1e-5
+    w = rnd(C, C, taps, seed=1, scale=(C * taps) ** -0.5)
+    gb = torch.cat([1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3), 0.1 * rnd(C, seed=5)])   # gain | beta | conv bias
+    g_off = comp.W.add("gb", gb)
+    x, out, other = Ten(A, 0, T, C), Ten(A, T * C, T, C), Ten(A, 2 * T * C, T, C)
+    comp.rconv(x, w, "w", out, taps=taps, bias_off=g_off + 2 * C, res=other, gn=(g_off, g_off + C, gsize, eps, True))
+    op = comp.ops[0]
+    op.p3 = ref(S, 0)
+    film = 0.3 * rnd(B, 2 * C, seed=9)
+    act = torch.cat([rnd(B * T * C, seed=4) * 1.5 + 0.3, rnd(B * T * C, seed=6), rnd(B * T * C, seed=7)])
+    weights = comp.W.pack()
+
+    def run(stride, f):
+        op.film_bstride = stride
+        return _run_gpu([op], weights, act, f.contiguous().flatten(), B)[B * T * C: 2 * B * T * C].view(B, T, C)
+    gn = torch.nn.functional.group_norm(act[: B * T * C].view(B, T, C).transpose(1, 2), C // gsize, gb[:C], gb[C: 2 * C], eps)
+
+    def want(f):
+        h = torch.nn.functional.silu(gn * (f[:, :C].unsqueeze(-1) + 1) + f[:, C:].unsqueeze(-1))
+        if T == 1:
+            y = torch.nn.functional.conv1d(h, w[:, :, 1:2], gb[2 * C:])
+        else:
+            y = torch.nn.functional.conv1d(h, w, gb[2 * C:], padding=1)
+        return y.transpose(1, 2) + act[2 * B * T * C:].view(B, T, C)
+    ref_rows = want(film)
+    scale = max(1.0, ref_rows.abs().max().item())
+    got = run(2 * C, film)
+    assert torch.isfinite(got).all() and (got - ref_rows).abs().max() < 1e-4 * scale, (got - ref_rows).abs().max().item()
+    shared = run(0, film)
+    assert (shared - want(film[:1].expand(B, -1))).abs().max() < 1e-4 * scale
+    assert torch.equal(shared, run(2 * C, film[:1].expand(B, -1)))
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "f32"])
+@pytest.mark.parametrize("cin,cout,B", [(16, 64, 5), (64, 16, 5), (16, 1, 7), (16, 64, 515)])
+def test_fused_resnet_block_with_one_film_row_per_sample(cin, cout, B, mode):
+    """k_resblock: the FiLM row is read inside the loop over the workgroup's samples (B = 515 wraps the persistent loop, odd B
+    leaves half a workgroup idle)."""
+    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
+    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
+    F = torch.nn.functional
+    p = "blk."
+    sd = {p + "block1.groupnorm.weight": 1 + 0.1 * rnd(cin, seed=1), p + "block1.groupnorm.bias": 0.1 * rnd(cin, seed=2),
+          p + "block1.project.weight": rnd(cout, cin, 3, seed=3, scale=(3 * cin) ** -0.5),
+          p + "block1.project.bias": 0.1 * rnd(cout, seed=4),
+          p + "block2.groupnorm.weight": 1 + 0.1 * rnd(cout, seed=5), p + "block2.groupnorm.bias": 0.1 * rnd(cout, seed=6),
+          p + "block2.project.weight": rnd(cout, cout, 3, seed=7, scale=(3 * cout) ** -0.5),
+          p + "block2.project.bias": 0.1 * rnd(cout, seed=8),
+          p + "to_out.weight": rnd(cout, cin, 1, seed=9, scale=cin ** -0.5), p + "to_out.bias": 0.1 * rnd(cout, seed=10)}
+    comp = UNetCompiler(inverse_unet_config(16, 64, 128, 12), 64, 12, sd, gemm_mode=mode)
+    cin_p, cout_p = (cin + 15) // 16 * 16, (cout + 15) // 16 * 16
+    comp.resnet(Ten(A, 0, 64, cin_p, cin), p, cin, cout, 1, free_input=False)
+    assert len(comp.ops) == 1 and comp.ops[0].kind == rt.OP_RESBLOCK
+    op = comp.ops[0]
+    op.out, op.p3 = ref(A, 64 * cin_p), ref(S, 0)
+    film = torch.zeros(B, 2 * cout_p)                  # [scale(cout_p) | shift(cout_p)] per sample, zero on the padding
+    film[:, :cout], film[:, cout_p: cout_p + cout] = 0.3 * rnd(B, cout, seed=11), 0.3 * rnd(B, cout, seed=12)
+    xin = torch.zeros(B, 64, cin_p)
+    xin[:, :, :cin] = (rnd(B * 64 * cin, seed=12) * 1.5 + 0.3).view(B, 64, cin)
+    n_in = B * 64 * cin_p
+    act = torch.cat([xin.view(-1), torch.full((B * 64 * cout_p,), 7.0)])
+    weights = comp.W.pack()
+
+    def run(stride, f):
+        op.film_bstride = stride
+        return _run_gpu([op], weights, act, f.contiguous().flatten(), B)[n_in:].view(B, 64, cout_p)
+    xt = xin[:, :, :cin].transpose(1, 2)
+    h = F.conv1d(F.silu(F.group_norm(xt, 1, sd[p + "block1.groupnorm.weight"], sd[p + "block1.groupnorm.bias"], 1e-5)),
+                 sd[p + "block1.project.weight"], sd[p + "block1.project.bias"], padding=1)
+    h = F.group_norm(h, 1, sd[p + "block2.groupnorm.weight"], sd[p + "block2.groupnorm.bias"], 1e-5)
+    skip = F.conv1d(xt, sd[p + "to_out.weight"], sd[p + "to_out.bias"])
+
+    def want(f):
+        hh = h * (f[:, :cout].unsqueeze(-1) + 1) + f[:, cout_p: cout_p + cout].unsqueeze(-1)
+        return (F.conv1d(F.silu(hh), sd[p + "block2.project.weight"], sd[p + "block2.project.bias"], padding=1) + skip).transpose(1, 2)
+    ref_rows = want(film)
+    scale = max(1.0, ref_rows.abs().max().item())
+    got = run(2 * cout_p, film)
+    assert torch.isfinite(got).all() and (got[:, :, :cout] - ref_rows).abs().max() < 1e-4 * scale
+    assert (got[:, :, cout:] == 0).all()
+    shared = run(0, film)
+    assert (shared[:, :, :cout] - want(film[:1].expand(B, -1))).abs().max() < 1e-4 * scale
+    assert torch.equal(shared, run(2 * cout_p, film[:1].expand(B, -1)))
