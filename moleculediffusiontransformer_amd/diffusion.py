@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -70,16 +70,59 @@ class Sampler(nn.Module):
         raise NotImplementedError("Inpainting not available with current sampler")
 
 
-class ADPM2Sampler(Sampler):
+def _step_inputs(name: str, x: Tensor, sigma, sigma_next):
+    """What every per-step path starts from: the two sigmas as 0-dim fp32 CPU tensors (the reference indexes a CPU schedule)
+    and the state as a contiguous fp32 HIP tensor."""
+    if x.device.type != "cuda":
+        raise RuntimeError(f"{name}.step runs on an AMD GPU through libmdt_hip.so (no CPU fallback)")
+    sigma = torch.as_tensor(sigma, dtype=torch.float32).cpu().reshape(())
+    sigma_next = torch.as_tensor(sigma_next, dtype=torch.float32).cpu().reshape(())
+    return x.detach().float().contiguous(), sigma, sigma_next
+
+
+def _step_draw(x: Tensor, noise: Optional[Tensor]) -> Tensor:
+    """The torch.randn_like(x) draw of a step (diffusion.py:514), or the caller's tensor in its place."""
+    return (torch.randn_like(x) if noise is None else noise.to(device=x.device, dtype=torch.float32)).contiguous()
+
+
+class _LoopSampler(Sampler):
+    """forward() of the three samplers built here.  With the denoiser of a QMDiffusion* model (BoundDenoise.fused) the whole
+    loop runs on the fused path (run_sampler); with any other ``fn``, or in a subclass that overrides step() (it is honoured),
+    forward() calls step() once per timestep as the reference does."""
+
+    diffusion_types = [_KAlias("k"), _KAlias("vk")]
+
+    def _fused(self, fn: Callable):
+        return getattr(fn, "fused", None) if fused_sampler_kind(self) else None
+
+    def _step_args(self, sigmas: Tensor, num_steps: int):
+        """(the sigmas step() is given, i -> the keyword arguments of step i beyond the two sigmas)."""
+        return sigmas, lambda i: {}
+
+    def forward(self, noise, fn: Callable, sigmas: Tensor, num_steps: int) -> Tensor:
+        """diffusion.py:437-453, :476-483, :517-524.  ``noise`` is the initial draw (B, C, L) or, on the fused path, a
+        NoiseSource."""
+        fused = self._fused(fn)
+        if fused is not None:
+            return fused.sample(noise, self, sigmas, num_steps)
+        if isinstance(noise, NoiseSource):
+            raise TypeError("a NoiseSource drives the fused path only; pass the initial noise tensor with a custom fn")
+        x = float(sigmas[0]) * noise
+        sigmas, extra = self._step_args(sigmas, num_steps)
+        for i in range(num_steps - 1):
+            x = self.step(x, fn=fn, sigma=sigmas[i], sigma_next=sigmas[i + 1], **extra(i))
+        return x
+
+
+class ADPM2Sampler(_LoopSampler):
     """diffusion.py:486-549: second-order ancestral DPM-2 sampler.
 
     ``fn(x, sigma=...)`` is any denoiser on HIP tensors.  When it is the denoiser of a QMDiffusion* model (the closure
-    DiffusionSampler / DiffusionInpainter build), forward()/inpaint() run the whole loop on the fused path (run_adpm2:
-    per-step scalars precomputed on the host, preconditioning + update fused, the U-Net as a replayed HIP graph); with any
-    other ``fn`` every step is two calls of ``fn`` and two mdt_adpm2_euler launches (the reference's arithmetic, fp32, no
-    contraction), drawing the step noise with torch.randn_like on the device exactly as diffusion.py:514 does."""
-
-    diffusion_types = [_KAlias("k"), _KAlias("vk")]
+    DiffusionSampler / DiffusionInpainter build), forward()/inpaint() run the whole loop on the fused path (run_sampler /
+    run_adpm2_inpaint: per-step scalars precomputed on the host, preconditioning + update fused, the U-Net as a replayed HIP
+    graph); with any other ``fn`` every step is two calls of ``fn`` and two mdt_adpm2_euler launches (the reference's
+    arithmetic, fp32, no contraction), drawing the step noise with torch.randn_like on the device exactly as
+    diffusion.py:514 does."""
 
     def __init__(self, rho: float = 1.0):
         super().__init__()
@@ -95,14 +138,10 @@ class ADPM2Sampler(Sampler):
     def step(self, x: Tensor, fn: Callable, sigma, sigma_next, *, noise: Optional[Tensor] = None) -> Tensor:
         """diffusion.py:502-515 for one step; ``noise`` replaces the torch.randn_like(x) draw (parity tests)."""
         lib = rt.load_library()
-        sigma = torch.as_tensor(sigma, dtype=torch.float32).cpu().reshape(())
-        sigma_next = torch.as_tensor(sigma_next, dtype=torch.float32).cpu().reshape(())
+        x, sigma, sigma_next = _step_inputs("ADPM2Sampler", x, sigma, sigma_next)
         sigma_up, sigma_down, sigma_mid = self.get_sigmas(sigma, sigma_next)
         dt_mid, dt_down = float(sigma_mid - sigma), float(sigma_down - sigma)     # fp32 tensor arithmetic, as the reference
         up32 = float(torch.tensor(sigma_up, dtype=torch.float32))
-        if x.device.type != "cuda":
-            raise RuntimeError("ADPM2Sampler.step runs on an AMD GPU through libmdt_hip.so (no CPU fallback)")
-        x = x.detach().float().contiguous()
         B, C, L = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
             st = rt.current_stream()
@@ -111,28 +150,16 @@ class ADPM2Sampler(Sampler):
             rt.check(lib.mdt_adpm2_euler(rt.ptr(x), rt.ptr(x), rt.ptr(den), 0, rt.ptr(x_mid), float(sigma), dt_mid, 0.0, 0,
                                          0, 0, 0, B, C, L, st))
             den_mid = fn(x_mid, sigma=torch.as_tensor(sigma_mid, dtype=torch.float32)).float().contiguous()
-            nz = (torch.randn_like(x) if noise is None else noise.to(device=x.device, dtype=torch.float32)).contiguous()
+            nz = _step_draw(x, noise)
             out = torch.empty_like(x)
             rt.check(lib.mdt_adpm2_euler(rt.ptr(x), rt.ptr(x_mid), rt.ptr(den_mid), rt.ptr(nz), rt.ptr(out),
                                          float(sigma_mid), dt_down, up32, 1, 0, 0, 0, B, C, L, st))
         return out
 
-    def forward(self, noise, fn: Callable, sigmas: Tensor, num_steps: int) -> Tensor:
-        """diffusion.py:517-524.  ``noise`` is the initial draw (B, C, L) or, on the fused path, a NoiseSource."""
-        fused = getattr(fn, "fused", None) if type(self).step is ADPM2Sampler.step else None   # a subclass's step() is honoured
-        if fused is not None:
-            return fused.sample(noise, self, sigmas, num_steps)
-        if isinstance(noise, NoiseSource):
-            raise TypeError("a NoiseSource drives the fused path only; pass the initial noise tensor with a custom fn")
-        x = float(sigmas[0]) * noise
-        for i in range(num_steps - 1):
-            x = self.step(x, fn=fn, sigma=sigmas[i], sigma_next=sigmas[i + 1])
-        return x
-
     def inpaint(self, source: Tensor, mask: Tensor, fn: Callable, sigmas: Tensor, num_steps: int,
                 num_resamples: int) -> Tensor:
         """diffusion.py:526-549."""
-        fused = getattr(fn, "fused", None) if type(self).step is ADPM2Sampler.step else None
+        fused = self._fused(fn)
         if fused is not None:
             return fused.inpaint(source, mask, self, sigmas, num_steps, num_resamples)
         x = float(sigmas[0]) * torch.randn_like(source)
@@ -147,25 +174,13 @@ class ADPM2Sampler(Sampler):
         return source * mask + x * ~mask
 
 
-def _step_inputs(name: str, x: Tensor, sigma, sigma_next):
-    """What every per-step path starts from: the two sigmas as 0-dim fp32 CPU tensors (the reference indexes a CPU schedule)
-    and the state as a contiguous fp32 HIP tensor."""
-    if x.device.type != "cuda":
-        raise RuntimeError(f"{name}.step runs on an AMD GPU through libmdt_hip.so (no CPU fallback)")
-    sigma = torch.as_tensor(sigma, dtype=torch.float32).cpu().reshape(())
-    sigma_next = torch.as_tensor(sigma_next, dtype=torch.float32).cpu().reshape(())
-    return x.detach().float().contiguous(), sigma, sigma_next
-
-
-class AEulerSampler(Sampler):
+class AEulerSampler(_LoopSampler):
     """diffusion.py:456-483: ancestral Euler sampler, ONE evaluation per step (ADPM2 and Karras take two).
 
     Same seams as ADPM2Sampler: with the denoiser of a QMDiffusion* model forward() runs the whole loop on the fused path
-    (run_aeuler: one mdt_aeuler_next launch per step around the replayed U-Net graph); with any other ``fn`` every step is
+    (_aeuler_steps: one mdt_aeuler_next launch per step around the replayed U-Net graph); with any other ``fn`` every step is
     one call of ``fn`` and one mdt_adpm2_euler launch.  inpaint() is the base class's NotImplementedError, as in the
     reference."""
-
-    diffusion_types = [_KAlias("k"), _KAlias("vk")]
 
     def get_sigmas(self, sigma, sigma_next):
         sigma_up = math.sqrt(sigma_next ** 2 * (sigma ** 2 - sigma_next ** 2) / sigma ** 2)
@@ -182,26 +197,14 @@ class AEulerSampler(Sampler):
         B, C, L = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
             den = fn(x, sigma=sigma).float().contiguous()
-            nz = (torch.randn_like(x) if noise is None else noise.to(device=x.device, dtype=torch.float32)).contiguous()
+            nz = _step_draw(x, noise)
             out = torch.empty_like(x)
             rt.check(lib.mdt_adpm2_euler(rt.ptr(x), rt.ptr(x), rt.ptr(den), rt.ptr(nz), rt.ptr(out), float(sigma), dt, up32, 1,
                                          0, 0, 0, B, C, L, rt.current_stream()))
         return out
 
-    def forward(self, noise, fn: Callable, sigmas: Tensor, num_steps: int) -> Tensor:
-        """diffusion.py:476-483.  ``noise`` is the initial draw (B, C, L) or, on the fused path, a NoiseSource."""
-        fused = getattr(fn, "fused", None) if fused_sampler_kind(self) else None          # a subclass's step() is honoured
-        if fused is not None:
-            return fused.sample(noise, self, sigmas, num_steps)
-        if isinstance(noise, NoiseSource):
-            raise TypeError("a NoiseSource drives the fused path only; pass the initial noise tensor with a custom fn")
-        x = float(sigmas[0]) * noise
-        for i in range(num_steps - 1):
-            x = self.step(x, fn=fn, sigma=sigmas[i], sigma_next=sigmas[i + 1])
-        return x
 
-
-class KarrasSampler(Sampler):
+class KarrasSampler(_LoopSampler):
     """diffusion.py:399-453: the stochastic second-order sampler of Karras et al. (arXiv:2206.00364, algorithm 2) AS THE
     REFERENCE WRITES IT.  Its correction line is ``x_next = x_hat + 0.5 * (sigma - sigma_hat) * (d + d_prime)`` (:434), not
     the paper's ``x_hat + 0.5 * (sigma_next - sigma_hat) * (d + d_prime)``: without churn (gamma = 0, the constructor's
@@ -209,10 +212,8 @@ class KarrasSampler(Sampler):
     for bit; with churn a step moves x by ``-0.5 gamma sigma (d + d')`` only.  This package reproduces the reference's
     arithmetic, so it does the same (pinned by tests/golden/tiny_b3_t8_karras0_sample.npz); it is not "fixed" here.
 
-    With the denoiser of a QMDiffusion* model forward() runs the fused loop (run_karras: mdt_karras_hat / _mid / _next around
-    the two evaluations of a step); with any other ``fn`` a step is two calls of ``fn`` plus elementwise launches."""
-
-    diffusion_types = [_KAlias("k"), _KAlias("vk")]
+    With the denoiser of a QMDiffusion* model forward() runs the fused loop (_karras_steps: mdt_karras_hat / _mid / _next
+    around the two evaluations of a step); with any other ``fn`` a step is two calls of ``fn`` plus elementwise launches."""
 
     def __init__(self, s_tmin: float = 0, s_tmax: float = float("inf"), s_churn: float = 0.0, s_noise: float = 1.0):
         super().__init__()
@@ -238,7 +239,7 @@ class KarrasSampler(Sampler):
         B, C, L = x.shape
         with torch.no_grad(), torch.cuda.device(x.device):
             st = rt.current_stream()
-            nz = (torch.randn_like(x) if noise is None else noise.to(device=x.device, dtype=torch.float32)).contiguous()
+            nz = _step_draw(x, noise)
             eps = (s_noise32 * nz).contiguous()
             x_hat = x.clone()
             rt.check(lib.mdt_add_noise(rt.ptr(x_hat), rt.ptr(eps), ns32, 0, 0, 0, B, C, L, st))
@@ -254,27 +255,18 @@ class KarrasSampler(Sampler):
                 x_next = x_hat + half * (d + d_prime)
         return x_next
 
-    def forward(self, noise, fn: Callable, sigmas: Tensor, num_steps: int) -> Tensor:
-        """diffusion.py:437-453.  ``noise`` is the initial draw (B, C, L) or, on the fused path, a NoiseSource."""
-        fused = getattr(fn, "fused", None) if fused_sampler_kind(self) else None          # a subclass's step() is honoured
-        if fused is not None:
-            return fused.sample(noise, self, sigmas, num_steps)
-        if isinstance(noise, NoiseSource):
-            raise TypeError("a NoiseSource drives the fused path only; pass the initial noise tensor with a custom fn")
-        x = float(sigmas[0]) * noise
+    def _step_args(self, sigmas: Tensor, num_steps: int):
         sigmas = torch.as_tensor(sigmas, dtype=torch.float32).cpu()
         gammas = self.get_gammas(sigmas, num_steps)
-        for i in range(num_steps - 1):
-            x = self.step(x, fn=fn, sigma=sigmas[i], sigma_next=sigmas[i + 1], gamma=gammas[i])
-        return x
+        return sigmas, lambda i: dict(gamma=gammas[i])
 
 
 def fused_sampler_kind(sampler) -> Optional[str]:
     """'adpm2' | 'aeuler' | 'karras' when ``sampler`` may take the fused loop of a QMDiffusion* model -- one of the three
     sampler classes with its own step() (a subclass that overrides step() is honoured: it gets the per-step path) -- else None."""
-    for kind, cls in (("adpm2", ADPM2Sampler), ("aeuler", AEulerSampler), ("karras", KarrasSampler)):
-        if isinstance(sampler, cls):
-            return kind if type(sampler).step is cls.step else None
+    for kind, k in FUSED_SAMPLERS.items():
+        if isinstance(sampler, k.cls):
+            return kind if type(sampler).step is k.cls.step else None
     return None
 
 
@@ -348,32 +340,38 @@ class StepScalars:
 _PLAN_CACHE: dict = {}
 
 
+def _cached_plan(num_steps: int, schedule, sampler, params: tuple, sigma_data: float, make_steps: Callable):
+    """(sigmas, steps) of a plan function: ``make_steps(sigmas)`` yields the per-step scalars when the cache has none.
+    A plan is a pure function of (sigmas, sampler class and ``params``, sigma_data) and costs ~10 ms of 0-dim tensor arithmetic
+    for 64 timesteps (it has to: the reference's mixed double / fp32 rounding is reproduced op by op).  Hidden while the GPU
+    queue is full, but a call that waits for its hand-off status (engine.note_handoff) exposes the NEXT call's host prologue:
+    keep the last plans."""
+    sigmas = schedule.detach().float().cpu() if isinstance(schedule, torch.Tensor) else schedule(num_steps)
+    key = (num_steps, sigmas.numpy().tobytes(), type(sampler), params, float(sigma_data))
+    steps = _PLAN_CACHE.get(key)
+    if steps is None:
+        steps = tuple(make_steps(sigmas))                # (a tuple: every caller shares it)
+        if len(_PLAN_CACHE) >= 16:
+            _PLAN_CACHE.pop(next(iter(_PLAN_CACHE)))
+        _PLAN_CACHE[key] = steps
+    return sigmas, steps
+
+
 def adpm2_plan(num_steps: int, schedule, sampler: ADPM2Sampler, sigma_data: float):
     """Per-step scalars of ADPM2Sampler.forward/step (diffusion.py:502-524), bit-for-bit as the reference
     computes them on CPU.  ``schedule`` is a KarrasSchedule or an already evaluated (num_steps + 1,) sigma tensor."""
-    sigmas = schedule.detach().float().cpu() if isinstance(schedule, torch.Tensor) else schedule(num_steps)
-    # The plan is a pure function of (sigmas, sampler, sigma_data) and costs ~10 ms of 0-dim tensor arithmetic for 64 timesteps
-    # (it has to: the reference's mixed double / fp32 rounding is reproduced op by op).  Hidden while the GPU queue is full, but a
-    # call that waits for its hand-off status (engine.note_handoff) exposes the NEXT call's host prologue: keep the last plans.
-    key = (num_steps, sigmas.numpy().tobytes(), type(sampler), float(getattr(sampler, "rho", 0.0)), float(sigma_data))
-    hit = _PLAN_CACHE.get(key)
-    if hit is not None:
-        return sigmas, hit                               # (a tuple: every caller shares it)
-    steps: List[StepScalars] = []
-    for i in range(num_steps - 1):
-        sigma, sigma_next = sigmas[i], sigmas[i + 1]
-        sigma_up, sigma_down, sigma_mid = sampler.get_sigmas(sigma, sigma_next)
-        dt_mid = sigma_mid - sigma                       # 0-dim fp32
-        dt_down = sigma_down - sigma                     # python double - fp32 tensor -> fp32 tensor
-        up32 = torch.tensor(sigma_up, dtype=torch.float32)
-        renoise = math.sqrt(sigmas[i] ** 2 - sigmas[i + 1] ** 2)
-        steps.append(StepScalars(float(sigma), float(sigma_mid), float(up32), float(dt_mid), float(dt_down),
-                                 scale_weights(sigma, sigma_data), scale_weights(sigma_mid, sigma_data),
-                                 float(torch.tensor(renoise, dtype=torch.float32))))
-    if len(_PLAN_CACHE) >= 16:
-        _PLAN_CACHE.pop(next(iter(_PLAN_CACHE)))
-    _PLAN_CACHE[key] = tuple(steps)
-    return sigmas, _PLAN_CACHE[key]
+    def make_steps(sigmas):
+        for i in range(num_steps - 1):
+            sigma, sigma_next = sigmas[i], sigmas[i + 1]
+            sigma_up, sigma_down, sigma_mid = sampler.get_sigmas(sigma, sigma_next)
+            dt_mid = sigma_mid - sigma                       # 0-dim fp32
+            dt_down = sigma_down - sigma                     # python double - fp32 tensor -> fp32 tensor
+            up32 = torch.tensor(sigma_up, dtype=torch.float32)
+            renoise = math.sqrt(sigmas[i] ** 2 - sigmas[i + 1] ** 2)
+            yield StepScalars(float(sigma), float(sigma_mid), float(up32), float(dt_mid), float(dt_down),
+                              scale_weights(sigma, sigma_data), scale_weights(sigma_mid, sigma_data),
+                              float(torch.tensor(renoise, dtype=torch.float32)))
+    return _cached_plan(num_steps, schedule, sampler, (float(getattr(sampler, "rho", 0.0)),), sigma_data, make_steps)
 
 
 @dataclass(frozen=True)
@@ -403,62 +401,41 @@ class KarrasStep:
     row_next: int            # -1 when euler_only
 
 
-def _plan_sigmas(num_steps: int, schedule) -> Tensor:
-    return schedule.detach().float().cpu() if isinstance(schedule, torch.Tensor) else schedule(num_steps)
-
-
-def _plan_store(key, steps) -> tuple:
-    if len(_PLAN_CACHE) >= 16:
-        _PLAN_CACHE.pop(next(iter(_PLAN_CACHE)))
-    _PLAN_CACHE[key] = tuple(steps)
-    return _PLAN_CACHE[key]
-
-
 def aeuler_plan(num_steps: int, schedule, sampler: AEulerSampler, sigma_data: float):
     """Per-step scalars of AEulerSampler.forward/step (diffusion.py:465-483), bit for bit as the reference computes them on
     CPU; ``schedule`` and the cache as adpm2_plan.  One time row per step."""
-    sigmas = _plan_sigmas(num_steps, schedule)
-    key = (num_steps, sigmas.numpy().tobytes(), type(sampler), (), float(sigma_data))
-    hit = _PLAN_CACHE.get(key)
-    if hit is not None:
-        return sigmas, hit
-    steps: List[AEulerStep] = []
-    for i in range(num_steps - 1):
-        sigma, sigma_next = sigmas[i], sigmas[i + 1]
-        sigma_up, sigma_down = sampler.get_sigmas(sigma, sigma_next)
-        dt = sigma_down - sigma                          # python double - fp32 tensor -> fp32 tensor
-        up32 = torch.tensor(sigma_up, dtype=torch.float32)
-        steps.append(AEulerStep(float(sigma), float(up32), float(dt), scale_weights(sigma, sigma_data)))
-    return sigmas, _plan_store(key, steps)
+    def make_steps(sigmas):
+        for i in range(num_steps - 1):
+            sigma, sigma_next = sigmas[i], sigmas[i + 1]
+            sigma_up, sigma_down = sampler.get_sigmas(sigma, sigma_next)
+            dt = sigma_down - sigma                          # python double - fp32 tensor -> fp32 tensor
+            up32 = torch.tensor(sigma_up, dtype=torch.float32)
+            yield AEulerStep(float(sigma), float(up32), float(dt), scale_weights(sigma, sigma_data))
+    return _cached_plan(num_steps, schedule, sampler, (), sigma_data, make_steps)
 
 
 def karras_plan(num_steps: int, schedule, sampler: KarrasSampler, sigma_data: float):
     """Per-step scalars of KarrasSampler.forward/step (diffusion.py:417-453), bit for bit as the reference computes them on
     CPU; ``schedule`` and the cache as adpm2_plan.  Two time rows per step, one when sigma_next == 0 (reachable with an
     evaluated sigma tensor that ends in 0; a KarrasSchedule's padded 0 is never reached)."""
-    sigmas = _plan_sigmas(num_steps, schedule)
+    def make_steps(sigmas):
+        gammas = sampler.get_gammas(sigmas, num_steps)
+        s_noise32 = float(torch.tensor(sampler.s_noise, dtype=torch.float32))     # python double * fp32 tensor: rounded first
+        rows = 0
+        for i in range(num_steps - 1):
+            sigma, sigma_next, gamma = sigmas[i], sigmas[i + 1], gammas[i]
+            sigma_hat = sigma + gamma * sigma                                     # 0-dim fp32
+            ns32 = torch.tensor(math.sqrt(sigma_hat ** 2 - sigma ** 2), dtype=torch.float32)
+            dt = sigma_next - sigma_hat
+            half = 0.5 * (sigma - sigma_hat)
+            euler_only = not bool(sigma_next != 0)
+            yield KarrasStep(float(sigma), float(sigma_next), float(gamma), float(sigma_hat), float(ns32), s_noise32,
+                             float(dt), float(half), scale_weights(sigma_hat, sigma_data),
+                             None if euler_only else scale_weights(sigma_next, sigma_data), euler_only,
+                             rows, -1 if euler_only else rows + 1)
+            rows += 1 if euler_only else 2
     params = (float(sampler.s_tmin), float(sampler.s_tmax), float(sampler.s_churn), float(sampler.s_noise))
-    key = (num_steps, sigmas.numpy().tobytes(), type(sampler), params, float(sigma_data))
-    hit = _PLAN_CACHE.get(key)
-    if hit is not None:
-        return sigmas, hit
-    gammas = sampler.get_gammas(sigmas, num_steps)
-    s_noise32 = float(torch.tensor(sampler.s_noise, dtype=torch.float32))     # python double * fp32 tensor: rounded first
-    steps: List[KarrasStep] = []
-    rows = 0
-    for i in range(num_steps - 1):
-        sigma, sigma_next, gamma = sigmas[i], sigmas[i + 1], gammas[i]
-        sigma_hat = sigma + gamma * sigma                                     # 0-dim fp32
-        ns32 = torch.tensor(math.sqrt(sigma_hat ** 2 - sigma ** 2), dtype=torch.float32)
-        dt = sigma_next - sigma_hat
-        half = 0.5 * (sigma - sigma_hat)
-        euler_only = not bool(sigma_next != 0)
-        steps.append(KarrasStep(float(sigma), float(sigma_next), float(gamma), float(sigma_hat), float(ns32), s_noise32,
-                                float(dt), float(half), scale_weights(sigma_hat, sigma_data),
-                                None if euler_only else scale_weights(sigma_next, sigma_data), euler_only,
-                                rows, -1 if euler_only else rows + 1))
-        rows += 1 if euler_only else 2
-    return sigmas, _plan_store(key, steps)
+    return _cached_plan(num_steps, schedule, sampler, params, sigma_data, make_steps)
 
 
 def plan_time_rows(steps) -> List[float]:
@@ -600,103 +577,38 @@ def _guided_eval(engine, lib, B: int, guided: bool, dual: bool, embedding_scale:
     return pred
 
 
-def run_adpm2(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource,
-              schedule, sampler: ADPM2Sampler, sigma_data: float, embedding_scale: float = 1.0,
-              clamp: bool = False, trace: Optional[dict] = None, timer=None, tokens: Optional[Tensor] = None,
-              dynamic_threshold: float = 0.0) -> Tensor:
-    """DiffusionSampler.forward (diffusion.py:577-591) + ADPM2Sampler.forward (:517-524) +
-    KDiffusion_mod.denoise_fn (:798-814) + UNetCFG1d.forward (modules.py:1228-1255) on the GPU.
-    ``tokens`` (B, L) int32: also the decode step after the path, argmax over channels of the final sample
-    (generative.py:1212-1213), written by the last update kernel."""
-    lib = rt.load_library()
-    dev = engine.device
-    B = embedding.shape[0]
-    C, L, Cp = pred_dim, engine.c.length, engine.c.in_pad
-    sigmas, steps = adpm2_plan(num_steps, schedule, sampler, sigma_data)
-    guided = embedding_scale != 1.0
-
-    with torch.cuda.device(dev):
-        st = rt.current_stream()
-        engine.handoff_check()                        # a time-out of the previous call's pair hand-offs is reported here
-        dual = _guided_setup(engine, embedding, guided)
-        c_noise = torch.tensor([v for s in steps for v in (s.w.c_noise, s.w_mid.c_noise)], dtype=torch.float32)
-        engine.prepare_times(c_noise)
-
-        x = torch.empty(B, C, L, device=dev)
-        x_mid = torch.empty_like(x)
-        seed = noise.seed or 0
-        dscale = torch.empty(B, device=dev) if dynamic_threshold else None      # clip()'s per-sample dynamic threshold
-
-        def dyn(xs, pred, w):
-            if dscale is not None:
-                rt.check(lib.mdt_dyn_scale(rt.ptr(xs), rt.ptr(pred), rt.ptr(dscale), w.c_skip, w.c_out, float(dynamic_threshold),
-                                           B, C, L, Cp, st))
-            return rt.ptr(dscale)
-        init = None if noise.init is None else _f32(noise.init, dev)
-        rt.check(lib.mdt_init_noise(rt.ptr(x), rt.ptr(init), float(sigmas[0]), seed, 0, noise.sample0, B, C, L, st))
-        if not steps:
-            x = x.clamp(-1.0, 1.0) if clamp else x
-            if tokens is not None:
-                rt.check(lib.mdt_argmax_tokens(rt.ptr(x), rt.ptr(tokens), B, C, L, st))
-            return x
-        rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(engine.xin), steps[0].w.c_in, B, C, L, Cp, st))
-
-        def unet(row: int) -> Tensor:
-            engine.select_time(row)
-            if timer is not None:
-                timer.start()
-            pred = _guided_eval(engine, lib, B, guided, dual, embedding_scale, st)
-            if timer is not None:
-                timer.stop()
-            return pred
-
-        for i, s in enumerate(steps):
-            pred = unet(2 * i)
-            rt.check(lib.mdt_adpm2_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(x_mid), rt.ptr(engine.xin), s.w.c_skip,
-                                       s.w.c_out, s.sigma, s.dt_mid, s.w_mid.c_in, B, C, L, Cp, dyn(x, pred, s.w), st))
-            pred = unet(2 * i + 1)
-            nz = None if noise.steps is None else _f32(noise.steps(i), dev)
-            last = i + 1 == len(steps)
-            c_in_next = 0.0 if last else steps[i + 1].w.c_in
-            rt.check(lib.mdt_adpm2_next(rt.ptr(x), rt.ptr(x_mid), rt.ptr(pred), rt.ptr(nz),
-                                        0 if last else rt.ptr(engine.xin), s.w_mid.c_skip, s.w_mid.c_out,
-                                        s.sigma_mid, s.dt_down, s.sigma_up, c_in_next, seed, i + 1, noise.sample0,
-                                        B, C, L, Cp, rt.ptr(tokens) if (last and not clamp) else 0, dyn(x_mid, pred, s.w_mid), st))
-            if trace is not None and (i + 1) in trace.get("want", ()):
-                trace[i + 1] = x.clone()
-        if clamp:
-            rt.check(lib.mdt_clamp(rt.ptr(x), -1.0, 1.0, x.numel(), st))
-            if tokens is not None:        # clamping creates ties (first maximum wins): decode the clamped sample
-                rt.check(lib.mdt_argmax_tokens(rt.ptr(x), rt.ptr(tokens), B, C, L, st))
-        engine.note_handoff()
-    return x
-
-
 class _Loop:
-    """What run_aeuler / run_karras share with run_adpm2's prologue and epilogue: context and time table, the state
-    initialised from the first draw, the timed guided evaluation, the per-sample dynamic threshold, final clamp and decode."""
+    """The scaffold every fused loop runs on: context and time table, the state initialised from the first draw, the draws in
+    call order, the timed guided evaluation, the per-sample dynamic threshold, the step trace, final clamp and decode.
 
-    def __init__(self, engine, embedding, pred_dim, noise, sigmas, steps, embedding_scale, timer, dynamic_threshold):
-        self.lib, self.engine, self.noise, self.timer = rt.load_library(), engine, noise, timer
-        self.B, self.C, self.L, self.Cp = embedding.shape[0], pred_dim, engine.c.length, engine.c.in_pad
+    ``explicit(k)`` returns the caller's tensor for draw k of the call (0 = the initial draw) or None: that draw then comes
+    from the counter-based generator keyed by (seed, k, sample0 + b)."""
+
+    def __init__(self, engine, embedding, shape, sigmas, steps, explicit, seed, sample0, embedding_scale, dynamic_threshold,
+                 clamp=False, trace=None, timer=None, tokens=None):
+        self.lib, self.engine = rt.load_library(), engine
+        (self.B, self.C, self.L), self.Cp = shape, engine.c.in_pad
+        self.explicit, self.seed, self.sample0, self.draws = explicit, seed or 0, sample0, 0
         self.scale, self.guided, self.q = embedding_scale, embedding_scale != 1.0, float(dynamic_threshold)
+        self.clamp, self.trace, self.timer, self.tokens = clamp, trace, timer, tokens
         self.st = rt.current_stream()
         engine.handoff_check()                        # a time-out of the previous call's pair hand-offs is reported here
         self.dual = _guided_setup(engine, embedding, self.guided)
         engine.prepare_times(torch.tensor(plan_time_rows(steps), dtype=torch.float32))
         self.x = torch.empty(self.B, self.C, self.L, device=engine.device)
-        self.seed = noise.seed or 0
-        self.dscale = torch.empty(self.B, device=engine.device) if dynamic_threshold else None
-        init = None if noise.init is None else _f32(noise.init, engine.device)
-        rt.check(self.lib.mdt_init_noise(rt.ptr(self.x), rt.ptr(init), float(sigmas[0]), self.seed, 0, noise.sample0,
+        self.dscale = torch.empty(self.B, device=engine.device) if dynamic_threshold else None   # clip()'s dynamic threshold
+        nz, k = self.draw()
+        rt.check(self.lib.mdt_init_noise(rt.ptr(self.x), rt.ptr(nz), float(sigmas[0]), self.seed, k, self.sample0,
                                          self.B, self.C, self.L, self.st))
 
     def dims(self):
         return self.B, self.C, self.L, self.Cp
 
-    def draw(self, i: int) -> Optional[Tensor]:
-        """The explicit torch.randn_like draw of step i, or None for the counter-based generator (draw index i + 1)."""
-        return None if self.noise.steps is None else _f32(self.noise.steps(i), self.engine.device)
+    def draw(self):
+        """The next draw of the call: (the explicit tensor on the device or None, its index for the generator)."""
+        k, self.draws = self.draws, self.draws + 1
+        nz = self.explicit(k)
+        return (None if nz is None else _f32(nz, self.engine.device)), k
 
     def dyn(self, xs: Tensor, pred: Tensor, w: ScaleWeights) -> int:
         if self.dscale is not None:
@@ -713,79 +625,140 @@ class _Loop:
             self.timer.stop()
         return pred
 
-    def finish(self, x: Tensor, clamp: bool, tokens: Optional[Tensor], decoded: bool, handoff: bool = True) -> Tensor:
+    def tok(self, last: bool) -> int:
+        """``tokens`` for the last update kernel (it decodes what it writes) -- unless the final clamp comes first."""
+        return rt.ptr(self.tokens) if (last and not self.clamp) else 0
+
+    def record(self, i: int, x: Tensor) -> None:
+        if self.trace is not None and (i + 1) in self.trace.get("want", ()):
+            self.trace[i + 1] = x.clone()
+
+    def finish(self, x: Tensor, decoded: bool, handoff: bool = True) -> Tensor:
         """Final clamp (mdt_clamp) and the decode when the last update kernel has not done it."""
-        if clamp:
+        if self.clamp:
             rt.check(self.lib.mdt_clamp(rt.ptr(x), -1.0, 1.0, x.numel(), self.st))
-        if tokens is not None and (clamp or not decoded):   # clamping creates ties (first maximum wins): decode the clamped sample
-            rt.check(self.lib.mdt_argmax_tokens(rt.ptr(x), rt.ptr(tokens), self.B, self.C, self.L, self.st))
+        if self.tokens is not None and (self.clamp or not decoded):   # clamping creates ties (first maximum wins): decode after it
+            rt.check(self.lib.mdt_argmax_tokens(rt.ptr(x), rt.ptr(self.tokens), self.B, self.C, self.L, self.st))
         if handoff:
             self.engine.note_handoff()
         return x
 
 
-def run_aeuler(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource,
-               schedule, sampler: AEulerSampler, sigma_data: float, embedding_scale: float = 1.0,
-               clamp: bool = False, trace: Optional[dict] = None, timer=None, tokens: Optional[Tensor] = None,
-               dynamic_threshold: float = 0.0) -> Tensor:
-    """DiffusionSampler.forward (diffusion.py:577-591) + AEulerSampler.forward (:476-483) + KDiffusion_mod.denoise_fn
-    (:798-814) + UNetCFG1d.forward (modules.py:1228-1255) on the GPU: run_adpm2's arguments and structure, one evaluation
-    and one mdt_aeuler_next launch per step."""
-    sigmas, steps = aeuler_plan(num_steps, schedule, sampler, sigma_data)
-    with torch.cuda.device(engine.device):
-        lp = _Loop(engine, embedding, pred_dim, noise, sigmas, steps, embedding_scale, timer, dynamic_threshold)
-        lib, x, st = lp.lib, lp.x, lp.st
-        if not steps:
-            return lp.finish(x, clamp, tokens, False, handoff=False)
-        rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(engine.xin), steps[0].w.c_in, *lp.dims(), st))
-        for i, s in enumerate(steps):
-            pred = lp.unet(i)
-            nz = lp.draw(i)
-            last = i + 1 == len(steps)
-            c_in_next = 0.0 if last else steps[i + 1].w.c_in
-            rt.check(lib.mdt_aeuler_next(rt.ptr(x), rt.ptr(pred), rt.ptr(nz), 0 if last else rt.ptr(engine.xin), s.w.c_skip,
-                                         s.w.c_out, s.sigma, s.dt, s.sigma_up, c_in_next, lp.seed, i + 1, noise.sample0,
-                                         *lp.dims(), rt.ptr(tokens) if (last and not clamp) else 0, lp.dyn(x, pred, s.w), st))
-            if trace is not None and (i + 1) in trace.get("want", ()):
-                trace[i + 1] = x.clone()
-        return lp.finish(x, clamp, tokens, True)
+def _adpm2_step(lp: _Loop, i: int, s: StepScalars, x_mid: Tensor, c_in_next: Optional[float], tok: int) -> None:
+    """ADPM2Sampler.step (diffusion.py:502-515) on lp.x, whose scaled copy is in engine.xin: evaluation at sigma,
+    mdt_adpm2_mid, evaluation at sigma_mid, the step's draw, mdt_adpm2_next.  ``c_in_next``: the input scale of the NEXT
+    evaluation, which mdt_adpm2_next then prepares in engine.xin (None: it does not)."""
+    lib, x, xin, st = lp.lib, lp.x, lp.engine.xin, lp.st
+    pred = lp.unet(2 * i)
+    rt.check(lib.mdt_adpm2_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(x_mid), rt.ptr(xin), s.w.c_skip, s.w.c_out, s.sigma, s.dt_mid,
+                               s.w_mid.c_in, *lp.dims(), lp.dyn(x, pred, s.w), st))
+    pred = lp.unet(2 * i + 1)
+    nz, k = lp.draw()
+    rt.check(lib.mdt_adpm2_next(rt.ptr(x), rt.ptr(x_mid), rt.ptr(pred), rt.ptr(nz), 0 if c_in_next is None else rt.ptr(xin),
+                                s.w_mid.c_skip, s.w_mid.c_out, s.sigma_mid, s.dt_down, s.sigma_up,
+                                0.0 if c_in_next is None else c_in_next, lp.seed, k, lp.sample0, *lp.dims(), tok,
+                                lp.dyn(x_mid, pred, s.w_mid), st))
 
 
-def run_karras(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource,
-               schedule, sampler: KarrasSampler, sigma_data: float, embedding_scale: float = 1.0,
-               clamp: bool = False, trace: Optional[dict] = None, timer=None, tokens: Optional[Tensor] = None,
-               dynamic_threshold: float = 0.0) -> Tensor:
-    """DiffusionSampler.forward (diffusion.py:577-591) + KarrasSampler.forward (:437-453) + KDiffusion_mod.denoise_fn
-    (:798-814) + UNetCFG1d.forward (modules.py:1228-1255) on the GPU: run_adpm2's arguments.  Per step: mdt_karras_hat
-    (churn; in place on x), evaluation at sigma_hat, mdt_karras_mid, evaluation at sigma_next, mdt_karras_next."""
-    sigmas, steps = karras_plan(num_steps, schedule, sampler, sigma_data)
+def _adpm2_steps(lp: _Loop, steps) -> Tensor:
+    """ADPM2Sampler.forward (diffusion.py:517-524): two evaluations per step."""
+    x_mid = torch.empty_like(lp.x)
+    rt.check(lp.lib.mdt_precond_in(rt.ptr(lp.x), rt.ptr(lp.engine.xin), steps[0].w.c_in, *lp.dims(), lp.st))
+    for i, s in enumerate(steps):
+        last = i + 1 == len(steps)
+        _adpm2_step(lp, i, s, x_mid, None if last else steps[i + 1].w.c_in, lp.tok(last))
+        lp.record(i, lp.x)
+    return lp.x
+
+
+def _aeuler_steps(lp: _Loop, steps) -> Tensor:
+    """AEulerSampler.forward (diffusion.py:476-483): one evaluation and one mdt_aeuler_next launch per step."""
+    lib, x, xin, st = lp.lib, lp.x, lp.engine.xin, lp.st
+    rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(xin), steps[0].w.c_in, *lp.dims(), st))
+    for i, s in enumerate(steps):
+        pred = lp.unet(i)
+        nz, k = lp.draw()
+        last = i + 1 == len(steps)
+        c_in_next = 0.0 if last else steps[i + 1].w.c_in
+        rt.check(lib.mdt_aeuler_next(rt.ptr(x), rt.ptr(pred), rt.ptr(nz), 0 if last else rt.ptr(xin), s.w.c_skip, s.w.c_out,
+                                     s.sigma, s.dt, s.sigma_up, c_in_next, lp.seed, k, lp.sample0, *lp.dims(), lp.tok(last),
+                                     lp.dyn(x, pred, s.w), st))
+        lp.record(i, x)
+    return x
+
+
+def _karras_steps(lp: _Loop, steps) -> Tensor:
+    """KarrasSampler.forward (diffusion.py:437-453).  Per step: the draw, mdt_karras_hat (churn; in place on x), evaluation at
+    sigma_hat, mdt_karras_mid, evaluation at sigma_next, mdt_karras_next."""
+    lib, x, xin, st = lp.lib, lp.x, lp.engine.xin, lp.st
+    d, x_next = torch.empty_like(x), torch.empty_like(x)
+    for i, s in enumerate(steps):
+        nz, k = lp.draw()
+        rt.check(lib.mdt_karras_hat(rt.ptr(x), rt.ptr(nz), rt.ptr(x), rt.ptr(xin), s.noise_scale, s.s_noise, s.w_hat.c_in,
+                                    lp.seed, k, lp.sample0, *lp.dims(), st))                        # x is x_hat from here
+        pred = lp.unet(s.row_hat)
+        tok = lp.tok(i + 1 == len(steps))
+        if s.euler_only:
+            rt.check(lib.mdt_karras_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(d), rt.ptr(x_next), 0, s.w_hat.c_skip, s.w_hat.c_out,
+                                        s.sigma_hat, s.dt, 0.0, *lp.dims(), tok, lp.dyn(x, pred, s.w_hat), st))
+            x, x_next = x_next, x
+        else:
+            rt.check(lib.mdt_karras_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(d), rt.ptr(x_next), rt.ptr(xin), s.w_hat.c_skip,
+                                        s.w_hat.c_out, s.sigma_hat, s.dt, s.w_next.c_in, *lp.dims(), 0,
+                                        lp.dyn(x, pred, s.w_hat), st))
+            pred = lp.unet(s.row_next)
+            rt.check(lib.mdt_karras_next(rt.ptr(x), rt.ptr(x_next), rt.ptr(d), rt.ptr(pred), rt.ptr(x), s.w_next.c_skip,
+                                         s.w_next.c_out, s.sigma_next, s.half, *lp.dims(), tok,
+                                         lp.dyn(x_next, pred, s.w_next), st))
+        lp.record(i, x)
+    return x
+
+
+class FusedKind(NamedTuple):
+    cls: type           # the sampler class; a subclass without a step() of its own takes the same loop
+    params: tuple       # its constructor parameters: sampler_params of mdt::sample_with, in this order
+    plan: Callable      # (num_steps, schedule, sampler, sigma_data) -> (sigmas, per-step scalars)
+    steps: Callable     # (_Loop, per-step scalars) -> the final state
+
+
+# kind -> everything that differs between the fused loops; a kind's position is its sampler_kind in mdt::sample_with
+FUSED_SAMPLERS = {"adpm2": FusedKind(ADPM2Sampler, ("rho",), adpm2_plan, _adpm2_steps),
+                  "aeuler": FusedKind(AEulerSampler, (), aeuler_plan, _aeuler_steps),
+                  "karras": FusedKind(KarrasSampler, ("s_tmin", "s_tmax", "s_churn", "s_noise"), karras_plan, _karras_steps)}
+
+
+def require_fused_kind(sampler) -> str:
+    kind = fused_sampler_kind(sampler)
+    if kind is None:
+        raise TypeError(f"{type(sampler).__name__} has no fused loop")
+    return kind
+
+
+def run_sampler(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource, schedule, sampler: Sampler,
+                sigma_data: float, embedding_scale: float = 1.0, clamp: bool = False, trace: Optional[dict] = None, timer=None,
+                tokens: Optional[Tensor] = None, dynamic_threshold: float = 0.0) -> Tensor:
+    """DiffusionSampler.forward (diffusion.py:577-591) + the sampler's forward() + KDiffusion_mod.denoise_fn (:798-814) +
+    UNetCFG1d.forward (modules.py:1228-1255) on the GPU, for any sampler with a fused kind.
+    ``tokens`` (B, L) int32: also the decode step after the path, argmax over channels of the final sample
+    (generative.py:1212-1213), written by the last update kernel."""
+    kind = FUSED_SAMPLERS[require_fused_kind(sampler)]
+    sigmas, steps = kind.plan(num_steps, schedule, sampler, sigma_data)
+
+    def explicit(k: int):            # every sampler draws once per step: draw 0 is the initial one, draw i + 1 that of step i
+        if k == 0:
+            return noise.init
+        return None if noise.steps is None else noise.steps(k - 1)
     with torch.cuda.device(engine.device):
-        lp = _Loop(engine, embedding, pred_dim, noise, sigmas, steps, embedding_scale, timer, dynamic_threshold)
-        lib, x, st = lp.lib, lp.x, lp.st
-        if not steps:
-            return lp.finish(x, clamp, tokens, False, handoff=False)
-        d, x_next = torch.empty_like(x), torch.empty_like(x)
-        for i, s in enumerate(steps):
-            nz = lp.draw(i)
-            rt.check(lib.mdt_karras_hat(rt.ptr(x), rt.ptr(nz), rt.ptr(x), rt.ptr(engine.xin), s.noise_scale, s.s_noise,
-                                        s.w_hat.c_in, lp.seed, i + 1, noise.sample0, *lp.dims(), st))      # x is x_hat from here
-            pred = lp.unet(s.row_hat)
-            tok = rt.ptr(tokens) if (i + 1 == len(steps) and not clamp) else 0
-            if s.euler_only:
-                rt.check(lib.mdt_karras_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(d), rt.ptr(x_next), 0, s.w_hat.c_skip, s.w_hat.c_out,
-                                            s.sigma_hat, s.dt, 0.0, *lp.dims(), tok, lp.dyn(x, pred, s.w_hat), st))
-                x, x_next = x_next, x
-            else:
-                rt.check(lib.mdt_karras_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(d), rt.ptr(x_next), rt.ptr(engine.xin), s.w_hat.c_skip,
-                                            s.w_hat.c_out, s.sigma_hat, s.dt, s.w_next.c_in, *lp.dims(), 0,
-                                            lp.dyn(x, pred, s.w_hat), st))
-                pred = lp.unet(s.row_next)
-                rt.check(lib.mdt_karras_next(rt.ptr(x), rt.ptr(x_next), rt.ptr(d), rt.ptr(pred), rt.ptr(x), s.w_next.c_skip,
-                                             s.w_next.c_out, s.sigma_next, s.half, *lp.dims(), tok,
-                                             lp.dyn(x_next, pred, s.w_next), st))
-            if trace is not None and (i + 1) in trace.get("want", ()):
-                trace[i + 1] = x.clone()
-        return lp.finish(x, clamp, tokens, True)
+        lp = _Loop(engine, embedding, (embedding.shape[0], pred_dim, engine.c.length), sigmas, steps, explicit, noise.seed,
+                   noise.sample0, embedding_scale, dynamic_threshold, clamp, trace, timer, tokens)
+        if steps:
+            return lp.finish(kind.steps(lp, steps), decoded=True)
+        # num_steps == 1: the clamped first draw, decoded; nothing was evaluated, so there is no hand-off to note.  The ADPM2
+        # loop has always clamped it with Tensor.clamp, which keeps a NaN (KarrasSchedule(num_steps=1) is 0 / 0) where
+        # mdt_clamp returns -1; each sampler keeps what it did
+        if clamp and kind.cls is ADPM2Sampler:
+            lp.x, lp.clamp = lp.x.clamp(-1.0, 1.0), False
+        return lp.finish(lp.x, decoded=False, handoff=False)
 
 
 def run_adpm2_inpaint(engine, embedding: Tensor, source: Tensor, mask: Tensor, num_steps: int, num_resamples: int,
@@ -795,63 +768,27 @@ def run_adpm2_inpaint(engine, embedding: Tensor, source: Tensor, mask: Tensor, n
     """ADPM2Sampler.inpaint (diffusion.py:526-549) behind DiffusionInpainter.forward (:612-625).
     ``draw()`` returns the next torch.randn_like tensor in the reference's call order (parity mode);
     otherwise draws come from the counter-based generator keyed by (seed, draw index)."""
-    lib = rt.load_library()
-    dev = engine.device
-    B, C, L = source.shape
-    Cp = engine.c.in_pad
     sigmas, steps = adpm2_plan(num_steps, schedule, sampler, sigma_data)
-    guided = embedding_scale != 1.0
     if mask.dtype != torch.bool or tuple(mask.shape) != tuple(source.shape):
         raise ValueError("in_paint_mask must be a bool tensor of the same shape as inpaint")
-
-    counter = {"n": 0}
-
-    def next_draw():
-        counter["n"] += 1
-        return (None if draw is None else _f32(draw(), dev)), counter["n"] - 1
-
+    dev = engine.device
     with torch.cuda.device(dev):
-        st = rt.current_stream()
-        engine.handoff_check()
-        dual = _guided_setup(engine, embedding, guided)
-        c_noise = torch.tensor([v for s in steps for v in (s.w.c_noise, s.w_mid.c_noise)], dtype=torch.float32)
-        engine.prepare_times(c_noise)
+        lp = _Loop(engine, embedding, tuple(source.shape), sigmas, steps, lambda k: None if draw is None else draw(), seed,
+                   sample0, embedding_scale, dynamic_threshold)
+        lib, x, st = lp.lib, lp.x, lp.st
+        B, C, L, Cp = lp.dims()
         src = _f32(source, dev)
         mk = mask.to(device=dev).to(torch.uint8).contiguous()
-        x = torch.empty(B, C, L, device=dev)
         x_mid = torch.empty_like(x)
-        dscale = torch.empty(B, device=dev) if dynamic_threshold else None
-
-        def dyn(xs, pred, w):
-            if dscale is not None:
-                rt.check(lib.mdt_dyn_scale(rt.ptr(xs), rt.ptr(pred), rt.ptr(dscale), w.c_skip, w.c_out, float(dynamic_threshold),
-                                           B, C, L, Cp, st))
-            return rt.ptr(dscale)
-        sd = seed or 0
-        nz, k = next_draw()
-        rt.check(lib.mdt_init_noise(rt.ptr(x), rt.ptr(nz), float(sigmas[0]), sd, k, sample0, B, C, L, st))
-
-        def unet(row: int) -> Tensor:
-            engine.select_time(row)
-            return _guided_eval(engine, lib, B, guided, dual, embedding_scale, st)
-
         for i, s in enumerate(steps):
-            src_nz, src_k = next_draw()                   # source_noisy = source + sigmas[i] * randn_like(source)
+            src_nz, src_k = lp.draw()                     # source_noisy = source + sigmas[i] * randn_like(source)
             for r in range(num_resamples):
-                rt.check(lib.mdt_inpaint_merge(rt.ptr(x), rt.ptr(src), rt.ptr(mk), rt.ptr(src_nz), s.sigma, sd,
+                rt.check(lib.mdt_inpaint_merge(rt.ptr(x), rt.ptr(src), rt.ptr(mk), rt.ptr(src_nz), s.sigma, lp.seed,
                                                src_k, sample0, B, C, L, st))
                 rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(engine.xin), s.w.c_in, B, C, L, Cp, st))
-                pred = unet(2 * i)
-                rt.check(lib.mdt_adpm2_mid(rt.ptr(x), rt.ptr(pred), rt.ptr(x_mid), rt.ptr(engine.xin), s.w.c_skip,
-                                           s.w.c_out, s.sigma, s.dt_mid, s.w_mid.c_in, B, C, L, Cp, dyn(x, pred, s.w), st))
-                pred = unet(2 * i + 1)
-                nz, k = next_draw()
-                rt.check(lib.mdt_adpm2_next(rt.ptr(x), rt.ptr(x_mid), rt.ptr(pred), rt.ptr(nz), 0, s.w_mid.c_skip,
-                                            s.w_mid.c_out, s.sigma_mid, s.dt_down, s.sigma_up, 0.0, sd, k, sample0,
-                                            B, C, L, Cp, 0, dyn(x_mid, pred, s.w_mid), st))
+                _adpm2_step(lp, i, s, x_mid, None, 0)
                 if r < num_resamples - 1:
-                    nz, k = next_draw()
-                    rt.check(lib.mdt_add_noise(rt.ptr(x), rt.ptr(nz), s.renoise, sd, k, sample0, B, C, L, st))
-        rt.check(lib.mdt_inpaint_merge(rt.ptr(x), rt.ptr(src), rt.ptr(mk), 0, 0.0, sd, 0, sample0, B, C, L, st))
-        engine.note_handoff()
-    return x
+                    nz, k = lp.draw()
+                    rt.check(lib.mdt_add_noise(rt.ptr(x), rt.ptr(nz), s.renoise, lp.seed, k, sample0, B, C, L, st))
+        rt.check(lib.mdt_inpaint_merge(rt.ptr(x), rt.ptr(src), rt.ptr(mk), 0, 0.0, lp.seed, 0, sample0, B, C, L, st))
+        return lp.finish(x, decoded=True)

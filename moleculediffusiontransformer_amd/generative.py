@@ -15,9 +15,8 @@ import torch.nn as nn
 
 from . import ops, runtime as rt
 from .compiler import compile_unet
-from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler, KarrasSchedule,
-                        LogNormalDistribution, NoiseSource, fused_sampler_kind, run_adpm2, run_adpm2_inpaint, run_aeuler,
-                        run_karras, scale_weights, scale_weights_rows)
+from .diffusion import (FUSED_SAMPLERS, ADPM2Sampler, DiffusionInpainter, DiffusionSampler, KarrasSchedule, LogNormalDistribution,
+                        NoiseSource, run_adpm2_inpaint, run_sampler, scale_weights, scale_weights_rows)
 from .engine import UNetEngine, _require_gpu
 from .modules import PositionalEncoding1D, UNetCFG1d
 from .netspec import forward_unet_config, inverse_unet_config
@@ -99,8 +98,8 @@ class XDiffusion_x(nn.Module):
 
 class _FusedLoop:
     """What ADPM2Sampler.forward / inpaint and AEulerSampler / KarrasSampler.forward call when the denoiser belongs to a
-    QMDiffusion* model: the whole loop on the fused path (run_adpm2 / run_aeuler / run_karras / run_adpm2_inpaint) instead of
-    one callback per evaluation."""
+    QMDiffusion* model: the whole loop on the fused path (run_sampler / run_adpm2_inpaint) instead of one callback per
+    evaluation."""
 
     def __init__(self, owner, kwargs: dict, extra: dict):
         unknown = set(kwargs) - {"embedding", "embedding_scale"}
@@ -115,38 +114,25 @@ class _FusedLoop:
         guided = self.kw.get("embedding_scale", 1.0) != 1.0
         eng = o.engine(emb.device, emb.shape[1], emb.shape[0] * (2 if guided else 1))
         ns = o._noise_source(noise, emb.shape[0], emb.device)
-        x = self.extra
-        sigma_data = o.diffusion.diffusion.sigma_data
-        scale = self.kw.get("embedding_scale", 1.0)
-        if ns.steps is None and x.get("trace") is None and x.get("timer") is None and type(sampler) is ADPM2Sampler:
-            # the plain call (counter-based step noise, nothing to record): the whole loop as ONE custom op
-            tok = x.get("tokens")
-            init = None if ns.init is None else ns.init.to(device=emb.device, dtype=torch.float32)
-            out, t = torch.ops.mdt.sample(emb, init, None, torch.as_tensor(sigmas, dtype=torch.float32).cpu(),
-                                          ops.register_engine(eng), o.pred_dim, float(sampler.rho), float(sigma_data), float(scale),
-                                          bool(x.get("clamp", False)), int(ns.seed or 0), int(ns.sample0), tok is not None,
-                                          float(o.diffusion.diffusion.dynamic_threshold))
-            if tok is not None:
-                tok.copy_(t)
-            return out
-        kind = fused_sampler_kind(sampler)
-        if kind is None:
-            raise TypeError(f"{type(sampler).__name__} has no fused loop")
-        if ns.steps is None and x.get("trace") is None and x.get("timer") is None and type(sampler) in (AEulerSampler, KarrasSampler):
-            # the plain call with one of the other samplers: ONE custom op too (mdt::sample stays ADPM2's)
-            tok = x.get("tokens")
-            init = None if ns.init is None else ns.init.to(device=emb.device, dtype=torch.float32)
-            skind, sparams = ops.sampler_spec(sampler)
-            out, t = torch.ops.mdt.sample_with(emb, init, None, torch.as_tensor(sigmas, dtype=torch.float32).cpu(),
-                                               ops.register_engine(eng), o.pred_dim, skind, sparams, float(sigma_data),
-                                               float(scale), bool(x.get("clamp", False)), int(ns.seed or 0), int(ns.sample0),
-                                               tok is not None, float(o.diffusion.diffusion.dynamic_threshold))
-            if tok is not None:
-                tok.copy_(t)
-            return out
-        run = {"adpm2": run_adpm2, "aeuler": run_aeuler, "karras": run_karras}[kind]
-        return run(eng, emb, o.pred_dim, num_steps, ns, sigmas, sampler, sigma_data, scale, bool(x.get("clamp", False)),
-                   x.get("trace"), x.get("timer"), x.get("tokens"), float(o.diffusion.diffusion.dynamic_threshold))
+        x, kd = self.extra, o.diffusion.diffusion
+        scale, clamp, tok = self.kw.get("embedding_scale", 1.0), bool(x.get("clamp", False)), x.get("tokens")
+        plain = ns.steps is None and x.get("trace") is None and x.get("timer") is None
+        if not (plain and any(type(sampler) is k.cls for k in FUSED_SAMPLERS.values())):
+            return run_sampler(eng, emb, o.pred_dim, num_steps, ns, sigmas, sampler, kd.sigma_data, scale, clamp, x.get("trace"),
+                               x.get("timer"), tok, float(kd.dynamic_threshold))
+        # the plain call (counter-based step noise, nothing to record) with a sampler of exactly one of the three classes: the
+        # whole loop as ONE custom op, mdt::sample for ADPM2 (it stays ADPM2's), mdt::sample_with for the other two
+        init = None if ns.init is None else ns.init.to(device=emb.device, dtype=torch.float32)
+        head = (emb, init, None, torch.as_tensor(sigmas, dtype=torch.float32).cpu(), ops.register_engine(eng), o.pred_dim)
+        rest = (float(kd.sigma_data), float(scale), clamp, int(ns.seed or 0), int(ns.sample0), tok is not None,
+                float(kd.dynamic_threshold))
+        if type(sampler) is ADPM2Sampler:
+            out, t = torch.ops.mdt.sample(*head, float(sampler.rho), *rest)
+        else:
+            out, t = torch.ops.mdt.sample_with(*head, *ops.sampler_spec(sampler), *rest)
+        if tok is not None:
+            tok.copy_(t)
+        return out
 
     def inpaint(self, source, mask, sampler, sigmas, num_steps, num_resamples):
         o, emb = self.owner, self.kw["embedding"]

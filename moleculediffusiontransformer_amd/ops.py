@@ -31,6 +31,7 @@ import torch
 from torch.library import custom_op
 
 from . import runtime as rt
+from .diffusion import FUSED_SAMPLERS, ADPM2Sampler, NoiseSource, require_fused_kind, run_sampler
 
 Tensor = torch.Tensor
 
@@ -54,6 +55,14 @@ def _engine(handle: int):
     if e is None:
         raise RuntimeError(f"mdt: unknown or released engine handle {handle}")
     return e
+
+
+def _engine_on(handle: int, dev, what: str):
+    """The engine of ``handle``, which must live on the tensors' device ``dev``; ``what`` names the op in the message."""
+    eng = _engine(handle)
+    if eng.device != dev:
+        raise RuntimeError(f"{what}: engine lives on {eng.device}, tensors on {dev}")
+    return eng
 
 
 def _hip(*tensors: Optional[Tensor]) -> torch.device:
@@ -379,9 +388,7 @@ def unet_eval(xin: Tensor, embedding: Tensor, c_noise: float, embedding_scale: f
     """xin (B, L, Cp) token-major network input, embedding (B, n, F); returns the prediction (B, L, Cp)."""
     dev = _hip(xin, embedding)
     lib = rt.load_library()
-    eng = _engine(handle)
-    if eng.device != dev:
-        raise RuntimeError(f"mdt::unet_eval: engine lives on {eng.device}, tensors on {dev}")
+    eng = _engine_on(handle, dev, "mdt::unet_eval")
     xin = _f32c(xin)
     B = xin.shape[0]
     if tuple(xin.shape[1:]) != (eng.c.length, eng.c.in_pad):
@@ -411,9 +418,7 @@ def _(xin, embedding, c_noise, embedding_scale, handle):
 
 
 def _rows_engine(handle: int, dev, what: str):
-    eng = _engine(handle)
-    if eng.device != dev:
-        raise RuntimeError(f"{what}: engine lives on {eng.device}, tensors on {dev}")
+    eng = _engine_on(handle, dev, what)
     if not eng.c.rows:
         raise RuntimeError(f"{what}: the handle names an engine of the shared-row programs; the per-row form is compiled with "
                            "compile_unet(rows=True) (model.engine(device, n_ctx, batch, rows=True))")
@@ -553,18 +558,31 @@ def _(x0, noise, embedding, coef, handle, dynamic_threshold, seed, sample0):
     return x0.new_empty(x0.shape[0], dtype=torch.float32)
 
 
-@custom_op("mdt::sample", mutates_args=())
-def sample(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Optional[Tensor], sigmas: Tensor, handle: int,
-           pred_dim: int, rho: float, sigma_data: float, embedding_scale: float, clamp: bool, seed: int, sample0: int,
-           want_tokens: bool, dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
-    """The whole ADPM2 loop for an evaluated sigma schedule (num_steps + 1 values).  init_noise (B, C, L) / step_noise
-    (num_steps - 1, B, C, L): explicit draws in the reference's call order; each one that is None comes from the counter-based
-    generator keyed by (seed, draw index, sample0 + b) instead.  Returns (x (B, C, L), tokens (B, L) int32 or an empty tensor)."""
-    from .diffusion import ADPM2Sampler, NoiseSource, run_adpm2
+SAMPLER_KINDS = {kind: i for i, kind in enumerate(FUSED_SAMPLERS)}      # sampler_kind of mdt::sample_with
+
+
+def sampler_spec(sampler) -> Tuple[int, list]:
+    """(sampler_kind, sampler_params) of mdt::sample_with for a sampler object that may take the fused loop."""
+    kind = require_fused_kind(sampler)
+    return SAMPLER_KINDS[kind], [float(getattr(sampler, name)) for name in FUSED_SAMPLERS[kind].params]
+
+
+def _make_sampler(kind: int, params):
+    """The sampler object of sampler_spec()'s pair."""
+    kinds = list(FUSED_SAMPLERS.values())
+    if not 0 <= int(kind) < len(kinds) or len(params) != len(kinds[int(kind)].params):
+        table = ", ".join(f"{i} = {k.cls.__name__[:-len('Sampler')]} [{', '.join(k.params)}]" for i, k in enumerate(kinds))
+        raise RuntimeError(f"mdt::sample_with: sampler_kind {kind} with {len(params)} parameters ({table})")
+    k = kinds[int(kind)]
+    return k.cls(**dict(zip(k.params, params)))
+
+
+def _sample(op: str, make_sampler, embedding, init_noise, step_noise, sigmas, handle, pred_dim, sigma_data, embedding_scale,
+            clamp, seed, sample0, want_tokens, dynamic_threshold) -> Tuple[Tensor, Tensor]:
+    """mdt::sample and mdt::sample_with behind their schemas; ``make_sampler()`` gives the sampler object of the call."""
     dev = _hip(embedding, step_noise)
-    eng = _engine(handle)
-    if eng.device != dev:
-        raise RuntimeError(f"mdt::sample: engine lives on {eng.device}, tensors on {dev}")
+    eng = _engine_on(handle, dev, op)
+    sampler = make_sampler()
     B = embedding.shape[0]
     num_steps = sigmas.numel() - 1
     ns = NoiseSource(seed=int(seed), sample0=int(sample0))
@@ -572,48 +590,36 @@ def sample(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Optional
         ns.init = init_noise
     if step_noise is not None:
         if step_noise.shape[0] != max(num_steps - 1, 0):
-            raise RuntimeError(f"mdt::sample: step_noise holds {step_noise.shape[0]} draws, the loop makes {num_steps - 1}")
+            raise RuntimeError(f"{op}: step_noise holds {step_noise.shape[0]} draws, the loop makes {num_steps - 1}")
         ns.steps = lambda i: step_noise[i]
     tok = torch.zeros(B, eng.c.length, dtype=torch.int32, device=dev) if want_tokens else None
-    x = run_adpm2(eng, embedding, pred_dim, num_steps, ns, sigmas, ADPM2Sampler(rho=rho), float(sigma_data),
-                  float(embedding_scale), bool(clamp), None, None, tok if B else None, float(dynamic_threshold))
+    x = run_sampler(eng, embedding, pred_dim, num_steps, ns, sigmas, sampler, float(sigma_data), float(embedding_scale),
+                    bool(clamp), None, None, tok if B else None, float(dynamic_threshold))
     return x, (tok if want_tokens else torch.empty(0, dtype=torch.int32, device=dev))
 
 
-@sample.register_fake
-def _(embedding, init_noise, step_noise, sigmas, handle, pred_dim, rho, sigma_data, embedding_scale, clamp, seed, sample0,
-      want_tokens, dynamic_threshold=0.0):
+def _sample_fake(embedding, handle, pred_dim, want_tokens):
     eng = _engine(handle)
     B = embedding.shape[0]
     return (embedding.new_empty(B, pred_dim, eng.c.length, dtype=torch.float32),
             embedding.new_empty((B, eng.c.length) if want_tokens else (0,), dtype=torch.int32))
 
 
-SAMPLER_KINDS = {"adpm2": 0, "aeuler": 1, "karras": 2}      # sampler_kind of mdt::sample_with
+@custom_op("mdt::sample", mutates_args=())
+def sample(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Optional[Tensor], sigmas: Tensor, handle: int,
+           pred_dim: int, rho: float, sigma_data: float, embedding_scale: float, clamp: bool, seed: int, sample0: int,
+           want_tokens: bool, dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """The whole ADPM2 loop for an evaluated sigma schedule (num_steps + 1 values).  init_noise (B, C, L) / step_noise
+    (num_steps - 1, B, C, L): explicit draws in the reference's call order; each one that is None comes from the counter-based
+    generator keyed by (seed, draw index, sample0 + b) instead.  Returns (x (B, C, L), tokens (B, L) int32 or an empty tensor)."""
+    return _sample("mdt::sample", lambda: ADPM2Sampler(rho=rho), embedding, init_noise, step_noise, sigmas, handle, pred_dim,
+                   sigma_data, embedding_scale, clamp, seed, sample0, want_tokens, dynamic_threshold)
 
 
-def sampler_spec(sampler) -> Tuple[int, list]:
-    """(sampler_kind, sampler_params) of mdt::sample_with for a sampler object that may take the fused loop."""
-    from .diffusion import fused_sampler_kind
-    kind = fused_sampler_kind(sampler)
-    if kind is None:
-        raise TypeError(f"{type(sampler).__name__} has no fused loop")
-    params = {"adpm2": lambda s: [s.rho], "aeuler": lambda s: [],
-              "karras": lambda s: [s.s_tmin, s.s_tmax, s.s_churn, s.s_noise]}[kind](sampler)
-    return SAMPLER_KINDS[kind], [float(p) for p in params]
-
-
-def _make_sampler(kind: int, params):
-    from .diffusion import ADPM2Sampler, AEulerSampler, KarrasSampler, run_adpm2, run_aeuler, run_karras
-    want = {0: 1, 1: 0, 2: 4}.get(int(kind))
-    if want is None or len(params) != want:
-        raise RuntimeError(f"mdt::sample_with: sampler_kind {kind} with {len(params)} parameters (0 = ADPM2 [rho], 1 = AEuler [], "
-                           "2 = Karras [s_tmin, s_tmax, s_churn, s_noise])")
-    if kind == 0:
-        return ADPM2Sampler(rho=params[0]), run_adpm2
-    if kind == 1:
-        return AEulerSampler(), run_aeuler
-    return KarrasSampler(*params), run_karras
+@sample.register_fake
+def _(embedding, init_noise, step_noise, sigmas, handle, pred_dim, rho, sigma_data, embedding_scale, clamp, seed, sample0,
+      want_tokens, dynamic_threshold=0.0):
+    return _sample_fake(embedding, handle, pred_dim, want_tokens)
 
 
 @custom_op("mdt::sample_with", mutates_args=())
@@ -622,35 +628,16 @@ def sample_with(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Opt
                 clamp: bool, seed: int, sample0: int, want_tokens: bool, dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
     """mdt::sample with the sampler chosen by the caller: sampler_kind 0 = ADPM2Sampler (sampler_params [rho]), 1 =
     AEulerSampler ([]), 2 = KarrasSampler ([s_tmin, s_tmax, s_churn, s_noise]).  Every other argument and both results as
-    mdt::sample; each sampler makes one draw per step, so step_noise holds num_steps - 1 draws for all of them."""
-    from .diffusion import NoiseSource
-    dev = _hip(embedding, step_noise)
-    eng = _engine(handle)
-    if eng.device != dev:
-        raise RuntimeError(f"mdt::sample_with: engine lives on {eng.device}, tensors on {dev}")
-    sampler, run = _make_sampler(sampler_kind, list(sampler_params))
-    B = embedding.shape[0]
-    num_steps = sigmas.numel() - 1
-    ns = NoiseSource(seed=int(seed), sample0=int(sample0))
-    if init_noise is not None:
-        ns.init = init_noise
-    if step_noise is not None:
-        if step_noise.shape[0] != max(num_steps - 1, 0):
-            raise RuntimeError(f"mdt::sample_with: step_noise holds {step_noise.shape[0]} draws, the loop makes {num_steps - 1}")
-        ns.steps = lambda i: step_noise[i]
-    tok = torch.zeros(B, eng.c.length, dtype=torch.int32, device=dev) if want_tokens else None
-    x = run(eng, embedding, pred_dim, num_steps, ns, sigmas, sampler, float(sigma_data), float(embedding_scale), bool(clamp),
-            None, None, tok if B else None, float(dynamic_threshold))
-    return x, (tok if want_tokens else torch.empty(0, dtype=torch.int32, device=dev))
+    mdt::sample; each sampler makes one draw per step, so step_noise has num_steps - 1 draws for all of them."""
+    return _sample("mdt::sample_with", lambda: _make_sampler(sampler_kind, list(sampler_params)), embedding, init_noise,
+                   step_noise, sigmas, handle, pred_dim, sigma_data, embedding_scale, clamp, seed, sample0, want_tokens,
+                   dynamic_threshold)
 
 
 @sample_with.register_fake
 def _(embedding, init_noise, step_noise, sigmas, handle, pred_dim, sampler_kind, sampler_params, sigma_data, embedding_scale,
       clamp, seed, sample0, want_tokens, dynamic_threshold=0.0):
-    eng = _engine(handle)
-    B = embedding.shape[0]
-    return (embedding.new_empty(B, pred_dim, eng.c.length, dtype=torch.float32),
-            embedding.new_empty((B, eng.c.length) if want_tokens else (0,), dtype=torch.int32))
+    return _sample_fake(embedding, handle, pred_dim, want_tokens)
 
 
 @custom_op("mdt::all_gather_samples", mutates_args=())

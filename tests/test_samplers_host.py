@@ -87,7 +87,7 @@ def test_karras_plan_without_churn_and_with_a_final_zero_sigma():
     assert steps[-1].dt == -steps[-1].sigma_hat
     _, ae = aeuler_plan(4, hand, AEulerSampler(), 0.5)                          # AEuler: sigma_up = sigma_down = 0 there
     assert ae[-1].sigma_up == 0.0 and ae[-1].dt == -0.25 and len(plan_time_rows(ae)) == 3
-    # the ADPM2 plan's rows are what run_adpm2 uploads
+    # the ADPM2 plan's rows are what the ADPM2 loop uploads
     _, ad = D.adpm2_plan(6, KarrasSchedule(**SCHEDULE), ADPM2Sampler(rho=1), 0.5)
     assert plan_time_rows(ad) == [v for s in ad for v in (s.w.c_noise, s.w_mid.c_noise)]
 
@@ -159,6 +159,29 @@ def test_dispatch_predicate_honours_a_subclass_that_overrides_step():
     assert ops.sampler_spec(ADPM2Sampler(rho=1)) == (0, [1.0])
     with pytest.raises(TypeError, match="no fused loop"):
         ops.sampler_spec(MyEuler())
+
+
+def test_every_fused_kind_round_trips_through_the_sample_with_arguments():
+    """D.FUSED_SAMPLERS is the one table of kind -> class, parameters, plan, loop: what sampler_spec() says of a sampler of
+    every kind, _make_sampler() turns back into that sampler."""
+    from moleculediffusiontransformer_amd import ops
+    samplers = (ADPM2Sampler(rho=3.0), AEulerSampler(), KarrasSampler(0.05, 5.0, 4.0, 1.003))
+    assert [type(s) for s in samplers] == [k.cls for k in D.FUSED_SAMPLERS.values()]            # one of every kind
+    for i, (s, (name, k)) in enumerate(zip(samplers, D.FUSED_SAMPLERS.items())):
+        kind, params = ops.sampler_spec(s)
+        assert kind == i == ops.SAMPLER_KINDS[name] and fused_sampler_kind(s) == name
+        assert [getattr(k.cls(*params), n) for n in k.params] == params          # ... in the constructor's own order
+        back = ops._make_sampler(kind, params)
+        assert type(back) is type(s) and ops.sampler_spec(back) == (kind, params)
+        assert [getattr(back, n) for n in k.params] == [getattr(s, n) for n in k.params]
+        with pytest.raises(RuntimeError, match=f"sampler_kind {kind} with {len(params) + 1} parameters"):
+            ops._make_sampler(kind, params + [1.0])
+    with pytest.raises(RuntimeError) as e:
+        ops._make_sampler(3, [])
+    assert str(e.value) == ("mdt::sample_with: sampler_kind 3 with 0 parameters (0 = ADPM2 [rho], 1 = AEuler [], "
+                            "2 = Karras [s_tmin, s_tmax, s_churn, s_noise])")
+    with pytest.raises(RuntimeError, match="sampler_kind -1 with 1 parameters"):
+        ops._make_sampler(-1, [1.0])
 
 
 def test_sample_with_shape_inference_and_the_default_route(monkeypatch):
