@@ -524,6 +524,25 @@ int mdt_inpaint_merge(float *x, const float *src, const uint8_t *mask, const flo
 /* x += s * noise (inpaint re-noise, diffusion.py:546-547). */
 int mdt_add_noise(float *x, const float *noise, float s, uint64_t seed, uint32_t step, int64_t sample0,
                   int32_t B, int32_t C, int32_t L, void *stream);
+/* ---- fused inpainting entry and exit (ADPM2Sampler.inpaint, diffusion.py:526-549); additions inside ABI version 5.
+ * The source is given either dense, src fp32 (B,C,L) (draft == NULL), or as draft token ids, draft int32 (B,L) (src == NULL), which
+ * stand for their +-1 one-hot: src[b,c,l] = (c == draft[b,l]) ? 1 : -1 (encode_SMILES_into_one_hot, generative.py:1567-1569, :1603).
+ * keep is uint8 (B,C,L), or with keep_per_token != 0 uint8 (B,L) broadcast over the channels (in_paint_mask before its
+ * repeat 'b l -> b p l', generative.py:1600).  Non-zero = keep. ---- */
+/* The entry of one resample in one pass (in place on x):
+ *   x = keep ? src + sigma * n_src : x + renoise * n_re;   xin = c_in * x  (token-major, channels padded to Cp with 0)
+ * -- mdt_add_noise(renoise, n_re) (skipped when renoise == 0: the first resample of a step), mdt_inpaint_merge(sigma, n_src),
+ * mdt_precond_in(c_in), op for op: the result equals that composition bit for bit.  n_src / n_re == NULL: the counter-based
+ * generator keyed by (seed, step_src / step_re) at the global element index (sample0 + b)*C*L + c*L + l, as those two. */
+int mdt_inpaint_enter(float *x, float *xin, const float *src, const int32_t *draft, const uint8_t *keep,
+                      int32_t keep_per_token, const float *n_src, const float *n_re, float sigma, float renoise,
+                      float c_in, uint64_t seed, uint32_t step_src, uint32_t step_re, int64_t sample0, int32_t B,
+                      int32_t C, int32_t L, int32_t Cp, void *stream);
+/* The last merge (diffusion.py:549: sigma 0) and the decode (generative.py:1613-1614):
+ *   x = keep ? src : x;   tokens[b,l] = argmax_c x[b,c,l]   (first maximum, as mdt_argmax_tokens; tokens may be NULL)
+ * With draft ids and a per-token keep, a kept position's token is draft[b,l]. */
+int mdt_inpaint_finish(float *x, const float *src, const int32_t *draft, const uint8_t *keep, int32_t keep_per_token,
+                       int32_t *tokens, int32_t B, int32_t C, int32_t L, void *stream);
 /* Decode step after the path (generative.py:1212-1213): tokens[b,l] = argmax_c x[b,c,l] (int32). */
 int mdt_argmax_tokens(const float *x, int32_t *tokens, int32_t B, int32_t C, int32_t L, void *stream);
 

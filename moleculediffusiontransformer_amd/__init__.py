@@ -11,7 +11,8 @@ hand-written gfx950 kernels (csrc/, C ABI in include/mdt_hip.h).  So does the VA
 from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler,  # noqa: F401
                         KarrasSchedule, LogNormalDistribution, NoiseSource, Sampler)
 from .generative import (KDiffusion_mod, QMDiffusion, QMDiffusionForward, XDiffusion_x,  # noqa: F401
-                         generate_and_validate, predict_properties_from_tokens, tokens_to_forward_input)
+                         complete_and_validate, generate_and_validate, one_hot_draft, predict_properties_from_tokens,
+                         tokens_to_forward_input)
 from .graphmodel import AnalogDiffusionFull, AnalogDiffusionSparse  # noqa: F401
 from .modules import PositionalEncoding1D, UNetCFG1d  # noqa: F401
 from .netspec import UNetConfig, forward_unet_config, inverse_unet_config  # noqa: F401

@@ -498,6 +498,91 @@ __global__ __launch_bounds__(256) void k_inpaint_merge(float* x, const float* sr
   }
 }
 
+// The entry of one inpainting resample (diffusion.py:539-547, :810) in one pass: k_add_noise (re-noise of the previous resample,
+// skipped when renoise == 0), k_inpaint_merge and k_precond_in, op for op, on one read of x:
+//   x = keep ? src + sigma * n_src : x + renoise * n_re;   xin = c_in * x (token-major, padded)
+// src: dense fp32 (B, C, L), or draft ids (B, L) standing for their +-1 one-hot (generative.py:1567-1569, :1603).  keep: uint8
+// (B, C, L), or (B, L) broadcast over channels (keep_tok).  n_src / n_re == nullptr: the counter-based generator at draw index
+// step_src / step_re and the GLOBAL element index, as the flat kernels.  One workgroup per sample, as k_precond_in.
+__global__ __launch_bounds__(256) void k_inpaint_enter(float* x, float* xin, const float* src, const int32_t* draft,
+                                                        const uint8_t* keep, int keep_tok, const float* n_src,
+                                                        const float* n_re, float sigma, float renoise, float c_in,
+                                                        uint64_t seed, uint32_t step_src, uint32_t step_re, int64_t sample0,
+                                                        int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l, ot = (int64_t)b * L + l;
+    const uint64_t quad = (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2;
+    const uchar4 mk = *reinterpret_cast<const uchar4*>(keep + (keep_tok ? ot : o));
+    const bool kv[4] = {mk.x != 0, mk.y != 0, mk.z != 0, mk.w != 0};
+    const bool any = kv[0] || kv[1] || kv[2] || kv[3], all = kv[0] && kv[1] && kv[2] && kv[3];
+    const float4 v = *reinterpret_cast<const float4*>(x + o);
+    float xn[4] = {v.x, v.y, v.z, v.w};
+    if (renoise != 0.0f && !all) {                       // (a kept element's re-noised value is overwritten by the merge)
+      const float4 nz = n_re ? *reinterpret_cast<const float4*>(n_re + o) : normal4(seed, step_re, quad);
+      const float nv[4] = {nz.x, nz.y, nz.z, nz.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) xn[q] = xn[q] + renoise * nv[q];
+    }
+    if (any) {
+      float sv[4];
+      if (src) {
+        const float4 s4 = *reinterpret_cast<const float4*>(src + o);
+        sv[0] = s4.x; sv[1] = s4.y; sv[2] = s4.z; sv[3] = s4.w;
+      } else {
+        const int4 d4 = *reinterpret_cast<const int4*>(draft + ot);
+        sv[0] = c == d4.x ? 1.0f : -1.0f; sv[1] = c == d4.y ? 1.0f : -1.0f;
+        sv[2] = c == d4.z ? 1.0f : -1.0f; sv[3] = c == d4.w ? 1.0f : -1.0f;
+      }
+      if (sigma != 0.0f) {
+        const float4 nz = n_src ? *reinterpret_cast<const float4*>(n_src + o) : normal4(seed, step_src, quad);
+        const float nv[4] = {nz.x, nz.y, nz.z, nz.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (kv[q]) xn[q] = sv[q] + sigma * nv[q];
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (kv[q]) xn[q] = sv[q];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tile[(l + q) * (Cp + 1) + c] = c_in * xn[q];
+    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  }
+  tile_zero_pad(tile, C, L, Cp);
+  __syncthreads();
+  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+}
+
+// The last merge of ADPM2Sampler.inpaint (diffusion.py:549: sigma 0) and the decode (generative.py:1613-1614), one thread per
+// position: x = keep ? src : x; tokens[b,l] = argmax_c x[b,c,l] (first maximum, as k_argmax) -- with draft ids and a per-position
+// keep, a kept position's token is its draft id.  src / draft / keep / keep_tok as k_inpaint_enter; tokens may be nullptr.
+__global__ __launch_bounds__(256) void k_inpaint_finish(float* x, const float* src, const int32_t* draft, const uint8_t* keep,
+                                                         int keep_tok, int32_t* tokens, int B, int C, int L) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * L) return;
+  const int b = (int)(i / L), l = (int)(i - (int64_t)b * L);
+  const int d = draft ? draft[i] : -1;
+  const bool kt = keep_tok && keep[i] != 0;
+  float* p = x + (int64_t)b * C * L + l;
+  float best = 0.f;
+  int arg = 0;
+  for (int c = 0; c < C; ++c) {
+    const int64_t o = (int64_t)c * L;
+    float v = p[o];
+    if (keep_tok ? kt : keep[(int64_t)b * C * L + l + o] != 0) {
+      v = src ? src[(int64_t)b * C * L + l + o] : (c == d ? 1.0f : -1.0f);
+      p[o] = v;
+    }
+    if (c == 0 || v > best || (v != v && best == best)) { best = v; arg = c; }
+  }
+  if (tokens) tokens[i] = (draft && kt) ? d : arg;
+}
+
 // dst[0..n) = src[0..n): the FiLM rows of ONE evaluation out of the table the time program fills once per call.  One small launch on
 // the caller's stream (hipMemcpyAsync of the same bytes ran as up to three runtime copy kernels of ~4 us each in front of every
 // evaluation graph: profiles/r6_kernel_stats.csv, __amd_rocclr_copyBuffer).
@@ -1010,6 +1095,31 @@ int mdt_inpaint_merge(float* x, const float* src, const uint8_t* mask, const flo
   hipLaunchKernelGGL(mdt::k_inpaint_merge, dim3(mdt::grid_for(n4)), dim3(256), 0, (hipStream_t)stream, x, src, mask,
                      noise, sigma, seed, step, sample0 * C * L, n4);
   return finish("mdt_inpaint_merge");
+}
+
+int mdt_inpaint_enter(float* x, float* xin, const float* src, const int32_t* draft, const uint8_t* keep,
+                      int32_t keep_per_token, const float* n_src, const float* n_re, float sigma, float renoise, float c_in,
+                      uint64_t seed, uint32_t step_src, uint32_t step_re, int64_t sample0, int32_t B, int32_t C, int32_t L,
+                      int32_t Cp, void* stream) {
+  MDT_CHECK_TILE("mdt_inpaint_enter")
+  if (!x || !xin || !keep) return bad("mdt_inpaint_enter: null pointer");
+  if (!src == !draft) return bad("mdt_inpaint_enter: give the source either dense (src) or as draft ids (draft)");
+  MDT_BIG_LDS(mdt::k_inpaint_enter);
+  hipLaunchKernelGGL(mdt::k_inpaint_enter, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, src, draft, keep,
+                     keep_per_token ? 1 : 0, n_src, n_re, sigma, renoise, c_in, seed, step_src, step_re, sample0, C, L, Cp);
+  return finish("mdt_inpaint_enter");
+}
+
+int mdt_inpaint_finish(float* x, const float* src, const int32_t* draft, const uint8_t* keep, int32_t keep_per_token,
+                       int32_t* tokens, int32_t B, int32_t C, int32_t L, void* stream) {
+  if (B <= 0) return 0;
+  if (!x || !keep) return bad("mdt_inpaint_finish: null pointer");
+  if (!src == !draft) return bad("mdt_inpaint_finish: give the source either dense (src) or as draft ids (draft)");
+  if (C <= 0 || L <= 0) return bad("mdt_inpaint_finish: bad dims");
+  const int64_t n = (int64_t)B * L;
+  hipLaunchKernelGGL(mdt::k_inpaint_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, src, draft,
+                     keep, keep_per_token ? 1 : 0, tokens, B, C, L);
+  return finish("mdt_inpaint_finish");
 }
 
 int mdt_adpm2_euler(const float* x_base, const float* x_from, const float* denoised, const float* noise, float* out,

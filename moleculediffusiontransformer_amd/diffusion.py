@@ -162,6 +162,8 @@ class ADPM2Sampler(_LoopSampler):
         fused = self._fused(fn)
         if fused is not None:
             return fused.inpaint(source, mask, self, sigmas, num_steps, num_resamples)
+        if not source.is_floating_point():
+            raise TypeError("draft token ids drive the fused path only; pass the one-hot draft (one_hot_draft) with a custom fn")
         x = float(sigmas[0]) * torch.randn_like(source)
         for i in range(num_steps - 1):
             source_noisy = source + float(sigmas[i]) * torch.randn_like(source)
@@ -537,8 +539,12 @@ class DiffusionInpainter(nn.Module):
         self.sigma_schedule = sigma_schedule
 
     @torch.no_grad()
-    def forward(self, inpaint: Tensor, inpaint_mask: Tensor, *, draw=None, seed=None, **kwargs) -> Tensor:
-        fn = BoundDenoise(self.denoise_fn, kwargs, dict(draw=draw, seed=seed))
+    def forward(self, inpaint: Tensor, inpaint_mask: Tensor, *, draw=None, seed=None, sample0: int = 0, tokens=None,
+                **kwargs) -> Tensor:
+        """``inpaint`` / ``inpaint_mask``: the dense fp32 (B, C, L) source and its bool mask, as in the reference -- or, on the
+        fused path only, integer (B, L) draft ids and the bool (B, L) keep mask (run_adpm2_inpaint's token form).  ``tokens``
+        (B, L) int32: receives the decode of the result (fused path)."""
+        fn = BoundDenoise(self.denoise_fn, kwargs, dict(draw=draw, seed=seed, sample0=sample0, tokens=tokens))
         return self.inpaint_fn(source=inpaint, mask=inpaint_mask, fn=fn, sigmas=self.sigma_schedule(self.num_steps, inpaint.device),
                                num_steps=self.num_steps, num_resamples=self.num_resamples)
 
@@ -764,31 +770,49 @@ def run_sampler(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise:
 def run_adpm2_inpaint(engine, embedding: Tensor, source: Tensor, mask: Tensor, num_steps: int, num_resamples: int,
                       draw: Optional[Callable[[], Tensor]], seed: Optional[int], schedule,
                       sampler: ADPM2Sampler, sigma_data: float, embedding_scale: float = 1.0,
-                      sample0: int = 0, dynamic_threshold: float = 0.0) -> Tensor:
+                      sample0: int = 0, dynamic_threshold: float = 0.0, *, draft: Optional[Tensor] = None,
+                      keep: Optional[Tensor] = None, pred_dim: Optional[int] = None, tokens: Optional[Tensor] = None) -> Tensor:
     """ADPM2Sampler.inpaint (diffusion.py:526-549) behind DiffusionInpainter.forward (:612-625).
     ``draw()`` returns the next torch.randn_like tensor in the reference's call order (parity mode);
-    otherwise draws come from the counter-based generator keyed by (seed, draw index)."""
+    otherwise draws come from the counter-based generator keyed by (seed, draw index).
+
+    The source comes dense -- ``source`` fp32 (B, C, L) with the bool ``mask`` of its shape -- or, with ``source`` and ``mask``
+    None, as token ids: ``draft`` integer (B, L) standing for its +-1 one-hot over ``pred_dim`` channels and ``keep`` bool
+    (B, L), the mask before its repeat over the channels (generative.py:1600-1603).  Both forms run the same loop on
+    mdt_inpaint_enter / mdt_inpaint_finish.  ``tokens`` (B, L) int32: also the decode of the result (argmax over channels; with a
+    draft, the draft id at a kept position), written by mdt_inpaint_finish."""
     sigmas, steps = adpm2_plan(num_steps, schedule, sampler, sigma_data)
-    if mask.dtype != torch.bool or tuple(mask.shape) != tuple(source.shape):
-        raise ValueError("in_paint_mask must be a bool tensor of the same shape as inpaint")
     dev = engine.device
+    if source is not None:
+        if draft is not None or keep is not None:
+            raise ValueError("give the source either dense (source, mask) or as token ids (draft, keep)")
+        if mask.dtype != torch.bool or tuple(mask.shape) != tuple(source.shape):
+            raise ValueError("in_paint_mask must be a bool tensor of the same shape as inpaint")
+        shape, per_token, kp = tuple(source.shape), 0, mask
+    else:
+        if draft is None or keep is None or pred_dim is None:
+            raise ValueError("the token form needs draft, keep and pred_dim")
+        if draft.dim() != 2 or keep.dtype != torch.bool or tuple(keep.shape) != tuple(draft.shape):
+            raise ValueError("draft must be (B, L) token ids and keep a bool tensor of the same shape")
+        shape, per_token, kp = (draft.shape[0], int(pred_dim), draft.shape[1]), 1, keep
     with torch.cuda.device(dev):
-        lp = _Loop(engine, embedding, tuple(source.shape), sigmas, steps, lambda k: None if draw is None else draw(), seed,
+        lp = _Loop(engine, embedding, shape, sigmas, steps, lambda k: None if draw is None else draw(), seed,
                    sample0, embedding_scale, dynamic_threshold)
         lib, x, st = lp.lib, lp.x, lp.st
         B, C, L, Cp = lp.dims()
-        src = _f32(source, dev)
-        mk = mask.to(device=dev).to(torch.uint8).contiguous()
+        src = None if source is None else _f32(source, dev)
+        ids = None if draft is None else draft.to(device=dev, dtype=torch.int32).contiguous()
+        mk = kp.to(device=dev).to(torch.uint8).contiguous()
         x_mid = torch.empty_like(x)
         for i, s in enumerate(steps):
             src_nz, src_k = lp.draw()                     # source_noisy = source + sigmas[i] * randn_like(source)
+            re_nz, re_k, renoise = None, 0, 0.0           # the re-noise of the previous resample: applied on entry to the next
             for r in range(num_resamples):
-                rt.check(lib.mdt_inpaint_merge(rt.ptr(x), rt.ptr(src), rt.ptr(mk), rt.ptr(src_nz), s.sigma, lp.seed,
-                                               src_k, sample0, B, C, L, st))
-                rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(engine.xin), s.w.c_in, B, C, L, Cp, st))
+                rt.check(lib.mdt_inpaint_enter(rt.ptr(x), rt.ptr(engine.xin), rt.ptr(src), rt.ptr(ids), rt.ptr(mk), per_token,
+                                               rt.ptr(src_nz), rt.ptr(re_nz), s.sigma, renoise, s.w.c_in, lp.seed, src_k, re_k,
+                                               sample0, B, C, L, Cp, st))
                 _adpm2_step(lp, i, s, x_mid, None, 0)
                 if r < num_resamples - 1:
-                    nz, k = lp.draw()
-                    rt.check(lib.mdt_add_noise(rt.ptr(x), rt.ptr(nz), s.renoise, lp.seed, k, sample0, B, C, L, st))
-        rt.check(lib.mdt_inpaint_merge(rt.ptr(x), rt.ptr(src), rt.ptr(mk), 0, 0.0, lp.seed, 0, sample0, B, C, L, st))
+                    (re_nz, re_k), renoise = lp.draw(), s.renoise
+        rt.check(lib.mdt_inpaint_finish(rt.ptr(x), rt.ptr(src), rt.ptr(ids), rt.ptr(mk), per_token, rt.ptr(tokens), B, C, L, st))
         return lp.finish(x, decoded=True)

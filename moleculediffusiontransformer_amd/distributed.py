@@ -89,3 +89,23 @@ def sample_tokens_sharded(local_sample_tokens: Callable[[Tensor, int], Tensor], 
     if world == 1:
         return local.long()
     return all_gather_tokens(local, sequences.shape[0], vocab, group)
+
+
+def inpaint_tokens_sharded(local_inpaint_tokens: Callable[[Tensor, Tensor, Tensor, int], Tensor], sequences: Tensor,
+                           draft_tokens: Tensor, keep_mask: Tensor, vocab: int, group=None, model=None,
+                           guided: bool = False) -> Tensor:
+    """As sample_tokens_sharded, for draft completion: every rank passes the same global ``sequences`` (B, n), ``draft_tokens``
+    and ``keep_mask`` (B, L); rank r completes its contiguous slice via
+    ``local_inpaint_tokens(seq_slice, draft_slice, keep_slice, first_global_index) -> (b_r, L)`` token ids
+    (model.inpaint_tokens(..., seed=s, sample0=first_global_index)) and all ranks receive the full (B, L) result."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    total = sequences.shape[0]
+    if draft_tokens.shape[0] != total or keep_mask.shape[0] != total:
+        raise ValueError(f"sequences, draft_tokens and keep_mask must hold the same {total} samples")
+    pin_for_shards(model, total, world, guided)
+    lo, hi = shard_bounds(total, world, rank)
+    local = local_inpaint_tokens(sequences[lo:hi], draft_tokens[lo:hi], keep_mask[lo:hi], lo)
+    if world == 1:
+        return local.long()
+    return all_gather_tokens(local, total, vocab, group)

@@ -141,9 +141,22 @@ class _FusedLoop:
         draw, seed = self.extra.get("draw"), self.extra.get("seed")
         if draw is None and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return run_adpm2_inpaint(eng, emb, source, mask, num_steps, num_resamples, draw, seed, sigmas, sampler,
-                                 o.diffusion.diffusion.sigma_data, self.kw.get("embedding_scale", 1.0),
-                                 dynamic_threshold=float(o.diffusion.diffusion.dynamic_threshold))
+        sample0, tok, kd = int(self.extra.get("sample0") or 0), self.extra.get("tokens"), o.diffusion.diffusion
+        scale = self.kw.get("embedding_scale", 1.0)
+        if source.is_floating_point():
+            return run_adpm2_inpaint(eng, emb, source, mask, num_steps, num_resamples, draw, seed, sigmas, sampler, kd.sigma_data,
+                                     scale, sample0, float(kd.dynamic_threshold), tokens=tok)
+        # a draft of token ids (inpaint_tokens): without a draw callback the whole loop is ONE custom op, as mdt::sample is
+        if draw is None and type(sampler) is ADPM2Sampler:
+            x, t = torch.ops.mdt.inpaint_tokens(emb, source, mask, torch.as_tensor(sigmas, dtype=torch.float32).cpu(),
+                                                ops.register_engine(eng), o.pred_dim, int(num_resamples), float(sampler.rho),
+                                                float(kd.sigma_data), float(scale), int(seed), sample0,
+                                                float(kd.dynamic_threshold))
+            if tok is not None:
+                tok.copy_(t)
+            return x
+        return run_adpm2_inpaint(eng, emb, None, None, num_steps, num_resamples, draw, seed, sigmas, sampler, kd.sigma_data, scale,
+                                 sample0, float(kd.dynamic_threshold), draft=source, keep=mask, pred_dim=o.pred_dim, tokens=tok)
 
 
 class _QMBase(nn.Module):
@@ -434,12 +447,47 @@ class _QMBase(nn.Module):
         return (tok, x) if return_sample else tok
 
     def inpaint(self, sequences, device, cond_scale=7.5, timesteps=100, num_resamples=1, inpaint=None,
-                in_paint_mask=None, *, draw=None, seed=None):
+                in_paint_mask=None, *, draw=None, seed=None, sample0=0):
+        """``sample0``: the global index of this call's first sample (seed mode: the counter-based draws are keyed by
+        sample0 + b, so a batch split over calls or ranks returns the rows of the whole batch)."""
         emb = self._embed(sequences, device)
         return self.diffusion.inpaint(num_steps=timesteps, num_resamples=num_resamples, sampler=ADPM2Sampler(rho=1),
                                       sigma_schedule=KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0),
                                       inpaint=inpaint, in_paint_mask=in_paint_mask, embedding=emb,
-                                      embedding_scale=cond_scale, draw=draw, seed=seed)
+                                      embedding_scale=cond_scale, draw=draw, seed=seed, sample0=sample0)
+
+    def inpaint_tokens(self, sequences, device, draft_tokens, keep_mask, cond_scale=7.5, timesteps=100, num_resamples=1, *,
+                       draw=None, seed=None, sample0=0, return_sample: bool = False):
+        """inpaint() for a draft given as token ids, decoded: what inpaint_from_draft_and_conditioning does around
+        model.inpaint (generative.py:1600-1614) -- the +-1 one-hot of the draft, the mask repeated over the channels, the
+        argmax of the result -- inside the loop's own kernels (mdt_inpaint_enter / mdt_inpaint_finish), so neither the (B, C, L)
+        source nor the full-shape mask is ever built.  ``draft_tokens``: integer (B, max_length), ids in [0, pred_dim);
+        ``keep_mask``: bool (B, max_length), True = keep the position (the reference's in_paint_mask before its repeat).
+        Returns (B, max_length) int64 token ids on ``device`` -- the draft id at a kept position -- and with ``return_sample``
+        also the fp32 sample, bit for bit inpaint()'s on one_hot_draft(draft_tokens, pred_dim) and the repeated mask."""
+        draft_tokens, keep_mask = torch.as_tensor(draft_tokens), torch.as_tensor(keep_mask)
+        B, L = sequences.shape[0], self.max_length
+        if draft_tokens.is_floating_point() or draft_tokens.is_complex() or draft_tokens.dtype == torch.bool:
+            raise ValueError(f"draft_tokens must hold integer token ids, got {draft_tokens.dtype}")
+        if keep_mask.dtype != torch.bool:
+            raise ValueError(f"keep_mask must be a bool tensor (True = keep), got {keep_mask.dtype}")
+        if tuple(draft_tokens.shape) != (B, L) or tuple(keep_mask.shape) != (B, L):
+            raise ValueError(f"draft_tokens and keep_mask must be ({B}, {L}); got {tuple(draft_tokens.shape)} and "
+                             f"{tuple(keep_mask.shape)}")
+        device = torch.device(device)
+        if B == 0:                                  # nothing to complete (sample() returns an empty tensor too)
+            tok, x = torch.zeros(0, L, dtype=torch.int64, device=device), torch.empty(0, self.pred_dim, L, device=device)
+            return (tok, x) if return_sample else tok
+        lo, hi = (int(v) for v in torch.aminmax(draft_tokens))
+        if lo < 0 or hi >= self.pred_dim:
+            raise ValueError(f"draft_tokens holds ids in [{lo}, {hi}], the model has pred_dim = {self.pred_dim} classes")
+        tok = torch.zeros(B, L, dtype=torch.int32, device=device)
+        emb = self._embed(sequences, device)
+        x = self.diffusion.inpaint(num_steps=timesteps, num_resamples=num_resamples, sampler=ADPM2Sampler(rho=1),
+                                   sigma_schedule=KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0),
+                                   inpaint=draft_tokens.to(device), in_paint_mask=keep_mask.to(device), embedding=emb,
+                                   embedding_scale=cond_scale, draw=draw, seed=seed, sample0=sample0, tokens=tok)
+        return (tok.long(), x) if return_sample else tok.long()
 
 
 class QMDiffusion(_QMBase):
@@ -532,4 +580,32 @@ def generate_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForwa
                                            X_norm_factor=X_norm_factor,
                                            context_embedding_max_length=conditioning.shape[1], noise=forward_noise,
                                            sampler=sampler, sigma_schedule=sigma_schedule)
+    return tokens, props
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the draft-completion chain of the reference's callers (inpaint_from_draft_and_conditioning), kept on the device
+# ----------------------------------------------------------------------------------------------------------------------
+def one_hot_draft(tokens: Tensor, num_classes: int) -> Tensor:
+    """The tensor half of encode_SMILES_into_one_hot (generative.py:1567-1569) and the permute of its caller (:1603): token ids
+    (B, L) -> fp32 (B, num_classes, L) with +1 at the id's channel and -1 elsewhere.  What the dense inpaint() takes as
+    ``inpaint``; inpaint_tokens() never builds it."""
+    tok = torch.as_tensor(tokens).long()
+    cls = torch.arange(num_classes, device=tok.device).view(1, num_classes, 1)
+    return torch.where(tok.unsqueeze(1) == cls, 1.0, -1.0).to(torch.float32)
+
+
+def complete_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForward", conditioning: Tensor, draft_tokens: Tensor,
+                          keep_mask: Tensor, device, cond_scale: float = 1.0, timesteps: int = 100,
+                          forward_timesteps: int = 100, num_resamples: int = 1, X_norm_factor: float = 1.0, forward_noise=None, *,
+                          draw=None, seed=None, sample0: int = 0):
+    """inpaint_from_draft_and_conditioning's core (generative.py:1600-1660) without leaving the GPU: complete the draft under
+    the conditioning -- kept positions stay, the rest is regenerated -- decode inside the loop's last kernel, re-predict the
+    properties of the completed molecules with the forward model.  Returns (tokens (B, L) int64, predicted properties
+    (B, n_cond)).  ``draw`` / ``seed`` / ``sample0`` as inpaint_tokens; ``forward_noise`` as generate_and_validate."""
+    tokens = model.inpaint_tokens(conditioning, device, draft_tokens, keep_mask, cond_scale=cond_scale, timesteps=timesteps,
+                                  num_resamples=num_resamples, draw=draw, seed=seed, sample0=sample0)
+    props = predict_properties_from_tokens(model_forward, tokens, device, cond_scale=1.0, timesteps=forward_timesteps,
+                                           X_norm_factor=X_norm_factor,
+                                           context_embedding_max_length=conditioning.shape[1], noise=forward_noise)
     return tokens, props

@@ -17,6 +17,7 @@ fake / meta tensors).
     karras_hat / _mid / _next   the three stages of KarrasSampler.step (diffusion.py:417-435)
     sample              DiffusionSampler.forward + ADPM2Sampler.forward, the whole loop (diffusion.py:577-591, :517-524)
     sample_with         the same with the sampler chosen: ADPM2Sampler, AEulerSampler (:476-483) or KarrasSampler (:437-453)
+    inpaint_tokens      DiffusionInpainter.forward + ADPM2Sampler.inpaint on a draft of token ids, decoded (diffusion.py:526-549, :612-625)
     all_gather_samples  the one collective of a sharded call (RCCL all_gather_into_tensor)
     precond_in_rows / precond_out_rows   the denoise scaling with ONE coefficient per sample (denoise_fn(sigmas=(B,)))
     unet_eval_rows      net(x, time=(B,), ...) as ONE evaluation: one time-mapping / FiLM row per sample
@@ -31,7 +32,7 @@ import torch
 from torch.library import custom_op
 
 from . import runtime as rt
-from .diffusion import FUSED_SAMPLERS, ADPM2Sampler, NoiseSource, require_fused_kind, run_sampler
+from .diffusion import FUSED_SAMPLERS, ADPM2Sampler, NoiseSource, require_fused_kind, run_adpm2_inpaint, run_sampler
 
 Tensor = torch.Tensor
 
@@ -638,6 +639,36 @@ def sample_with(embedding: Tensor, init_noise: Optional[Tensor], step_noise: Opt
 def _(embedding, init_noise, step_noise, sigmas, handle, pred_dim, sampler_kind, sampler_params, sigma_data, embedding_scale,
       clamp, seed, sample0, want_tokens, dynamic_threshold=0.0):
     return _sample_fake(embedding, handle, pred_dim, want_tokens)
+
+
+@custom_op("mdt::inpaint_tokens", mutates_args=())
+def inpaint_tokens(embedding: Tensor, draft: Tensor, keep: Tensor, sigmas: Tensor, handle: int, pred_dim: int,
+                   num_resamples: int, rho: float, sigma_data: float, embedding_scale: float, seed: int, sample0: int,
+                   dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """The whole ADPM2 inpainting loop (ADPM2Sampler.inpaint, diffusion.py:526-549) for an evaluated sigma schedule (num_steps + 1
+    values) on a draft given as token ids: draft (B, L) integer ids in [0, pred_dim) standing for their +-1 one-hot, keep (B, L)
+    bool, True = keep the position.  Every draw comes from the counter-based generator keyed by (seed, draw index, sample0 + b).
+    Returns (x (B, pred_dim, L) fp32, tokens (B, L) int32: argmax over channels, the draft id at a kept position)."""
+    dev = _hip(embedding, draft, keep)
+    eng = _engine_on(handle, dev, "mdt::inpaint_tokens")
+    B = embedding.shape[0]
+    if draft.is_floating_point() or keep.dtype != torch.bool or tuple(draft.shape) != (B, eng.c.length) or keep.shape != draft.shape:
+        raise RuntimeError(f"mdt::inpaint_tokens: draft must be integer ids and keep bool, both ({B}, {eng.c.length}); got "
+                           f"{draft.dtype} {tuple(draft.shape)} and {keep.dtype} {tuple(keep.shape)}")
+    tok = torch.zeros(B, eng.c.length, dtype=torch.int32, device=dev)
+    if B == 0:
+        return torch.empty(0, pred_dim, eng.c.length, device=dev), tok
+    x = run_adpm2_inpaint(eng, embedding, None, None, sigmas.numel() - 1, int(num_resamples), None, int(seed), sigmas,
+                          ADPM2Sampler(rho=rho), float(sigma_data), float(embedding_scale), int(sample0), float(dynamic_threshold),
+                          draft=draft, keep=keep, pred_dim=int(pred_dim), tokens=tok)
+    return x, tok
+
+
+@inpaint_tokens.register_fake
+def _(embedding, draft, keep, sigmas, handle, pred_dim, num_resamples, rho, sigma_data, embedding_scale, seed, sample0,
+      dynamic_threshold=0.0):
+    B, L = draft.shape
+    return embedding.new_empty(B, pred_dim, L, dtype=torch.float32), draft.new_empty((B, L), dtype=torch.int32)
 
 
 @custom_op("mdt::all_gather_samples", mutates_args=())
