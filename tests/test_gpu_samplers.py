@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from elem_ref import dyn_scale_ref
 from gpu_util import DEV, make_model, rnd
 from helpers import noise_fns, to_t
 from moleculediffusiontransformer_amd import ADPM2Sampler, AEulerSampler, KarrasSampler, KarrasSchedule, NoiseSource
@@ -119,7 +120,10 @@ def _dyn(lib, gx, gp, c_skip, c_out, dims, st, on):
     B, C, L, Cp = dims
     ds = torch.empty(B, device=DEV)
     rt.check(lib.mdt_dyn_scale(rt.ptr(gx), rt.ptr(gp), rt.ptr(ds), c_skip, c_out, 0.9, B, C, L, Cp, st))
-    return ds
+    # the expected scale is the bit-level host reference's (tests/elem_ref.py), which the kernel's has to equal
+    want = dyn_scale_ref(gx.cpu(), gp.cpu(), c_skip, c_out, 0.9)
+    assert torch.equal(ds.cpu(), want), (ds.cpu(), want)
+    return want.to(DEV)
 
 
 def _same(got, want, dyn):
