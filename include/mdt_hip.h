@@ -453,6 +453,12 @@ int mdt_loss_rows(const float *x0, const float *x_noisy, const float *pred, cons
                   void *stream);
 /* UNetCFG1d.forward guidance mix (modules.py:1253): out = um + (cond - um) * scale, token-major. */
 int mdt_cfg_mix(const float *cond, const float *uncond, float *out, float scale, int64_t n, void *stream);
+/* The mix with one scale per sample, rows of row_elems floats (a positive multiple of 4; any B, any total):
+ *   out[b] = scale[b] == 1 ? cond[b] : uncond[b] + (cond[b] - uncond[b]) * scale[b]
+ * in mdt_cfg_mix's evaluation order.  At scale 1 the reference skips guidance (modules.py:1248): the row is cond bit for bit and
+ * uncond is not read.  out == cond (in place) is allowed.  scale: B floats on the device. */
+int mdt_cfg_mix_rows(const float *cond, const float *uncond, float *out, const float *scale, int32_t B, int64_t row_elems,
+                     void *stream);
 /* First half of ADPM2Sampler.step (diffusion.py:506-508) fused with the denoise output:
  *   D = clamp(c_skip*x + c_out*pred, -1, 1); d = (x - D) / sigma; x_mid = x + d * dt_mid
  * and, for the next U-Net call, xin_mid = c_in_mid * x_mid (token-major, padded). */

@@ -614,6 +614,29 @@ __global__ __launch_bounds__(256) void k_cfg_mix(const float* cond, const float*
   }
 }
 
+// k_cfg_mix with one scale per sample: out[b] = scale[b] == 1 ? cond[b] : um[b] + (cond[b] - um[b]) * scale[b].  A row of row4
+// float4s is cut into segments of G float4s (G a power of two <= 256: the lanes of one segment); a workgroup holds 256 / G
+// segments per trip of the grid-stride loop over the B * segs segments.  A segment reads its sample's scale once; at scale 1 the
+// reference skips guidance (modules.py:1248) -- um is not read, and u + (c - u) would not be c in fp32.
+__global__ __launch_bounds__(256) void k_cfg_mix_rows(const float* cond, const float* um, float* out, const float* scale,
+                                                       int64_t row4, int64_t segs, int64_t units, int G) {
+  const int per_wg = 256 / G, lane = threadIdx.x & (G - 1);
+  for (int64_t u = blockIdx.x * (int64_t)per_wg + threadIdx.x / G; u < units; u += (int64_t)gridDim.x * per_wg) {
+    const int64_t b = u / segs, i = (u - b * segs) * G + lane;
+    if (i >= row4) continue;
+    const float s = scale[b];
+    const int64_t o = b * row4 + i;
+    const float4 c = reinterpret_cast<const float4*>(cond)[o];
+    if (s == 1.0f) {
+      reinterpret_cast<float4*>(out)[o] = c;
+    } else {
+      const float4 v = reinterpret_cast<const float4*>(um)[o];
+      reinterpret_cast<float4*>(out)[o] = make_float4(v.x + (c.x - v.x) * s, v.y + (c.y - v.y) * s, v.z + (c.z - v.z) * s,
+                                                      v.w + (c.w - v.w) * s);
+    }
+  }
+}
+
 // tokens[b,l] = argmax_c x[b,c,l] (first maximum, as torch.argmax)          (generative.py:1212-1213)
 __global__ __launch_bounds__(256) void k_argmax(const float* x, int32_t* tok, int B, int C, int L) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -1156,6 +1179,20 @@ int mdt_cfg_mix(const float* cond, const float* uncond, float* out, float scale,
   hipLaunchKernelGGL(mdt::k_cfg_mix, dim3(mdt::grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, cond, uncond, out,
                      scale, n / 4);
   return finish("mdt_cfg_mix");
+}
+
+int mdt_cfg_mix_rows(const float* cond, const float* uncond, float* out, const float* scale, int32_t B, int64_t row_elems,
+                     void* stream) {
+  if (B <= 0) return 0;
+  if (!cond || !uncond || !out || !scale) return bad("mdt_cfg_mix_rows: null pointer");
+  if (row_elems <= 0 || row_elems % 4) return bad("mdt_cfg_mix_rows: row_elems must be a positive multiple of 4");
+  const int64_t row4 = row_elems / 4;
+  int G = 256;                                          // lanes of a segment: the power of two that covers a short row
+  while (G > 1 && G / 2 >= row4) G /= 2;
+  const int64_t segs = (row4 + G - 1) / G, units = (int64_t)B * segs;
+  hipLaunchKernelGGL(mdt::k_cfg_mix_rows, dim3(mdt::grid_for(units * G)), dim3(256), 0, (hipStream_t)stream, cond, uncond, out,
+                     scale, row4, segs, units, G);
+  return finish("mdt_cfg_mix_rows");
 }
 
 int mdt_argmax_tokens(const float* x, int32_t* tokens, int32_t B, int32_t C, int32_t L, void* stream) {

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Callable, List, NamedTuple, Optional
+from typing import Callable, List, NamedTuple, Optional, Union
 
 import torch
 import torch.nn as nn
@@ -556,6 +556,59 @@ def _f32(t: Tensor, device) -> Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def guidance_rows(cond_scale, B: int, name: str = "cond_scale") -> Union[float, Tensor]:
+    """The guidance scale of a call in the form the fused loops take: a float -- ONE scale for the batch, today's path -- or an
+    fp32 CPU tensor of B values, one per sample (mdt_cfg_mix_rows).
+
+    A Python number or a 0-dim tensor / array gives the float.  A 1-D list, tuple, ndarray or tensor of exactly B finite values
+    gives the tensor -- or, when all its values are equal, that value as a float: the call is then literally the scalar call.
+    Anything else raises ValueError naming the argument (``name``).  Sample b at scale 1 is not guided, as in the reference
+    (modules.py:1248): it keeps its conditional prediction bit for bit."""
+    def refuse(why):
+        return ValueError(f"{name} must be a number or hold one finite value per sample ({B}): {why}")
+    if isinstance(cond_scale, (bool, complex)):
+        raise refuse(f"got a {type(cond_scale).__name__}")
+    if isinstance(cond_scale, (int, float)):
+        if not math.isfinite(cond_scale):
+            raise refuse(f"got {cond_scale}")
+        return float(cond_scale)
+    try:
+        t = torch.as_tensor(cond_scale)
+    except Exception as e:
+        raise refuse(f"got {type(cond_scale).__name__} ({e})") from None
+    if t.dtype == torch.bool or t.is_complex():
+        raise refuse(f"got dtype {t.dtype}")
+    if t.dim() > 1:
+        raise refuse(f"got {t.dim()} dimensions, shape {tuple(t.shape)}")
+    if t.dim() == 0:
+        return guidance_rows(t.item(), B, name)
+    # rounded to fp32 once, here: the kernels take the scale as a float
+    t = t.detach().to(device="cpu", dtype=torch.float32)
+    if not bool(torch.isfinite(t).all()):
+        raise refuse("got a NaN or an infinity")
+    if t.numel() != B:
+        raise refuse(f"got {t.numel()} values")
+    if B == 0:
+        return 1.0                                   # an empty batch: nothing to guide
+    if bool((t == t[0]).all()):
+        return float(t[0])
+    return t.contiguous().clone()
+
+
+def is_guided(scale) -> bool:
+    """Whether a normalised guidance scale (guidance_rows) asks for the unconditional pass: a float != 1, or a tensor."""
+    return isinstance(scale, torch.Tensor) or scale != 1.0
+
+
+def scalar_guidance(scale, what: str) -> float:
+    """The scale for a per-step seam (a caller's fn, a sampler with its own step(), denoise_fn / net() called directly): these
+    evaluate the network with ONE scale."""
+    if isinstance(scale, (list, tuple)) or getattr(scale, "ndim", 0) > 0:
+        raise TypeError(f"{what}: a per-sample guidance scale needs the fused loop (sample() / inpaint() with ADPM2Sampler, "
+                        "AEulerSampler or KarrasSampler); this seam takes one scale per call")
+    return float(scale)
+
+
 def _guided_setup(engine, embedding: Tensor, guided: bool) -> bool:
     """reserve() + prepare_context() for a sampling run.  Guidance runs both passes of UNetCFG1d.forward
     (modules.py:1248-1253) as ONE evaluation of the doubled batch [samples | samples] when the engine has that program
@@ -569,8 +622,9 @@ def _guided_setup(engine, embedding: Tensor, guided: bool) -> bool:
     return dual
 
 
-def _guided_eval(engine, lib, B: int, guided: bool, dual: bool, embedding_scale: float, st) -> Tensor:
-    """net(x, t, embedding, embedding_scale) of engine.xin[:B] -> prediction rows [:B] (UNetCFG1d.forward)."""
+def _guided_eval(engine, lib, B: int, guided: bool, dual: bool, embedding_scale, st) -> Tensor:
+    """net(x, t, embedding, embedding_scale) of engine.xin[:B] -> prediction rows [:B] (UNetCFG1d.forward).  ``embedding_scale``:
+    a float, or the (B,) fp32 DEVICE tensor of one scale per sample (mdt_cfg_mix_rows)."""
     if dual:
         engine.xin[B:].copy_(engine.xin[:B], non_blocking=True)
         both = engine.eval(dual=True)
@@ -578,7 +632,9 @@ def _guided_eval(engine, lib, B: int, guided: bool, dual: bool, embedding_scale:
     else:
         pred = engine.eval(False)
         um = engine.eval(True) if guided else None
-    if guided:
+    if guided and isinstance(embedding_scale, torch.Tensor):
+        rt.check(lib.mdt_cfg_mix_rows(rt.ptr(pred), rt.ptr(um), rt.ptr(pred), rt.ptr(embedding_scale), B, pred.numel() // B, st))
+    elif guided:
         rt.check(lib.mdt_cfg_mix(rt.ptr(pred), rt.ptr(um), rt.ptr(pred), float(embedding_scale), pred.numel(), st))
     return pred
 
@@ -588,14 +644,18 @@ class _Loop:
     call order, the timed guided evaluation, the per-sample dynamic threshold, the step trace, final clamp and decode.
 
     ``explicit(k)`` returns the caller's tensor for draw k of the call (0 = the initial draw) or None: that draw then comes
-    from the counter-based generator keyed by (seed, k, sample0 + b)."""
+    from the counter-based generator keyed by (seed, k, sample0 + b).  ``embedding_scale``: whatever guidance_rows takes -- one
+    scale, or one per sample."""
 
     def __init__(self, engine, embedding, shape, sigmas, steps, explicit, seed, sample0, embedding_scale, dynamic_threshold,
                  clamp=False, trace=None, timer=None, tokens=None):
         self.lib, self.engine = rt.load_library(), engine
         (self.B, self.C, self.L), self.Cp = shape, engine.c.in_pad
         self.explicit, self.seed, self.sample0, self.draws = explicit, seed or 0, sample0, 0
-        self.scale, self.guided, self.q = embedding_scale, embedding_scale != 1.0, float(dynamic_threshold)
+        scale = guidance_rows(embedding_scale, self.B, "embedding_scale")
+        self.guided, self.q = is_guided(scale), float(dynamic_threshold)
+        # one scale per sample: uploaded once per call, read by mdt_cfg_mix_rows after every evaluation
+        self.scale = scale.to(engine.device) if isinstance(scale, torch.Tensor) else scale
         self.clamp, self.trace, self.timer, self.tokens = clamp, trace, timer, tokens
         self.st = rt.current_stream()
         engine.handoff_check()                        # a time-out of the previous call's pair hand-offs is reported here
@@ -741,12 +801,13 @@ def require_fused_kind(sampler) -> str:
 
 
 def run_sampler(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource, schedule, sampler: Sampler,
-                sigma_data: float, embedding_scale: float = 1.0, clamp: bool = False, trace: Optional[dict] = None, timer=None,
+                sigma_data: float, embedding_scale=1.0, clamp: bool = False, trace: Optional[dict] = None, timer=None,
                 tokens: Optional[Tensor] = None, dynamic_threshold: float = 0.0) -> Tensor:
     """DiffusionSampler.forward (diffusion.py:577-591) + the sampler's forward() + KDiffusion_mod.denoise_fn (:798-814) +
     UNetCFG1d.forward (modules.py:1228-1255) on the GPU, for any sampler with a fused kind.
     ``tokens`` (B, L) int32: also the decode step after the path, argmax over channels of the final sample
-    (generative.py:1212-1213), written by the last update kernel."""
+    (generative.py:1212-1213), written by the last update kernel.  ``embedding_scale``: one guidance scale, or one per sample
+    (guidance_rows): row b is then the row of the call at scale[b], bit for bit under one kernel_choice."""
     kind = FUSED_SAMPLERS[require_fused_kind(sampler)]
     sigmas, steps = kind.plan(num_steps, schedule, sampler, sigma_data)
 
@@ -769,7 +830,7 @@ def run_sampler(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise:
 
 def run_adpm2_inpaint(engine, embedding: Tensor, source: Tensor, mask: Tensor, num_steps: int, num_resamples: int,
                       draw: Optional[Callable[[], Tensor]], seed: Optional[int], schedule,
-                      sampler: ADPM2Sampler, sigma_data: float, embedding_scale: float = 1.0,
+                      sampler: ADPM2Sampler, sigma_data: float, embedding_scale=1.0,
                       sample0: int = 0, dynamic_threshold: float = 0.0, *, draft: Optional[Tensor] = None,
                       keep: Optional[Tensor] = None, pred_dim: Optional[int] = None, tokens: Optional[Tensor] = None) -> Tensor:
     """ADPM2Sampler.inpaint (diffusion.py:526-549) behind DiffusionInpainter.forward (:612-625).
@@ -780,7 +841,7 @@ def run_adpm2_inpaint(engine, embedding: Tensor, source: Tensor, mask: Tensor, n
     None, as token ids: ``draft`` integer (B, L) standing for its +-1 one-hot over ``pred_dim`` channels and ``keep`` bool
     (B, L), the mask before its repeat over the channels (generative.py:1600-1603).  Both forms run the same loop on
     mdt_inpaint_enter / mdt_inpaint_finish.  ``tokens`` (B, L) int32: also the decode of the result (argmax over channels; with a
-    draft, the draft id at a kept position), written by mdt_inpaint_finish."""
+    draft, the draft id at a kept position), written by mdt_inpaint_finish.  ``embedding_scale`` as run_sampler."""
     sigmas, steps = adpm2_plan(num_steps, schedule, sampler, sigma_data)
     dev = engine.device
     if source is not None:

@@ -16,7 +16,8 @@ import torch.nn as nn
 from . import ops, runtime as rt
 from .compiler import compile_unet
 from .diffusion import (FUSED_SAMPLERS, ADPM2Sampler, DiffusionInpainter, DiffusionSampler, KarrasSchedule, LogNormalDistribution,
-                        NoiseSource, run_adpm2_inpaint, run_sampler, scale_weights, scale_weights_rows)
+                        NoiseSource, guidance_rows, is_guided, run_adpm2_inpaint, run_sampler, scalar_guidance, scale_weights,
+                        scale_weights_rows)
 from .engine import UNetEngine, _require_gpu
 from .modules import PositionalEncoding1D, UNetCFG1d
 from .netspec import forward_unet_config, inverse_unet_config
@@ -83,17 +84,27 @@ class XDiffusion_x(nn.Module):
 
     def sample(self, noise, num_steps: int, sigma_schedule, sampler, clamp: bool, **kwargs) -> Tensor:
         """diffusion.py:724-741: builds a DiffusionSampler and calls it.  ``noise``: the initial draw (B, C, L) as in the
-        reference, a NoiseSource, or None (drawn like generative.py:853)."""
+        reference, a NoiseSource, or None (drawn like generative.py:853).  ``embedding_scale``: one guidance scale, or one per
+        sample (guidance_rows; the fused loops only)."""
+        _normalise_scale(kwargs)
         diffusion_sampler = DiffusionSampler(diffusion=self.diffusion, sampler=sampler, sigma_schedule=sigma_schedule,
                                              num_steps=num_steps, clamp=clamp)
         return diffusion_sampler(noise, **kwargs)
 
     def inpaint(self, sigma_schedule, sampler, inpaint, in_paint_mask, num_steps: int, num_resamples: int,
                 **kwargs) -> Tensor:
-        """diffusion.py:744-767: builds a DiffusionInpainter and calls it."""
+        """diffusion.py:744-767: builds a DiffusionInpainter and calls it.  ``embedding_scale`` as sample()."""
+        _normalise_scale(kwargs)
         inpainter = DiffusionInpainter(diffusion=self.diffusion, sampler=sampler, sigma_schedule=sigma_schedule,
                                        num_steps=num_steps, num_resamples=num_resamples)
         return inpainter(inpaint, in_paint_mask, **kwargs)
+
+
+def _normalise_scale(kwargs: dict) -> None:
+    """embedding_scale of a sample() / inpaint() call in guidance_rows' form, checked against the embedding's batch."""
+    emb = kwargs.get("embedding")
+    if "embedding_scale" in kwargs and isinstance(emb, torch.Tensor):
+        kwargs["embedding_scale"] = guidance_rows(kwargs["embedding_scale"], emb.shape[0], "embedding_scale")
 
 
 class _FusedLoop:
@@ -111,17 +122,17 @@ class _FusedLoop:
         o, emb = self.owner, self.kw["embedding"]
         if emb.shape[0] == 0:                       # nothing to generate (the reference returns an empty tensor too)
             return torch.empty(0, o.pred_dim, o.max_length, device=emb.device)
-        guided = self.kw.get("embedding_scale", 1.0) != 1.0
-        eng = o.engine(emb.device, emb.shape[1], emb.shape[0] * (2 if guided else 1))
+        scale = guidance_rows(self.kw.get("embedding_scale", 1.0), emb.shape[0], "embedding_scale")
+        eng = o.engine(emb.device, emb.shape[1], emb.shape[0] * (2 if is_guided(scale) else 1))
         ns = o._noise_source(noise, emb.shape[0], emb.device)
         x, kd = self.extra, o.diffusion.diffusion
-        scale, clamp, tok = self.kw.get("embedding_scale", 1.0), bool(x.get("clamp", False)), x.get("tokens")
-        plain = ns.steps is None and x.get("trace") is None and x.get("timer") is None
+        clamp, tok = bool(x.get("clamp", False)), x.get("tokens")
+        plain = ns.steps is None and x.get("trace") is None and x.get("timer") is None and not isinstance(scale, torch.Tensor)
         if not (plain and any(type(sampler) is k.cls for k in FUSED_SAMPLERS.values())):
             return run_sampler(eng, emb, o.pred_dim, num_steps, ns, sigmas, sampler, kd.sigma_data, scale, clamp, x.get("trace"),
                                x.get("timer"), tok, float(kd.dynamic_threshold))
-        # the plain call (counter-based step noise, nothing to record) with a sampler of exactly one of the three classes: the
-        # whole loop as ONE custom op, mdt::sample for ADPM2 (it stays ADPM2's), mdt::sample_with for the other two
+        # the plain call (counter-based step noise, nothing to record, one guidance scale) with a sampler of exactly one of the
+        # three classes: the whole loop as ONE custom op, mdt::sample for ADPM2 (it stays ADPM2's), mdt::sample_with for the other two
         init = None if ns.init is None else ns.init.to(device=emb.device, dtype=torch.float32)
         head = (emb, init, None, torch.as_tensor(sigmas, dtype=torch.float32).cpu(), ops.register_engine(eng), o.pred_dim)
         rest = (float(kd.sigma_data), float(scale), clamp, int(ns.seed or 0), int(ns.sample0), tok is not None,
@@ -136,18 +147,18 @@ class _FusedLoop:
 
     def inpaint(self, source, mask, sampler, sigmas, num_steps, num_resamples):
         o, emb = self.owner, self.kw["embedding"]
-        guided = self.kw.get("embedding_scale", 1.0) != 1.0
-        eng = o.engine(emb.device, emb.shape[1], emb.shape[0] * (2 if guided else 1))
+        scale = guidance_rows(self.kw.get("embedding_scale", 1.0), emb.shape[0], "embedding_scale")
+        eng = o.engine(emb.device, emb.shape[1], emb.shape[0] * (2 if is_guided(scale) else 1))
         draw, seed = self.extra.get("draw"), self.extra.get("seed")
         if draw is None and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         sample0, tok, kd = int(self.extra.get("sample0") or 0), self.extra.get("tokens"), o.diffusion.diffusion
-        scale = self.kw.get("embedding_scale", 1.0)
         if source.is_floating_point():
             return run_adpm2_inpaint(eng, emb, source, mask, num_steps, num_resamples, draw, seed, sigmas, sampler, kd.sigma_data,
                                      scale, sample0, float(kd.dynamic_threshold), tokens=tok)
-        # a draft of token ids (inpaint_tokens): without a draw callback the whole loop is ONE custom op, as mdt::sample is
-        if draw is None and type(sampler) is ADPM2Sampler:
+        # a draft of token ids (inpaint_tokens): without a draw callback and with one guidance scale the whole loop is ONE custom
+        # op, as mdt::sample is
+        if draw is None and type(sampler) is ADPM2Sampler and not isinstance(scale, torch.Tensor):
             x, t = torch.ops.mdt.inpaint_tokens(emb, source, mask, torch.as_tensor(sigmas, dtype=torch.float32).cpu(),
                                                 ops.register_engine(eng), o.pred_dim, int(num_resamples), float(sampler.rho),
                                                 float(kd.sigma_data), float(scale), int(seed), sample0,
@@ -320,6 +331,7 @@ class _QMBase(nn.Module):
         """net(x, time, embedding=..., embedding_scale=...) (modules.py:1228-1255); x is (B, C, L) as in the reference,
         ``time`` a scalar or one value per row (rows sharing a time value are evaluated together; ``batched=True``: all rows in
         ONE evaluation of the per-row program)."""
+        embedding_scale = scalar_guidance(embedding_scale, "net()")
         t = torch.as_tensor(time, dtype=torch.float32).flatten().cpu()
         B = x.shape[0]
         if t.numel() not in (1, B):
@@ -351,6 +363,7 @@ class _QMBase(nn.Module):
     def _denoise(self, x_noisy: Tensor, sigma, embedding: Tensor, embedding_scale: float = 1.0) -> Tensor:
         """KDiffusion_mod.denoise_fn for a scalar sigma (diffusion.py:798-814) as three ops: input scaling, the network,
         output mix + clip."""
+        embedding_scale = scalar_guidance(embedding_scale, "denoise_fn")
         device = x_noisy.device
         _require_gpu(device)
         eng = self.engine(device, embedding.shape[1], x_noisy.shape[0])
@@ -363,6 +376,7 @@ class _QMBase(nn.Module):
     def _denoise_rows(self, x_noisy: Tensor, sigmas: Tensor, embedding: Tensor, embedding_scale: float = 1.0) -> Tensor:
         """KDiffusion_mod.denoise_fn with one sigma per sample (diffusion.py:798-814) as ONE per-row evaluation: the per-sample
         coefficients are computed on the host in the reference's fp32 expressions and uploaded once."""
+        embedding_scale = scalar_guidance(embedding_scale, "denoise_fn")
         device = x_noisy.device
         _require_gpu(device)
         B = x_noisy.shape[0]
@@ -422,7 +436,11 @@ class _QMBase(nn.Module):
 
     def _do_sample(self, sequences, device, cond_scale, timesteps, clamp, noise=None, trace=None, timer=None, tokens=None,
                    sampler=None, sigma_schedule=None):
-        """``sampler`` / ``sigma_schedule`` None: the objects every sample() of the reference hard-codes (generative.py:855-858)."""
+        """``sampler`` / ``sigma_schedule`` None: the objects every sample() of the reference hard-codes (generative.py:855-858).
+        ``cond_scale``: one guidance scale for the batch, or one per sample (a 1-D list / tuple / ndarray / tensor of B values,
+        diffusion.guidance_rows): row b is then row b of the call at cond_scale[b] -- bit for bit when ``kernel_choice`` is pinned,
+        to rounding under 'auto' (the per-sample call asks for the engine of 2 B rows, the call at scale 1 for B)."""
+        cond_scale = guidance_rows(cond_scale, sequences.shape[0])          # (refused before anything is launched)
         emb = self._embed(sequences, device)
         if sampler is None:
             sampler = ADPM2Sampler(rho=1)
@@ -440,6 +458,7 @@ class _QMBase(nn.Module):
         if cond_scale is None:
             cond_scale = 7.5 if self._inverse else 1.0
         B = sequences.shape[0]
+        cond_scale = guidance_rows(cond_scale, B)
         tok = torch.zeros(B, self.max_length, dtype=torch.int32, device=device)
         x = self._do_sample(sequences, device, cond_scale, timesteps, clamp, noise, tokens=tok if B else None,
                             sampler=sampler, sigma_schedule=sigma_schedule)
@@ -449,7 +468,9 @@ class _QMBase(nn.Module):
     def inpaint(self, sequences, device, cond_scale=7.5, timesteps=100, num_resamples=1, inpaint=None,
                 in_paint_mask=None, *, draw=None, seed=None, sample0=0):
         """``sample0``: the global index of this call's first sample (seed mode: the counter-based draws are keyed by
-        sample0 + b, so a batch split over calls or ranks returns the rows of the whole batch)."""
+        sample0 + b, so a batch split over calls or ranks returns the rows of the whole batch).  ``cond_scale``: one guidance
+        scale, or one per sample, as sample()."""
+        cond_scale = guidance_rows(cond_scale, sequences.shape[0])
         emb = self._embed(sequences, device)
         return self.diffusion.inpaint(num_steps=timesteps, num_resamples=num_resamples, sampler=ADPM2Sampler(rho=1),
                                       sigma_schedule=KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0),
@@ -464,9 +485,11 @@ class _QMBase(nn.Module):
         source nor the full-shape mask is ever built.  ``draft_tokens``: integer (B, max_length), ids in [0, pred_dim);
         ``keep_mask``: bool (B, max_length), True = keep the position (the reference's in_paint_mask before its repeat).
         Returns (B, max_length) int64 token ids on ``device`` -- the draft id at a kept position -- and with ``return_sample``
-        also the fp32 sample, bit for bit inpaint()'s on one_hot_draft(draft_tokens, pred_dim) and the repeated mask."""
+        also the fp32 sample, bit for bit inpaint()'s on one_hot_draft(draft_tokens, pred_dim) and the repeated mask.
+        ``cond_scale``: one guidance scale, or one per sample, as sample()."""
         draft_tokens, keep_mask = torch.as_tensor(draft_tokens), torch.as_tensor(keep_mask)
         B, L = sequences.shape[0], self.max_length
+        cond_scale = guidance_rows(cond_scale, B)
         if draft_tokens.is_floating_point() or draft_tokens.is_complex() or draft_tokens.dtype == torch.bool:
             raise ValueError(f"draft_tokens must hold integer token ids, got {draft_tokens.dtype}")
         if keep_mask.dtype != torch.bool:
@@ -581,6 +604,27 @@ def generate_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForwa
                                            context_embedding_max_length=conditioning.shape[1], noise=forward_noise,
                                            sampler=sampler, sigma_schedule=sigma_schedule)
     return tokens, props
+
+
+def guidance_sweep(model, sequences: Tensor, cond_scales, device, *, tokens: bool = False, **sample_kwargs):
+    """The guidance sweep of the reference's callers -- ``for s in cond_scales: model.sample(sequences, device, cond_scale=s)``
+    (sample_loop_generative, generative.py:1206) -- as ONE fused call of batch S * B: row s * B + b is conditioning b at
+    cond_scales[s], and the result comes back as (S, B, ...).  ``tokens``: one sample_tokens() call instead of one sample() call
+    (token ids (S, B, L); with return_sample=True the pair of ids and samples).  ``sample_kwargs`` go to that call; a ``noise``
+    tensor holds S * B rows, and with ``noise=NoiseSource(seed=..., sample0=n)`` sweep s equals the scalar call whose sample0 is
+    n + s * B (bit for bit under a pinned ``kernel_choice``)."""
+    try:
+        ndim = torch.as_tensor(cond_scales).dim()
+    except Exception:
+        ndim = -1
+    if ndim != 1:
+        raise ValueError("cond_scales must be a 1-D sequence of guidance scales, one per sweep")
+    S, B = len(cond_scales), sequences.shape[0]
+    scales = torch.as_tensor(guidance_rows(cond_scales, S, "cond_scales"), dtype=torch.float32).reshape(-1).expand(S)
+    call = model.sample_tokens if tokens else model.sample
+    out = call(sequences.repeat(S, *([1] * (sequences.dim() - 1))), device, cond_scale=scales.repeat_interleave(B), **sample_kwargs)
+    unflat = lambda t: t.reshape(S, B, *t.shape[1:])          # noqa: E731
+    return tuple(unflat(t) for t in out) if isinstance(out, tuple) else unflat(out)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ fake / meta tensors).
     cond_embed          generative.py:838-850 (fc1 -> GELU, PositionalEncoding1D, cat)
     precond_in / _out   KDiffusion_mod.denoise_fn scaling + clip (diffusion.py:798-814)
     cfg_mix             UNetCFG1d.forward guidance mix (modules.py:1253)
+    cfg_mix_rows        the mix with one guidance scale per sample (a sample at scale 1 keeps its conditional prediction)
     adpm2_mid / _next   the two halves of ADPM2Sampler.step (diffusion.py:502-515)
     adpm2_euler         one Euler move of the step for a caller-supplied denoiser
     argmax_tokens       decode step after the path (generative.py:1212-1213)
@@ -190,6 +191,33 @@ def cfg_mix(cond: Tensor, uncond: Tensor, scale: float) -> Tensor:
 
 @cfg_mix.register_fake
 def _(cond, uncond, scale):
+    return cond.new_empty(cond.shape, dtype=torch.float32)
+
+
+@custom_op("mdt::cfg_mix_rows", mutates_args=())
+def cfg_mix_rows(cond: Tensor, uncond: Tensor, scale: Tensor) -> Tensor:
+    """cfg_mix with one scale per sample: scale holds cond.shape[0] values; a sample at scale 1 is its cond bit for bit."""
+    dev = _hip(cond, uncond, scale)
+    lib = rt.load_library()
+    cond, uncond, scale = _f32c(cond), _f32c(uncond), _f32c(scale).flatten()
+    if cond.shape != uncond.shape:
+        raise RuntimeError("mdt::cfg_mix_rows: shape mismatch")
+    if cond.dim() < 1 or scale.numel() != cond.shape[0]:
+        raise RuntimeError(f"mdt::cfg_mix_rows: scale holds {scale.numel()} values for cond {tuple(cond.shape)}")
+    out = torch.empty_like(cond)
+    if cond.numel():
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_cfg_mix_rows(rt.ptr(cond), rt.ptr(uncond), rt.ptr(out), rt.ptr(scale), cond.shape[0],
+                                          cond.numel() // cond.shape[0], rt.current_stream()))
+    return out
+
+
+@cfg_mix_rows.register_fake
+def _(cond, uncond, scale):
+    if cond.shape != uncond.shape:
+        raise RuntimeError("mdt::cfg_mix_rows: shape mismatch")
+    if cond.dim() < 1 or scale.numel() != cond.shape[0]:
+        raise RuntimeError(f"mdt::cfg_mix_rows: scale holds {scale.numel()} values for cond {tuple(cond.shape)}")
     return cond.new_empty(cond.shape, dtype=torch.float32)
 
 

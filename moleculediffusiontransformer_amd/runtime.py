@@ -86,6 +86,7 @@ SYMBOLS = {
     "mdt_dyn_scale_rows": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
     "mdt_loss_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "mdt_cfg_mix": (_I, [_P, _P, _P, _F, _L, _P]),
+    "mdt_cfg_mix_rows": (_I, [_P, _P, _P, _P, _I, _L, _P]),
     "mdt_adpm2_mid": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P]),
     "mdt_adpm2_next": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P, _P, _P]),
     "mdt_adpm2_euler": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _I, _U64, _U32, _L, _I, _I, _I, _P]),
