@@ -549,6 +549,15 @@ int mdt_inpaint_enter(float *x, float *xin, const float *src, const int32_t *dra
  * With draft ids and a per-token keep, a kept position's token is draft[b,l]. */
 int mdt_inpaint_finish(float *x, const float *src, const int32_t *draft, const uint8_t *keep, int32_t keep_per_token,
                        int32_t *tokens, int32_t B, int32_t C, int32_t L, void *stream);
+/* The entry of a refine call (noise a source up to the level of step i, the expression of diffusion.py:535, then :810), per
+ * sample: a row with start[b] == step_i gets
+ *   x = src + sigma * n;   xin = c_in * x  (token-major, channels padded to Cp with 0)
+ * with separate multiply and add; a row with start[b] != step_i is written neither in x nor in xin.  start is int32 (B).
+ * src / draft as mdt_inpaint_enter (exactly one of them); noise == NULL: the counter-based generator keyed by (seed, step) at the
+ * global element index (sample0 + b)*C*L + c*L + l.  An addition inside ABI version 5. */
+int mdt_refine_enter(float *x, float *xin, const int32_t *start, int32_t step_i, const float *src, const int32_t *draft,
+                     const float *noise, float sigma, float c_in, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
+                     int32_t C, int32_t L, int32_t Cp, void *stream);
 /* Decode step after the path (generative.py:1212-1213): tokens[b,l] = argmax_c x[b,c,l] (int32). */
 int mdt_argmax_tokens(const float *x, int32_t *tokens, int32_t B, int32_t C, int32_t L, void *stream);
 

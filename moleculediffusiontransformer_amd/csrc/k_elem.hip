@@ -558,6 +558,47 @@ __global__ __launch_bounds__(256) void k_inpaint_enter(float* x, float* xin, con
   tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
 }
 
+// The entry of a refine call (the expression of diffusion.py:535, then :810): the rows whose start step is the loop's current
+// step i get their noised source as state and its scaled copy as network input,
+//   start[b] == i:  x = src + sigma * n;   xin = c_in * x (token-major, padded)
+// and every other workgroup returns at once, writing neither x nor xin: a row that has not started yet rides along with its
+// state ignored, a row that has started keeps what the update kernels left.  src / draft, n == nullptr and the quad index as
+// k_inpaint_enter.  One workgroup per sample.
+__global__ __launch_bounds__(256) void k_refine_enter(float* x, float* xin, const int32_t* start, int step_i, const float* src,
+                                                       const int32_t* draft, const float* noise, float sigma, float c_in,
+                                                       uint64_t seed, uint32_t step, int64_t sample0, int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  const int b = blockIdx.x;
+  if (start[b] != step_i) return;                        // (uniform over the workgroup: no barrier is skipped by a part of it)
+  const int l4n = L / 4;
+  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
+    const int c = e / l4n, l = (e - c * l4n) * 4;
+    const int64_t o = (int64_t)b * C * L + c * L + l, ot = (int64_t)b * L + l;
+    const uint64_t quad = (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2;
+    float sv[4];
+    if (src) {
+      const float4 s4 = *reinterpret_cast<const float4*>(src + o);
+      sv[0] = s4.x; sv[1] = s4.y; sv[2] = s4.z; sv[3] = s4.w;
+    } else {
+      const int4 d4 = *reinterpret_cast<const int4*>(draft + ot);
+      sv[0] = c == d4.x ? 1.0f : -1.0f; sv[1] = c == d4.y ? 1.0f : -1.0f;
+      sv[2] = c == d4.z ? 1.0f : -1.0f; sv[3] = c == d4.w ? 1.0f : -1.0f;
+    }
+    const float4 nz = noise ? *reinterpret_cast<const float4*>(noise + o) : normal4(seed, step, quad);
+    const float nv[4] = {nz.x, nz.y, nz.z, nz.w};
+    float xn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      xn[q] = sv[q] + sigma * nv[q];
+      tile[(l + q) * (Cp + 1) + c] = c_in * xn[q];
+    }
+    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  }
+  tile_zero_pad(tile, C, L, Cp);
+  __syncthreads();
+  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+}
+
 // The last merge of ADPM2Sampler.inpaint (diffusion.py:549: sigma 0) and the decode (generative.py:1613-1614), one thread per
 // position: x = keep ? src : x; tokens[b,l] = argmax_c x[b,c,l] (first maximum, as k_argmax) -- with draft ids and a per-position
 // keep, a kept position's token is its draft id.  src / draft / keep / keep_tok as k_inpaint_enter; tokens may be nullptr.
@@ -1131,6 +1172,18 @@ int mdt_inpaint_enter(float* x, float* xin, const float* src, const int32_t* dra
   hipLaunchKernelGGL(mdt::k_inpaint_enter, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, src, draft, keep,
                      keep_per_token ? 1 : 0, n_src, n_re, sigma, renoise, c_in, seed, step_src, step_re, sample0, C, L, Cp);
   return finish("mdt_inpaint_enter");
+}
+
+int mdt_refine_enter(float* x, float* xin, const int32_t* start, int32_t step_i, const float* src, const int32_t* draft,
+                     const float* noise, float sigma, float c_in, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
+                     int32_t C, int32_t L, int32_t Cp, void* stream) {
+  MDT_CHECK_TILE("mdt_refine_enter")
+  if (!x || !xin || !start) return bad("mdt_refine_enter: null pointer");
+  if (!src == !draft) return bad("mdt_refine_enter: give the source either dense (src) or as draft ids (draft)");
+  MDT_BIG_LDS(mdt::k_refine_enter);
+  hipLaunchKernelGGL(mdt::k_refine_enter, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, start, step_i, src,
+                     draft, noise, sigma, c_in, seed, step, sample0, C, L, Cp);
+  return finish("mdt_refine_enter");
 }
 
 int mdt_inpaint_finish(float* x, const float* src, const int32_t* draft, const uint8_t* keep, int32_t keep_per_token,

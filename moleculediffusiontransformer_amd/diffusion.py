@@ -645,10 +645,15 @@ class _Loop:
 
     ``explicit(k)`` returns the caller's tensor for draw k of the call (0 = the initial draw) or None: that draw then comes
     from the counter-based generator keyed by (seed, k, sample0 + b).  ``embedding_scale``: whatever guidance_rows takes -- one
-    scale, or one per sample."""
+    scale, or one per sample.
+
+    ``first`` / ``hook``: the step functions run steps ``first .. len(steps) - 1`` of the plan and call ``hook(i, x)`` in front of
+    step i, x being the state that step reads.  Without a hook the state is the scaled first draw, as every sampler's forward()
+    starts; with one (run_refine) it starts zero-filled, the hook fills it, and the draws of the steps keep their absolute index
+    (step i takes draw i + 1), so draw 0 is left to the hook."""
 
     def __init__(self, engine, embedding, shape, sigmas, steps, explicit, seed, sample0, embedding_scale, dynamic_threshold,
-                 clamp=False, trace=None, timer=None, tokens=None):
+                 clamp=False, trace=None, timer=None, tokens=None, first=0, hook=None):
         self.lib, self.engine = rt.load_library(), engine
         (self.B, self.C, self.L), self.Cp = shape, engine.c.in_pad
         self.explicit, self.seed, self.sample0, self.draws = explicit, seed or 0, sample0, 0
@@ -661,8 +666,13 @@ class _Loop:
         engine.handoff_check()                        # a time-out of the previous call's pair hand-offs is reported here
         self.dual = _guided_setup(engine, embedding, self.guided)
         engine.prepare_times(torch.tensor(plan_time_rows(steps), dtype=torch.float32))
-        self.x = torch.empty(self.B, self.C, self.L, device=engine.device)
+        self.first, self.hook = first, hook
         self.dscale = torch.empty(self.B, device=engine.device) if dynamic_threshold else None   # clip()'s dynamic threshold
+        if hook is not None:
+            self.x, self.draws = torch.zeros(self.B, self.C, self.L, device=engine.device), first + 1
+            engine.xin[:self.B].zero_()               # a row that has not started yet rides along on zeros
+            return
+        self.x = torch.empty(self.B, self.C, self.L, device=engine.device)
         nz, k = self.draw()
         rt.check(self.lib.mdt_init_noise(rt.ptr(self.x), rt.ptr(nz), float(sigmas[0]), self.seed, k, self.sample0,
                                          self.B, self.C, self.L, self.st))
@@ -675,6 +685,10 @@ class _Loop:
         k, self.draws = self.draws, self.draws + 1
         nz = self.explicit(k)
         return (None if nz is None else _f32(nz, self.engine.device)), k
+
+    def enter(self, i: int, x: Tensor) -> None:
+        if self.hook is not None:
+            self.hook(i, x)
 
     def dyn(self, xs: Tensor, pred: Tensor, w: ScaleWeights) -> int:
         if self.dscale is not None:
@@ -729,9 +743,11 @@ def _adpm2_step(lp: _Loop, i: int, s: StepScalars, x_mid: Tensor, c_in_next: Opt
 def _adpm2_steps(lp: _Loop, steps) -> Tensor:
     """ADPM2Sampler.forward (diffusion.py:517-524): two evaluations per step."""
     x_mid = torch.empty_like(lp.x)
-    rt.check(lp.lib.mdt_precond_in(rt.ptr(lp.x), rt.ptr(lp.engine.xin), steps[0].w.c_in, *lp.dims(), lp.st))
-    for i, s in enumerate(steps):
-        last = i + 1 == len(steps)
+    if lp.hook is None:
+        rt.check(lp.lib.mdt_precond_in(rt.ptr(lp.x), rt.ptr(lp.engine.xin), steps[0].w.c_in, *lp.dims(), lp.st))
+    for i in range(lp.first, len(steps)):
+        s, last = steps[i], i + 1 == len(steps)
+        lp.enter(i, lp.x)
         _adpm2_step(lp, i, s, x_mid, None if last else steps[i + 1].w.c_in, lp.tok(last))
         lp.record(i, lp.x)
     return lp.x
@@ -740,8 +756,11 @@ def _adpm2_steps(lp: _Loop, steps) -> Tensor:
 def _aeuler_steps(lp: _Loop, steps) -> Tensor:
     """AEulerSampler.forward (diffusion.py:476-483): one evaluation and one mdt_aeuler_next launch per step."""
     lib, x, xin, st = lp.lib, lp.x, lp.engine.xin, lp.st
-    rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(xin), steps[0].w.c_in, *lp.dims(), st))
-    for i, s in enumerate(steps):
+    if lp.hook is None:
+        rt.check(lib.mdt_precond_in(rt.ptr(x), rt.ptr(xin), steps[0].w.c_in, *lp.dims(), st))
+    for i in range(lp.first, len(steps)):
+        s = steps[i]
+        lp.enter(i, x)
         pred = lp.unet(i)
         nz, k = lp.draw()
         last = i + 1 == len(steps)
@@ -758,7 +777,9 @@ def _karras_steps(lp: _Loop, steps) -> Tensor:
     sigma_hat, mdt_karras_mid, evaluation at sigma_next, mdt_karras_next."""
     lib, x, xin, st = lp.lib, lp.x, lp.engine.xin, lp.st
     d, x_next = torch.empty_like(x), torch.empty_like(x)
-    for i, s in enumerate(steps):
+    for i in range(lp.first, len(steps)):
+        s = steps[i]
+        lp.enter(i, x)
         nz, k = lp.draw()
         rt.check(lib.mdt_karras_hat(rt.ptr(x), rt.ptr(nz), rt.ptr(x), rt.ptr(xin), s.noise_scale, s.s_noise, s.w_hat.c_in,
                                     lp.seed, k, lp.sample0, *lp.dims(), st))                        # x is x_hat from here
@@ -877,3 +898,126 @@ def run_adpm2_inpaint(engine, embedding: Tensor, source: Tensor, mask: Tensor, n
                     (re_nz, re_k), renoise = lp.draw(), s.renoise
         rt.check(lib.mdt_inpaint_finish(rt.ptr(x), rt.ptr(src), rt.ptr(ids), rt.ptr(mk), per_token, rt.ptr(tokens), B, C, L, st))
         return lp.finish(x, decoded=True)
+
+
+# ----------------------------------------------------------------------------------------------
+# refine: noise a source up to the level of step k and run the remaining steps, k per sample
+# ----------------------------------------------------------------------------------------------
+def refine_start(timesteps: int, strength):
+    """The start step of a refine call for a ``strength`` in (0, 1], the share of the schedule that is run:
+    ``steps_run = min(T - 1, max(1, ceil(strength * (T - 1))))`` and ``start = T - 1 - steps_run``.  Strength 1 is start 0 (all
+    T - 1 steps from the highest noise level: far-away results), a small strength the last step alone (near ones).  ``strength``
+    may be a 1-D sequence, one entry per sample: the result is then a list of ints."""
+    if isinstance(timesteps, bool) or not isinstance(timesteps, int) or timesteps < 2:
+        raise ValueError(f"timesteps must be an int >= 2 (a refine call runs at least one step), got {timesteps!r}")
+
+    def one(v) -> int:
+        if isinstance(v, (bool, complex)) or not isinstance(v, (int, float)) or not (0.0 < v <= 1.0):
+            raise ValueError(f"strength must lie in (0, 1], got {v!r}")
+        return timesteps - 1 - min(timesteps - 1, max(1, math.ceil(v * (timesteps - 1))))
+    if isinstance(strength, (bool, int, float, complex)):
+        return one(strength)
+    try:
+        t = torch.as_tensor(strength)
+    except Exception as e:
+        raise ValueError(f"strength must be a number in (0, 1] or a 1-D sequence of them ({e})") from None
+    if t.dim() == 0:
+        return one(t.item())
+    if t.dim() != 1 or t.dtype == torch.bool or t.is_complex():
+        raise ValueError(f"strength must be a number in (0, 1] or a 1-D sequence of them, got shape {tuple(t.shape)} {t.dtype}")
+    return [one(v) for v in t.double().tolist()]
+
+
+def start_rows(start_step, B: int, timesteps: int, name: str = "start_step") -> Union[int, Tensor]:
+    """The start step of a refine call in the form run_refine takes: an int -- ONE start for the batch -- or an int32 CPU tensor
+    of B values, one per sample.
+
+    A Python int or a 0-dim integer tensor / array gives the int.  A 1-D list, tuple, ndarray or integer tensor of exactly B
+    entries gives the tensor -- or, when all entries are equal, that entry as an int: the call is then literally the scalar call.
+    Every entry lies in [0, timesteps - 2].  Anything else (a float, a bool, a wrong length, a value out of range) raises
+    ValueError naming the argument (``name``)."""
+    def refuse(why):
+        return ValueError(f"{name} must be an int in [0, {timesteps - 2}] (timesteps - 2) or hold one per sample ({B}): {why}")
+    if isinstance(timesteps, bool) or not isinstance(timesteps, int) or timesteps < 2:
+        raise ValueError(f"timesteps must be an int >= 2 (a refine call runs at least one step), got {timesteps!r}")
+    if isinstance(start_step, (bool, float, complex)) or start_step is None:
+        raise refuse(f"got {start_step!r} ({type(start_step).__name__})")
+    if isinstance(start_step, int):
+        if not 0 <= start_step <= timesteps - 2:
+            raise refuse(f"got {start_step}")
+        return int(start_step)
+    try:
+        t = torch.as_tensor(start_step)
+    except Exception as e:
+        raise refuse(f"got {type(start_step).__name__} ({e})") from None
+    if B == 0 and t.dim() == 1 and t.numel() == 0:
+        return 0                                     # an empty batch: nothing to start (an empty list has no integer dtype)
+    if t.dtype == torch.bool or t.is_floating_point() or t.is_complex():
+        raise refuse(f"got dtype {t.dtype}")
+    if t.dim() > 1:
+        raise refuse(f"got {t.dim()} dimensions, shape {tuple(t.shape)}")
+    t = t.detach().to(device="cpu", dtype=torch.int64)
+    if t.dim() == 0:
+        return start_rows(int(t), B, timesteps, name)
+    if t.numel() != B:
+        raise refuse(f"got {t.numel()} values")
+    if int(t.min()) < 0 or int(t.max()) > timesteps - 2:
+        raise refuse(f"got values in [{int(t.min())}, {int(t.max())}]")
+    if bool((t == t[0]).all()):
+        return int(t[0])
+    return t.to(torch.int32).contiguous()
+
+
+def run_refine(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource, schedule, sampler: Sampler,
+               sigma_data: float, start, *, source: Optional[Tensor] = None, draft: Optional[Tensor] = None,
+               embedding_scale=1.0, clamp: bool = False, trace: Optional[dict] = None, timer=None,
+               tokens: Optional[Tensor] = None, dynamic_threshold: float = 0.0) -> Tensor:
+    """Partial-noise editing on the fused loop, for any sampler with a fused kind: row b is
+    ``x = source + sigmas[k] * draw0`` (the expression of diffusion.py:535) followed by the sampler's unchanged step() for
+    i = k .. num_steps - 2, with k = ``start`` (an int) or ``start[b]`` (int32, B entries; start_rows).
+
+    The source comes dense -- ``source`` fp32 (B, C, L) -- or as ``draft`` integer ids (B, L) standing for their +-1 one-hot over
+    ``pred_dim`` channels, the two source forms of run_adpm2_inpaint.  The plan and the time table are those of the full
+    ``num_steps`` call, so a step keeps its scalars and its time row; steps min(start) .. num_steps - 2 run.  Draw 0 is the entry
+    noise of every row whatever its start, step i takes draw i + 1 (run_sampler's index): a row's result depends on its own start
+    only -- row b of a per-sample call is row b of the scalar call at start[b], bit for bit under one kernel_choice -- and
+    ``noise.steps(i)`` is not called for i < min(start).  A row that has not started yet rides along, its state ignored, until
+    mdt_refine_enter overwrites its state and network input in front of its step: a per-sample call costs every row the steps
+    from min(start).  ``clamp`` / ``trace`` / ``timer`` / ``tokens`` / ``embedding_scale`` / ``dynamic_threshold`` as run_sampler."""
+    kind = FUSED_SAMPLERS[require_fused_kind(sampler)]
+    sigmas, steps = kind.plan(num_steps, schedule, sampler, sigma_data)
+    dev, B = engine.device, embedding.shape[0]
+    if B == 0:
+        raise ValueError("run_refine needs at least one sample (refine() returns the empty result itself)")
+    start = start_rows(start, B, num_steps, "start")
+    if (source is None) == (draft is None):
+        raise ValueError("give the source either dense (source) or as token ids (draft)")
+    shape = (B, int(pred_dim), engine.c.length)
+    if source is not None and tuple(source.shape) != shape:
+        raise ValueError(f"source is {tuple(source.shape)}, the call refines {shape}")
+    if draft is not None and (draft.is_floating_point() or tuple(draft.shape) != (B, engine.c.length)):
+        raise ValueError(f"draft must be integer token ids ({B}, {engine.c.length}), got {draft.dtype} {tuple(draft.shape)}")
+    if noise.init is not None and tuple(noise.init.shape) != shape:
+        raise ValueError(f"the entry noise is {tuple(noise.init.shape)}, the call refines {shape}")
+    rows = start if isinstance(start, torch.Tensor) else torch.full((B,), start, dtype=torch.int32)
+    entries = set(rows.tolist())
+
+    def explicit(k: int):            # run_sampler's draws: 0 is the entry noise, i + 1 that of step i
+        if k == 0:
+            return noise.init
+        return None if noise.steps is None else noise.steps(k - 1)
+    with torch.cuda.device(dev):
+        src = None if source is None else _f32(source, dev)
+        ids = None if draft is None else draft.to(device=dev, dtype=torch.int32).contiguous()
+        nz0 = None if noise.init is None else _f32(noise.init, dev)
+        start_dev = rows.to(dev)
+
+        def enter(i: int, x: Tensor) -> None:
+            if i in entries:
+                s = steps[i]
+                c_in = (s.w_hat if isinstance(s, KarrasStep) else s.w).c_in
+                rt.check(lp.lib.mdt_refine_enter(rt.ptr(x), rt.ptr(engine.xin), rt.ptr(start_dev), i, rt.ptr(src), rt.ptr(ids),
+                                                 rt.ptr(nz0), float(sigmas[i]), c_in, lp.seed, 0, lp.sample0, *lp.dims(), lp.st))
+        lp = _Loop(engine, embedding, shape, sigmas, steps, explicit, noise.seed, noise.sample0, embedding_scale,
+                   dynamic_threshold, clamp, trace, timer, tokens, first=min(entries), hook=enter)
+        return lp.finish(kind.steps(lp, steps), decoded=True)

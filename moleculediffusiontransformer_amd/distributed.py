@@ -109,3 +109,26 @@ def inpaint_tokens_sharded(local_inpaint_tokens: Callable[[Tensor, Tensor, Tenso
     if world == 1:
         return local.long()
     return all_gather_tokens(local, total, vocab, group)
+
+
+def refine_tokens_sharded(local_refine_tokens: Callable[[Tensor, Tensor, object, int], Tensor], sequences: Tensor,
+                          draft_tokens: Tensor, start_step, vocab: int, group=None, model=None, guided: bool = False) -> Tensor:
+    """As inpaint_tokens_sharded, for lead refinement: every rank passes the same global ``sequences`` (B, n), ``draft_tokens``
+    (B, L) and ``start_step`` -- one int, or one per sample (B entries, sliced with the other two); rank r refines its contiguous
+    slice via ``local_refine_tokens(seq_slice, draft_slice, start_slice, first_global_index) -> (b_r, L)`` token ids
+    (model.refine_tokens(..., start_step=start_slice, noise=NoiseSource(seed=s, sample0=first_global_index))) and all ranks
+    receive the full (B, L) result.  A row's result depends on its own start only, so the split does not change it."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    total = sequences.shape[0]
+    if draft_tokens.shape[0] != total:
+        raise ValueError(f"sequences and draft_tokens must hold the same {total} samples")
+    per_sample = not isinstance(start_step, int) and getattr(torch.as_tensor(start_step), "ndim", 0) == 1
+    if per_sample and len(start_step) != total:
+        raise ValueError(f"start_step must be one int or hold one entry for each of the {total} samples")
+    pin_for_shards(model, total, world, guided)
+    lo, hi = shard_bounds(total, world, rank)
+    local = local_refine_tokens(sequences[lo:hi], draft_tokens[lo:hi], start_step[lo:hi] if per_sample else start_step, lo)
+    if world == 1:
+        return local.long()
+    return all_gather_tokens(local, total, vocab, group)

@@ -16,8 +16,8 @@ import torch.nn as nn
 from . import ops, runtime as rt
 from .compiler import compile_unet
 from .diffusion import (FUSED_SAMPLERS, ADPM2Sampler, DiffusionInpainter, DiffusionSampler, KarrasSchedule, LogNormalDistribution,
-                        NoiseSource, guidance_rows, is_guided, run_adpm2_inpaint, run_sampler, scalar_guidance, scale_weights,
-                        scale_weights_rows)
+                        NoiseSource, guidance_rows, is_guided, refine_start, require_fused_kind, run_adpm2_inpaint, run_refine,
+                        run_sampler, scalar_guidance, scale_weights, scale_weights_rows, start_rows)
 from .engine import UNetEngine, _require_gpu
 from .modules import PositionalEncoding1D, UNetCFG1d
 from .netspec import forward_unet_config, inverse_unet_config
@@ -512,6 +512,119 @@ class _QMBase(nn.Module):
                                    embedding_scale=cond_scale, draw=draw, seed=seed, sample0=sample0, tokens=tok)
         return (tok.long(), x) if return_sample else tok.long()
 
+    # ------------------------------------------------------------------ refine: start from a lead, k per sample
+    def _check_draft(self, draft_tokens, B: int) -> Tensor:
+        """The draft of inpaint_tokens() / refine_tokens(): integer ids (B, max_length) in [0, pred_dim)."""
+        draft_tokens = torch.as_tensor(draft_tokens)
+        if draft_tokens.is_floating_point() or draft_tokens.is_complex() or draft_tokens.dtype == torch.bool:
+            raise ValueError(f"draft_tokens must hold integer token ids, got {draft_tokens.dtype}")
+        if tuple(draft_tokens.shape) != (B, self.max_length):
+            raise ValueError(f"draft_tokens must be ({B}, {self.max_length}); got {tuple(draft_tokens.shape)}")
+        if B:
+            lo, hi = (int(v) for v in torch.aminmax(draft_tokens))
+            if lo < 0 or hi >= self.pred_dim:
+                raise ValueError(f"draft_tokens holds ids in [{lo}, {hi}], the model has pred_dim = {self.pred_dim} classes")
+        return draft_tokens
+
+    @staticmethod
+    def _refine_sampler(sampler):
+        """The sampler of a refine call (None: ADPM2Sampler(rho=1), sample()'s), which must have a fused kind."""
+        if sampler is None:
+            return ADPM2Sampler(rho=1)
+        try:
+            require_fused_kind(sampler)
+        except TypeError:
+            raise TypeError(f"{type(sampler).__name__}: refine() needs the fused loop (ADPM2Sampler, AEulerSampler or KarrasSampler "
+                            "with the class's own step()): the start step enters inside the loop, which a per-step seam does not "
+                            "have") from None
+        return sampler
+
+    def _do_refine(self, sequences, device, start, cond_scale, timesteps, clamp, noise, sampler, sigma_schedule, trace=None,
+                   source=None, draft=None, tokens=None) -> Tensor:
+        """refine() / refine_tokens() behind their checks: ``start`` and ``cond_scale`` are normalised (start_rows,
+        guidance_rows), ``sampler`` has a fused kind (_refine_sampler), the batch is not empty.  The plain call -- seeded step noise, one guidance scale, no trace, token ids in
+        and out -- is ONE custom op (mdt::refine_tokens); every other call is run_refine."""
+        if sigma_schedule is None:
+            sigma_schedule = KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0)
+        device = torch.device(device)
+        B = sequences.shape[0]
+        emb = self._embed(sequences, device)
+        eng = self.engine(device, emb.shape[1], B * (2 if is_guided(cond_scale) else 1))
+        ns = self._noise_source(noise, B, device)
+        kd = self.diffusion.diffusion
+        sigmas = torch.as_tensor(sigma_schedule(timesteps, device), dtype=torch.float32).cpu()
+        plain = (draft is not None and tokens is not None and ns.steps is None and trace is None and not clamp
+                 and not isinstance(cond_scale, torch.Tensor) and any(type(sampler) is k.cls for k in FUSED_SAMPLERS.values()))
+        if plain:
+            rows = start if isinstance(start, torch.Tensor) else torch.full((B,), start, dtype=torch.int32)
+            init = None if ns.init is None else ns.init.to(device=device, dtype=torch.float32)
+            x, t = torch.ops.mdt.refine_tokens(emb, draft.to(device), rows.to(device), init, sigmas, ops.register_engine(eng),
+                                               self.pred_dim, *ops.sampler_spec(sampler), float(kd.sigma_data), float(cond_scale),
+                                               int(ns.seed or 0), int(ns.sample0), float(kd.dynamic_threshold))
+            tokens.copy_(t)
+            return x
+        with torch.no_grad():
+            return run_refine(eng, emb, self.pred_dim, timesteps, ns, sigmas, sampler, kd.sigma_data, start, source=source,
+                              draft=None if draft is None else draft.to(device), embedding_scale=cond_scale, clamp=clamp,
+                              trace=trace, tokens=tokens, dynamic_threshold=float(kd.dynamic_threshold))
+
+    def refine(self, sequences, device, source, start_step, cond_scale=None, timesteps=100, clamp=False, *, noise=None,
+               sampler=None, sigma_schedule=None, trace=None):
+        """Partial-noise editing (the k-diffusion form): noise ``source`` -- fp32 (B, pred_dim, max_length), e.g.
+        one_hot_draft(tokens, pred_dim) -- up to the level of timestep ``start_step`` of the schedule,
+        ``x = source + sigmas[k] * randn_like(source)`` (the expression of diffusion.py:535), and run the remaining
+        ``timesteps - 1 - k`` sampler steps under the conditioning.  A small k (much noise) gives far-away results, a large k near
+        ones; a zero source at k = 0 is sample().
+
+        ``start_step``: one int in [0, timesteps - 2], or one per sample (a 1-D list / tuple / ndarray / integer tensor of B
+        entries, diffusion.start_rows): row b is then row b of the call at start_step[b], bit for bit under a pinned
+        ``kernel_choice``.  Cost: a per-sample call runs EVERY row from min(start_step) -- rows that start later ride along
+        until their step -- so it costs what the scalar call at min(start_step) costs.  ``cond_scale`` (None: sample()'s default),
+        ``noise`` (a tensor = the entry noise, a NoiseSource, or None), ``sampler``, ``sigma_schedule``, ``trace``, ``clamp`` as
+        sample().  The sampler must have a fused loop: a sampler with its own step() raises TypeError."""
+        sampler = self._refine_sampler(sampler)
+        if cond_scale is None:
+            cond_scale = 7.5 if self._inverse else 1.0
+        B = sequences.shape[0]
+        cond_scale = guidance_rows(cond_scale, B)
+        start = start_rows(start_step, B, timesteps)
+        source = torch.as_tensor(source)
+        if not source.is_floating_point() or tuple(source.shape) != (B, self.pred_dim, self.max_length):
+            raise ValueError(f"source must be a floating-point tensor ({B}, {self.pred_dim}, {self.max_length}); got {source.dtype} "
+                             f"{tuple(source.shape)}")
+        if B == 0:
+            return torch.empty(0, self.pred_dim, self.max_length, device=torch.device(device))
+        return self._do_refine(sequences, device, start, cond_scale, timesteps, clamp, noise, sampler, sigma_schedule, trace,
+                               source=source)
+
+    def refine_tokens(self, sequences, device, draft_tokens, start_step=None, *, strength=None, cond_scale=None, timesteps=100,
+                      noise=None, sampler=None, sigma_schedule=None, return_sample: bool = False):
+        """refine() for a lead given as token ids, decoded: the +-1 one-hot of the draft and the argmax of the result live inside
+        the loop's own kernels (mdt_refine_enter, the last update kernel), so the (B, C, L) source is never built.
+        ``draft_tokens``: integer (B, max_length), ids in [0, pred_dim).  Give exactly one of ``start_step`` (as refine()) or
+        ``strength`` in (0, 1] (diffusion.refine_start; one value or one per sample): the share of the schedule that is run.
+        Returns (B, max_length) int64 token ids on ``device`` and with ``return_sample`` also the fp32 sample, bit for bit
+        refine()'s on one_hot_draft(draft_tokens, pred_dim).  Cost of a per-sample call: every row runs from min(start_step)."""
+        sampler = self._refine_sampler(sampler)
+        if (start_step is None) == (strength is None):
+            raise ValueError("give exactly one of start_step and strength")
+        if strength is not None:
+            start_step = refine_start(timesteps, strength)
+        if cond_scale is None:
+            cond_scale = 7.5 if self._inverse else 1.0
+        B, L = sequences.shape[0], self.max_length
+        cond_scale = guidance_rows(cond_scale, B)
+        start = start_rows(start_step, B, timesteps, "start_step" if strength is None else "strength")
+        draft_tokens = self._check_draft(draft_tokens, B)
+        device = torch.device(device)
+        if B == 0:                                  # nothing to refine (sample() returns an empty tensor too)
+            tok, x = torch.zeros(0, L, dtype=torch.int64, device=device), torch.empty(0, self.pred_dim, L, device=device)
+            return (tok, x) if return_sample else tok
+        tok = torch.zeros(B, L, dtype=torch.int32, device=device)
+        x = self._do_refine(sequences, device, start, cond_scale, timesteps, False, noise, sampler, sigma_schedule,
+                            draft=draft_tokens, tokens=tok)
+        return (tok.long(), x) if return_sample else tok.long()
+
 
 class QMDiffusion(_QMBase):
     """Generative inverse diffusion model (generative.py:718-914)."""
@@ -649,6 +762,49 @@ def complete_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForwa
     (B, n_cond)).  ``draw`` / ``seed`` / ``sample0`` as inpaint_tokens; ``forward_noise`` as generate_and_validate."""
     tokens = model.inpaint_tokens(conditioning, device, draft_tokens, keep_mask, cond_scale=cond_scale, timesteps=timesteps,
                                   num_resamples=num_resamples, draw=draw, seed=seed, sample0=sample0)
+    props = predict_properties_from_tokens(model_forward, tokens, device, cond_scale=1.0, timesteps=forward_timesteps,
+                                           X_norm_factor=X_norm_factor,
+                                           context_embedding_max_length=conditioning.shape[1], noise=forward_noise)
+    return tokens, props
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# lead refinement: explore the neighbourhood of a draft under new target properties
+# ----------------------------------------------------------------------------------------------------------------------
+def strength_sweep(model, sequences: Tensor, draft_tokens: Tensor, strengths, device, **refine_kwargs):
+    """The strength sweep over the same leads -- ``for s in strengths: model.refine_tokens(sequences, device, draft_tokens,
+    strength=s)`` -- as ONE fused call of batch S * B, the counterpart of guidance_sweep: row s * B + b is lead b at strengths[s],
+    and the token ids come back as (S, B, L) (with return_sample=True the pair of ids and samples (S, B, C, L)).
+    ``refine_kwargs`` go to refine_tokens(); a ``noise`` tensor holds S * B rows, and with ``noise=NoiseSource(seed=..., sample0=n)``
+    sweep s equals the scalar call whose sample0 is n + s * B (bit for bit under a pinned ``kernel_choice``).  Cost: every row runs
+    from the start step of the LARGEST strength, so the sweep pays off only while its scalar calls underfill the GPU."""
+    try:
+        ndim = torch.as_tensor(strengths).dim()
+    except Exception:
+        ndim = -1
+    if ndim != 1 or len(strengths) == 0:
+        raise ValueError("strengths must be a non-empty 1-D sequence, one strength per sweep")
+    if "start_step" in refine_kwargs or "strength" in refine_kwargs:
+        raise ValueError("strength_sweep sets the start steps itself: give strengths, not start_step / strength")
+    S, B = len(strengths), sequences.shape[0]
+    starts = refine_start(int(refine_kwargs.get("timesteps", 100)), strengths)
+    draft_tokens = torch.as_tensor(draft_tokens)
+    out = model.refine_tokens(sequences.repeat(S, *([1] * (sequences.dim() - 1))), device, draft_tokens.repeat(S, 1),
+                              start_step=torch.tensor(starts, dtype=torch.int64).repeat_interleave(B), **refine_kwargs)
+    unflat = lambda t: t.reshape(S, B, *t.shape[1:])          # noqa: E731
+    return tuple(unflat(t) for t in out) if isinstance(out, tuple) else unflat(out)
+
+
+def refine_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForward", conditioning: Tensor, draft_tokens: Tensor,
+                        device, start_step=None, *, strength=None, cond_scale: float = 1.0, timesteps: int = 100,
+                        forward_timesteps: int = 100, X_norm_factor: float = 1.0, noise=None, forward_noise=None, sampler=None,
+                        sigma_schedule=None):
+    """The chain into the forward model, as complete_and_validate: refine the leads under the conditioning, decode inside the
+    last sampler update, re-predict the properties of the refined molecules with the forward model.  Returns (tokens (B, L)
+    int64, predicted properties (B, n_cond)).  ``start_step`` / ``strength`` / ``noise`` as refine_tokens; ``forward_noise`` as
+    generate_and_validate."""
+    tokens = model.refine_tokens(conditioning, device, draft_tokens, start_step, strength=strength, cond_scale=cond_scale,
+                                 timesteps=timesteps, noise=noise, sampler=sampler, sigma_schedule=sigma_schedule)
     props = predict_properties_from_tokens(model_forward, tokens, device, cond_scale=1.0, timesteps=forward_timesteps,
                                            X_norm_factor=X_norm_factor,
                                            context_embedding_max_length=conditioning.shape[1], noise=forward_noise)

@@ -19,6 +19,7 @@ fake / meta tensors).
     sample              DiffusionSampler.forward + ADPM2Sampler.forward, the whole loop (diffusion.py:577-591, :517-524)
     sample_with         the same with the sampler chosen: ADPM2Sampler, AEulerSampler (:476-483) or KarrasSampler (:437-453)
     inpaint_tokens      DiffusionInpainter.forward + ADPM2Sampler.inpaint on a draft of token ids, decoded (diffusion.py:526-549, :612-625)
+    refine_tokens       noise a draft of token ids up to the level of step k and run the remaining sampler steps, k per sample, decoded
     all_gather_samples  the one collective of a sharded call (RCCL all_gather_into_tensor)
     precond_in_rows / precond_out_rows   the denoise scaling with ONE coefficient per sample (denoise_fn(sigmas=(B,)))
     unet_eval_rows      net(x, time=(B,), ...) as ONE evaluation: one time-mapping / FiLM row per sample
@@ -33,7 +34,8 @@ import torch
 from torch.library import custom_op
 
 from . import runtime as rt
-from .diffusion import FUSED_SAMPLERS, ADPM2Sampler, NoiseSource, require_fused_kind, run_adpm2_inpaint, run_sampler
+from .diffusion import (FUSED_SAMPLERS, ADPM2Sampler, NoiseSource, require_fused_kind, run_adpm2_inpaint, run_refine,
+                        run_sampler)
 
 Tensor = torch.Tensor
 
@@ -695,6 +697,46 @@ def inpaint_tokens(embedding: Tensor, draft: Tensor, keep: Tensor, sigmas: Tenso
 @inpaint_tokens.register_fake
 def _(embedding, draft, keep, sigmas, handle, pred_dim, num_resamples, rho, sigma_data, embedding_scale, seed, sample0,
       dynamic_threshold=0.0):
+    B, L = draft.shape
+    return embedding.new_empty(B, pred_dim, L, dtype=torch.float32), draft.new_empty((B, L), dtype=torch.int32)
+
+
+@custom_op("mdt::refine_tokens", mutates_args=())
+def refine_tokens(embedding: Tensor, draft: Tensor, start: Tensor, init_noise: Optional[Tensor], sigmas: Tensor, handle: int,
+                  pred_dim: int, sampler_kind: int, sampler_params: Sequence[float], sigma_data: float, embedding_scale: float,
+                  seed: int, sample0: int, dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """The whole refine loop (diffusion.run_refine) for an evaluated sigma schedule (num_steps + 1 values) on a draft given as
+    token ids: draft (B, L) integer ids in [0, pred_dim) standing for their +-1 one-hot, start (B,) int32 in [0, num_steps - 2]:
+    row b is ``one_hot(draft[b]) + sigmas[start[b]] * draw0[b]`` followed by steps start[b] .. num_steps - 2 of the sampler
+    (sampler_kind / sampler_params as mdt::sample_with).  init_noise (B, pred_dim, L): the entry noise, or None; it and every step
+    draw otherwise come from the counter-based generator keyed by (seed, draw index, sample0 + b), draw 0 = the entry, draw i + 1 =
+    step i.  Returns (x (B, pred_dim, L) fp32, tokens (B, L) int32: argmax over channels)."""
+    dev = _hip(embedding, draft, start, init_noise)
+    eng = _engine_on(handle, dev, "mdt::refine_tokens")
+    B, L = embedding.shape[0], eng.c.length
+    if draft.is_floating_point() or tuple(draft.shape) != (B, L) or start.dtype != torch.int32 or tuple(start.shape) != (B,):
+        raise RuntimeError(f"mdt::refine_tokens: draft must be integer ids ({B}, {L}) and start int32 ({B},); got {draft.dtype} "
+                           f"{tuple(draft.shape)} and {start.dtype} {tuple(start.shape)}")
+    if init_noise is not None and tuple(init_noise.shape) != (B, pred_dim, L):
+        raise RuntimeError(f"mdt::refine_tokens: init_noise is {tuple(init_noise.shape)}, not ({B}, {pred_dim}, {L})")
+    tok = torch.zeros(B, L, dtype=torch.int32, device=dev)
+    if B == 0:
+        return torch.empty(0, pred_dim, L, device=dev), tok
+    ns = NoiseSource(seed=int(seed), sample0=int(sample0))
+    if init_noise is not None:
+        ns.init = init_noise
+    try:
+        x = run_refine(eng, embedding, int(pred_dim), sigmas.numel() - 1, ns, sigmas, _make_sampler(sampler_kind, list(sampler_params)),
+                       float(sigma_data), start.cpu(), draft=draft, embedding_scale=float(embedding_scale), tokens=tok,
+                       dynamic_threshold=float(dynamic_threshold))
+    except ValueError as e:                      # (the ops' convention: every failure is a RuntimeError)
+        raise RuntimeError(f"mdt::refine_tokens: {e}") from None
+    return x, tok
+
+
+@refine_tokens.register_fake
+def _(embedding, draft, start, init_noise, sigmas, handle, pred_dim, sampler_kind, sampler_params, sigma_data, embedding_scale,
+      seed, sample0, dynamic_threshold=0.0):
     B, L = draft.shape
     return embedding.new_empty(B, pred_dim, L, dtype=torch.float32), draft.new_empty((B, L), dtype=torch.int32)
 

@@ -101,6 +101,7 @@ SYMBOLS = {
     "mdt_add_noise": (_I, [_P, _P, _F, _U64, _U32, _L, _I, _I, _I, _P]),
     "mdt_inpaint_enter": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _U64, _U32, _U32, _L, _I, _I, _I, _I, _P]),
     "mdt_inpaint_finish": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "mdt_refine_enter": (_I, [_P, _P, _P, _I, _P, _P, _P, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P]),
     "mdt_argmax_tokens": (_I, [_P, _P, _I, _I, _I, _P]),
     "mdt_timer_create": (_P, [_I]),
     "mdt_timer_destroy": (None, [_P]),
