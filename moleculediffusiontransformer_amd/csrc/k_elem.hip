@@ -7,7 +7,10 @@
 // Sampler state, noise and results are (B, C, L) channel-major as in the reference; the U-Net consumes and
 // produces token-major (B, L, Cp) tiles.  One workgroup handles one sample: the (L x Cp) tile is transposed
 // through LDS so that both the channel-major and the token-major side are read and written as 16-byte
-// coalesced accesses.
+// coalesced accesses.  That pass exists once (tile_pass); an update kernel is its per-quad arithmetic on it,
+// with one noise draw (draw4 / tile_draw) and one launcher (launch_tile) shared by all of them.  Two exceptions:
+// k_inpaint_enter is left as it was, with its own loop, draws, source block and tail (measured slower in every
+// shared form); the k_dyn_scale pair sorts a flat LDS array (dyn_scale_sample).  Both share only the launcher.
 #include "mdt_kernels.h"
 #include "../../include/mdt_hip.h"
 
@@ -80,45 +83,117 @@ __device__ __forceinline__ void tile_zero_pad(float* tile, int C, int L, int Cp)
   }
 }
 
-// xin[b,l,c] = c_in * x[b,c,l]                                             (diffusion.py:810)
-__global__ __launch_bounds__(256) void k_precond_in(const float* x, float* xin, float c_in, int C, int L, int Cp) {
-  extern __shared__ float tile[];
+// tokens[b,l] = argmax_c tile[l][c] (first maximum, NaN wins, as torch.argmax) of a tile that carries the final x
+__device__ __forceinline__ void tile_argmax(const float* tile, int32_t* tokens, int b, int C, int L, int Cp) {
+  for (int l = threadIdx.x; l < L; l += blockDim.x) {
+    const float* t = tile + l * (Cp + 1);
+    float best = t[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = t[c];
+      if (v > best || (v != v && best == best)) { best = v; arg = c; }
+    }
+    tokens[(int64_t)b * L + l] = arg;
+  }
+}
+
+// Four consecutive positions of one channel: what one thread moves per 16-byte access of a channel-major tensor.
+struct Quad {
+  float v[4];
+  __device__ __forceinline__ float& operator[](int q) { return v[q]; }
+  __device__ __forceinline__ float operator[](int q) const { return v[q]; }
+};
+__device__ __forceinline__ Quad load4(const float* p) {
+  const float4 v = *reinterpret_cast<const float4*>(p);
+  return {{v.x, v.y, v.z, v.w}};
+}
+__device__ __forceinline__ void store4(float* p, const Quad& a) { *reinterpret_cast<float4*>(p) = make_float4(a[0], a[1], a[2], a[3]); }
+
+// A coefficient of the preconditioning: one for the batch, or one per sample (the *_rows kernels).
+__device__ __forceinline__ float coef(float v, int) { return v; }
+__device__ __forceinline__ float coef(const float* v, int b) { return v[b]; }
+
+// The noise of quad i of a (B, C, L) tensor: the caller's tensor, or the counter-based generator at the GLOBAL quad index
+// (elem0 = the flat index of the call's first element in the whole batch, a multiple of 4).
+__device__ __forceinline__ float4 draw4(const float* noise, uint64_t seed, uint32_t step, int64_t elem0, int64_t i) {
+  return noise ? reinterpret_cast<const float4*>(noise)[i] : normal4(seed, step, (uint64_t)((elem0 >> 2) + i));
+}
+// ... of the quad at element o of a tile kernel's shard, whose first sample is sample0 of the batch
+__device__ __forceinline__ Quad tile_draw(const float* noise, uint64_t seed, uint32_t step, int64_t sample0, int C, int L, int64_t o) {
+  const float4 nz = draw4(noise, seed, step, sample0 * C * L, o >> 2);
+  return {{nz.x, nz.y, nz.z, nz.w}};
+}
+
+// The source of an inpaint / refine entry at channel c, positions ot .. ot + 3 of the flat (B, L) index: dense fp32 (B, C, L) at
+// element o, or draft ids (B, L) standing for their +-1 one-hot (generative.py:1567-1569, :1603).
+__device__ __forceinline__ Quad source4(const float* src, const int32_t* draft, int64_t o, int64_t ot, int c) {
+  if (src) return load4(src + o);
+  const int4 d4 = *reinterpret_cast<const int4*>(draft + ot);
+  return {{c == d4.x ? 1.0f : -1.0f, c == d4.y ? 1.0f : -1.0f, c == d4.z ? 1.0f : -1.0f, c == d4.w ? 1.0f : -1.0f}};
+}
+
+// The scaffold of every "one workgroup per sample, one (L x Cp) tile in LDS" kernel.  A kernel is its per-quad arithmetic, a
+// body(const TileQuad&) called once per (channel, four positions) of the sample, between
+//   prologue: the U-Net's token-major output pred[b] staged in the tile (LoadPred) and the sample's dynamic-threshold scale;
+//   tail:     xin != nullptr: the tile, zero-padded to Cp channels, stored token-major as the next network input;
+//             else tokens != nullptr: the decode, tokens[b,l] = argmax_c tile[l][c]; else nothing.
+// The body reads and writes channel-major tensors at p.o and the tile at p.t[q * p.pitch], q = 0..3 -- element (c, l + q) is
+// touched by this one thread only, so the tile is reused in place (pred in, next input or final x out).
+struct TileQuad {
+  int b, c, l;     // sample (= workgroup), channel, first of the four positions
+  int64_t o;       // flat (B, C, L) index of (b, c, l)
+  float* t;        // tile element (l, c)
+  int pitch;       // tile floats from position l to l + 1
+  float ds;        // the sample's dynamic-threshold scale for clip_dyn, 0 = static clamp
+};
+template <bool LoadPred, class Body>
+__device__ __forceinline__ void tile_pass(float* tile, const float* pred, const float* dscale, float* xin, int32_t* tokens,
+                                          int C, int L, int Cp, Body body) {
   const int b = blockIdx.x;
-  const float* xb = x + (int64_t)b * C * L;
+  const float ds = dscale ? dscale[b] : 0.f;
+  if (LoadPred) { tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp); __syncthreads(); }
   const int l4n = L / 4;
   for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
     const int c = e / l4n, l = (e - c * l4n) * 4;
-    const float4 v = *reinterpret_cast<const float4*>(xb + c * L + l);
-    tile[(l + 0) * (Cp + 1) + c] = c_in * v.x;
-    tile[(l + 1) * (Cp + 1) + c] = c_in * v.y;
-    tile[(l + 2) * (Cp + 1) + c] = c_in * v.z;
-    tile[(l + 3) * (Cp + 1) + c] = c_in * v.w;
+    body(TileQuad{b, c, l, (int64_t)b * C * L + c * L + l, tile + l * (Cp + 1) + c, Cp + 1, ds});
   }
-  tile_zero_pad(tile, C, L, Cp);
-  __syncthreads();
-  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+  // (a kernel whose xin is not optional stores nothing for a null xin, where its own tail would have faulted)
+  if (xin) { tile_zero_pad(tile, C, L, Cp); __syncthreads(); tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp); }
+  else if (tokens) { __syncthreads(); tile_argmax(tile, tokens, b, C, L, Cp); }
+}
+
+// xin[b,l,c] = c_in * x[b,c,l]                                             (diffusion.py:810)
+template <class Coef>
+__device__ __forceinline__ void precond_in(float* tile, const float* x, float* xin, Coef c_in, int C, int L, int Cp) {
+  const float ci = coef(c_in, blockIdx.x);
+  tile_pass<false>(tile, nullptr, nullptr, xin, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x + p.o);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) p.t[q * p.pitch] = ci * xv[q];
+  });
+}
+__global__ __launch_bounds__(256) void k_precond_in(const float* x, float* xin, float c_in, int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  precond_in(tile, x, xin, c_in, C, L, Cp);
 }
 
 // D = clamp(c_skip*x + c_out*pred, -1, 1)                                  (diffusion.py:811-814)
+template <class Coef>
+__device__ __forceinline__ void precond_out(float* tile, const float* x, const float* pred, float* D, Coef c_skip, Coef c_out,
+                                            int C, int L, int Cp, const float* dscale) {
+  const float cs = coef(c_skip, blockIdx.x), co = coef(c_out, blockIdx.x);
+  tile_pass<true>(tile, pred, dscale, nullptr, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x + p.o);
+    Quad d;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) d[q] = clip_dyn(cs * xv[q] + co * p.t[q * p.pitch], p.ds);
+    store4(D + p.o, d);
+  });
+}
 __global__ __launch_bounds__(256) void k_precond_out(const float* x, const float* pred, float* D, float c_skip,
                                                       float c_out, int C, int L, int Cp, const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f;
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x + o);
-    float4 d;
-    d.x = clip_dyn(c_skip * v.x + c_out * tile[(l + 0) * (Cp + 1) + c], ds);
-    d.y = clip_dyn(c_skip * v.y + c_out * tile[(l + 1) * (Cp + 1) + c], ds);
-    d.z = clip_dyn(c_skip * v.z + c_out * tile[(l + 2) * (Cp + 1) + c], ds);
-    d.w = clip_dyn(c_skip * v.w + c_out * tile[(l + 3) * (Cp + 1) + c], ds);
-    *reinterpret_cast<float4*>(D + o) = d;
-  }
+  precond_out(tile, x, pred, D, c_skip, c_out, C, L, Cp, dscale);
 }
 
 // Dynamic thresholding (clip() with dynamic_threshold = q > 0, diffusion.py:78-88): per sample
@@ -180,30 +255,19 @@ __global__ __launch_bounds__(256) void k_adpm2_mid(const float* x, const float* 
                                                     float c_skip, float c_out, float sigma, float dt_mid,
                                                     float c_in_mid, int C, int L, int Cp, const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f;
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x + o);
-    const float xv[4] = {v.x, v.y, v.z, v.w};
-    float xm[4];
+  tile_pass<true>(tile, pred, dscale, xin_mid, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x + p.o);
+    Quad xm;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float* t = tile + (l + q) * (Cp + 1) + c;
-      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), ds);
+      float* t = p.t + q * p.pitch;
+      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), p.ds);
       const float d = (xv[q] - den) / sigma;
       xm[q] = xv[q] + d * dt_mid;
       *t = c_in_mid * xm[q];   // same thread owns (l, c): in-place reuse of the tile for xin_mid
     }
-    *reinterpret_cast<float4*>(x_mid + o) = make_float4(xm[0], xm[1], xm[2], xm[3]);
-  }
-  tile_zero_pad(tile, C, L, Cp);
-  __syncthreads();
-  tile_store(tile, xin_mid + (int64_t)b * L * Cp, L, Cp);
+    store4(x_mid + p.o, xm);
+  });
 }
 
 // Second half of ADPM2Sampler.step                                        (diffusion.py:510-515)
@@ -216,65 +280,22 @@ __global__ __launch_bounds__(256) void k_adpm2_next(float* x, const float* x_mid
                                                      uint64_t seed, uint32_t step, int64_t sample0, int C, int L,
                                                      int Cp, int32_t* tokens, const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f;
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
   const bool keep_x = tokens && !xin_next;       // the tile then carries x itself (not c_in_next * x) for the argmax
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x + o);
-    const float4 m = *reinterpret_cast<const float4*>(x_mid + o);
-    float4 nz;
-    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
-    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
-    const float xv[4] = {v.x, v.y, v.z, v.w}, mv[4] = {m.x, m.y, m.z, m.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
-    float xn[4];
+  tile_pass<true>(tile, pred, dscale, xin_next, tokens, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x + p.o), mv = load4(x_mid + p.o), nv = tile_draw(noise, seed, step, sample0, C, L, p.o);
+    Quad xn;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float* t = tile + (l + q) * (Cp + 1) + c;
-      const float den = clip_dyn(c_skip * mv[q] + c_out * (*t), ds);
+      float* t = p.t + q * p.pitch;
+      const float den = clip_dyn(c_skip * mv[q] + c_out * (*t), p.ds);
       const float d = (mv[q] - den) / sigma_mid;
       float xx = xv[q] + d * dt_down;
       xx = xx + nv[q] * sigma_up;
       xn[q] = xx;
       *t = keep_x ? xx : c_in_next * xx;
     }
-    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-  }
-  if (xin_next) {
-    tile_zero_pad(tile, C, L, Cp);
-    __syncthreads();
-    tile_store(tile, xin_next + (int64_t)b * L * Cp, L, Cp);
-  } else if (tokens) {
-    __syncthreads();
-    for (int l = threadIdx.x; l < L; l += blockDim.x) {
-      const float* t = tile + l * (Cp + 1);
-      float best = t[0];
-      int arg = 0;
-      for (int c = 1; c < C; ++c) {
-        const float v = t[c];
-        if (v > best || (v != v && best == best)) { best = v; arg = c; }
-      }
-      tokens[(int64_t)b * L + l] = arg;
-    }
-  }
-}
-
-// tokens[b,l] = argmax_c tile[l][c] (first maximum, NaN wins, as torch.argmax) of a tile that carries the final x
-__device__ __forceinline__ void tile_argmax(const float* tile, int32_t* tokens, int b, int C, int L, int Cp) {
-  for (int l = threadIdx.x; l < L; l += blockDim.x) {
-    const float* t = tile + l * (Cp + 1);
-    float best = t[0];
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-      const float v = t[c];
-      if (v > best || (v != v && best == best)) { best = v; arg = c; }
-    }
-    tokens[(int64_t)b * L + l] = arg;
-  }
+    store4(x + p.o, xn);
+  });
 }
 
 // The whole AEulerSampler.step after its one evaluation                   (diffusion.py:465-474, :811-814)
@@ -285,41 +306,22 @@ __global__ __launch_bounds__(256) void k_aeuler_next(float* x, const float* pred
                                                       float c_in_next, uint64_t seed, uint32_t step, int64_t sample0,
                                                       int C, int L, int Cp, int32_t* tokens, const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f;
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
   const bool keep_x = tokens && !xin_next;       // the tile then carries x itself (not c_in_next * x) for the argmax
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x + o);
-    float4 nz;
-    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
-    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
-    const float xv[4] = {v.x, v.y, v.z, v.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
-    float xn[4];
+  tile_pass<true>(tile, pred, dscale, xin_next, tokens, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x + p.o), nv = tile_draw(noise, seed, step, sample0, C, L, p.o);
+    Quad xn;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float* t = tile + (l + q) * (Cp + 1) + c;
-      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), ds);
+      float* t = p.t + q * p.pitch;
+      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), p.ds);
       const float d = (xv[q] - den) / sigma;
       float xx = xv[q] + d * dt;
       xx = xx + nv[q] * sigma_up;
       xn[q] = xx;
       *t = keep_x ? xx : c_in_next * xx;
     }
-    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-  }
-  if (xin_next) {
-    tile_zero_pad(tile, C, L, Cp);
-    __syncthreads();
-    tile_store(tile, xin_next + (int64_t)b * L * Cp, L, Cp);
-  } else if (tokens) {
-    __syncthreads();
-    tile_argmax(tile, tokens, b, C, L, Cp);
-  }
+    store4(x + p.o, xn);
+  });
 }
 
 // KarrasSampler.step, the churn stage                                      (diffusion.py:424-425, :810)
@@ -329,28 +331,17 @@ __global__ __launch_bounds__(256) void k_karras_hat(const float* x, const float*
                                                      float s_noise, float c_in_hat, uint64_t seed, uint32_t step,
                                                      int64_t sample0, int C, int L, int Cp) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x + o);
-    float4 nz;
-    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
-    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
-    const float xv[4] = {v.x, v.y, v.z, v.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
-    float xh[4];
+  tile_pass<false>(tile, nullptr, nullptr, xin, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x + p.o), nv = tile_draw(noise, seed, step, sample0, C, L, p.o);
+    Quad xh;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float eps = s_noise * nv[q];
       xh[q] = xv[q] + ns * eps;
-      tile[(l + q) * (Cp + 1) + c] = c_in_hat * xh[q];
+      p.t[q * p.pitch] = c_in_hat * xh[q];
     }
-    *reinterpret_cast<float4*>(x_hat + o) = make_float4(xh[0], xh[1], xh[2], xh[3]);
-  }
-  tile_zero_pad(tile, C, L, Cp);
-  __syncthreads();
-  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+    store4(x_hat + p.o, xh);
+  });
 }
 
 // KarrasSampler.step, the Euler move from sigma_hat to sigma_next          (diffusion.py:427-429, :811-814)
@@ -362,36 +353,20 @@ __global__ __launch_bounds__(256) void k_karras_mid(const float* x_hat, const fl
                                                      float c_in_next, int C, int L, int Cp, int32_t* tokens,
                                                      const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f;
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x_hat + o);
-    const float xv[4] = {v.x, v.y, v.z, v.w};
-    float dv[4], xn[4];
+  tile_pass<true>(tile, pred, dscale, xin_next, tokens, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x_hat + p.o);
+    Quad dv, xn;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float* t = tile + (l + q) * (Cp + 1) + c;
-      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), ds);
+      float* t = p.t + q * p.pitch;
+      const float den = clip_dyn(c_skip * xv[q] + c_out * (*t), p.ds);
       dv[q] = (xv[q] - den) / sigma_hat;
       xn[q] = xv[q] + dt * dv[q];
       *t = xin_next ? c_in_next * xn[q] : xn[q];
     }
-    *reinterpret_cast<float4*>(d_out + o) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-    *reinterpret_cast<float4*>(x_next + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-  }
-  if (xin_next) {
-    tile_zero_pad(tile, C, L, Cp);
-    __syncthreads();
-    tile_store(tile, xin_next + (int64_t)b * L * Cp, L, Cp);
-  } else if (tokens) {
-    __syncthreads();
-    tile_argmax(tile, tokens, b, C, L, Cp);
-  }
+    store4(d_out + p.o, dv);
+    store4(x_next + p.o, xn);
+  });
 }
 
 // KarrasSampler.step, the second-order correction AS THE REFERENCE WRITES IT (diffusion.py:432-434, :811-814)
@@ -403,40 +378,26 @@ __global__ __launch_bounds__(256) void k_karras_next(const float* x_hat, const f
                                                       float sigma_next, float half, int C, int L, int Cp, int32_t* tokens,
                                                       const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f;
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 h = *reinterpret_cast<const float4*>(x_hat + o);
-    const float4 m = *reinterpret_cast<const float4*>(x_next + o);
-    const float4 dd = *reinterpret_cast<const float4*>(d_in + o);
-    const float hv[4] = {h.x, h.y, h.z, h.w}, mv[4] = {m.x, m.y, m.z, m.w}, dv[4] = {dd.x, dd.y, dd.z, dd.w};
-    float xn[4];
+  tile_pass<true>(tile, pred, dscale, nullptr, tokens, C, L, Cp, [=](const TileQuad& p) {
+    const Quad hv = load4(x_hat + p.o), mv = load4(x_next + p.o), dv = load4(d_in + p.o);
+    Quad xn;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      float* t = tile + (l + q) * (Cp + 1) + c;
-      const float den = clip_dyn(c_skip * mv[q] + c_out * (*t), ds);
+      float* t = p.t + q * p.pitch;
+      const float den = clip_dyn(c_skip * mv[q] + c_out * (*t), p.ds);
       const float dp = (mv[q] - den) / sigma_next;
       xn[q] = hv[q] + half * (dv[q] + dp);
       *t = xn[q];
     }
-    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-  }
-  if (tokens) {
-    __syncthreads();
-    tile_argmax(tile, tokens, b, C, L, Cp);
-  }
+    store4(x + p.o, xn);
+  });
 }
 
 // Flat (B*C*L) kernels: 4 elements per thread.
 __global__ __launch_bounds__(256) void k_init_noise(float* x, const float* noise, float sigma0, uint64_t seed,
                                                      uint32_t step, int64_t elem0, int64_t n4) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : normal4(seed, step, (uint64_t)((elem0 >> 2) + i));
+    const float4 nz = draw4(noise, seed, step, elem0, i);
     reinterpret_cast<float4*>(x)[i] = make_float4(sigma0 * nz.x, sigma0 * nz.y, sigma0 * nz.z, sigma0 * nz.w);
   }
 }
@@ -444,7 +405,7 @@ __global__ __launch_bounds__(256) void k_init_noise(float* x, const float* noise
 __global__ __launch_bounds__(256) void k_add_noise(float* x, const float* noise, float s, uint64_t seed, uint32_t step,
                                                     int64_t elem0, int64_t n4) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 nz = noise ? reinterpret_cast<const float4*>(noise)[i] : normal4(seed, step, (uint64_t)((elem0 >> 2) + i));
+    const float4 nz = draw4(noise, seed, step, elem0, i);
     float4 v = reinterpret_cast<float4*>(x)[i];
     v.x = v.x + s * nz.x; v.y = v.y + s * nz.y; v.z = v.z + s * nz.z; v.w = v.w + s * nz.w;
     reinterpret_cast<float4*>(x)[i] = v;
@@ -464,8 +425,7 @@ __global__ __launch_bounds__(256) void k_adpm2_euler(const float* xb, const floa
     o.x = b.x + ((f.x - d.x) / sigma) * dt; o.y = b.y + ((f.y - d.y) / sigma) * dt;
     o.z = b.z + ((f.z - d.z) / sigma) * dt; o.w = b.w + ((f.w - d.w) / sigma) * dt;
     if (noise_mode) {
-      const float4 nz = noise_mode == 1 ? reinterpret_cast<const float4*>(noise)[i]
-                                        : normal4(seed, step, (uint64_t)((elem0 >> 2) + i));
+      const float4 nz = draw4(noise_mode == 1 ? noise : nullptr, seed, step, elem0, i);   // mode 2: the generator
       o.x = o.x + nz.x * sigma_up; o.y = o.y + nz.y * sigma_up; o.z = o.z + nz.z * sigma_up; o.w = o.w + nz.w * sigma_up;
     }
     reinterpret_cast<float4*>(out)[i] = o;
@@ -478,8 +438,7 @@ __global__ __launch_bounds__(256) void k_inpaint_merge(float* x, const float* sr
                                                         int64_t elem0, int64_t n4) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sigma != 0.0f)
-      nz = noise ? reinterpret_cast<const float4*>(noise)[i] : normal4(seed, step, (uint64_t)((elem0 >> 2) + i));
+    if (sigma != 0.0f) nz = draw4(noise, seed, step, elem0, i);
     const float4 sv = reinterpret_cast<const float4*>(src)[i];
     const uchar4 mk = reinterpret_cast<const uchar4*>(mask)[i];
     float4 v = reinterpret_cast<float4*>(x)[i];
@@ -504,6 +463,10 @@ __global__ __launch_bounds__(256) void k_inpaint_merge(float* x, const float* sr
 // src: dense fp32 (B, C, L), or draft ids (B, L) standing for their +-1 one-hot (generative.py:1567-1569, :1603).  keep: uint8
 // (B, C, L), or (B, L) broadcast over channels (keep_tok).  n_src / n_re == nullptr: the counter-based generator at draw index
 // step_src / step_re and the GLOBAL element index, as the flat kernels.  One workgroup per sample, as k_precond_in.
+// Left as it was, on neither tile_pass nor the shared helpers: as a tile_pass body, with its own loop on tile_draw and source4, and
+// with its own loop and draws on source4 alone, it gave the same bits from the same registers but ran 7 - 8 % slower alone, far
+// outside the spread of repeats (profiles/tile_pass_ab.txt); the cause was not found.  Its quad index and its source block are
+// second copies of tile_draw's and source4's: a change to either is made here too.
 __global__ __launch_bounds__(256) void k_inpaint_enter(float* x, float* xin, const float* src, const int32_t* draft,
                                                         const uint8_t* keep, int keep_tok, const float* n_src,
                                                         const float* n_re, float sigma, float renoise, float c_in,
@@ -568,35 +531,18 @@ __global__ __launch_bounds__(256) void k_refine_enter(float* x, float* xin, cons
                                                        const int32_t* draft, const float* noise, float sigma, float c_in,
                                                        uint64_t seed, uint32_t step, int64_t sample0, int C, int L, int Cp) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  if (start[b] != step_i) return;                        // (uniform over the workgroup: no barrier is skipped by a part of it)
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l, ot = (int64_t)b * L + l;
-    const uint64_t quad = (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2;
-    float sv[4];
-    if (src) {
-      const float4 s4 = *reinterpret_cast<const float4*>(src + o);
-      sv[0] = s4.x; sv[1] = s4.y; sv[2] = s4.z; sv[3] = s4.w;
-    } else {
-      const int4 d4 = *reinterpret_cast<const int4*>(draft + ot);
-      sv[0] = c == d4.x ? 1.0f : -1.0f; sv[1] = c == d4.y ? 1.0f : -1.0f;
-      sv[2] = c == d4.z ? 1.0f : -1.0f; sv[3] = c == d4.w ? 1.0f : -1.0f;
-    }
-    const float4 nz = noise ? *reinterpret_cast<const float4*>(noise + o) : normal4(seed, step, quad);
-    const float nv[4] = {nz.x, nz.y, nz.z, nz.w};
-    float xn[4];
+  if (start[blockIdx.x] != step_i) return;               // (uniform over the workgroup, before any barrier: none is skipped by a part of it)
+  tile_pass<false>(tile, nullptr, nullptr, xin, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const Quad sv = source4(src, draft, p.o, (int64_t)p.b * L + p.l, p.c);
+    const Quad nv = tile_draw(noise, seed, step, sample0, C, L, p.o);
+    Quad xn;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       xn[q] = sv[q] + sigma * nv[q];
-      tile[(l + q) * (Cp + 1) + c] = c_in * xn[q];
+      p.t[q * p.pitch] = c_in * xn[q];
     }
-    *reinterpret_cast<float4*>(x + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-  }
-  tile_zero_pad(tile, C, L, Cp);
-  __syncthreads();
-  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+    store4(x + p.o, xn);
+  });
 }
 
 // The last merge of ADPM2Sampler.inpaint (diffusion.py:549: sigma 0) and the decode (generative.py:1613-1614), one thread per
@@ -783,70 +729,30 @@ __global__ __launch_bounds__(256) void k_noise_in_rows(const float* x0, const fl
                                                         float* x_noisy, float* xin, uint64_t seed, uint32_t step, int64_t sample0,
                                                         int C, int L, int Cp) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float sg = sigma[b], ci = c_in[b];
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x0 + o);
-    float4 nz;
-    if (noise) nz = *reinterpret_cast<const float4*>(noise + o);
-    else nz = normal4(seed, step, (uint64_t)(((sample0 + b) * C + c) * (int64_t)L + l) >> 2);
-    const float xv[4] = {v.x, v.y, v.z, v.w}, nv[4] = {nz.x, nz.y, nz.z, nz.w};
-    float xn[4];
+  const float sg = sigma[blockIdx.x], ci = c_in[blockIdx.x];
+  tile_pass<false>(tile, nullptr, nullptr, xin, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const Quad xv = load4(x0 + p.o), nv = tile_draw(noise, seed, step, sample0, C, L, p.o);
+    Quad xn;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       xn[q] = xv[q] + sg * nv[q];
-      tile[(l + q) * (Cp + 1) + c] = ci * xn[q];
+      p.t[q * p.pitch] = ci * xn[q];
     }
-    *reinterpret_cast<float4*>(x_noisy + o) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-  }
-  tile_zero_pad(tile, C, L, Cp);
-  __syncthreads();
-  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+    store4(x_noisy + p.o, xn);
+  });
 }
 
 // xin[b,l,c] = c_in[b] * x[b,c,l]
 __global__ __launch_bounds__(256) void k_precond_in_rows(const float* x, float* xin, const float* c_in, int C, int L, int Cp) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ci = c_in[b];
-  const float* xb = x + (int64_t)b * C * L;
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const float4 v = *reinterpret_cast<const float4*>(xb + c * L + l);
-    tile[(l + 0) * (Cp + 1) + c] = ci * v.x;
-    tile[(l + 1) * (Cp + 1) + c] = ci * v.y;
-    tile[(l + 2) * (Cp + 1) + c] = ci * v.z;
-    tile[(l + 3) * (Cp + 1) + c] = ci * v.w;
-  }
-  tile_zero_pad(tile, C, L, Cp);
-  __syncthreads();
-  tile_store(tile, xin + (int64_t)b * L * Cp, L, Cp);
+  precond_in(tile, x, xin, c_in, C, L, Cp);
 }
 
 // D = clip(c_skip[b] * x + c_out[b] * pred)
 __global__ __launch_bounds__(256) void k_precond_out_rows(const float* x, const float* pred, float* D, const float* c_skip,
                                                            const float* c_out, int C, int L, int Cp, const float* dscale) {
   extern __shared__ float tile[];
-  const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f, cs = c_skip[b], co = c_out[b];
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x + o);
-    float4 d;
-    d.x = clip_dyn(cs * v.x + co * tile[(l + 0) * (Cp + 1) + c], ds);
-    d.y = clip_dyn(cs * v.y + co * tile[(l + 1) * (Cp + 1) + c], ds);
-    d.z = clip_dyn(cs * v.z + co * tile[(l + 2) * (Cp + 1) + c], ds);
-    d.w = clip_dyn(cs * v.w + co * tile[(l + 3) * (Cp + 1) + c], ds);
-    *reinterpret_cast<float4*>(D + o) = d;
-  }
+  precond_out(tile, x, pred, D, c_skip, c_out, C, L, Cp, dscale);
 }
 
 // loss[b] = weight[b] * mean_{c,l} ((clip(c_skip[b] x_noisy + c_out[b] pred) - x0)^2)   (diffusion.py:838-844), the denoised
@@ -859,24 +765,17 @@ __global__ __launch_bounds__(256) void k_loss_rows(const float* x0, const float*
   extern __shared__ float tile[];
   float* red = tile;                                 // the waves' partial sums reuse the tile once every thread is done with it
   const int b = blockIdx.x;
-  const float ds = dscale ? dscale[b] : 0.f, cs = c_skip[b], co = c_out[b];
-  tile_load(tile, pred + (int64_t)b * L * Cp, L, Cp);
-  __syncthreads();
-  const int l4n = L / 4;
+  const float cs = c_skip[b], co = c_out[b];
   float acc = 0.f;
-  for (int e = threadIdx.x; e < C * l4n; e += blockDim.x) {
-    const int c = e / l4n, l = (e - c * l4n) * 4;
-    const int64_t o = (int64_t)b * C * L + c * L + l;
-    const float4 v = *reinterpret_cast<const float4*>(x_noisy + o);
-    const float4 t = *reinterpret_cast<const float4*>(x0 + o);
-    const float xv[4] = {v.x, v.y, v.z, v.w}, tv[4] = {t.x, t.y, t.z, t.w};
+  tile_pass<true>(tile, pred, dscale, nullptr, nullptr, C, L, Cp, [=, &acc](const TileQuad& p) {
+    const Quad xv = load4(x_noisy + p.o), tv = load4(x0 + p.o);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float den = clip_dyn(cs * xv[q] + co * tile[(l + q) * (Cp + 1) + c], ds);
+      const float den = clip_dyn(cs * xv[q] + co * p.t[q * p.pitch], p.ds);
       const float r = den - tv[q];
       acc = acc + r * r;
     }
-  }
+  });
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
   __syncthreads();
@@ -933,7 +832,46 @@ inline int bad(const char* msg) {
   mdt_set_error(msg);
   return 2;
 }
+inline int bad(const char* name, const char* msg) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s%s", name, msg);
+  return bad(buf);
+}
 inline size_t tile_bytes(int L, int Cp) { return (size_t)L * (Cp + 1) * sizeof(float); }
+
+// Launch of a kernel that holds one sample in dynamic LDS, one workgroup of 256 per sample: up to the CU's 160 KiB (the default limit
+// of a launch is 64 KiB: raised once per kernel and device -- per device, not per process, mdt_kernels.h).
+constexpr size_t kMaxLds = 160 * 1024;
+template <auto Kernel, class... A>
+int launch_lds(const char* name, int B, size_t lds, void* stream, A... args) {
+  static mdt::DevOnce once;
+  if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+  hipLaunchKernelGGL(Kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, args...);
+  return finish(name);
+}
+// The entry of every tile kernel: an empty batch is no error, the tile's shape is checked (max_length = 1024, the reference
+// constructors' default, at 16 padded channels is 68 KiB), then `refuse` -- what this entry point excludes beyond that, or nullptr.
+template <auto Kernel, class... A>
+int launch_tile(const char* name, const char* refuse, int B, int C, int L, int Cp, void* stream, A... args) {
+  if (B <= 0) return 0;
+  if (L % 4 || Cp % 16 || Cp < C) return bad(name, ": need L % 4 == 0, Cp % 16 == 0, Cp >= C");
+  if (tile_bytes(L, Cp) > kMaxLds) return bad(name, ": (L, Cp) tile exceeds the 160 KiB of LDS of a compute unit");
+  if (refuse) return bad(name, refuse);
+  return launch_lds<Kernel>(name, B, tile_bytes(L, Cp), stream, args...);
+}
+// mdt_dyn_scale / mdt_dyn_scale_rows: the coefficients as float or as const float* per sample; `refuse` as launch_tile's
+template <auto Kernel, class Coef>
+int launch_dyn_scale(const char* name, const char* refuse, const float* x, const float* pred, float* scale, Coef c_skip, Coef c_out, float q,
+                     int B, int C, int L, int Cp, void* stream) {
+  if (B <= 0) return 0;
+  if (refuse) return bad(name, refuse);
+  if (!(q > 0.0f && q <= 1.0f)) return bad(name, ": the quantile must lie in (0, 1]");
+  if (C <= 0 || L <= 0 || Cp < C) return bad(name, ": bad dims");
+  int npad = 1;
+  while (npad < C * L) npad <<= 1;
+  if ((size_t)npad * sizeof(float) > kMaxLds) return bad(name, ": C * L exceeds 32768 values (the sort runs in one compute unit's LDS)");
+  return launch_lds<Kernel>(name, B, (size_t)npad * sizeof(float), stream, x, pred, scale, c_skip, c_out, q, C, L, Cp, npad);
+}
 }  // namespace
 
 extern "C" {
@@ -957,178 +895,109 @@ int mdt_cond_embed_add(const float* seq, const float* fc1_w, const float* fc1_b,
   return finish("mdt_cond_embed_add");
 }
 
-// the sampler kernels stage one sample's (L x Cp) tile in LDS: up to the CU's 160 KiB (the default limit of a launch is 64 KiB:
-// raised once per kernel and device).  max_length = 1024 (the reference constructors' default) at 16 padded channels is 68 KiB.
-#define MDT_CHECK_TILE(name)                                                                   \
-  if (B <= 0) return 0;                                                                        \
-  if (L % 4 || Cp % 16 || Cp < C) return bad(name ": need L % 4 == 0, Cp % 16 == 0, Cp >= C"); \
-  if (tile_bytes(L, Cp) > 160 * 1024) return bad(name ": (L, Cp) tile exceeds the 160 KiB of LDS of a compute unit");
-#define MDT_BIG_LDS(kernel)                                                                                          \
-  do {                                                                                                                \
-    static mdt::DevOnce once_;                                    /* per device, not per process (mdt_kernels.h) */     \
-    if (once_.first())                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-  } while (0)
-
 int mdt_precond_in(const float* x, float* xin, float c_in, int32_t B, int32_t C, int32_t L, int32_t Cp,
                    void* stream) {
-  MDT_CHECK_TILE("mdt_precond_in")
-  MDT_BIG_LDS(mdt::k_precond_in);
-  hipLaunchKernelGGL(mdt::k_precond_in, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, c_in, C, L,
-                     Cp);
-  return finish("mdt_precond_in");
+  return launch_tile<mdt::k_precond_in>("mdt_precond_in", nullptr, B, C, L, Cp, stream, x, xin, c_in, C, L, Cp);
 }
 
 int mdt_precond_out(const float* x, const float* pred, float* D, float c_skip, float c_out, int32_t B, int32_t C,
                     int32_t L, int32_t Cp, const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_precond_out")
-  MDT_BIG_LDS(mdt::k_precond_out);
-  hipLaunchKernelGGL(mdt::k_precond_out, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, pred, D,
-                     c_skip, c_out, C, L, Cp, dyn_scale);
-  return finish("mdt_precond_out");
+  return launch_tile<mdt::k_precond_out>("mdt_precond_out", nullptr, B, C, L, Cp, stream, x, pred, D, c_skip, c_out, C, L, Cp,
+                                         dyn_scale);
 }
 
 int mdt_dyn_scale(const float* x, const float* pred, float* scale, float c_skip, float c_out, float q, int32_t B, int32_t C,
                   int32_t L, int32_t Cp, void* stream) {
-  if (B <= 0) return 0;
-  if (!x || !pred || !scale) return bad("mdt_dyn_scale: null pointer");
-  if (!(q > 0.0f && q <= 1.0f)) return bad("mdt_dyn_scale: the quantile must lie in (0, 1]");
-  if (C <= 0 || L <= 0 || Cp < C) return bad("mdt_dyn_scale: bad dims");
-  int npad = 1;
-  while (npad < C * L) npad <<= 1;
-  if ((size_t)npad * sizeof(float) > 160 * 1024) return bad("mdt_dyn_scale: C * L exceeds 32768 values (the sort runs in one compute unit's LDS)");
-  MDT_BIG_LDS(mdt::k_dyn_scale);
-  hipLaunchKernelGGL(mdt::k_dyn_scale, dim3(B), dim3(256), (size_t)npad * sizeof(float), (hipStream_t)stream, x, pred, scale,
-                     c_skip, c_out, q, C, L, Cp, npad);
-  return finish("mdt_dyn_scale");
+  const char* refuse = !x || !pred || !scale ? ": null pointer" : nullptr;
+  return launch_dyn_scale<mdt::k_dyn_scale>("mdt_dyn_scale", refuse, x, pred, scale, c_skip, c_out, q, B, C, L, Cp, stream);
 }
 
 /* ---- one noise level per sample (include/mdt_hip.h: "per-sample noise levels") ---- */
 int mdt_noise_in_rows(const float* x0, const float* noise, const float* sigma, const float* c_in, float* x_noisy, float* xin,
                       uint64_t seed, uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L, int32_t Cp, void* stream) {
-  MDT_CHECK_TILE("mdt_noise_in_rows")
-  if (!x0 || !sigma || !c_in || !x_noisy || !xin) return bad("mdt_noise_in_rows: null pointer");
-  MDT_BIG_LDS(mdt::k_noise_in_rows);
-  hipLaunchKernelGGL(mdt::k_noise_in_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x0, noise, sigma, c_in,
-                     x_noisy, xin, seed, step, sample0, C, L, Cp);
-  return finish("mdt_noise_in_rows");
+  const char* refuse = !x0 || !sigma || !c_in || !x_noisy || !xin ? ": null pointer" : nullptr;
+  return launch_tile<mdt::k_noise_in_rows>("mdt_noise_in_rows", refuse, B, C, L, Cp, stream, x0, noise, sigma, c_in, x_noisy, xin,
+                                           seed, step, sample0, C, L, Cp);
 }
 
 int mdt_precond_in_rows(const float* x, float* xin, const float* c_in, int32_t B, int32_t C, int32_t L, int32_t Cp, void* stream) {
-  MDT_CHECK_TILE("mdt_precond_in_rows")
-  if (!x || !xin || !c_in) return bad("mdt_precond_in_rows: null pointer");
-  MDT_BIG_LDS(mdt::k_precond_in_rows);
-  hipLaunchKernelGGL(mdt::k_precond_in_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, c_in, C, L, Cp);
-  return finish("mdt_precond_in_rows");
+  const char* refuse = !x || !xin || !c_in ? ": null pointer" : nullptr;
+  return launch_tile<mdt::k_precond_in_rows>("mdt_precond_in_rows", refuse, B, C, L, Cp, stream, x, xin, c_in, C, L, Cp);
 }
 
 int mdt_precond_out_rows(const float* x, const float* pred, float* D, const float* c_skip, const float* c_out, int32_t B, int32_t C,
                          int32_t L, int32_t Cp, const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_precond_out_rows")
-  if (!x || !pred || !D || !c_skip || !c_out) return bad("mdt_precond_out_rows: null pointer");
-  MDT_BIG_LDS(mdt::k_precond_out_rows);
-  hipLaunchKernelGGL(mdt::k_precond_out_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, pred, D, c_skip,
-                     c_out, C, L, Cp, dyn_scale);
-  return finish("mdt_precond_out_rows");
+  const char* refuse = !x || !pred || !D || !c_skip || !c_out ? ": null pointer" : nullptr;
+  return launch_tile<mdt::k_precond_out_rows>("mdt_precond_out_rows", refuse, B, C, L, Cp, stream, x, pred, D, c_skip, c_out, C, L,
+                                              Cp, dyn_scale);
 }
 
 int mdt_dyn_scale_rows(const float* x, const float* pred, float* scale, const float* c_skip, const float* c_out, float q, int32_t B,
                        int32_t C, int32_t L, int32_t Cp, void* stream) {
-  if (B <= 0) return 0;
-  if (!x || !pred || !scale || !c_skip || !c_out) return bad("mdt_dyn_scale_rows: null pointer");
-  if (!(q > 0.0f && q <= 1.0f)) return bad("mdt_dyn_scale_rows: the quantile must lie in (0, 1]");
-  if (C <= 0 || L <= 0 || Cp < C) return bad("mdt_dyn_scale_rows: bad dims");
-  int npad = 1;
-  while (npad < C * L) npad <<= 1;
-  if ((size_t)npad * sizeof(float) > 160 * 1024) return bad("mdt_dyn_scale_rows: C * L exceeds 32768 values (the sort runs in one compute unit's LDS)");
-  MDT_BIG_LDS(mdt::k_dyn_scale_rows);
-  hipLaunchKernelGGL(mdt::k_dyn_scale_rows, dim3(B), dim3(256), (size_t)npad * sizeof(float), (hipStream_t)stream, x, pred, scale,
-                     c_skip, c_out, q, C, L, Cp, npad);
-  return finish("mdt_dyn_scale_rows");
+  const char* refuse = !x || !pred || !scale || !c_skip || !c_out ? ": null pointer" : nullptr;
+  return launch_dyn_scale<mdt::k_dyn_scale_rows>("mdt_dyn_scale_rows", refuse, x, pred, scale, c_skip, c_out, q, B, C, L, Cp, stream);
 }
 
 int mdt_loss_rows(const float* x0, const float* x_noisy, const float* pred, const float* c_skip, const float* c_out,
                   const float* weight, const float* dyn_scale, float* loss, int32_t B, int32_t C, int32_t L, int32_t Cp,
                   void* stream) {
-  MDT_CHECK_TILE("mdt_loss_rows")
-  if (!x0 || !x_noisy || !pred || !c_skip || !c_out || !weight || !loss) return bad("mdt_loss_rows: null pointer");
-  if ((int64_t)C * L > 32768) return bad("mdt_loss_rows: C * L exceeds 32768 values");
-  MDT_BIG_LDS(mdt::k_loss_rows);
-  hipLaunchKernelGGL(mdt::k_loss_rows, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x0, x_noisy, pred, c_skip,
-                     c_out, weight, dyn_scale, loss, C, L, Cp);
-  return finish("mdt_loss_rows");
+  const char* refuse = !x0 || !x_noisy || !pred || !c_skip || !c_out || !weight || !loss ? ": null pointer" : nullptr;
+  if (!refuse && (int64_t)C * L > 32768) refuse = ": C * L exceeds 32768 values";
+  return launch_tile<mdt::k_loss_rows>("mdt_loss_rows", refuse, B, C, L, Cp, stream, x0, x_noisy, pred, c_skip, c_out, weight,
+                                       dyn_scale, loss, C, L, Cp);
 }
 
 int mdt_adpm2_mid(const float* x, const float* pred, float* x_mid, float* xin_mid, float c_skip, float c_out,
                   float sigma, float dt_mid, float c_in_mid, int32_t B, int32_t C, int32_t L, int32_t Cp,
                   const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_adpm2_mid")
-  MDT_BIG_LDS(mdt::k_adpm2_mid);
-  hipLaunchKernelGGL(mdt::k_adpm2_mid, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, pred, x_mid,
-                     xin_mid, c_skip, c_out, sigma, dt_mid, c_in_mid, C, L, Cp, dyn_scale);
-  return finish("mdt_adpm2_mid");
+  return launch_tile<mdt::k_adpm2_mid>("mdt_adpm2_mid", nullptr, B, C, L, Cp, stream, x, pred, x_mid, xin_mid, c_skip, c_out, sigma,
+                                       dt_mid, c_in_mid, C, L, Cp, dyn_scale);
 }
 
 int mdt_adpm2_next(float* x, const float* x_mid, const float* pred, const float* noise, float* xin_next, float c_skip,
                    float c_out, float sigma_mid, float dt_down, float sigma_up, float c_in_next, uint64_t seed,
                    uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L, int32_t Cp, int32_t* tokens,
                    const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_adpm2_next")
-  if (tokens && xin_next) return bad("mdt_adpm2_next: tokens are decoded on the LAST update of a call (xin_next == NULL)");
-  MDT_BIG_LDS(mdt::k_adpm2_next);
-  hipLaunchKernelGGL(mdt::k_adpm2_next, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, x_mid, pred,
-                     noise, xin_next, c_skip, c_out, sigma_mid, dt_down, sigma_up, c_in_next, seed, step, sample0, C, L,
-                     Cp, tokens, dyn_scale);
-  return finish("mdt_adpm2_next");
+  const char* refuse = tokens && xin_next ? ": tokens are decoded on the LAST update of a call (xin_next == NULL)" : nullptr;
+  return launch_tile<mdt::k_adpm2_next>("mdt_adpm2_next", refuse, B, C, L, Cp, stream, x, x_mid, pred, noise, xin_next, c_skip,
+                                        c_out, sigma_mid, dt_down, sigma_up, c_in_next, seed, step, sample0, C, L, Cp, tokens,
+                                        dyn_scale);
 }
 
 int mdt_aeuler_next(float* x, const float* pred, const float* noise, float* xin_next, float c_skip, float c_out, float sigma,
                     float dt, float sigma_up, float c_in_next, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
                     int32_t C, int32_t L, int32_t Cp, int32_t* tokens, const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_aeuler_next")
-  if (!x || !pred) return bad("mdt_aeuler_next: null pointer");
-  if (tokens && xin_next) return bad("mdt_aeuler_next: tokens are decoded on the LAST update of a call (xin_next == NULL)");
-  MDT_BIG_LDS(mdt::k_aeuler_next);
-  hipLaunchKernelGGL(mdt::k_aeuler_next, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, pred, noise,
-                     xin_next, c_skip, c_out, sigma, dt, sigma_up, c_in_next, seed, step, sample0, C, L, Cp, tokens,
-                     dyn_scale);
-  return finish("mdt_aeuler_next");
+  const char* refuse = !x || !pred ? ": null pointer" : nullptr;
+  if (!refuse && tokens && xin_next) refuse = ": tokens are decoded on the LAST update of a call (xin_next == NULL)";
+  return launch_tile<mdt::k_aeuler_next>("mdt_aeuler_next", refuse, B, C, L, Cp, stream, x, pred, noise, xin_next, c_skip, c_out,
+                                         sigma, dt, sigma_up, c_in_next, seed, step, sample0, C, L, Cp, tokens, dyn_scale);
 }
 
 int mdt_karras_hat(const float* x, const float* noise, float* x_hat, float* xin, float noise_scale, float s_noise,
                    float c_in_hat, uint64_t seed, uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L,
                    int32_t Cp, void* stream) {
-  MDT_CHECK_TILE("mdt_karras_hat")
-  if (!x || !x_hat || !xin) return bad("mdt_karras_hat: null pointer");
-  MDT_BIG_LDS(mdt::k_karras_hat);
-  hipLaunchKernelGGL(mdt::k_karras_hat, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, noise, x_hat, xin,
-                     noise_scale, s_noise, c_in_hat, seed, step, sample0, C, L, Cp);
-  return finish("mdt_karras_hat");
+  const char* refuse = !x || !x_hat || !xin ? ": null pointer" : nullptr;
+  return launch_tile<mdt::k_karras_hat>("mdt_karras_hat", refuse, B, C, L, Cp, stream, x, noise, x_hat, xin, noise_scale, s_noise,
+                                        c_in_hat, seed, step, sample0, C, L, Cp);
 }
 
 int mdt_karras_mid(const float* x_hat, const float* pred, float* d, float* x_next, float* xin_next, float c_skip,
                    float c_out, float sigma_hat, float dt, float c_in_next, int32_t B, int32_t C, int32_t L, int32_t Cp,
                    int32_t* tokens, const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_karras_mid")
-  if (!x_hat || !pred || !d || !x_next) return bad("mdt_karras_mid: null pointer");
-  if (x_next == x_hat || d == x_hat || d == x_next) return bad("mdt_karras_mid: x_hat, d and x_next are three buffers");
-  if (tokens && xin_next) return bad("mdt_karras_mid: tokens are decoded when the Euler move ends the call (xin_next == NULL)");
-  MDT_BIG_LDS(mdt::k_karras_mid);
-  hipLaunchKernelGGL(mdt::k_karras_mid, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x_hat, pred, d, x_next,
-                     xin_next, c_skip, c_out, sigma_hat, dt, c_in_next, C, L, Cp, tokens, dyn_scale);
-  return finish("mdt_karras_mid");
+  const char* refuse = !x_hat || !pred || !d || !x_next ? ": null pointer" : nullptr;
+  if (!refuse && (x_next == x_hat || d == x_hat || d == x_next)) refuse = ": x_hat, d and x_next are three buffers";
+  if (!refuse && tokens && xin_next) refuse = ": tokens are decoded when the Euler move ends the call (xin_next == NULL)";
+  return launch_tile<mdt::k_karras_mid>("mdt_karras_mid", refuse, B, C, L, Cp, stream, x_hat, pred, d, x_next, xin_next, c_skip,
+                                        c_out, sigma_hat, dt, c_in_next, C, L, Cp, tokens, dyn_scale);
 }
 
 int mdt_karras_next(const float* x_hat, const float* x_next, const float* d, const float* pred, float* x, float c_skip,
                     float c_out, float sigma_next, float half, int32_t B, int32_t C, int32_t L, int32_t Cp,
                     int32_t* tokens, const float* dyn_scale, void* stream) {
-  MDT_CHECK_TILE("mdt_karras_next")
-  if (!x_hat || !x_next || !d || !pred || !x) return bad("mdt_karras_next: null pointer");
-  if (sigma_next == 0.0f) return bad("mdt_karras_next: sigma_next == 0 has no correction (the Euler move is the step)");
-  MDT_BIG_LDS(mdt::k_karras_next);
-  hipLaunchKernelGGL(mdt::k_karras_next, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x_hat, x_next, d, pred,
-                     x, c_skip, c_out, sigma_next, half, C, L, Cp, tokens, dyn_scale);
-  return finish("mdt_karras_next");
+  const char* refuse = !x_hat || !x_next || !d || !pred || !x ? ": null pointer" : nullptr;
+  if (!refuse && sigma_next == 0.0f) refuse = ": sigma_next == 0 has no correction (the Euler move is the step)";
+  return launch_tile<mdt::k_karras_next>("mdt_karras_next", refuse, B, C, L, Cp, stream, x_hat, x_next, d, pred, x, c_skip, c_out,
+                                         sigma_next, half, C, L, Cp, tokens, dyn_scale);
 }
 
 int mdt_init_noise(float* x, const float* noise, float sigma0, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
@@ -1165,25 +1034,20 @@ int mdt_inpaint_enter(float* x, float* xin, const float* src, const int32_t* dra
                       int32_t keep_per_token, const float* n_src, const float* n_re, float sigma, float renoise, float c_in,
                       uint64_t seed, uint32_t step_src, uint32_t step_re, int64_t sample0, int32_t B, int32_t C, int32_t L,
                       int32_t Cp, void* stream) {
-  MDT_CHECK_TILE("mdt_inpaint_enter")
-  if (!x || !xin || !keep) return bad("mdt_inpaint_enter: null pointer");
-  if (!src == !draft) return bad("mdt_inpaint_enter: give the source either dense (src) or as draft ids (draft)");
-  MDT_BIG_LDS(mdt::k_inpaint_enter);
-  hipLaunchKernelGGL(mdt::k_inpaint_enter, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, src, draft, keep,
-                     keep_per_token ? 1 : 0, n_src, n_re, sigma, renoise, c_in, seed, step_src, step_re, sample0, C, L, Cp);
-  return finish("mdt_inpaint_enter");
+  const char* refuse = !x || !xin || !keep ? ": null pointer" : nullptr;
+  if (!refuse && !src == !draft) refuse = ": give the source either dense (src) or as draft ids (draft)";
+  return launch_tile<mdt::k_inpaint_enter>("mdt_inpaint_enter", refuse, B, C, L, Cp, stream, x, xin, src, draft, keep,
+                                           keep_per_token ? 1 : 0, n_src, n_re, sigma, renoise, c_in, seed, step_src, step_re,
+                                           sample0, C, L, Cp);
 }
 
 int mdt_refine_enter(float* x, float* xin, const int32_t* start, int32_t step_i, const float* src, const int32_t* draft,
                      const float* noise, float sigma, float c_in, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
                      int32_t C, int32_t L, int32_t Cp, void* stream) {
-  MDT_CHECK_TILE("mdt_refine_enter")
-  if (!x || !xin || !start) return bad("mdt_refine_enter: null pointer");
-  if (!src == !draft) return bad("mdt_refine_enter: give the source either dense (src) or as draft ids (draft)");
-  MDT_BIG_LDS(mdt::k_refine_enter);
-  hipLaunchKernelGGL(mdt::k_refine_enter, dim3(B), dim3(256), tile_bytes(L, Cp), (hipStream_t)stream, x, xin, start, step_i, src,
-                     draft, noise, sigma, c_in, seed, step, sample0, C, L, Cp);
-  return finish("mdt_refine_enter");
+  const char* refuse = !x || !xin || !start ? ": null pointer" : nullptr;
+  if (!refuse && !src == !draft) refuse = ": give the source either dense (src) or as draft ids (draft)";
+  return launch_tile<mdt::k_refine_enter>("mdt_refine_enter", refuse, B, C, L, Cp, stream, x, xin, start, step_i, src, draft, noise,
+                                          sigma, c_in, seed, step, sample0, C, L, Cp);
 }
 
 int mdt_inpaint_finish(float* x, const float* src, const int32_t* draft, const uint8_t* keep, int32_t keep_per_token,

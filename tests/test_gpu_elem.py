@@ -557,7 +557,7 @@ def test_per_sample_kernels_over_edge_shapes(dims, dyn):
 
 
 def test_tile_kernels_refuse_what_the_abi_excludes():
-    """Every entry point behind MDT_CHECK_TILE: a tile above 160 KiB (L = 2412 at Cp = 16: 164,016 B), L % 4, Cp % 16, Cp < C --
+    """Every entry point behind launch_tile's shape check: a tile above 160 KiB (L = 2412 at Cp = 16: 164,016 B), L % 4, Cp % 16, Cp < C --
     each returns non-zero and launches nothing (no buffer is touched)."""
     lib = rt.load_library()
     bad = [(2, 3, 2412, 16), (2, 3, 6, 16), (2, 3, 32, 24), (2, 20, 32, 16)]

@@ -114,7 +114,8 @@ def test_seed_mode_equals_dense_inpaint_bit_for_bit(models, cond_scale, R):
     assert not torch.equal(other, x)
 
 
-@pytest.mark.parametrize("B,C,L,Cp", [(5, 22, 32, 32), (3, 16, 64, 16)])
+# the last three are EDGE_SHAPES of test_gpu_elem.py: C = 1 at L = 4; odd C with Cp no power of two; L / 4 one past a wave
+@pytest.mark.parametrize("B,C,L,Cp", [(5, 22, 32, 32), (3, 16, 64, 16), (3, 1, 4, 16), (2, 33, 36, 48), (2, 7, 260, 16)])
 def test_enter_and_finish_kernels_equal_the_kernels_they_fuse_bit_for_bit(B, C, L, Cp):
     lib = rt.load_library()
     gen = torch.Generator().manual_seed(100 + C)

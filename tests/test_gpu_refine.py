@@ -106,7 +106,8 @@ def test_fixture_parity(models, name, model, sampler, tag):
 # ----------------------------------------------------------------------------------------------------------------------
 # 2. the entry kernel against the host reference (refine_ref.py)
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,C,L,Cp", [(5, 22, 32, 32), (3, 16, 64, 16)])
+# the last three are EDGE_SHAPES of test_gpu_elem.py: C = 1 at L = 4; odd C with Cp no power of two; L / 4 one past a wave
+@pytest.mark.parametrize("B,C,L,Cp", [(5, 22, 32, 32), (3, 16, 64, 16), (3, 1, 4, 16), (2, 33, 36, 48), (2, 7, 260, 16)])
 def test_entry_kernel_against_the_host_reference(B, C, L, Cp):
     """Explicit noise: float32 arithmetic in the kernel's order, bit for bit (sigma 2.75).  Seeded: against the float64 normals of
     noise_ref at NOISE_TOL, the bound of mdt_init_noise -- with sigma 0.5 the product is exact, the generator's deviation is halved

@@ -85,6 +85,8 @@ def run_updates(a):
     x, xm, d = (torch.randn(B, C, L, device=device) for _ in range(3))
     xn, nz = torch.empty_like(x), torch.randn(B, C, L, device=device)
     pred, xin = torch.randn(B, L, Cp, device=device), torch.empty(B, L, Cp, device=device)
+    keep = (torch.rand(B, C, L, device=device) < 0.5).to(torch.uint8)        # k_inpaint_enter: a dense mask, half of it kept
+    rows = torch.full((B,), 0.5, device=device)                              # k_noise_in_rows: sigma[b] and c_in[b]
     st = rt.current_stream()
     p = rt.ptr
     calls = (
@@ -101,7 +103,14 @@ def run_updates(a):
         ("k_karras_mid", 5, lambda: lib.mdt_karras_mid(p(x), p(pred), p(d), p(xn), p(xin), 0.5, 0.5, 1.0, -0.1, 0.7,
                                                        B, C, L, Cp, 0, 0, st)),
         ("k_karras_next", 5, lambda: lib.mdt_karras_next(p(x), p(xn), p(d), p(pred), p(x), 0.5, 0.5, 1.0, -0.01,
-                                                         B, C, L, Cp, 0, 0, st)))
+                                                         B, C, L, Cp, 0, 0, st)),
+        # the tile kernels around the samplers: preconditioning, the first ADPM2 half, the inpaint and training entries
+        ("k_adpm2_mid", 4, lambda: lib.mdt_adpm2_mid(p(x), p(pred), p(xm), p(xin), 0.5, 0.5, 1.0, -0.1, 0.7, B, C, L, Cp, 0, st)),
+        ("k_precond_in", 2, lambda: lib.mdt_precond_in(p(x), p(xin), 0.7, B, C, L, Cp, st)),
+        ("k_precond_out", 3, lambda: lib.mdt_precond_out(p(x), p(pred), p(xn), 0.5, 0.5, B, C, L, Cp, 0, st)),
+        ("k_inpaint_enter", 4.25, lambda: lib.mdt_inpaint_enter(p(x), p(xin), p(d), 0, p(keep), 0, 0, 0, 0.01, 0.0, 0.7, 9, 1, 2, 0,
+                                                                B, C, L, Cp, st)),
+        ("k_noise_in_rows", 3, lambda: lib.mdt_noise_in_rows(p(d), 0, p(rows), p(rows), p(xn), p(xin), 9, 1, 0, B, C, L, Cp, st)))
     res = {"batch": B}
     for name, nbuf, call in calls:
         for _ in range(5):
