@@ -562,6 +562,45 @@ int mdt_refine_enter(float *x, float *xin, const int32_t *start, int32_t step_i,
 int mdt_argmax_tokens(const float *x, int32_t *tokens, int32_t B, int32_t C, int32_t L, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* candidate screening (csrc/k_screen.hip); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* What the reference's callers do with generated molecules (sample_loop_generative, generate_from_conditioning:
+ * generative.py:1196-1291, :1685-1738): re-predict, compare with the target, ask is_novel (:1063) -- on token ids.  Row layout
+ * everywhere: row r = c * G + g, candidate c of group g (a group is one target conditioning).  A molecule is its compacted id row:
+ * the non-zero ids in order (the string of a character-level tokenizer, which skips id 0). */
+/* Per row: the non-zero ids in order, left-packed and zero-padded, into packed (B,L); their number into length (B); into key (B)
+ *   key = sum over j < length, mod 2^64, of mix((j << 32) | (uint32_t)packed[j]),
+ *   mix(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *           z ^ (z >> 31)                                     (one splitmix64 step, 64-bit wrap-around arithmetic)
+ * -- order-independent, so exact and deterministic; an empty row has key 0.  Equal rows have equal keys; the converse is never
+ * assumed (mdt_screen_select confirms every key match on length and packed).  fwd_in fp32 (B,Lf), or NULL: the forward model's
+ * input (generative.py:425-429 on ids), fwd_in[b,j] = (float)((double)packed[b,j] / x_norm) for j < min(length, Lf), 0 beyond.
+ * packed must not be tokens. */
+int mdt_tokens_compact(const int32_t *tokens, int32_t B, int32_t L, float *fwd_in, int32_t Lf, double x_norm, int32_t *packed,
+                       int32_t *length, uint64_t *key, void *stream);
+/* score[r] = (sum_i w_i * (p[r,i] - t[g,i])^2) / n in fp32: i ascending, separate subtract, square, multiply by w_i and add, one
+ * divide by (float)n at the end; weights == NULL: w_i = 1.  p[r,i] = props[r * row_stride + i] (the forward sample (B,1,Lf) read
+ * in place: row_stride = Lf); target is (G,n), weights (n), score (N*G).  1 <= n <= 64, row_stride >= n. */
+int mdt_screen_score(const float *props, int64_t row_stride, const float *target, const float *weights, int32_t N, int32_t G,
+                     int32_t n, float *score, void *stream);
+/* status bits of a candidate (mdt_screen_select) */
+enum mdt_screen_status {
+  MDT_SCREEN_EMPTY = 1,     /* length == 0 */
+  MDT_SCREEN_NONFINITE = 2, /* the score is a NaN or an infinity */
+  MDT_SCREEN_DUPLICATE = 4, /* a candidate c' < c of the same group holds the same molecule (whatever the status of c') */
+  MDT_SCREEN_KNOWN = 8      /* the molecule is in the known set */
+};
+/* Per group g: status uint8 (N*G) of every candidate; index int32 (G,K): the eligible (status == 0) candidates c in ascending
+ * order of (score, c) -- ties go to the lower c -- and -1 in the slots beyond count[g] = min(K, number of eligible candidates).
+ * score, key, packed (N*G,L), length as written by the two calls above.  The known set: known_key uint64 (M) ASCENDING,
+ * known_packed int32 (M,L), known_len int32 (M), rows of the same width L, compacted and keyed as mdt_tokens_compact does; a
+ * candidate is KNOWN when an entry of the run of known keys equal to its key has its length and its packed row.
+ * Limits: 1 <= N <= 1024, 1 <= K <= N, 1 <= L <= 1024, M >= 0; the known pointers may be NULL only when M == 0. */
+int mdt_screen_select(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L, int32_t N,
+                      int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len, int32_t M,
+                      int32_t K, uint8_t *status, int32_t *index, int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */
 /* ------------------------------------------------------------------ */
 typedef struct mdt_timer mdt_timer;

@@ -1,0 +1,237 @@
+// Candidate screening on gfx950: what the reference's callers do with generated molecules after the forward model has
+// re-predicted their properties (sample_loop_generative / generate_from_conditioning, generative.py:1196-1291, :1685-1738) --
+// compare with the target, ask is_novel() (:1063), keep the best -- on token ids, without leaving the device.
+//
+//   k_tokens_compact   ids (B, L) -> non-zero ids left-packed, their number, a 64-bit key of the packed row, and (optionally) the
+//                      forward model's input (generative.py:425-429 on ids: tokens_to_forward_input)
+//   k_screen_score     weighted mean squared distance of the re-predicted properties from the group's target
+//   k_screen_select    per group: status bits (empty / non-finite / duplicate / known) and the K best eligible candidates
+//
+// Rows are r = c * G + g: candidate c of group g (a group is one target conditioning), the layout of guidance_sweep.
+// A molecule IS its compacted id row (the reference's string: a character-level tokenizer, id 0 skipped), so equality is decided
+// on (length, packed row); the key only spares comparisons and is never trusted on its own.
+//
+// Built with -ffp-contract=off: the score keeps separate fp32 multiplies and adds, so a numpy fp32 loop reproduces it.
+#include "mdt_kernels.h"
+#include "../../include/mdt_hip.h"
+
+#include <climits>
+#include <cmath>
+
+namespace mdt {
+
+// The key word of packed element j with id `id` (mdt_hip.h, mdt_tokens_compact): one splitmix64 step of (j << 32) | id.
+__device__ __forceinline__ uint64_t key_word(uint32_t j, uint32_t id) {
+  uint64_t z = (((uint64_t)j << 32) | id) + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int off) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// One 64-lane wave per row, four rows per block.  Positions in chunks of 64: ballot the non-zero lanes, the popcount of the lanes
+// below is the slot, a running base carries over the chunks.  No LDS.  tokens and packed must not overlap.
+__global__ __launch_bounds__(256) void k_tokens_compact(const int32_t* __restrict__ tokens, int B, int L, float* __restrict__ fwd_in,
+                                                        int Lf, double x_norm, int32_t* __restrict__ packed,
+                                                        int32_t* __restrict__ length, uint64_t* __restrict__ key) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= B) return;                                      // (a whole wave leaves: no barrier, no cross-wave traffic below)
+  const int32_t* src = tokens + (int64_t)row * L;
+  int32_t* dst = packed + (int64_t)row * L;
+  float* fin = fwd_in ? fwd_in + (int64_t)row * Lf : nullptr;
+  const uint64_t below = ((uint64_t)1 << lane) - 1;
+  int base = 0;
+  uint64_t k = 0;
+  for (int c0 = 0; c0 < L; c0 += 64) {
+    const int p = c0 + lane;
+    const int32_t id = p < L ? src[p] : 0;
+    const uint64_t mask = __ballot(id != 0);
+    if (id != 0) {
+      const int slot = base + __popcll(mask & below);
+      dst[slot] = id;
+      k += key_word((uint32_t)slot, (uint32_t)id);
+      if (fin && slot < Lf) fin[slot] = (float)((double)id / x_norm);
+    }
+    base += __popcll(mask);
+  }
+  for (int j = base + lane; j < L; j += 64) dst[j] = 0;
+  if (fin)
+    for (int j = base + lane; j < Lf; j += 64) fin[j] = 0.0f;
+  for (int off = 32; off >= 1; off >>= 1) k += shfl_xor_u64(k, off);     // (a sum mod 2^64: exact in any order)
+  if (lane == 0) {
+    length[row] = base;
+    key[row] = k;
+  }
+}
+
+// One thread per row; i ascending, separate multiply and add.
+__global__ __launch_bounds__(256) void k_screen_score(const float* __restrict__ props, int64_t row_stride,
+                                                      const float* __restrict__ target, const float* __restrict__ weights, int rows,
+                                                      int G, int n, float* __restrict__ score) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const float* p = props + (int64_t)r * row_stride;
+  const float* t = target + (int64_t)(r % G) * n;
+  float acc = 0.0f;
+  for (int i = 0; i < n; ++i) {
+    const float d = p[i] - t[i];
+    float sq = d * d;
+    if (weights) sq = weights[i] * sq;
+    acc = acc + sq;
+  }
+  score[r] = acc / (float)n;
+}
+
+constexpr int kScreenMaxN = 1024;
+
+__device__ __forceinline__ bool same_row(const int32_t* a, const int32_t* b, int len) {
+  for (int j = 0; j < len; ++j)
+    if (a[j] != b[j]) return false;
+  return true;
+}
+
+// One workgroup of 256 per group; the group's keys, scores, lengths and status bytes sit in LDS (17 KiB at N = 1024).
+__global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__ score, const uint64_t* __restrict__ key,
+                                                       const int32_t* __restrict__ packed, const int32_t* __restrict__ length, int L,
+                                                       int N, int G, const uint64_t* __restrict__ known_key,
+                                                       const int32_t* __restrict__ known_packed,
+                                                       const int32_t* __restrict__ known_len, int M, int K,
+                                                       uint8_t* __restrict__ status, int32_t* __restrict__ index,
+                                                       int32_t* __restrict__ count) {
+  __shared__ uint64_t s_key[kScreenMaxN];
+  __shared__ float s_score[kScreenMaxN];
+  __shared__ int32_t s_len[kScreenMaxN];
+  __shared__ uint8_t s_status[kScreenMaxN];
+  __shared__ int s_eligible;
+  const int g = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_eligible = 0;
+  for (int c = tid; c < N; c += 256) {
+    const int64_t r = (int64_t)c * G + g;
+    s_key[c] = key[r];
+    s_score[c] = score[r];
+    const int len = length[r];
+    s_len[c] = len < 0 ? 0 : (len > L ? L : len);                // (never read a row past its L ids, whatever length holds)
+  }
+  __syncthreads();
+
+  int mine = 0;
+  for (int c = tid; c < N; c += 256) {
+    const uint64_t k = s_key[c];
+    const int len = s_len[c];
+    const int32_t* row = packed + ((int64_t)c * G + g) * L;
+    int st = 0;
+    if (len == 0) st |= MDT_SCREEN_EMPTY;
+    if (!isfinite(s_score[c])) st |= MDT_SCREEN_NONFINITE;
+    for (int o = 0; o < c; ++o)                                  // the first occurrence stands for the molecule
+      if (s_key[o] == k && s_len[o] == len && same_row(row, packed + ((int64_t)o * G + g) * L, len)) {
+        st |= MDT_SCREEN_DUPLICATE;
+        break;
+      }
+    if (M > 0) {
+      int lo = 0, hi = M;                                        // lower bound of k in known_key (ascending)
+      while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (known_key[mid] < k) lo = mid + 1; else hi = mid;
+      }
+      for (int i = lo; i < M && known_key[i] == k; ++i)          // the whole run of equal keys
+        if (known_len[i] == len && same_row(row, known_packed + (int64_t)i * L, len)) {
+          st |= MDT_SCREEN_KNOWN;
+          break;
+        }
+    }
+    s_status[c] = (uint8_t)st;
+    status[(int64_t)c * G + g] = (uint8_t)st;
+    mine += st == 0;
+  }
+  if (mine) atomicAdd(&s_eligible, mine);
+  __syncthreads();
+
+  const int filled = s_eligible < K ? s_eligible : K;
+  for (int c = tid; c < N; c += 256) {
+    if (s_status[c]) continue;
+    const float sc = s_score[c];
+    int rank = 0;
+    for (int o = 0; o < N; ++o)
+      rank += s_status[o] == 0 && (s_score[o] < sc || (s_score[o] == sc && o < c));
+    if (rank < K) index[(int64_t)g * K + rank] = c;
+  }
+  for (int k = filled + tid; k < K; k += 256) index[(int64_t)g * K + k] = -1;
+  if (tid == 0) count[g] = filled;
+}
+
+}  // namespace mdt
+
+// ------------------------------------------------------------------------------------------------
+// C ABI entry points of this translation unit (declared in include/mdt_hip.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
+
+namespace {
+inline int finish(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    mdt_set_error(buf);
+    return 1;
+  }
+  return 0;
+}
+inline int bad(const char* msg) {
+  mdt_set_error(msg);
+  return 2;
+}
+}  // namespace
+
+extern "C" {
+
+int mdt_tokens_compact(const int32_t* tokens, int32_t B, int32_t L, float* fwd_in, int32_t Lf, double x_norm, int32_t* packed,
+                       int32_t* length, uint64_t* key, void* stream) {
+  if (B <= 0) return 0;
+  if (!tokens || !packed || !length || !key) return bad("mdt_tokens_compact: null pointer");
+  if (tokens == packed) return bad("mdt_tokens_compact: packed must not be the tokens themselves");
+  if (L < 1) return bad("mdt_tokens_compact: need L >= 1");
+  if (fwd_in && Lf < 1) return bad("mdt_tokens_compact: need Lf >= 1 with fwd_in");
+  if (fwd_in && !(std::isfinite(x_norm) && x_norm != 0.0)) return bad("mdt_tokens_compact: x_norm must be finite and non-zero");
+  hipLaunchKernelGGL(mdt::k_tokens_compact, dim3(((unsigned)B + 3) / 4), dim3(256), 0, (hipStream_t)stream, tokens, B, L, fwd_in,
+                     Lf, x_norm, packed, length, key);
+  return finish("mdt_tokens_compact");
+}
+
+int mdt_screen_score(const float* props, int64_t row_stride, const float* target, const float* weights, int32_t N, int32_t G,
+                     int32_t n, float* score, void* stream) {
+  if (N <= 0 || G <= 0) return 0;
+  if (!props || !target || !score) return bad("mdt_screen_score: null pointer");
+  if (n < 1 || n > 64) return bad("mdt_screen_score: need 1 <= n <= 64 properties");
+  if (row_stride < n) return bad("mdt_screen_score: row_stride must be at least n");
+  if ((int64_t)N * G > INT_MAX) return bad("mdt_screen_score: N * G exceeds 2^31 - 1 rows");
+  const int rows = N * G;
+  hipLaunchKernelGGL(mdt::k_screen_score, dim3(((unsigned)rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, props, row_stride,
+                     target, weights, rows, G, n, score);
+  return finish("mdt_screen_score");
+}
+
+int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L, int32_t N,
+                      int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len, int32_t M,
+                      int32_t K, uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+  if (G <= 0) return 0;
+  if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select: need 1 <= N <= 1024 candidates per group");
+  if (K < 1 || K > N) return bad("mdt_screen_select: need 1 <= K <= N");
+  if (L < 1 || L > 1024) return bad("mdt_screen_select: need 1 <= L <= 1024");
+  if (M < 0) return bad("mdt_screen_select: need M >= 0");
+  if (M > 0 && (!known_key || !known_packed || !known_len))
+    return bad("mdt_screen_select: the known-set pointers may be NULL only when M == 0");
+  if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select: null pointer");
+  hipLaunchKernelGGL(mdt::k_screen_select, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
+                     known_key, known_packed, known_len, M, K, status, index, count);
+  return finish("mdt_screen_select");
+}
+
+}  // extern "C"

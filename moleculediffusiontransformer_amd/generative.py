@@ -8,7 +8,7 @@ path runs on an MI355X through libmdt_hip.so; there is no CPU implementation beh
 from __future__ import annotations
 
 import os
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -809,3 +809,203 @@ def refine_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForward
                                            X_norm_factor=X_norm_factor,
                                            context_embedding_max_length=conditioning.shape[1], noise=forward_noise)
     return tokens, props
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# screening: the best distinct, novel molecules out of N tries per target, on the device (csrc/k_screen.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_CANDIDATES = 1024           # mdt_screen_select's limits (include/mdt_hip.h)
+MAX_SCREEN_LENGTH = 1024
+MAX_SCREEN_PROPERTIES = 64
+
+
+def _integer_ids(ids, name: str):
+    """``ids`` as a numpy array (host data) or a tensor, refused unless its dtype is an integer one."""
+    import numpy as np
+    if not isinstance(ids, Tensor):
+        ids = np.asarray(ids)
+        if ids.dtype.kind not in "iu":
+            raise ValueError(f"{name} must hold integer token ids, got dtype {ids.dtype}")
+    elif ids.dtype == torch.bool or ids.is_floating_point() or ids.is_complex():
+        raise ValueError(f"{name} must hold integer token ids, got dtype {ids.dtype}")
+    if ids.ndim != 2:
+        raise ValueError(f"{name} must be 2-D (rows, positions), got shape {tuple(ids.shape)}")
+    return ids
+
+
+def token_keys(packed, length):
+    """The 64-bit key of mdt_tokens_compact (include/mdt_hip.h) on the host: numpy uint64 (M,) for left-packed rows (M, L) and
+    their lengths -- the sum mod 2^64 over j < length of one splitmix64 step of (j << 32) | uint32(id)."""
+    import numpy as np
+    packed = np.asarray(packed).astype(np.int64)
+    M, L = packed.shape
+    j = np.arange(L, dtype=np.uint64)[None, :]
+    with np.errstate(over="ignore"):
+        z = ((j << np.uint64(32)) | (packed & 0xFFFFFFFF).astype(np.uint64)) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+        z = np.where(j < np.asarray(length).astype(np.uint64)[:, None], z, np.uint64(0))
+        return z.sum(axis=1, dtype=np.uint64)
+
+
+class KnownSet:
+    """The molecules a generated one is "novel" against (ALL_SMILES of is_novel, generative.py:1063), as token ids: built once on the
+    host from (M, L_any) integer ids -- the training set through the tokenizer -- for generated rows of ``length`` positions.
+
+    Every row is compacted (non-zero ids in order: the string of the character-level tokenizer, which skips id 0); rows with more
+    than ``length`` non-zero ids are dropped (they equal no generated molecule), exact duplicates are dropped, and the rest is sorted
+    by the key of mdt_tokens_compact (stable).  ``packed`` int32 (M, length), ``lengths`` int32 (M), ``key`` uint64 (M), numpy.
+    The device copy is made on first use and cached, one per device."""
+
+    def __init__(self, tokens, length: int):
+        import numpy as np
+        if isinstance(length, bool) or not isinstance(length, int) or not 1 <= length <= MAX_SCREEN_LENGTH:
+            raise ValueError(f"length must be an int in [1, {MAX_SCREEN_LENGTH}], got {length!r}")
+        ids = _integer_ids(tokens, "known_tokens")
+        ids = (ids.detach().cpu().numpy() if isinstance(ids, Tensor) else ids).astype(np.int64)
+        M, L = ids.shape
+        order = np.argsort(ids == 0, axis=1, kind="stable")                  # non-zero ids first, original order kept
+        packed = np.take_along_axis(ids, order, axis=1)
+        n = (ids != 0).sum(axis=1)
+        packed = packed[n <= length]
+        wide = np.zeros((packed.shape[0], max(L, length)), dtype=np.int64)
+        wide[:, :L] = packed
+        packed = np.unique(wide[:, :length], axis=0) if len(wide) else wide[:, :length]
+        lengths = (packed != 0).sum(axis=1)
+        key = token_keys(packed, lengths)
+        by_key = np.argsort(key, kind="stable")
+        self.width = length
+        self.packed = np.ascontiguousarray(packed[by_key].astype(np.int32))
+        self.lengths = np.ascontiguousarray(lengths[by_key].astype(np.int32))
+        self.key = np.ascontiguousarray(key[by_key])
+        self._on = {}
+
+    def __len__(self) -> int:
+        return int(self.key.shape[0])
+
+    def on(self, device):
+        """(key int64: the uint64 bits, packed int32 (M, length), lengths int32 (M)) on ``device``."""
+        import numpy as np
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._on:
+            self._on[device] = (torch.from_numpy(self.key.view(np.int64)).to(device), torch.from_numpy(self.packed).to(device),
+                                torch.from_numpy(self.lengths).to(device))
+        return self._on[device]
+
+
+class Screened(NamedTuple):
+    """screen_tokens' result, G groups (targets), K = ``keep`` slots per group in ascending order of score."""
+    tokens: Tensor     # (G, K, L) int64: the kept candidates' ids as they were given; 0 in unfilled slots
+    props: Tensor      # (G, K, n): their re-predicted (scaled) properties; NaN in unfilled slots
+    score: Tensor      # (G, K): the weighted mean squared distance from the target; +inf in unfilled slots
+    index: Tensor      # (G, K) int64: the candidate c (row c * G + g of the input); -1 in unfilled slots
+    count: Tensor      # (G,) int64: filled slots = min(K, eligible candidates)
+    status: Tensor     # (N, G) uint8: 1 empty | 2 non-finite score | 4 duplicate of a lower c | 8 in the known set
+
+
+def _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=None, length=None):
+    """Every refusal of screen_tokens / screen_candidates, before anything is launched.  Returns (weights fp32 CPU or None,
+    KnownSet or None)."""
+    for name, v in (("candidates", candidates), ("keep", keep)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if not 1 <= candidates <= MAX_CANDIDATES:
+        raise ValueError(f"candidates must lie in [1, {MAX_CANDIDATES}], got {candidates}")
+    if not 1 <= keep <= candidates:
+        raise ValueError(f"keep must lie in [1, candidates = {candidates}], got {keep}")
+    if not isinstance(conditioning, Tensor) or conditioning.dim() != 2:
+        raise ValueError("conditioning must be a 2-D tensor (G, n): one target per group")
+    G, n = conditioning.shape
+    if not 1 <= n <= MAX_SCREEN_PROPERTIES:
+        raise ValueError(f"conditioning must hold 1 to {MAX_SCREEN_PROPERTIES} properties per target, got {n}")
+    if tokens is not None:
+        tokens = _integer_ids(tokens, "tokens")
+        if tokens.shape[0] != candidates * G:
+            raise ValueError(f"tokens must hold candidates * G = {candidates * G} rows (row c * G + g), got {tokens.shape[0]}")
+        length = tokens.shape[1]
+    if not 1 <= length <= MAX_SCREEN_LENGTH:
+        raise ValueError(f"tokens must hold 1 to {MAX_SCREEN_LENGTH} positions per row, got {length}")
+    if weights is not None:
+        try:
+            weights = torch.as_tensor(weights).detach().to(device="cpu", dtype=torch.float32)
+        except Exception as e:
+            raise ValueError(f"weights must hold one number per property ({e})") from None
+        if tuple(weights.shape) != (n,):
+            raise ValueError(f"weights must hold one value per property ({n}), got shape {tuple(weights.shape)}")
+        if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+            raise ValueError("weights must be finite and not negative")
+    if known_tokens is not None and not isinstance(known_tokens, KnownSet):
+        known_tokens = KnownSet(known_tokens, length)
+    if known_tokens is not None and known_tokens.width != length:
+        raise ValueError(f"known_tokens was built for rows of {known_tokens.width} positions, tokens has {length}")
+    return weights, known_tokens
+
+
+def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int, keep: int, *,
+                  known_tokens=None, weights=None, forward_timesteps: int = 100, X_norm_factor: float = 1.0, forward_noise=None,
+                  sampler=None, sigma_schedule=None) -> Screened:
+    """The last mile of the reference's callers (sample_loop_generative / generate_from_conditioning, generative.py:1196-1291,
+    :1685-1738) for N = ``candidates`` tries per target: re-predict the properties of the generated molecules with the forward
+    model, compare them with the target, drop what is empty, repeated or already known (is_novel, :1063), keep the K = ``keep``
+    best per target -- without leaving the device.
+
+    ``tokens``: (N * G, L) ids from ANY producer (sample_tokens, inpaint_tokens, refine_tokens), row c * G + g = candidate c of
+    target g -- the layout of guidance_sweep and of ``conditioning.repeat(N, 1)``; ``conditioning``: (G, n), the targets.
+    A molecule is its compacted id row -- the non-zero ids in order, which is the reference's string: its tokenizer is
+    character-level and skips id 0 -- so two rows that differ only in where their zeros sit are the same molecule.
+    ``known_tokens``: a KnownSet, or raw (M, L_any) ids (wrapped; build the KnownSet once when calling repeatedly).
+    ``weights``: (n,) non-negative; score = sum_i w_i (p_i - t_i)^2 / n on the scaled properties (None: all 1).
+    Sequence: mdt::tokens_compact -> model_forward.sample on the compacted input (tokens_to_forward_input's, bit for bit) ->
+    mdt::screen_score -> mdt::screen_select -> a gather.  Of equal molecules in a group the lowest c stands for all; ties in the
+    score go to the lower c.  Returns Screened; the reference's "fraction of novel structures" is
+    ``((status & 8) == 0).float().mean()``."""
+    weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
+    device = torch.device(device)
+    N, K = candidates, keep
+    G, n = conditioning.shape
+    tok = torch.as_tensor(tokens).to(device)
+    if n > model_forward.max_length:
+        raise ValueError(f"conditioning holds {n} properties, the forward model predicts {model_forward.max_length} positions")
+    packed, length, key, data = torch.ops.mdt.tokens_compact(tok, model_forward.max_length, float(X_norm_factor))
+    result = model_forward.sample(data, device, cond_scale=1.0, timesteps=forward_timesteps, clamp=False, noise=forward_noise,
+                                  sampler=sampler, sigma_schedule=sigma_schedule)
+    target = conditioning.detach().to(device=device, dtype=torch.float32)
+    score = torch.ops.mdt.screen_score(result, target, None if weights is None else weights.to(device), N)
+    kk, kp, kl = known.on(device) if known is not None and len(known) else (None, None, None)
+    status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
+    index = index.long()
+    filled = index >= 0
+    rows = index.clamp(min=0) * G + torch.arange(G, device=device).unsqueeze(1)
+    props = result.reshape(N * G, -1)[:, :n]
+    return Screened(tokens=torch.where(filled.unsqueeze(2), tok.long()[rows], 0),
+                    props=torch.where(filled.unsqueeze(2), props[rows], float("nan")),
+                    score=torch.where(filled, score[rows], float("inf")),
+                    index=index, count=count.long(), status=status.view(N, G))
+
+
+def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward", conditioning: Tensor, device, candidates: int,
+                      keep: int, *, cond_scale=1.0, timesteps: int = 100, noise=None, **screen_tokens_kwargs) -> Screened:
+    """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
+    of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes;
+    ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
+    candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
+    ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
+    pinned ``kernel_choice``)."""
+    extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
+                                         "sigma_schedule"}
+    if extra:
+        raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
+    _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
+                            screen_tokens_kwargs.get("weights"), length=model.max_length)
+    if known is not None:
+        screen_tokens_kwargs["known_tokens"] = known
+    N, G = candidates, conditioning.shape[0]
+    scale = guidance_rows(cond_scale, N, "cond_scale")
+    if isinstance(scale, Tensor):
+        scale = scale.repeat_interleave(G)
+    tokens = model.sample_tokens(conditioning.repeat(N, 1), device, cond_scale=scale, timesteps=timesteps, noise=noise,
+                                 sampler=screen_tokens_kwargs.get("sampler"), sigma_schedule=screen_tokens_kwargs.get("sigma_schedule"))
+    return screen_tokens(model_forward, tokens, conditioning, device, candidates, keep, **screen_tokens_kwargs)

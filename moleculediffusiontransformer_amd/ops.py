@@ -13,6 +13,9 @@ fake / meta tensors).
     adpm2_mid / _next   the two halves of ADPM2Sampler.step (diffusion.py:502-515)
     adpm2_euler         one Euler move of the step for a caller-supplied denoiser
     argmax_tokens       decode step after the path (generative.py:1212-1213)
+    tokens_compact      ids -> non-zero ids left-packed, length, 64-bit key, forward input (generative.py:425-429 on ids)
+    screen_score        weighted mean squared distance of re-predicted properties from the group's target
+    screen_select       status (empty / non-finite / duplicate / known: is_novel, generative.py:1063) and the K best per group
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
     aeuler_next         the whole AEulerSampler.step after its evaluation (diffusion.py:465-474)
     karras_hat / _mid / _next   the three stages of KarrasSampler.step (diffusion.py:417-435)
@@ -409,6 +412,119 @@ def argmax_tokens(x: Tensor) -> Tensor:
 @argmax_tokens.register_fake
 def _(x):
     return x.new_empty(x.shape[0], x.shape[2], dtype=torch.int32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# candidate screening (csrc/k_screen.hip): rows are r = c * G + g, candidate c of group g
+def _i32c(t: Tensor, what: str) -> Tensor:
+    if t.dtype in (torch.bool,) or t.is_floating_point() or t.is_complex():
+        raise RuntimeError(f"{what} must hold integers, got {t.dtype}")
+    return t.detach().to(torch.int32).contiguous()
+
+
+@custom_op("mdt::tokens_compact", mutates_args=())
+def tokens_compact(tokens: Tensor, forward_length: int, x_norm: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(B, L) ids -> (packed int32 (B, L), length int32 (B), key int64 (B): the bits of the uint64 key, forward input fp32
+    (B, forward_length)); forward_length == 0: no forward input is written and (B, 0) is returned."""
+    dev = _hip(tokens)
+    lib = rt.load_library()
+    if tokens.dim() != 2:
+        raise RuntimeError("mdt::tokens_compact: tokens must be (B, L)")
+    tok = _i32c(tokens, "mdt::tokens_compact: tokens")
+    B, L = tok.shape
+    if forward_length < 0:
+        raise RuntimeError("mdt::tokens_compact: forward_length must not be negative")
+    packed = torch.empty(B, L, dtype=torch.int32, device=dev)
+    length = torch.empty(B, dtype=torch.int32, device=dev)
+    key = torch.empty(B, dtype=torch.int64, device=dev)
+    fwd = torch.empty(B, forward_length, dtype=torch.float32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_tokens_compact(rt.ptr(tok), B, L, rt.ptr(fwd) if forward_length else 0, forward_length, float(x_norm),
+                                            rt.ptr(packed), rt.ptr(length), rt.ptr(key), rt.current_stream()))
+    return packed, length, key, fwd
+
+
+@tokens_compact.register_fake
+def _(tokens, forward_length, x_norm):
+    B, L = tokens.shape
+    return (tokens.new_empty(B, L, dtype=torch.int32), tokens.new_empty(B, dtype=torch.int32),
+            tokens.new_empty(B, dtype=torch.int64), tokens.new_empty(B, forward_length, dtype=torch.float32))
+
+
+@custom_op("mdt::screen_score", mutates_args=())
+def screen_score(props: Tensor, target: Tensor, weights: Optional[Tensor], candidates: int) -> Tensor:
+    """props (N * G, ...) fp32, read in place: the first n values of every row; target (G, n); weights (n) or None -> (N * G)."""
+    dev = _hip(props, target, weights)
+    lib = rt.load_library()
+    if target.dim() != 2:
+        raise RuntimeError("mdt::screen_score: target must be (G, n)")
+    G, n = target.shape
+    rows = candidates * G
+    if props.dim() < 2 or props.shape[0] != rows:
+        raise RuntimeError(f"mdt::screen_score: props must hold candidates * G = {rows} rows")
+    p, t = _f32c(props), _f32c(target)
+    w = None if weights is None else _f32c(weights)
+    if w is not None and tuple(w.shape) != (n,):
+        raise RuntimeError("mdt::screen_score: weights must be (n,)")
+    score = torch.empty(rows, dtype=torch.float32, device=dev)
+    if rows:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_screen_score(rt.ptr(p), p.numel() // rows, rt.ptr(t), rt.ptr(w), candidates, G, n, rt.ptr(score),
+                                          rt.current_stream()))
+    return score
+
+
+@screen_score.register_fake
+def _(props, target, weights, candidates):
+    return props.new_empty(candidates * target.shape[0], dtype=torch.float32)
+
+
+@custom_op("mdt::screen_select", mutates_args=())
+def screen_select(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                  known_key: Optional[Tensor], known_packed: Optional[Tensor],
+                  known_len: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (status uint8 (N * G), index int32 (G, K), count int32 (G)).  The known set: keys int64 (the uint64 bits, ascending AS
+    uint64), packed rows int32 (M, L), lengths int32 (M) -- all three or none."""
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len)
+    lib = rt.load_library()
+    rows, L = packed.shape
+    N, K = candidates, keep
+    if N < 1 or rows % N:
+        raise RuntimeError(f"mdt::screen_select: {rows} rows are no multiple of candidates = {N}")
+    G = rows // N
+    if key.dtype != torch.int64 or packed.dtype != torch.int32 or length.dtype != torch.int32:
+        raise RuntimeError("mdt::screen_select: key must be int64, packed and length int32 (as mdt::tokens_compact returns them)")
+    if score.numel() != rows or key.numel() != rows or length.numel() != rows:
+        raise RuntimeError("mdt::screen_select: score, key and length must hold one value per row of packed")
+    known = (known_key, known_packed, known_len)
+    if any(k is None for k in known) != all(k is None for k in known):
+        raise RuntimeError("mdt::screen_select: give known_key, known_packed and known_len together")
+    M = 0
+    if known_key is not None:
+        M = known_key.numel()
+        if known_key.dtype != torch.int64 or known_packed.dtype != torch.int32 or known_len.dtype != torch.int32:
+            raise RuntimeError("mdt::screen_select: known_key must be int64, known_packed and known_len int32")
+        if tuple(known_packed.shape) != (M, L) or known_len.numel() != M:
+            raise RuntimeError(f"mdt::screen_select: the known set must be (M, {L}) rows with M keys and M lengths")
+        known = tuple(k.contiguous() for k in known)
+    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
+    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    index = torch.full((G, K), -1, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_screen_select(rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, N, G,
+                                           *(rt.ptr(k) if M else 0 for k in known), M, K, rt.ptr(status), rt.ptr(index),
+                                           rt.ptr(count), rt.current_stream()))
+    return status, index, count
+
+
+@screen_select.register_fake
+def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len):
+    G = packed.shape[0] // candidates
+    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
+            packed.new_empty(G, dtype=torch.int32))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

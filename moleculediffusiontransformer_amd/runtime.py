@@ -45,6 +45,7 @@ B_KV2, B_WF32 = 11, 12
 (F_C, F_T, F_NT, F_NVEC, F_TK, F_KV_BSTRIDE, F_LDKV, F_HEADS, F_HAS_IN, F_NBLOCKS, F_NFF, F_NPOST, F_KV2, F_CROSS,
  F_KV_LSTRIDE, F_RES_KIND, F_N_RES, F_RES_PAIR1, F_RES_PAIR2, F_NFILM, F_NSPLIT, F_PAIR_STRIDE, F_WF32) = range(23)
 FF_EPS_LN, FF_SCALE, FF_EPS_GN, FF_EPS_RES, FF_SKIP_SCALE = range(5)
+SCREEN_EMPTY, SCREEN_NONFINITE, SCREEN_DUPLICATE, SCREEN_KNOWN = 1, 2, 4, 8      # enum mdt_screen_status
 
 
 class MdtRef(C.Structure):
@@ -103,6 +104,9 @@ SYMBOLS = {
     "mdt_inpaint_finish": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mdt_refine_enter": (_I, [_P, _P, _P, _I, _P, _P, _P, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P]),
     "mdt_argmax_tokens": (_I, [_P, _P, _I, _I, _I, _P]),
+    "mdt_tokens_compact": (_I, [_P, _I, _I, _P, _I, C.c_double, _P, _P, _P, _P]),
+    "mdt_screen_score": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P]),
+    "mdt_screen_select": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mdt_timer_create": (_P, [_I]),
     "mdt_timer_destroy": (None, [_P]),
     "mdt_timer_start": (_I, [_P, _P]),
