@@ -558,6 +558,19 @@ int mdt_inpaint_finish(float *x, const float *src, const int32_t *draft, const u
 int mdt_refine_enter(float *x, float *xin, const int32_t *start, int32_t step_i, const float *src, const int32_t *draft,
                      const float *noise, float sigma, float c_in, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
                      int32_t C, int32_t L, int32_t Cp, void *stream);
+/* The per-step entry of a refine call around a kept scaffold: launched in front of EVERY step i from min(start), it is the entry
+ * of mdt_refine_enter and the merge of ADPM2Sampler.inpaint (diffusion.py:539-542, as a select) on one read of the state:
+ *   start[b] >  step_i:  the row is written neither in x nor in xin;
+ *   start[b] == step_i:  x = keep ? src + sigma * n_src : src + sigma * n_entry;
+ *   start[b] <  step_i:  x = keep ? src + sigma * n_src : x;
+ * with separate multiply and add, and for the rows that run xin = c_in * x (token-major, channels padded to Cp with 0).
+ * src / draft as mdt_inpaint_enter (exactly one of them), keep / keep_per_token as mdt_inpaint_enter, start as mdt_refine_enter.
+ * n_entry / n_src == NULL: the counter-based generator keyed by (seed, step_entry / step_src) at the global element index
+ * (sample0 + b)*C*L + c*L + l.  An addition inside ABI version 5. */
+int mdt_refine_keep_enter(float *x, float *xin, const int32_t *start, int32_t step_i, const float *src, const int32_t *draft,
+                          const uint8_t *keep, int32_t keep_per_token, const float *n_entry, const float *n_src, float sigma,
+                          float c_in, uint64_t seed, uint32_t step_entry, uint32_t step_src, int64_t sample0, int32_t B,
+                          int32_t C, int32_t L, int32_t Cp, void *stream);
 /* Decode step after the path (generative.py:1212-1213): tokens[b,l] = argmax_c x[b,c,l] (int32). */
 int mdt_argmax_tokens(const float *x, int32_t *tokens, int32_t B, int32_t C, int32_t L, void *stream);
 

@@ -545,6 +545,51 @@ __global__ __launch_bounds__(256) void k_refine_enter(float* x, float* xin, cons
   });
 }
 
+// The per-step entry of a refine call around a kept scaffold: k_refine_enter's entry and the merge of ADPM2Sampler.inpaint
+// (diffusion.py:539-542, as a select) in front of step i, then :810, on one read of the state:
+//   start[b] >  i:  nothing -- the workgroup returns at once, writing neither x nor xin;
+//   start[b] == i:  x = keep ? src + sigma * n_src : src + sigma * n_entry;
+//   start[b] <  i:  x = keep ? src + sigma * n_src : x;
+// and for the rows that run xin = c_in * x (token-major, padded).  A quad takes only the draws it needs: a fully kept quad no
+// entry draw, a started quad with nothing kept none (nor its source, nor a store of x).  src / draft as k_refine_enter, keep /
+// keep_tok as k_inpaint_enter; n_entry / n_src == nullptr: the generator at draw index step_entry / step_src.  One workgroup
+// per sample.
+__global__ __launch_bounds__(256) void k_refine_keep_enter(float* x, float* xin, const int32_t* start, int step_i, const float* src,
+                                                            const int32_t* draft, const uint8_t* keep, int keep_tok,
+                                                            const float* n_entry, const float* n_src, float sigma, float c_in,
+                                                            uint64_t seed, uint32_t step_entry, uint32_t step_src, int64_t sample0,
+                                                            int C, int L, int Cp) {
+  extern __shared__ float tile[];
+  const int s0 = start[blockIdx.x];
+  if (s0 > step_i) return;                               // (uniform over the workgroup, before any barrier: none is skipped by a part of it)
+  const bool entering = s0 == step_i;
+  tile_pass<false>(tile, nullptr, nullptr, xin, nullptr, C, L, Cp, [=](const TileQuad& p) {
+    const int64_t ot = (int64_t)p.b * L + p.l;
+    const uchar4 mk = *reinterpret_cast<const uchar4*>(keep + (keep_tok ? ot : p.o));
+    const bool kv[4] = {mk.x != 0, mk.y != 0, mk.z != 0, mk.w != 0};
+    const bool any = kv[0] || kv[1] || kv[2] || kv[3], all = kv[0] && kv[1] && kv[2] && kv[3];
+    Quad xn = {{0.f, 0.f, 0.f, 0.f}};
+    if (!entering) xn = load4(x + p.o);
+    if (entering || any) {
+      const Quad sv = source4(src, draft, p.o, ot, p.c);
+      if (entering && !all) {                            // (a kept element's entry value is overwritten by the merge)
+        const Quad nv = tile_draw(n_entry, seed, step_entry, sample0, C, L, p.o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xn[q] = sv[q] + sigma * nv[q];
+      }
+      if (any) {
+        const Quad nv = tile_draw(n_src, seed, step_src, sample0, C, L, p.o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (kv[q]) xn[q] = sv[q] + sigma * nv[q];
+      }
+      store4(x + p.o, xn);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) p.t[q * p.pitch] = c_in * xn[q];
+  });
+}
+
 // The last merge of ADPM2Sampler.inpaint (diffusion.py:549: sigma 0) and the decode (generative.py:1613-1614), one thread per
 // position: x = keep ? src : x; tokens[b,l] = argmax_c x[b,c,l] (first maximum, as k_argmax) -- with draft ids and a per-position
 // keep, a kept position's token is its draft id.  src / draft / keep / keep_tok as k_inpaint_enter; tokens may be nullptr.
@@ -1048,6 +1093,17 @@ int mdt_refine_enter(float* x, float* xin, const int32_t* start, int32_t step_i,
   if (!refuse && !src == !draft) refuse = ": give the source either dense (src) or as draft ids (draft)";
   return launch_tile<mdt::k_refine_enter>("mdt_refine_enter", refuse, B, C, L, Cp, stream, x, xin, start, step_i, src, draft, noise,
                                           sigma, c_in, seed, step, sample0, C, L, Cp);
+}
+
+int mdt_refine_keep_enter(float* x, float* xin, const int32_t* start, int32_t step_i, const float* src, const int32_t* draft,
+                          const uint8_t* keep, int32_t keep_per_token, const float* n_entry, const float* n_src, float sigma,
+                          float c_in, uint64_t seed, uint32_t step_entry, uint32_t step_src, int64_t sample0, int32_t B, int32_t C,
+                          int32_t L, int32_t Cp, void* stream) {
+  const char* refuse = !x || !xin || !start || !keep ? ": null pointer" : nullptr;
+  if (!refuse && !src == !draft) refuse = ": give the source either dense (src) or as draft ids (draft)";
+  return launch_tile<mdt::k_refine_keep_enter>("mdt_refine_keep_enter", refuse, B, C, L, Cp, stream, x, xin, start, step_i, src,
+                                               draft, keep, keep_per_token ? 1 : 0, n_entry, n_src, sigma, c_in, seed, step_entry,
+                                               step_src, sample0, C, L, Cp);
 }
 
 int mdt_inpaint_finish(float* x, const float* src, const int32_t* draft, const uint8_t* keep, int32_t keep_per_token,

@@ -462,13 +462,16 @@ class NoiseSource:
       returns the torch.randn_like draw of step i (diffusion.py:514) already on the device;
     * ``seed`` (throughput mode): on-device Philox4x32-10 keyed by (seed, draw index) with the counter
       taken from the GLOBAL sample index ``sample0 + b`` so results do not depend on the sharding.
+
+    ``sources(i)`` (explicit mode, a refine call with a keep mask only): the torch.randn_like draw that noises the kept source in
+    front of step i (diffusion.py:539), already on the device.
     """
 
     def __init__(self, init: Optional[Tensor] = None, steps: Optional[Callable[[int], Tensor]] = None,
-                 seed: Optional[int] = None, sample0: int = 0):
+                 seed: Optional[int] = None, sample0: int = 0, sources: Optional[Callable[[int], Tensor]] = None):
         if (init is None) != (steps is None) or (init is None) == (seed is None):
             raise ValueError("give either (init, steps) tensors or a seed")
-        self.init, self.steps, self.seed, self.sample0 = init, steps, seed, sample0
+        self.init, self.steps, self.seed, self.sample0, self.sources = init, steps, seed, sample0, sources
 
 
 class BoundDenoise:
@@ -971,7 +974,8 @@ def start_rows(start_step, B: int, timesteps: int, name: str = "start_step") -> 
 def run_refine(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: NoiseSource, schedule, sampler: Sampler,
                sigma_data: float, start, *, source: Optional[Tensor] = None, draft: Optional[Tensor] = None,
                embedding_scale=1.0, clamp: bool = False, trace: Optional[dict] = None, timer=None,
-               tokens: Optional[Tensor] = None, dynamic_threshold: float = 0.0) -> Tensor:
+               tokens: Optional[Tensor] = None, dynamic_threshold: float = 0.0, keep: Optional[Tensor] = None,
+               keep_per_token: bool = False) -> Tensor:
     """Partial-noise editing on the fused loop, for any sampler with a fused kind: row b is
     ``x = source + sigmas[k] * draw0`` (the expression of diffusion.py:535) followed by the sampler's unchanged step() for
     i = k .. num_steps - 2, with k = ``start`` (an int) or ``start[b]`` (int32, B entries; start_rows).
@@ -983,7 +987,16 @@ def run_refine(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: 
     only -- row b of a per-sample call is row b of the scalar call at start[b], bit for bit under one kernel_choice -- and
     ``noise.steps(i)`` is not called for i < min(start).  A row that has not started yet rides along, its state ignored, until
     mdt_refine_enter overwrites its state and network input in front of its step: a per-sample call costs every row the steps
-    from min(start).  ``clamp`` / ``trace`` / ``timer`` / ``tokens`` / ``embedding_scale`` / ``dynamic_threshold`` as run_sampler."""
+    from min(start).  ``clamp`` / ``trace`` / ``timer`` / ``tokens`` / ``embedding_scale`` / ``dynamic_threshold`` as run_sampler.
+
+    ``keep`` (bool, True = keep; (B, C, L), or (B, L) with ``keep_per_token``): refine around a kept scaffold.  In front of EVERY
+    step i from min(start), mdt_refine_keep_enter sets the kept positions of the rows that run to ``source + sigmas[i] * n_src(i)``
+    (the merge of ADPM2Sampler.inpaint, diffusion.py:539-542, as a select) and enters the rows whose start is i; after the last
+    step mdt_inpaint_finish sets them to the source (:549) and decodes -- the last update kernel does not -- and the clamp comes
+    after that merge.  There are no resamples.  The source draw of step i is draw ``num_steps + i`` of the generator, or
+    ``noise.sources(i)`` next to explicit (init, steps) -- which is then required, and like steps(i) not called for
+    i < min(start): the draws 0 and i + 1 stay what they are, so an all-False mask gives the unmasked call's result and a row
+    still depends on its own start only.  Without ``keep`` the call launches exactly what it launched before the mask existed."""
     kind = FUSED_SAMPLERS[require_fused_kind(sampler)]
     sigmas, steps = kind.plan(num_steps, schedule, sampler, sigma_data)
     dev, B = engine.device, embedding.shape[0]
@@ -999,6 +1012,13 @@ def run_refine(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: 
         raise ValueError(f"draft must be integer token ids ({B}, {engine.c.length}), got {draft.dtype} {tuple(draft.shape)}")
     if noise.init is not None and tuple(noise.init.shape) != shape:
         raise ValueError(f"the entry noise is {tuple(noise.init.shape)}, the call refines {shape}")
+    if keep is not None:
+        want = (B, engine.c.length) if keep_per_token else shape
+        if keep.dtype != torch.bool or tuple(keep.shape) != want:
+            raise ValueError(f"keep must be a bool tensor {want}, got {keep.dtype} {tuple(keep.shape)}")
+        if noise.steps is not None and noise.sources is None:
+            raise ValueError("a refine call with a keep mask and explicit (init, steps) noise needs NoiseSource(sources=...): the "
+                             "draw that noises the kept source in front of step i")
     rows = start if isinstance(start, torch.Tensor) else torch.full((B,), start, dtype=torch.int32)
     entries = set(rows.tolist())
 
@@ -1018,6 +1038,23 @@ def run_refine(engine, embedding: Tensor, pred_dim: int, num_steps: int, noise: 
                 c_in = (s.w_hat if isinstance(s, KarrasStep) else s.w).c_in
                 rt.check(lp.lib.mdt_refine_enter(rt.ptr(x), rt.ptr(engine.xin), rt.ptr(start_dev), i, rt.ptr(src), rt.ptr(ids),
                                                  rt.ptr(nz0), float(sigmas[i]), c_in, lp.seed, 0, lp.sample0, *lp.dims(), lp.st))
+        if keep is None:
+            lp = _Loop(engine, embedding, shape, sigmas, steps, explicit, noise.seed, noise.sample0, embedding_scale,
+                       dynamic_threshold, clamp, trace, timer, tokens, first=min(entries), hook=enter)
+            return lp.finish(kind.steps(lp, steps), decoded=True)
+        mk, per_token = keep.to(device=dev).to(torch.uint8).contiguous(), 1 if keep_per_token else 0
+
+        def enter_keep(i: int, x: Tensor) -> None:
+            s = steps[i]
+            c_in = (s.w_hat if isinstance(s, KarrasStep) else s.w).c_in
+            nsrc = None if noise.steps is None else _f32(noise.sources(i), dev)
+            rt.check(lp.lib.mdt_refine_keep_enter(rt.ptr(x), rt.ptr(engine.xin), rt.ptr(start_dev), i, rt.ptr(src), rt.ptr(ids),
+                                                  rt.ptr(mk), per_token, rt.ptr(nz0), rt.ptr(nsrc), float(sigmas[i]), c_in, lp.seed,
+                                                  0, num_steps + i, lp.sample0, *lp.dims(), lp.st))
+        # the loop decodes nothing (tokens=None): mdt_inpaint_finish merges and decodes, then finish() clamps and decodes again
         lp = _Loop(engine, embedding, shape, sigmas, steps, explicit, noise.seed, noise.sample0, embedding_scale,
-                   dynamic_threshold, clamp, trace, timer, tokens, first=min(entries), hook=enter)
-        return lp.finish(kind.steps(lp, steps), decoded=True)
+                   dynamic_threshold, clamp, trace, timer, None, first=min(entries), hook=enter_keep)
+        x = kind.steps(lp, steps)
+        rt.check(lp.lib.mdt_inpaint_finish(rt.ptr(x), rt.ptr(src), rt.ptr(ids), rt.ptr(mk), per_token, rt.ptr(tokens), *shape, lp.st))
+        lp.tokens = tokens
+        return lp.finish(x, decoded=True)

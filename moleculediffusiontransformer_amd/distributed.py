@@ -118,6 +118,15 @@ def refine_tokens_sharded(local_refine_tokens: Callable[[Tensor, Tensor, object,
     slice via ``local_refine_tokens(seq_slice, draft_slice, start_slice, first_global_index) -> (b_r, L)`` token ids
     (model.refine_tokens(..., start_step=start_slice, noise=NoiseSource(seed=s, sample0=first_global_index))) and all ranks
     receive the full (B, L) result.  A row's result depends on its own start only, so the split does not change it."""
+    return refine_keep_tokens_sharded(local_refine_tokens, sequences, draft_tokens, start_step, vocab, group, model, guided)
+
+
+def refine_keep_tokens_sharded(local_refine_tokens: Callable[..., Tensor], sequences: Tensor, draft_tokens: Tensor, start_step,
+                               vocab: int, group=None, model=None, guided: bool = False,
+                               keep_mask: Optional[Tensor] = None) -> Tensor:
+    """refine_tokens_sharded around a kept scaffold: ``keep_mask`` (B, L) bool is sliced by rows with the draft and handed on as
+    ``local_refine_tokens(seq_slice, draft_slice, start_slice, first_global_index, keep_mask=keep_slice)`` (for
+    model.refine_keep_tokens(..., keep_mask=keep_slice)); None: the callback is called as refine_tokens_sharded calls it."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     total = sequences.shape[0]
@@ -126,9 +135,12 @@ def refine_tokens_sharded(local_refine_tokens: Callable[[Tensor, Tensor, object,
     per_sample = not isinstance(start_step, int) and getattr(torch.as_tensor(start_step), "ndim", 0) == 1
     if per_sample and len(start_step) != total:
         raise ValueError(f"start_step must be one int or hold one entry for each of the {total} samples")
+    if keep_mask is not None and keep_mask.shape[0] != total:
+        raise ValueError(f"keep_mask must hold the same {total} samples as sequences and draft_tokens")
     pin_for_shards(model, total, world, guided)
     lo, hi = shard_bounds(total, world, rank)
-    local = local_refine_tokens(sequences[lo:hi], draft_tokens[lo:hi], start_step[lo:hi] if per_sample else start_step, lo)
+    more = {} if keep_mask is None else dict(keep_mask=keep_mask[lo:hi])
+    local = local_refine_tokens(sequences[lo:hi], draft_tokens[lo:hi], start_step[lo:hi] if per_sample else start_step, lo, **more)
     if world == 1:
         return local.long()
     return all_gather_tokens(local, total, vocab, group)

@@ -539,11 +539,25 @@ class _QMBase(nn.Module):
                             "have") from None
         return sampler
 
+    def _check_keep(self, keep_mask, B: int, per_token_only: bool) -> Optional[Tensor]:
+        """The keep mask of a refine call: None, or bool, True = keep -- (B, max_length), or (unless ``per_token_only``)
+        (B, pred_dim, max_length)."""
+        if keep_mask is None:
+            return None
+        keep_mask = torch.as_tensor(keep_mask)
+        shapes = [(B, self.max_length)] + ([] if per_token_only else [(B, self.pred_dim, self.max_length)])
+        if keep_mask.dtype != torch.bool:
+            raise ValueError(f"keep_mask must be a bool tensor (True = keep), got {keep_mask.dtype}")
+        if tuple(keep_mask.shape) not in shapes:
+            raise ValueError(f"keep_mask must be {' or '.join(str(v) for v in shapes)}; got {tuple(keep_mask.shape)}")
+        return keep_mask
+
     def _do_refine(self, sequences, device, start, cond_scale, timesteps, clamp, noise, sampler, sigma_schedule, trace=None,
-                   source=None, draft=None, tokens=None) -> Tensor:
+                   source=None, draft=None, tokens=None, keep=None) -> Tensor:
         """refine() / refine_tokens() behind their checks: ``start`` and ``cond_scale`` are normalised (start_rows,
         guidance_rows), ``sampler`` has a fused kind (_refine_sampler), the batch is not empty.  The plain call -- seeded step noise, one guidance scale, no trace, token ids in
-        and out -- is ONE custom op (mdt::refine_tokens); every other call is run_refine."""
+        and out -- is ONE custom op (mdt::refine_tokens; with a keep mask, checked by _check_keep, mdt::refine_keep_tokens);
+        every other call is run_refine."""
         if sigma_schedule is None:
             sigma_schedule = KarrasSchedule(sigma_min=0.001, sigma_max=9.0, rho=3.0)
         device = torch.device(device)
@@ -558,15 +572,19 @@ class _QMBase(nn.Module):
         if plain:
             rows = start if isinstance(start, torch.Tensor) else torch.full((B,), start, dtype=torch.int32)
             init = None if ns.init is None else ns.init.to(device=device, dtype=torch.float32)
-            x, t = torch.ops.mdt.refine_tokens(emb, draft.to(device), rows.to(device), init, sigmas, ops.register_engine(eng),
-                                               self.pred_dim, *ops.sampler_spec(sampler), float(kd.sigma_data), float(cond_scale),
-                                               int(ns.seed or 0), int(ns.sample0), float(kd.dynamic_threshold))
+            tail = (init, sigmas, ops.register_engine(eng), self.pred_dim, *ops.sampler_spec(sampler), float(kd.sigma_data),
+                    float(cond_scale), int(ns.seed or 0), int(ns.sample0), float(kd.dynamic_threshold))
+            if keep is None:
+                x, t = torch.ops.mdt.refine_tokens(emb, draft.to(device), rows.to(device), *tail)
+            else:
+                x, t = torch.ops.mdt.refine_keep_tokens(emb, draft.to(device), rows.to(device), keep.to(device), *tail)
             tokens.copy_(t)
             return x
         with torch.no_grad():
             return run_refine(eng, emb, self.pred_dim, timesteps, ns, sigmas, sampler, kd.sigma_data, start, source=source,
                               draft=None if draft is None else draft.to(device), embedding_scale=cond_scale, clamp=clamp,
-                              trace=trace, tokens=tokens, dynamic_threshold=float(kd.dynamic_threshold))
+                              trace=trace, tokens=tokens, dynamic_threshold=float(kd.dynamic_threshold),
+                              keep=None if keep is None else keep.to(device), keep_per_token=keep is not None and keep.dim() == 2)
 
     def refine(self, sequences, device, source, start_step, cond_scale=None, timesteps=100, clamp=False, *, noise=None,
                sampler=None, sigma_schedule=None, trace=None):
@@ -581,7 +599,19 @@ class _QMBase(nn.Module):
         ``kernel_choice``.  Cost: a per-sample call runs EVERY row from min(start_step) -- rows that start later ride along
         until their step -- so it costs what the scalar call at min(start_step) costs.  ``cond_scale`` (None: sample()'s default),
         ``noise`` (a tensor = the entry noise, a NoiseSource, or None), ``sampler``, ``sigma_schedule``, ``trace``, ``clamp`` as
-        sample().  The sampler must have a fused loop: a sampler with its own step() raises TypeError."""
+        sample().  The sampler must have a fused loop: a sampler with its own step() raises TypeError.  Every position is free;
+        refine_keep() holds a scaffold fixed."""
+        return self.refine_keep(sequences, device, source, start_step, cond_scale, timesteps, clamp, noise=noise, sampler=sampler,
+                                sigma_schedule=sigma_schedule, trace=trace)
+
+    def refine_keep(self, sequences, device, source, start_step, cond_scale=None, timesteps=100, clamp=False, *, noise=None,
+                    sampler=None, sigma_schedule=None, trace=None, keep_mask=None):
+        """refine() around a kept scaffold: every argument as refine(), and ``keep_mask`` (bool, True = keep; (B, pred_dim,
+        max_length) or (B, max_length); None: refine() itself).  The kept positions are re-noised from ``source`` in front of
+        every step, as ADPM2Sampler.inpaint does, and equal ``source`` exactly in the result (before ``clamp``); the free
+        positions start from the noised source, not from pure noise.  With start_step = 0 this is scaffold-constrained
+        generation under any fused sampler.  No resamples.  An all-False mask is refine(), bit for bit.  Explicit noise needs
+        NoiseSource(sources=...).  Cost: one more elementwise launch per step, and EVERY row runs from min(start_step)."""
         sampler = self._refine_sampler(sampler)
         if cond_scale is None:
             cond_scale = 7.5 if self._inverse else 1.0
@@ -592,10 +622,11 @@ class _QMBase(nn.Module):
         if not source.is_floating_point() or tuple(source.shape) != (B, self.pred_dim, self.max_length):
             raise ValueError(f"source must be a floating-point tensor ({B}, {self.pred_dim}, {self.max_length}); got {source.dtype} "
                              f"{tuple(source.shape)}")
+        keep = self._check_keep(keep_mask, B, per_token_only=False)
         if B == 0:
             return torch.empty(0, self.pred_dim, self.max_length, device=torch.device(device))
         return self._do_refine(sequences, device, start, cond_scale, timesteps, clamp, noise, sampler, sigma_schedule, trace,
-                               source=source)
+                               source=source, keep=keep)
 
     def refine_tokens(self, sequences, device, draft_tokens, start_step=None, *, strength=None, cond_scale=None, timesteps=100,
                       noise=None, sampler=None, sigma_schedule=None, return_sample: bool = False):
@@ -604,7 +635,19 @@ class _QMBase(nn.Module):
         ``draft_tokens``: integer (B, max_length), ids in [0, pred_dim).  Give exactly one of ``start_step`` (as refine()) or
         ``strength`` in (0, 1] (diffusion.refine_start; one value or one per sample): the share of the schedule that is run.
         Returns (B, max_length) int64 token ids on ``device`` and with ``return_sample`` also the fp32 sample, bit for bit
-        refine()'s on one_hot_draft(draft_tokens, pred_dim).  Cost of a per-sample call: every row runs from min(start_step)."""
+        refine()'s on one_hot_draft(draft_tokens, pred_dim).  Cost of a per-sample call: every row runs from min(start_step).
+        Every position is free; refine_keep_tokens() holds a scaffold fixed."""
+        return self.refine_keep_tokens(sequences, device, draft_tokens, start_step, strength=strength, cond_scale=cond_scale,
+                                       timesteps=timesteps, noise=noise, sampler=sampler, sigma_schedule=sigma_schedule,
+                                       return_sample=return_sample)
+
+    def refine_keep_tokens(self, sequences, device, draft_tokens, start_step=None, *, strength=None, cond_scale=None,
+                           timesteps=100, noise=None, sampler=None, sigma_schedule=None, return_sample: bool = False,
+                           keep_mask=None):
+        """refine_tokens() around a kept scaffold (refine_keep() for a lead given as token ids): every argument as
+        refine_tokens(), and ``keep_mask``: bool (B, max_length), True = keep the position, as inpaint_tokens() (None:
+        refine_tokens() itself).  The scaffold is held exactly -- a kept position decodes to its draft id -- while the rest is
+        refined near the lead."""
         sampler = self._refine_sampler(sampler)
         if (start_step is None) == (strength is None):
             raise ValueError("give exactly one of start_step and strength")
@@ -616,13 +659,14 @@ class _QMBase(nn.Module):
         cond_scale = guidance_rows(cond_scale, B)
         start = start_rows(start_step, B, timesteps, "start_step" if strength is None else "strength")
         draft_tokens = self._check_draft(draft_tokens, B)
+        keep = self._check_keep(keep_mask, B, per_token_only=True)
         device = torch.device(device)
         if B == 0:                                  # nothing to refine (sample() returns an empty tensor too)
             tok, x = torch.zeros(0, L, dtype=torch.int64, device=device), torch.empty(0, self.pred_dim, L, device=device)
             return (tok, x) if return_sample else tok
         tok = torch.zeros(B, L, dtype=torch.int32, device=device)
         x = self._do_refine(sequences, device, start, cond_scale, timesteps, False, noise, sampler, sigma_schedule,
-                            draft=draft_tokens, tokens=tok)
+                            draft=draft_tokens, tokens=tok, keep=keep)
         return (tok.long(), x) if return_sample else tok.long()
 
 
@@ -775,7 +819,8 @@ def strength_sweep(model, sequences: Tensor, draft_tokens: Tensor, strengths, de
     """The strength sweep over the same leads -- ``for s in strengths: model.refine_tokens(sequences, device, draft_tokens,
     strength=s)`` -- as ONE fused call of batch S * B, the counterpart of guidance_sweep: row s * B + b is lead b at strengths[s],
     and the token ids come back as (S, B, L) (with return_sample=True the pair of ids and samples (S, B, C, L)).
-    ``refine_kwargs`` go to refine_tokens(); a ``noise`` tensor holds S * B rows, and with ``noise=NoiseSource(seed=..., sample0=n)``
+    ``refine_kwargs`` go to refine_tokens() -- with a ``keep_mask`` (B, L), the same scaffold at every strength, to
+    refine_keep_tokens(); a ``noise`` tensor holds S * B rows, and with ``noise=NoiseSource(seed=..., sample0=n)``
     sweep s equals the scalar call whose sample0 is n + s * B (bit for bit under a pinned ``kernel_choice``).  Cost: every row runs
     from the start step of the LARGEST strength, so the sweep pays off only while its scalar calls underfill the GPU."""
     try:
@@ -789,8 +834,14 @@ def strength_sweep(model, sequences: Tensor, draft_tokens: Tensor, strengths, de
     S, B = len(strengths), sequences.shape[0]
     starts = refine_start(int(refine_kwargs.get("timesteps", 100)), strengths)
     draft_tokens = torch.as_tensor(draft_tokens)
-    out = model.refine_tokens(sequences.repeat(S, *([1] * (sequences.dim() - 1))), device, draft_tokens.repeat(S, 1),
-                              start_step=torch.tensor(starts, dtype=torch.int64).repeat_interleave(B), **refine_kwargs)
+    call = model.refine_tokens
+    if refine_kwargs.get("keep_mask") is not None:            # the same scaffold at every strength
+        refine_kwargs["keep_mask"] = torch.as_tensor(refine_kwargs["keep_mask"]).repeat(S, 1)
+        call = model.refine_keep_tokens
+    else:
+        refine_kwargs.pop("keep_mask", None)
+    out = call(sequences.repeat(S, *([1] * (sequences.dim() - 1))), device, draft_tokens.repeat(S, 1),
+               start_step=torch.tensor(starts, dtype=torch.int64).repeat_interleave(B), **refine_kwargs)
     unflat = lambda t: t.reshape(S, B, *t.shape[1:])          # noqa: E731
     return tuple(unflat(t) for t in out) if isinstance(out, tuple) else unflat(out)
 
@@ -798,13 +849,14 @@ def strength_sweep(model, sequences: Tensor, draft_tokens: Tensor, strengths, de
 def refine_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForward", conditioning: Tensor, draft_tokens: Tensor,
                         device, start_step=None, *, strength=None, cond_scale: float = 1.0, timesteps: int = 100,
                         forward_timesteps: int = 100, X_norm_factor: float = 1.0, noise=None, forward_noise=None, sampler=None,
-                        sigma_schedule=None):
+                        sigma_schedule=None, keep_mask=None):
     """The chain into the forward model, as complete_and_validate: refine the leads under the conditioning, decode inside the
     last sampler update, re-predict the properties of the refined molecules with the forward model.  Returns (tokens (B, L)
-    int64, predicted properties (B, n_cond)).  ``start_step`` / ``strength`` / ``noise`` as refine_tokens; ``forward_noise`` as
-    generate_and_validate."""
-    tokens = model.refine_tokens(conditioning, device, draft_tokens, start_step, strength=strength, cond_scale=cond_scale,
-                                 timesteps=timesteps, noise=noise, sampler=sampler, sigma_schedule=sigma_schedule)
+    int64, predicted properties (B, n_cond)).  ``start_step`` / ``strength`` / ``noise`` as refine_tokens, ``keep_mask``
+    as refine_keep_tokens; ``forward_noise`` as generate_and_validate."""
+    call, more = (model.refine_tokens, {}) if keep_mask is None else (model.refine_keep_tokens, dict(keep_mask=keep_mask))
+    tokens = call(conditioning, device, draft_tokens, start_step, strength=strength, cond_scale=cond_scale, timesteps=timesteps,
+                  noise=noise, sampler=sampler, sigma_schedule=sigma_schedule, **more)
     props = predict_properties_from_tokens(model_forward, tokens, device, cond_scale=1.0, timesteps=forward_timesteps,
                                            X_norm_factor=X_norm_factor,
                                            context_embedding_max_length=conditioning.shape[1], noise=forward_noise)

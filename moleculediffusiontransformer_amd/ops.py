@@ -23,6 +23,7 @@ fake / meta tensors).
     sample_with         the same with the sampler chosen: ADPM2Sampler, AEulerSampler (:476-483) or KarrasSampler (:437-453)
     inpaint_tokens      DiffusionInpainter.forward + ADPM2Sampler.inpaint on a draft of token ids, decoded (diffusion.py:526-549, :612-625)
     refine_tokens       noise a draft of token ids up to the level of step k and run the remaining sampler steps, k per sample, decoded
+    refine_keep_tokens  the same around a kept scaffold: a bool keep mask is re-noised from the draft in front of every step and held exactly
     all_gather_samples  the one collective of a sharded call (RCCL all_gather_into_tensor)
     precond_in_rows / precond_out_rows   the denoise scaling with ONE coefficient per sample (denoise_fn(sigmas=(B,)))
     unet_eval_rows      net(x, time=(B,), ...) as ONE evaluation: one time-mapping / FiLM row per sample
@@ -852,6 +853,46 @@ def refine_tokens(embedding: Tensor, draft: Tensor, start: Tensor, init_noise: O
 
 @refine_tokens.register_fake
 def _(embedding, draft, start, init_noise, sigmas, handle, pred_dim, sampler_kind, sampler_params, sigma_data, embedding_scale,
+      seed, sample0, dynamic_threshold=0.0):
+    B, L = draft.shape
+    return embedding.new_empty(B, pred_dim, L, dtype=torch.float32), draft.new_empty((B, L), dtype=torch.int32)
+
+
+@custom_op("mdt::refine_keep_tokens", mutates_args=())
+def refine_keep_tokens(embedding: Tensor, draft: Tensor, start: Tensor, keep: Tensor, init_noise: Optional[Tensor], sigmas: Tensor,
+                       handle: int, pred_dim: int, sampler_kind: int, sampler_params: Sequence[float], sigma_data: float,
+                       embedding_scale: float, seed: int, sample0: int, dynamic_threshold: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """mdt::refine_tokens around a kept scaffold (diffusion.run_refine with ``keep``): keep (B, L) bool, True = the position is
+    re-noised from the draft in front of every step and is the draft in the result.  The source draw of step i is draw
+    num_steps + i of the generator; the other arguments and draws as mdt::refine_tokens.  Returns (x (B, pred_dim, L) fp32 with
+    the one-hot of the draft at the kept positions, tokens (B, L) int32: the draft id at a kept position, else the argmax)."""
+    dev = _hip(embedding, draft, start, keep, init_noise)
+    eng = _engine_on(handle, dev, "mdt::refine_keep_tokens")
+    B, L = embedding.shape[0], eng.c.length
+    if draft.is_floating_point() or tuple(draft.shape) != (B, L) or start.dtype != torch.int32 or tuple(start.shape) != (B,):
+        raise RuntimeError(f"mdt::refine_keep_tokens: draft must be integer ids ({B}, {L}) and start int32 ({B},); got {draft.dtype} "
+                           f"{tuple(draft.shape)} and {start.dtype} {tuple(start.shape)}")
+    if keep.dtype != torch.bool or tuple(keep.shape) != (B, L):
+        raise RuntimeError(f"mdt::refine_keep_tokens: keep must be bool ({B}, {L}); got {keep.dtype} {tuple(keep.shape)}")
+    if init_noise is not None and tuple(init_noise.shape) != (B, pred_dim, L):
+        raise RuntimeError(f"mdt::refine_keep_tokens: init_noise is {tuple(init_noise.shape)}, not ({B}, {pred_dim}, {L})")
+    tok = torch.zeros(B, L, dtype=torch.int32, device=dev)
+    if B == 0:
+        return torch.empty(0, pred_dim, L, device=dev), tok
+    ns = NoiseSource(seed=int(seed), sample0=int(sample0))
+    if init_noise is not None:
+        ns.init = init_noise
+    try:
+        x = run_refine(eng, embedding, int(pred_dim), sigmas.numel() - 1, ns, sigmas, _make_sampler(sampler_kind, list(sampler_params)),
+                       float(sigma_data), start.cpu(), draft=draft, embedding_scale=float(embedding_scale), tokens=tok,
+                       dynamic_threshold=float(dynamic_threshold), keep=keep, keep_per_token=True)
+    except ValueError as e:                      # (the ops' convention: every failure is a RuntimeError)
+        raise RuntimeError(f"mdt::refine_keep_tokens: {e}") from None
+    return x, tok
+
+
+@refine_keep_tokens.register_fake
+def _(embedding, draft, start, keep, init_noise, sigmas, handle, pred_dim, sampler_kind, sampler_params, sigma_data, embedding_scale,
       seed, sample0, dynamic_threshold=0.0):
     B, L = draft.shape
     return embedding.new_empty(B, pred_dim, L, dtype=torch.float32), draft.new_empty((B, L), dtype=torch.int32)

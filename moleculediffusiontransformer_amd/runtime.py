@@ -103,6 +103,7 @@ SYMBOLS = {
     "mdt_inpaint_enter": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _U64, _U32, _U32, _L, _I, _I, _I, _I, _P]),
     "mdt_inpaint_finish": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mdt_refine_enter": (_I, [_P, _P, _P, _I, _P, _P, _P, _F, _F, _U64, _U32, _L, _I, _I, _I, _I, _P]),
+    "mdt_refine_keep_enter": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _F, _F, _U64, _U32, _U32, _L, _I, _I, _I, _I, _P]),
     "mdt_argmax_tokens": (_I, [_P, _P, _I, _I, _I, _P]),
     "mdt_tokens_compact": (_I, [_P, _I, _I, _P, _I, C.c_double, _P, _P, _P, _P]),
     "mdt_screen_score": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P]),
