@@ -14,11 +14,9 @@
 #include <algorithm>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---- operand loads.  H = the tensor is bf16 (plain-bf16 mode: q | k | v come out of a bf16 x bf16 GEMM as bf16, MDT_A_IN16;
 // the values are widened to fp32 in registers -- exact -- and both contractions stay fp32 MFMAs): half the bytes of the launch,
@@ -293,7 +291,6 @@ hipError_t launch_attn(const AttnArgs& a, hipStream_t s) {
   }
 }
 
-
 // ------------------------------------------------------------------------------------------------------------------
 // Cross-attention against the NORMALISED CONTEXT ITSELF (MDT_OP_ATTN_CTX): the per-layer key / value projections are
 // folded into the query and output projections on the host (compiler.py::attention_layer_folded),
@@ -310,24 +307,8 @@ hipError_t launch_attn(const AttnArgs& a, hipStream_t s) {
 //                  row 16 kt + 4 g + s at floats [64 half + 4 lo, +4), a full 256 B row segment per lane quarter, and
 //                  lane (query, g) ends with out[query][64 half + 16 g + 4 r .. +4) per r = one dwordx4 store.
 // ------------------------------------------------------------------------------------------------------------------
-// lane-group exchanges over +-16 / +-32 lanes with the gfx950 permlane swaps (k_rconv.hip: VALU, no LDS round trip)
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
-MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
-#undef MDT_XG
-
 __device__ __forceinline__ void lds_read_f4(f32x4& dst, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
 }
 
 // Round 4: the context streams through LDS.  The first form loaded its operands straight from global memory into registers

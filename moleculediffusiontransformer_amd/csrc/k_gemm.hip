@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
@@ -25,14 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int BN = 64;
 constexpr int NTHREADS = 256;
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __device__ __forceinline__ float group16_sum(float v) {     // over the 16 lanes of a lane's group
 #pragma unroll
@@ -215,11 +209,11 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm(GemmArgs g) {
           }
           if (g.pro_silu) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) x[e] = silu_f(x[e]);
+            for (int e = 0; e < 4; ++e) x[e] = silu_exact(x[e]);
           }
         } else if constexpr (PRO == 3) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) x[e] = silu_f(x[e]);
+          for (int e = 0; e < 4; ++e) x[e] = silu_exact(x[e]);
         }
       }
       *reinterpret_cast<float4*>(&As[(r0 + i * ROWSTEP) * LDT + c4 * 4]) = make_float4(x[0], x[1], x[2], x[3]);

@@ -15,14 +15,13 @@
 #include <cstdlib>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float silu_as(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float gelu_as(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 constexpr int AS_BM = 64;     // rows per workgroup
@@ -141,11 +140,11 @@ __global__ __launch_bounds__(256) void k_gemm_as(GemmArgs g, int nsplit, int dbg
             const float sc = st[grp * 2 + 1] * ga[e];
             x[e] = x[e] * sc + (be[e] - sc * st[grp * 2]);
             x[e] = x[e] * (fa[e] + 1.0f) + fs[e];
-            if (g.pro_silu) x[e] = silu_as(x[e]);
+            if (g.pro_silu) x[e] = silu_exact(x[e]);
           }
         } else if constexpr (PRO == 3) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) x[e] = silu_as(x[e]);
+          for (int e = 0; e < 4; ++e) x[e] = silu_exact(x[e]);
         }
         u16x4 hi, lo;
 #pragma unroll

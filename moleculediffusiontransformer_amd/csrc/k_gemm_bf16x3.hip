@@ -23,15 +23,14 @@
 #include <cstdlib>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
 
-__device__ __forceinline__ float silu3(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float gelu3(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 __device__ __forceinline__ void split4(const float x[4], u16x4& hi, u16x4& lo) {
@@ -209,11 +208,11 @@ __global__ __launch_bounds__(256) void k_gemm3(GemmArgs g) {
         }
         if (g.pro_silu) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) x[e] = silu3(x[e]);
+          for (int e = 0; e < 4; ++e) x[e] = silu_exact(x[e]);
         }
       } else if constexpr (PRO == 3) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = silu3(x[e]);
+        for (int e = 0; e < 4; ++e) x[e] = silu_exact(x[e]);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) x[e] = R.va[i] ? x[e] : 0.f;     // conv zero padding / rows past M

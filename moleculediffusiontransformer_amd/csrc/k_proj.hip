@@ -21,63 +21,17 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define MDT_XGP(NAME, INSN)                                                              \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return a + b;                                                                        \
-  }
-MDT_XGP(pj_xg16_add, "v_permlane16_swap_b32")
-MDT_XGP(pj_xg32_add, "v_permlane32_swap_b32")
-#undef MDT_XGP
 
 constexpr int CS = 128;         // k-width of a weight tile
 constexpr int SLOT = 256 * CS;  // bytes per tile (bf16 hi plane + lo plane)
 constexpr int NS = 4;           // ring slots
 constexpr int IPT = CS / 16;    // DMA pieces per tile per loader wave
 constexpr int PJ_BIAS_PASSES = 8;   // bias slice of a workgroup in LDS: up to 8 x 256 floats = 32 chunks
-
-// 8 values of one k-step -> its two 128-bit operand registers: bf16 hi / lo planes, or (F32) the values themselves, slots 0..3 in
-// `hi`, 4..7 in `lo` (k_rconv.hip / k_tf128.hip)
-template <bool F32>
-__device__ __forceinline__ void pj_split8(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-template <int OFF>      // fragment read with the (feature tile, plane) part of the address as immediate offset
-__device__ __forceinline__ void pj_lds_read16(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned pj_lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void pj_lgkm_wait() {
-  if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 }  // namespace
 
@@ -159,7 +113,7 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
     constexpr int q = j >> 1, lo = j & 1;
     constexpr int off = F32 ? ((RTW == 4) ? ((2 * (u & 1) + q) * 8192 + lo * 1024) : (q * 8192 + lo * 1024))
                             : ((RTW == 4) ? ((2 * (u & 1) + q) * 16 * 4 * CS + lo * (2 * CS)) : (q * 16 * 4 * CS + lo * (2 * CS)));
-    pj_lds_read16<off>(lo ? frl[set][q] : frh[set][q], base);
+    lds_read16_off<off>(lo ? frl[set][q] : frh[set][q], base);
   };
   using J0 = std::integral_constant<int, 0>;
   using J1 = std::integral_constant<int, 1>;
@@ -207,7 +161,7 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
 #pragma unroll
       for (int st = 0; st < NST; ++st)
         s += ((xr[st][0] + xr[st][1]) + (xr[st][2] + xr[st][3])) + ((xr[st][4] + xr[st][5]) + (xr[st][6] + xr[st][7]));
-      s = pj_xg32_add(pj_xg16_add(s));
+      s = xg32_add(xg16_add(s));
       const float mean = s * (1.0f / (float)K);
       float ss = 0.f;
 #pragma unroll
@@ -217,7 +171,7 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
           const float d = xr[st][e] - mean;
           ss += d * d;
         }
-      ss = pj_xg32_add(pj_xg16_add(ss));
+      ss = xg32_add(xg16_add(ss));
       const float rstd = __builtin_amdgcn_rsqf(ss * (1.0f / (float)K) + a.eps);     // v_rsq_f32: 1 ulp (as k_rconv.hip)
       if constexpr (LN == 2) {
 #pragma unroll
@@ -237,12 +191,12 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
       }
     }
 #pragma unroll
-    for (int st = 0; st < NST; ++st) pj_split8<F32>(xr[st], xh[st], xl[st]);
+    for (int st = 0; st < NST; ++st) split8<F32>(xr[st], xh[st], xl[st]);
   }
 
   __builtin_amdgcn_s_barrier();                      // B(0): tile 0 has landed, the bias slice is in LDS (loader waves)
   {
-    const unsigned l0 = pj_lds_addr(slot_of(0));
+    const unsigned l0 = lds_addr(slot_of(0));
     const unsigned p0 = l0 + aP[0], p1 = l0 + aP[(RTW == 4) ? 0 : 1];
     frag_read(p0, J0{}, 0, J0{}); frag_read(p0, J0{}, 0, J1{}); frag_read(p0, J0{}, 0, J2{}); frag_read(p0, J0{}, 0, J3{});
     frag_read(p1, J1{}, 1, J0{}); frag_read(p1, J1{}, 1, J1{}); frag_read(p1, J1{}, 1, J2{}); frag_read(p1, J1{}, 1, J3{});
@@ -261,7 +215,7 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
       for (int q = 0; q < NFT; ++q) ir[q] = *reinterpret_cast<const float4*>(rsrc + 64 * cc + 16 * q);
     }
   };
-  const unsigned bias_l = pj_lds_addr(smem + NS * SLOT) + (16 * (NFT * fh) + 4 * g) * 4;
+  const unsigned bias_l = lds_addr(smem + NS * SLOT) + (16 * (NFT * fh) + 4 * g) * 4;
   auto chunk = [&](auto lastc, int cc, float4 (&ir)[HASR ? NFT : 1], float4 (&irn)[HASR ? NFT : 1]) {
     constexpr bool LAST = decltype(lastc)::value;               // the workgroup's last chunk: nothing behind its last tile
     const int f0 = 64 * (c0 + cc) + 16 * (NFT * fh) + 4 * g;   // this lane's first feature of feature tile 0
@@ -279,7 +233,7 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
       const int tau = cc * KH + kh;
       constexpr bool more_ct = !LAST;                           // (kh < KH - 1 is always followed by a tile)
       const bool more = (kh + 1 < KH) || more_ct;
-      const unsigned lc = pj_lds_addr(slot_of(tau)), ln = pj_lds_addr(slot_of(tau + 1));
+      const unsigned lc = lds_addr(slot_of(tau)), ln = lds_addr(slot_of(tau + 1));
       unsigned bc[4], bn[2];
 #pragma unroll
       for (int k = 0; k < 4; ++k) bc[k] = lc + aP[k];
@@ -296,7 +250,7 @@ __global__ __launch_bounds__(512) void k_proj(ProjArgs a) {
         constexpr bool in_tile = u + 2 < NU;
         const bool pre = in_tile || more;
         const bool later = (u + 1 < NU) || more;
-        if (later) pj_lgkm_wait<4>(); else pj_lgkm_wait<0>();
+        if (later) lgkm_wait<4>(); else lgkm_wait<0>();
         constexpr int ia = (RTW == 4) ? 2 * (u & 1) : 0, ib_ = (RTW == 4) ? (u >> 1) : u;
         const bf16x8 oph = xh[4 * kh + ib_], opl = xl[4 * kh + ib_];
         auto rd = [&](auto jc) {

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 // Compiled twice: as is (split-bf16 products, launch_rconv) and through k_rconv_f32.hip with MDT_TF_F32 = 1 (exact fp32 MFMA
 // products on fp32 fragment tiles, launch_rconv_f32; tile format and MFMA order as k_tf128.hip).
@@ -36,92 +37,12 @@ namespace mdt {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// streaming store: the output is consumed by the next launch (through the memory side: the per-XCD L2s are written
-// back / invalidated at every kernel boundary anyway), so it need not stay dirty in this XCD's L2 until kernel end
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-// lane-group exchanges over +-16 / +-32 lanes with the gfx950 permlane swaps (VALU, no LDS round trip). The swap is in
-// place on two registers: fed the same value twice, v_permlane16_swap leaves (rows 0,0,2,2) and (rows 1,1,3,3),
-// v_permlane32_swap (halves lo,lo) and (hi,hi); combining the two gives every lane the pair it would get from xor 16 /
-// xor 32. Written as asm: through __builtin_amdgcn_permlane*_swap hipcc 7.2 folds the two results into one register.
-// The s_nop covers the VALU-write -> permlane-swap-read hazard for the copies the compiler places just before.
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
-MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
-#undef MDT_XG
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
 constexpr bool F32 = MDT_TF_F32 != 0;   // product type of this translation unit
 
 constexpr int CS = 128;         // k-width of a weight tile
 constexpr int SLOT = 256 * CS;  // bytes per tile (bf16 hi plane + lo plane)
 constexpr int NS = 4;           // ring slots
 constexpr int IPT = CS / 16;    // DMA pieces per tile per loader wave
-
-// 8 values of one k-step -> its two 128-bit operand registers: bf16 hi / lo planes, or (F32) the values themselves, slots
-// 0..3 in `hi`, 4..7 in `lo` (k_tf128.hip)
-__device__ __forceinline__ void split8_rc(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-__device__ __forceinline__ void lds_read16_rc(bf16x8& dst, const unsigned char* p) {
-  const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
-}
-
-template <int OFF>      // fragment read with the (tile, plane) part of the address as immediate offset (k_tblock_lw.hip)
-__device__ __forceinline__ void lds_read16_off_rc(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr_rc(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait_rc() {
-  if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// operand of the neighbouring token row: lane i takes lane i - 1 (SHR) or i + 1 inside its 16-lane row, 0 at the ends
-template <bool SHR>
-__device__ __forceinline__ bf16x8 row_shift(const bf16x8& v, bool keep) {
-  const i32x4 s = __builtin_bit_cast(i32x4, v);
-  i32x4 r;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int t = __builtin_amdgcn_update_dpp(0, s[k], SHR ? 0x111 : 0x101, 0xf, 0xf, true);
-    r[k] = keep ? t : 0;
-  }
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 }  // namespace
 
@@ -234,7 +155,7 @@ __global__ __launch_bounds__(512) void k_rconv(RConvArgs a) {
     constexpr int q = j >> 1, lo = j & 1;
     constexpr int off = F32 ? ((RTW == 4) ? ((2 * (u & 1) + q) * 8192 + lo * 1024) : (q * 8192 + lo * 1024))
                             : ((RTW == 4) ? ((2 * (u & 1) + q) * 16 * 4 * CS + lo * (2 * CS)) : (q * 16 * 4 * CS + lo * (2 * CS)));
-    lds_read16_off_rc<off>(lo ? frl[set][q] : frh[set][q], base);
+    lds_read16_off<off>(lo ? frl[set][q] : frh[set][q], base);
   };
   using J0 = std::integral_constant<int, 0>;
   using J1 = std::integral_constant<int, 1>;
@@ -499,7 +420,7 @@ __global__ __launch_bounds__(512) void k_rconv(RConvArgs a) {
 #pragma unroll
       for (int st = 0; st < NSTW; ++st) {
         bf16x8 h, l;
-        split8_rc(xr[st], h, l);
+        split8<F32>(xr[st], h, l);
         *reinterpret_cast<bf16x8*>(ex + (((wave * NSTW + st) * 2 + 0) * 64 + lane) * 16) = h;
         *reinterpret_cast<bf16x8*>(ex + (((wave * NSTW + st) * 2 + 1) * 64 + lane) * 16) = l;
       }
@@ -514,13 +435,13 @@ __global__ __launch_bounds__(512) void k_rconv(RConvArgs a) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     } else {
 #pragma unroll
-      for (int st = 0; st < NST; ++st) split8_rc(xr[st], xh[st], xl[st]);
+      for (int st = 0; st < NST; ++st) split8<F32>(xr[st], xh[st], xl[st]);
     }
   }
   MDT_STAMP();
   if (src == 0) {
     __builtin_amdgcn_s_barrier();                    // B(0)
-    const unsigned l0 = lds_addr_rc(slot_of(0));
+    const unsigned l0 = lds_addr(slot_of(0));
     const unsigned p0 = l0 + aP[0], p1 = l0 + aP[(RTW == 4) ? 0 : 1];
     frag_read(p0, J0{}, 0, J0{}); frag_read(p0, J0{}, 0, J1{}); frag_read(p0, J0{}, 0, J2{}); frag_read(p0, J0{}, 0, J3{});
     frag_read(p1, J1{}, 1, J0{}); frag_read(p1, J1{}, 1, J1{}); frag_read(p1, J1{}, 1, J2{}); frag_read(p1, J1{}, 1, J3{});
@@ -547,7 +468,7 @@ __global__ __launch_bounds__(512) void k_rconv(RConvArgs a) {
         const int tau = (tap * NKH + kh) * NCH + c;       // tile within this source (compile-time)
         const int off = (tau * NU) % 3;
         const bool more = (tau + 1 < NT) || (src + 1 < nsrc);
-        const unsigned lc = lds_addr_rc(slot_of(src * NT + tau)), ln = lds_addr_rc(slot_of(src * NT + tau + 1));
+        const unsigned lc = lds_addr(slot_of(src * NT + tau)), ln = lds_addr(slot_of(src * NT + tau + 1));
         unsigned bc[4], bn[2];
 #pragma unroll
         for (int k = 0; k < 4; ++k) bc[k] = lc + aP[k];
@@ -564,7 +485,7 @@ __global__ __launch_bounds__(512) void k_rconv(RConvArgs a) {
           constexpr bool in_tile = u + 2 < NU;
           const bool pre = in_tile || more;
           const bool later = (u + 1 < NU) || more;
-          if (later) lgkm_wait_rc<4>(); else lgkm_wait_rc<0>();
+          if (later) lgkm_wait<4>(); else lgkm_wait<0>();
           constexpr int ia = (RTW == 4) ? 2 * (u & 1) : 0, ib = (RTW == 4) ? (u >> 1) : u;
           auto rd = [&](auto jc) {
             if (!pre) return;

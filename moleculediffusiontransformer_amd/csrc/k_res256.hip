@@ -51,81 +51,13 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
-
-#define MDT_SLOT_IDX(t) ((t) & (NS - 1))
+#include "mdt_device.h"
 
 namespace mdt {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(4))) const unsigned* cu32p;   // constant address space: scalar loads
-
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-#undef MDT_XG
-
 enum { D_W = 0, D_SKIP = 1, D_X = 2, D_XV = 3 };     // tile descriptor kinds (2 bits), aux = descriptor >> 2
-
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
-
-template <bool F32>
-__device__ __forceinline__ void split8_rs(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-template <int OFF>
-__device__ __forceinline__ void lds_read16_off(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // at most N LDS operations still in flight
-  if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <bool SHR>      // operand of the neighbouring token row (k_rconv.hip): lane i takes lane i - 1 (SHR) / i + 1, 0 at the ends
-__device__ __forceinline__ bf16x8 row_shift_rs(const bf16x8& v, bool keep) {
-  const i32x4 s = __builtin_bit_cast(i32x4, v);
-  i32x4 r;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int t = __builtin_amdgcn_update_dpp(0, s[k], SHR ? 0x111 : 0x101, 0xf, 0xf, true);
-    r[k] = keep ? t : 0;
-  }
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 constexpr int C = 256;          // channels
 constexpr int CS = 128;         // sub-tile k-width
@@ -611,7 +543,7 @@ __global__ __launch_bounds__(512) void k_res256(TFArgs a) {
         for (int r = 0; r < 4; ++r) v[4 * q + r] = mvalid ? u[r] : 0.f;
       }
       bf16x8 h, l;
-      split8_rs<F32>(v, h, l);
+      split8<F32>(v, h, l);
       *reinterpret_cast<bf16x8*>(ex + (((wave * 4 + c) * 2 + 0) * 64 + lane) * 16) = h;
       *reinterpret_cast<bf16x8*>(ex + (((wave * 4 + c) * 2 + 1) * 64 + lane) * 16) = l;
     }
@@ -658,8 +590,8 @@ __global__ __launch_bounds__(512) void k_res256(TFArgs a) {
       for (int k = 0; k < 4; ++k) {
         const int st = 4 * kh + k;
         if (NTAPS == 1 || tap == 1) { oph[k] = xh[st]; opl[k] = xl[st]; }
-        else if (tap == 0) { oph[k] = row_shift_rs<true>(xh[st], has_prev); opl[k] = row_shift_rs<true>(xl[st], has_prev); }
-        else { oph[k] = row_shift_rs<false>(xh[st], has_next_row); opl[k] = row_shift_rs<false>(xl[st], has_next_row); }
+        else if (tap == 0) { oph[k] = row_shift<true>(xh[st], has_prev); opl[k] = row_shift<true>(xl[st], has_prev); }
+        else { oph[k] = row_shift<false>(xh[st], has_next_row); opl[k] = row_shift<false>(xl[st], has_next_row); }
       }
       constexpr int LAST = NTAPS * 2 * NCL - 1;
       phase(std::integral_constant<int, (P0 + 0) % 3>{}, P0 + 0 < LAST, dl[0], oph, opl);

@@ -22,17 +22,11 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
 
 constexpr int T = 64;                    // tokens per sample
 constexpr int ROWS = T + 2;              // + one zero row on either end
@@ -42,18 +36,7 @@ __host__ __device__ constexpr int pitch32_of(int c) { return 4 * c + 16; }    //
 __host__ __device__ constexpr int ksteps_of(int c) { return c == 64 ? 6 : 2; }   // k = 3 convolution over c channels
 __host__ __device__ constexpr int rsteps_of(int c) { return c == 64 ? 2 : 1; }   // 1 x 1 convolution over c channels
 
-// +-16 / +-32 lane exchanges with the gfx950 permlane swaps (k_tblock_lw.hip), the rest of a wave sum with DPP moves
-// inside the 16-lane row: no LDS round trip per step
-#define MDT_XG(NAME, INSN)                                                               \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return a + b;                                                                        \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32")
-MDT_XG(xg32_add, "v_permlane32_swap_b32")
-#undef MDT_XG
-
+// wave sum: DPP moves inside the 16-lane row, then the +-16 / +-32 lane exchanges: no LDS round trip per step
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
   const int m = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true);
@@ -67,15 +50,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   v = dpp_add<0x140>(v);     // row_mirror
   v = xg16_add(v);
   return xg32_add(v);
-}
-
-__device__ __forceinline__ void split4(const float v[4], bf16x4& hi, bf16x4& lo) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const __bf16 h = (__bf16)v[e];
-    hi[e] = h;
-    lo[e] = (__bf16)(v[e] - (float)h);
-  }
 }
 
 __device__ __forceinline__ float silu(float t) { return t * __builtin_amdgcn_rcpf(1.0f + __expf(-t)); }

@@ -14,96 +14,14 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// streaming store: the output is consumed by the next launch (through the memory side: the per-XCD L2s are written
-// back / invalidated at every kernel boundary anyway), so it need not stay dirty in this XCD's L2 until kernel end
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-// lane-group exchanges over +-16 / +-32 lanes with the gfx950 permlane swaps (VALU, no LDS round trip). The swap is in
-// place on two registers: fed the same value twice, v_permlane16_swap leaves (rows 0,0,2,2) and (rows 1,1,3,3),
-// v_permlane32_swap (halves lo,lo) and (hi,hi); combining the two gives every lane the pair it would get from xor 16 /
-// xor 32. Written as asm: through __builtin_amdgcn_permlane*_swap hipcc 7.2 folds the two results into one register.
-// The s_nop covers the VALU-write -> permlane-swap-read hazard for the copies the compiler places just before.
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
-MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
-#undef MDT_XG
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 enum { TB_SELF = 0, TB_CROSS = 1, TB_FF = 2 };
 enum { K_T = 0, K_N = 1, K_O = 2 };   // transposed projection, un-transposed projection, output projection
-
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
-
-__device__ __forceinline__ float gelu_32(float x) {   // exact-erf GELU, branch-free erf (A&S 7.1.26, |error| < 1.5e-7)
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erfa = 1.0f - poly * __expf(-z * z);
-  return 0.5f * x * (1.0f + copysignf(erfa, x));
-}
-
-// F32 (round 6, MDT_B_WF32 for variants 2..4): the values themselves, slots 0..3 in `hi`, 4..7 in `lo` -- operands of exact fp32
-// MFMAs on fp32 fragment sub-tiles, as in k_tblock_lw.hip / k_tf256.hip
-template <bool F32>
-__device__ __forceinline__ void split8_32(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-__device__ __forceinline__ void lds_read16_32(bf16x8& dst, const unsigned char* p) {
-  const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
-}
-
-template <int OFF>      // fragment read with the (tile, plane) part of the address as immediate offset (k_tblock_lw.hip)
-__device__ __forceinline__ void lds_read16_off(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-template <int OFF>      // per-chunk bias vector from LDS, read like a fragment (k_tblock_lw.hip)
-__device__ __forceinline__ void lds_read_f4_off(f32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // at most N LDS/scalar operations still in flight
-  if constexpr (N >= 8) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-  else if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 constexpr int C = 256;          // channels
 constexpr int CS = 128;         // sub-tile width: a [64][256] projection tile is streamed as two K halves, a
@@ -121,7 +39,6 @@ constexpr bool SHARED_PROLOGUE = true;
 #endif
 
 }  // namespace
-
 
 // x[m][c] += bias[c] + sum_k part[k][m][c]  (fixed order: the result does not depend on which workgroup finished first)
 __global__ __launch_bounds__(256) void k_tb_reduce(float* x, const float* part, const float* bo, int M, int nsplit) {
@@ -381,7 +298,7 @@ __global__ __launch_bounds__(512) void k_tblock32(TBlockArgs a) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = mvalid ? (xr[st][e] - mean) * rstd : 0.f;
-      split8_32<F32>(v, xh[st], xl[st]);
+      split8<F32>(v, xh[st], xl[st]);
     }
   }
   else
@@ -474,7 +391,7 @@ __global__ __launch_bounds__(512) void k_tblock32(TBlockArgs a) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (xr[st][e] - mean) * rs;
       bf16x8 hh, ll;
-      split8_32<F32>(v, hh, ll);
+      split8<F32>(v, hh, ll);
       *reinterpret_cast<bf16x8*>(xch + (NH * fh + st) * 2048) = hh;
       *reinterpret_cast<bf16x8*>(xch + (NH * fh + st) * 2048 + 1024) = ll;
     }
@@ -665,7 +582,7 @@ __global__ __launch_bounds__(512) void k_tblock32(TBlockArgs a) {
 #pragma unroll
       for (int q = 0; q < 2; ++q)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) oT[q][r] = gelu_32(oT[q][r] + b1[q][r]);
+        for (int r = 0; r < 4; ++r) oT[q][r] = gelu(oT[q][r] + b1[q][r]);
     } else if constexpr (MODE == TB_CROSS) {
       f32x4 qT[2], bq[2];
       lds_read_f4_off<0>(bq[0], bias_l + 256 * (h - h0)); lds_read_f4_off<64>(bq[1], bias_l + 256 * (h - h0));
@@ -828,7 +745,7 @@ __global__ __launch_bounds__(512) void k_tblock32(TBlockArgs a) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = oT[e >> 2][e & 3];
-      split8_32<F32>(v, oh[0], ol[0]);
+      split8<F32>(v, oh[0], ol[0]);
     }
     phase(kO, IC1{}, kO, true, accT, oh, ol);               // output rows 0..127
     if (NX > 0 && !more) phase(kO, IC2{}, kO, true, accT + 8, oh, ol);   // the folded convolution's sub-tiles follow

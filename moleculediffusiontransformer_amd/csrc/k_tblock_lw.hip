@@ -19,100 +19,14 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 namespace mdt {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// streaming store: the output is consumed by the next launch (through the memory side: the per-XCD L2s are written
-// back / invalidated at every kernel boundary anyway), so it need not stay dirty in this XCD's L2 until kernel end
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-// lane-group exchanges over +-16 / +-32 lanes with the gfx950 permlane swaps (VALU, no LDS round trip). The swap is in
-// place on two registers: fed the same value twice, v_permlane16_swap leaves (rows 0,0,2,2) and (rows 1,1,3,3),
-// v_permlane32_swap (halves lo,lo) and (hi,hi); combining the two gives every lane the pair it would get from xor 16 /
-// xor 32. Written as asm: through __builtin_amdgcn_permlane*_swap hipcc 7.2 folds the two results into one register.
-// The s_nop covers the VALU-write -> permlane-swap-read hazard for the copies the compiler places just before.
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
-MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
-#undef MDT_XG
-
 enum { TB_SELF = 0, TB_CROSS = 1, TB_FF = 2 };
 enum { K_T = 0, K_N = 1, K_O = 2 };   // transposed projection, un-transposed projection, output projection
-
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
-
-__device__ __forceinline__ float gelu_lw(float x) {   // exact-erf GELU, branch-free erf (A&S 7.1.26, |error| < 1.5e-7)
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erfa = 1.0f - poly * __expf(-z * z);
-  return 0.5f * x * (1.0f + copysignf(erfa, x));
-}
-
-// F32 (round 5, MDT_B_WF32): the values themselves, slots 0..3 in `hi`, 4..7 in `lo` -- operands of exact fp32 MFMAs on fp32 fragment
-// tiles, as in k_tf128.hip (which grew out of this kernel and carries the same branches)
-template <bool F32>
-__device__ __forceinline__ void split8_lw(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-__device__ __forceinline__ void lds_read16(bf16x8& dst, const unsigned char* p) {
-  const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
-}
-
-// fragment read with the (tile, plane) part of the address in the instruction's immediate offset: per read there is no
-// address arithmetic left (one v_add_u32 per ds_read_b128 was 127 of the 679 instructions of a self-attention head,
-// in a kernel whose compute waves are issue-bound)
-template <int OFF>
-__device__ __forceinline__ void lds_read16_off(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-// per-head bias vectors live in LDS behind the ring and are read like fragments (asm, counted in the lgkmcnt waits): a
-// global load issued by a compute wave queues behind the loader waves' DMA traffic and stalls its issue ~60 cycles
-template <int OFF>
-__device__ __forceinline__ void lds_read_f4_off(f32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // at most N LDS/scalar operations still in flight
-  if constexpr (N >= 8) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-  else if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 constexpr int C = 128;
 constexpr int SLOT = 256 * C;   // bytes per weight tile (bf16 hi plane + lo plane)
@@ -320,7 +234,7 @@ __global__ __launch_bounds__(512) void k_tblock_lw(TBlockArgs a) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = mvalid ? (xr[st][e] - mean) * rstd : 0.f;
-      split8_lw<F32>(v, xh[st], xl[st]);
+      split8<F32>(v, xh[st], xl[st]);
     }
   }
 
@@ -528,7 +442,7 @@ __global__ __launch_bounds__(512) void k_tblock_lw(TBlockArgs a) {
 #pragma unroll
       for (int ft = 0; ft < 4; ++ft)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) oT[ft][r] = gelu_lw(oT[ft][r] + b1[ft][r]);
+        for (int r = 0; r < 4; ++r) oT[ft][r] = gelu(oT[ft][r] + b1[ft][r]);
     } else if constexpr (MODE == TB_CROSS) {
       f32x4 qT[4], bq[4];
       lds_read_f4_off<0>(bq[0], bias_l + 256 * h); lds_read_f4_off<64>(bq[1], bias_l + 256 * h);
@@ -652,7 +566,7 @@ __global__ __launch_bounds__(512) void k_tblock_lw(TBlockArgs a) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = oT[2 * sp + (e >> 2)][e & 3];
-      split8_lw<F32>(v, oh[sp], ol[sp]);
+      split8<F32>(v, oh[sp], ol[sp]);
     }
     if (NX > 0 && !more) phase(kO, IC1{}, kO, true, accT, oh, ol);   // the folded convolution's tiles follow
     else phase(kO, IC1{}, kT, more, accT, oh, ol);

@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 // This file is compiled twice: as is (split-bf16 products, launch_tf128) and through k_tf128_f32.hip with MDT_TF_F32 = 1 (the
 // exact-fp32 instantiations, launch_tf128_f32) -- two translation units that build in parallel.
@@ -50,92 +51,11 @@
 #define MDT_KV_CPOL 2
 #endif
 
-// ring slot of tile t (run-time t): a mask, not the signed modulo (7 scalar instructions per use)
-#ifdef MDT_SLOT_MOD
-#define MDT_SLOT_IDX(t) ((t) % NS)
-#else
-#define MDT_SLOT_IDX(t) ((t) & (NS - 1))
-#endif
-
 namespace mdt {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(4))) const unsigned* cu32p;   // constant address space: scalar loads
-
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
-MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
-#undef MDT_XG
-
 enum { K_T = 0, K_N = 1, K_O = 2 };   // transposed projection, un-transposed projection, output projection
-
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
-
-__device__ __forceinline__ float gelu_tf(float x) {   // exact-erf GELU, branch-free erf (A&S 7.1.26, |error| < 1.5e-7)
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erfa = 1.0f - poly * __expf(-z * z);
-  return 0.5f * x * (1.0f + copysignf(erfa, x));
-}
-
-// 8 values of one k-step -> the two 128-bit operand registers of the step.  Split-bf16 products (F32 = false): bf16 hi plane /
-// lo plane (v = hi + lo to 2^-17).  Exact fp32 products (F32 = true): the values themselves, slots e = 0..3 in `hi`, 4..7 in
-// `lo` (bit casts: the operand arrays keep one type for both instantiations; an fp32 k-step is eight 16x16x4 MFMAs, slot
-// (g, e = 4 lo + r) of the bf16 step being contraction index g of MFMA (lo, r))
-template <bool F32>
-__device__ __forceinline__ void split8_tf(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-template <int OFF>
-__device__ __forceinline__ void lds_read16_off(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-template <int OFF>
-__device__ __forceinline__ void lds_read_f4_off(f32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // at most N LDS/scalar operations still in flight
-  if constexpr (N >= 8) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-  else if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 constexpr int C = 128;
 constexpr int SLOT = 256 * C;   // bytes per weight tile (bf16 hi plane + lo plane)
@@ -146,19 +66,6 @@ constexpr int NCT = C / 16;     // 16-row tiles of the output projection
 constexpr int NU = 8;           // units (4 fragment reads + 6 MFMAs) per tile, all three kinds
 
 }  // namespace
-
-template <bool SHR>      // operand of the neighbouring token row (k_rconv.hip): lane i takes lane i - 1 (SHR) / i + 1, 0 at the ends
-__device__ __forceinline__ bf16x8 row_shift_tf(const bf16x8& v, bool keep) {
-  typedef int i32x4 __attribute__((ext_vector_type(4)));
-  const i32x4 s = __builtin_bit_cast(i32x4, v);
-  i32x4 r;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int t = __builtin_amdgcn_update_dpp(0, s[k], SHR ? 0x111 : 0x101, 0xf, 0xf, true);
-    r[k] = keep ? t : 0;
-  }
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 // NPW: LDS-DMA pieces per loader wave per K / V tile = ceil(context rows of the workgroup / 16); 0 = no cross segment
 // RES: ResNet blocks in front of the transformer (0 none, 1 single source + skip stores, 2 two sources)
@@ -493,7 +400,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = mvalid ? (accT[2 * st + (e >> 2)][e & 3] - mean) * rstd : 0.f;
-      split8_tf<F32>(v, xh[st], xl[st]);
+      split8<F32>(v, xh[st], xl[st]);
     }
   };
   // accT += vec[off + 16 ct + 4 g + r] (the sub-block's output bias: accumulators start from residual + bias)
@@ -506,7 +413,6 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
       accT[ct] = replace ? bb : accT[ct] + bb;
     }
   };
-
 
   int voff = 0;                                      // running offset into the vectors: [ResNet blocks] [to_in bias] then per
                                                      // block [bq | bo] (self), [bq | bo] (cross), [b1 | b2] (feed-forward)
@@ -581,7 +487,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[4 * hf + r] = mvalid ? u[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-u[r])) : 0.f;
         }
-        split8_tf<F32>(v, xh[st], xl[st]);
+        split8<F32>(v, xh[st], xl[st]);
       }
     };
     auto raw_operands = [&](const f32x4* src) __attribute__((always_inline)) {
@@ -590,7 +496,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = mvalid ? src[2 * st + (e >> 2)][e & 3] : 0.f;
-        split8_tf<F32>(v, xh[st], xl[st]);
+        split8<F32>(v, xh[st], xl[st]);
       }
     };
     auto set_vec = [&](f32x4* acc, const float* p, bool add) __attribute__((always_inline)) {
@@ -610,13 +516,13 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
       using A2 = std::integral_constant<int, (O0 + 1) % 3>;
       bf16x8 sh[NST], sl[NST];
 #pragma unroll
-      for (int st = 0; st < NST; ++st) { sh[st] = row_shift_tf<true>(xh[st], keep_l); sl[st] = row_shift_tf<true>(xl[st], keep_l); }
+      for (int st = 0; st < NST; ++st) { sh[st] = row_shift<true>(xh[st], keep_l); sl[st] = row_shift<true>(xl[st], keep_l); }
       phase(kT, A0{}, kT, true, acc, sh, sl);
       phase(kT, A1{}, kT, true, acc + 4, sh, sl);
       phase(kT, A2{}, kT, true, acc, xh, xl);
       phase(kT, A0{}, kT, true, acc + 4, xh, xl);
 #pragma unroll
-      for (int st = 0; st < NST; ++st) { sh[st] = row_shift_tf<false>(xh[st], keep_r); sl[st] = row_shift_tf<false>(xl[st], keep_r); }
+      for (int st = 0; st < NST; ++st) { sh[st] = row_shift<false>(xh[st], keep_r); sl[st] = row_shift<false>(xl[st], keep_r); }
       phase(kT, A1{}, kT, true, acc, sh, sl);
       phase(kT, A2{}, kT, has_next, acc + 4, sh, sl);
     };
@@ -827,7 +733,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = oT[2 * sp + (e >> 2)][e & 3];
-          split8_tf<F32>(v, oh[sp], ol[sp]);
+          split8<F32>(v, oh[sp], ol[sp]);
         }
         phase(kO, IC1{}, kT, true, accT, oh, ol);      // a tile always follows (cross / feed-forward of this block)
       }
@@ -913,7 +819,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = oT[2 * sp + (e >> 2)][e & 3];
-          split8_tf<F32>(v, oh[sp], ol[sp]);
+          split8<F32>(v, oh[sp], ol[sp]);
         }
         phase(kO, IC1{}, kT, true, accT, oh, ol);      // the feed-forward block's tiles follow
       }
@@ -944,7 +850,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
 #ifdef MDT_ABL_GELU   // timing experiment only (wrong results): what the serial GELU costs
             for (int r = 0; r < 4; ++r) oT[ft][r] = oT[ft][r] + b1[ft][r];
 #else
-            for (int r = 0; r < 4; ++r) oT[ft][r] = gelu_tf(oT[ft][r] + b1[ft][r]);
+            for (int r = 0; r < 4; ++r) oT[ft][r] = gelu(oT[ft][r] + b1[ft][r]);
 #endif
         }
         bf16x8 oh[2], ol[2];
@@ -953,7 +859,7 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = oT[2 * sp + (e >> 2)][e & 3];
-          split8_tf<F32>(v, oh[sp], ol[sp]);
+          split8<F32>(v, oh[sp], ol[sp]);
         }
         if (npost > 0 && !more) phase(kO, IC1{}, kO, true, accT, oh, ol);   // the folded convolution's tiles follow
         else phase(kO, IC1{}, kT, more || !last_blk, accT, oh, ol);

@@ -44,6 +44,7 @@
 #include <type_traits>
 
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 
 // Compiled twice: as is (split-bf16 products, launch_tf256) and through k_tf256_f32.hip with MDT_TF_F32 = 1 (exact fp32 MFMA
 // products, launch_tf256_f32) -- two translation units that build in parallel.
@@ -56,95 +57,21 @@
 #define MDT_KV_CPOL 2
 #endif
 
-// ring slot of tile t (run-time t): a mask, not the signed modulo (7 scalar instructions per use)
-#ifdef MDT_SLOT_MOD
-#define MDT_SLOT_IDX(t) ((t) % NS)
-#else
-#define MDT_SLOT_IDX(t) ((t) & (NS - 1))
-#endif
-
 namespace mdt {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(4))) const unsigned* cu32p;   // constant address space: scalar loads
-
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-#define MDT_XG(NAME, INSN, COMBINE)                                                      \
-  __device__ __forceinline__ float NAME(float v) {                                       \
-    float a = v, b = v;                                                                  \
-    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
-    return COMBINE;                                                                      \
-  }
-MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
-MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
-MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
-MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
-#undef MDT_XG
-
 enum { K_T = 0, K_N = 1, K_O = 2 };   // transposed projection, un-transposed projection, output projection
 enum { D_P = 0, D_O = 1, D_K = 2, D_V = 3, D_SCRATCH = 4, D_SCRATCH_VEC = 5 };   // tile descriptor kinds (3 bits)
 
-#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
-
-__device__ __forceinline__ float gelu_tf(float x) {   // exact-erf GELU, branch-free erf (A&S 7.1.26, |error| < 1.5e-7)
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erfa = 1.0f - poly * __expf(-z * z);
-  return 0.5f * x * (1.0f + copysignf(erfa, x));
-}
-
-// 8 values of one k-step -> its two 128-bit operand registers: bf16 hi / lo planes, or (F32) the values themselves, slots
-// 0..3 in `hi`, 4..7 in `lo` (k_tf128.hip)
-template <bool F32>
-__device__ __forceinline__ void split8_tf(const float v[8], bf16x8& hi, bf16x8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
-    }
-  }
-}
-
-template <int OFF>
-__device__ __forceinline__ void lds_read16_off(bf16x8& dst, unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-template <int OFF>
-__device__ __forceinline__ void lds_read_f4_off(f32x4& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-
+// this kernel's wait for fragment reads: lgkm_wait<N>, unless the ablation below takes it out
 template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // at most N LDS/scalar operations still in flight
+__device__ __forceinline__ void frag_wait() {
 #ifdef MDT_ABL_LGKM   // ablation (WRONG results, timing only): no wait for fragment reads -- what the waits cost
   __builtin_amdgcn_sched_barrier(0);
-  return;
+#else
+  lgkm_wait<N>();
 #endif
-  if constexpr (N >= 8) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-  else if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 constexpr int C = 256;          // channels
@@ -505,7 +432,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
           MDT_BARRIER();                // B(tau + 1)
           __builtin_amdgcn_sched_barrier(0);
         }
-        lgkm_wait<0>();                 // pair v (read during the previous half-unit) has landed
+        frag_wait<0>();                 // pair v (read during the previous half-unit) has landed
         constexpr int s0 = v & 1, s1 = (v + 1) & 1;
         constexpr bool in_phase = v + 1 < 2 * NU;
         const bool pre = in_phase || has_next;
@@ -564,7 +491,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
       constexpr bool in_phase = u + 2 < NU;
       const bool pre = in_phase || has_next;
       const bool later = (u + 1 < NU) || has_next;
-      if (later) lgkm_wait<4>(); else lgkm_wait<0>();
+      if (later) frag_wait<4>(); else frag_wait<0>();
       constexpr int ia = (KIND == K_O) ? 2 * u : 0, ib = (KIND == K_O) ? 0 : u;
       auto rd = [&](auto jc) {
         if (!pre) return;
@@ -708,7 +635,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = mvalid ? (accT[2 * st + (e >> 2)][e & 3] - mean) * rstd : 0.f;
-      split8_tf<F32>(v, xh[st], xl[st]);
+      split8<F32>(v, xh[st], xl[st]);
     }
   };
   // start of a sub-block: wave fh = 0 carries residual + output bias (or the bias alone), wave fh = 1 starts from zero
@@ -947,7 +874,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         {
           f32x4 bq[2];
           lds_read_f4_off<0>(bq[0], bl + 256 * h); lds_read_f4_off<64>(bq[1], bl + 256 * h);
-          lgkm_wait<0>();
+          frag_wait<0>();
           qT[0] += bq[0];
           qT[1] += bq[1];
         }
@@ -998,7 +925,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = oT[e >> 2][e & 3];
-          split8_tf<F32>(v, oh[0], ol[0]);
+          split8<F32>(v, oh[0], ol[0]);
         }
         MDT_HSTAMP();                                           // attention core done
         phase(kO, IC1{}, kO, true, accT, oh, ol);               // output rows 0..127
@@ -1028,7 +955,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         {
           f32x4 bq[2];
           lds_read_f4_off<0>(bq[0], bl + 256 * h); lds_read_f4_off<64>(bq[1], bl + 256 * h);
-          lgkm_wait<0>();
+          frag_wait<0>();
           qT[0] += bq[0];
           qT[1] += bq[1];
         }
@@ -1112,7 +1039,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = oT[e >> 2][e & 3];
-          split8_tf<F32>(v, oh[0], ol[0]);
+          split8<F32>(v, oh[0], ol[0]);
         }
         phase(kO, IC1{}, kO, true, accT, oh, ol);
         phase(kO, IC2{}, kT, more, accT + 8, oh, ol);
@@ -1138,18 +1065,18 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         {
           f32x4 b1[2];
           lds_read_f4_off<0>(b1[0], bl + 256 * h); lds_read_f4_off<64>(b1[1], bl + 256 * h);
-          lgkm_wait<0>();
+          frag_wait<0>();
 #pragma unroll
           for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) oT[q][r] = gelu_tf(oT[q][r] + b1[q][r]);
+            for (int r = 0; r < 4; ++r) oT[q][r] = gelu(oT[q][r] + b1[q][r]);
         }
         bf16x8 oh[1], ol[1];
         {
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = oT[e >> 2][e & 3];
-          split8_tf<F32>(v, oh[0], ol[0]);
+          split8<F32>(v, oh[0], ol[0]);
         }
         phase(kO, IC1{}, kO, true, accT, oh, ol);
         if (npost > 0 && !more) phase(kO, IC2{}, kO, true, accT + 8, oh, ol);   // the folded convolution's sub-tiles follow

@@ -1,0 +1,145 @@
+// Device primitives shared by the ring and block kernels (k_tblock_lw, k_tblock32, k_tf128, k_tf256, k_rconv, k_res256, k_proj,
+// k_resblock, k_attn): vector types, MFMA names, lane-group exchanges, operand splits, counted LDS reads and their waits.
+// Device code only; included by the .hip files that use it, never through mdt_kernels.h (mdt_api.cpp does not see it).
+// Everything is __forceinline__: a kernel's code object does not depend on whether a primitive is defined here or in its file.
+// The rule: a primitive used by two kernels lives here, once, with its rationale; what one kernel alone uses stays in its file.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
+#define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
+
+// ring slot of tile t (run-time t; NS = the including file's slot count, a power of two): a mask, not the signed modulo
+// (7 scalar instructions per use)
+#ifdef MDT_SLOT_MOD
+#define MDT_SLOT_IDX(t) ((t) % NS)
+#else
+#define MDT_SLOT_IDX(t) ((t) & (NS - 1))
+#endif
+
+namespace mdt {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) const unsigned* cu32p;   // constant address space: scalar loads
+
+// streaming store: the output is consumed by the next launch (through the memory side: the per-XCD L2s are written
+// back / invalidated at every kernel boundary anyway), so it need not stay dirty in this XCD's L2 until kernel end
+__device__ __forceinline__ void store_nt(float* p, float4 v) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
+}
+
+// lane-group exchanges over +-16 / +-32 lanes with the gfx950 permlane swaps (VALU, no LDS round trip). The swap is in
+// place on two registers: fed the same value twice, v_permlane16_swap leaves (rows 0,0,2,2) and (rows 1,1,3,3),
+// v_permlane32_swap (halves lo,lo) and (hi,hi); combining the two gives every lane the pair it would get from xor 16 /
+// xor 32. Written as asm: through __builtin_amdgcn_permlane*_swap hipcc 7.2 folds the two results into one register.
+// The s_nop covers the VALU-write -> permlane-swap-read hazard for the copies the compiler places just before.
+#define MDT_XG(NAME, INSN, COMBINE)                                                      \
+  __device__ __forceinline__ float NAME(float v) {                                       \
+    float a = v, b = v;                                                                  \
+    asm("s_nop 1\n\t" INSN " %0, %1" : "+v"(a), "+v"(b));                                \
+    return COMBINE;                                                                      \
+  }
+MDT_XG(xg16_add, "v_permlane16_swap_b32", a + b)
+MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
+MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
+MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
+#undef MDT_XG
+
+__device__ __forceinline__ float gelu(float x) {   // exact-erf GELU, branch-free erf (A&S 7.1.26, |error| < 1.5e-7)
+  const float z = fabsf(x) * 0.70710678118654752440f;
+  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
+  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+  const float erfa = 1.0f - poly * __expf(-z * z);
+  return 0.5f * x * (1.0f + copysignf(erfa, x));
+}
+
+// SiLU as the tiled GEMMs' prologues apply it: full-precision division and expf (the fused block kernels keep their own
+// v_rcp / __expf form)
+__device__ __forceinline__ float silu_exact(float x) { return x / (1.0f + expf(-x)); }
+
+// 8 values of one k-step -> the two 128-bit operand registers of the step.  Split-bf16 products (F32 = false): bf16 hi plane /
+// lo plane (v = hi + lo to 2^-17).  Exact fp32 products (F32 = true): the values themselves, slots e = 0..3 in `hi`, 4..7 in
+// `lo` (bit casts: the operand arrays keep one type for both instantiations; an fp32 k-step is eight 16x16x4 MFMAs, slot
+// (g, e = 4 lo + r) of the bf16 step being contraction index g of MFMA (lo, r))
+template <bool F32>
+__device__ __forceinline__ void split8(const float v[8], bf16x8& hi, bf16x8& lo) {
+  if constexpr (F32) {
+    hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
+    lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const __bf16 h = (__bf16)v[e];
+      hi[e] = h;
+      lo[e] = (__bf16)(v[e] - (float)h);
+    }
+  }
+}
+
+// 4 values -> their bf16 hi / lo planes (8-byte LDS writes of an activation row)
+__device__ __forceinline__ void split4(const float v[4], bf16x4& hi, bf16x4& lo) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const __bf16 h = (__bf16)v[e];
+    hi[e] = h;
+    lo[e] = (__bf16)(v[e] - (float)h);
+  }
+}
+
+__device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
+}
+
+// 16-byte LDS read, whole address in the register.  The reads are asm volatile: they stay where they are written, between
+// the MFMAs that hide them, and the kernels count them themselves (lgkm_wait)
+__device__ __forceinline__ void lds_read16(bf16x8& dst, const unsigned char* p) {
+  const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
+}
+
+// fragment read with the (tile, plane) part of the address in the instruction's immediate offset: per read there is no
+// address arithmetic left (one v_add_u32 per ds_read_b128 was 127 of the 679 instructions of a self-attention head,
+// in a kernel whose compute waves are issue-bound)
+template <int OFF>
+__device__ __forceinline__ void lds_read16_off(bf16x8& dst, unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds_read_b128 offset field");
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+
+// per-head bias vectors live in LDS behind the ring and are read like fragments (asm, counted in the lgkmcnt waits): a
+// global load issued by a compute wave queues behind the loader waves' DMA traffic and stalls its issue ~60 cycles
+template <int OFF>
+__device__ __forceinline__ void lds_read_f4_off(f32x4& dst, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+
+// at most N LDS/scalar operations still in flight; the sched_barrier keeps the compiler from moving the MFMAs that
+// consume the awaited fragments across the wait.  Two tiers, the two that the kernels use.
+template <int N>
+__device__ __forceinline__ void lgkm_wait() {
+  static_assert(N == 0 || N == 4, "lgkm_wait has the tiers lgkmcnt(0) and lgkmcnt(4) only");
+  if constexpr (N >= 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
+  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// operand of the neighbouring token row: lane i takes lane i - 1 (SHR) or i + 1 inside its 16-lane row, 0 at the ends
+// (DPP row_shr / row_shl with zero fill); keep = false also zeroes it (sample boundaries inside the row)
+template <bool SHR>
+__device__ __forceinline__ bf16x8 row_shift(const bf16x8& v, bool keep) {
+  const i32x4 s = __builtin_bit_cast(i32x4, v);
+  i32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int t = __builtin_amdgcn_update_dpp(0, s[k], SHR ? 0x111 : 0x101, 0xf, 0xf, true);
+    r[k] = keep ? t : 0;
+  }
+  return __builtin_bit_cast(bf16x8, r);
+}
+
+}  // namespace mdt
