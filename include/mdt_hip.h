@@ -601,7 +601,8 @@ enum mdt_screen_status {
   MDT_SCREEN_EMPTY = 1,     /* length == 0 */
   MDT_SCREEN_NONFINITE = 2, /* the score is a NaN or an infinity */
   MDT_SCREEN_DUPLICATE = 4, /* a candidate c' < c of the same group holds the same molecule (whatever the status of c') */
-  MDT_SCREEN_KNOWN = 8      /* the molecule is in the known set */
+  MDT_SCREEN_KNOWN = 8,     /* the molecule is in the known set (mdt_screen_select_diverse: or closer to it than min_novelty) */
+  MDT_SCREEN_CLOSE = 16     /* mdt_screen_select_diverse only: closer than min_distance to a better candidate that was kept */
 };
 /* Per group g: status uint8 (N*G) of every candidate; index int32 (G,K): the eligible (status == 0) candidates c in ascending
  * order of (score, c) -- ties go to the lower c -- and -1 in the slots beyond count[g] = min(K, number of eligible candidates).
@@ -612,6 +613,41 @@ enum mdt_screen_status {
 int mdt_screen_select(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L, int32_t N,
                       int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len, int32_t M,
                       int32_t K, uint8_t *status, int32_t *index, int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* edit distance between molecules (csrc/k_edit.hip, csrc/k_screen.hip); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* The global Levenshtein distance (insert, delete, substitute: 1 each) between compacted rows a[0:la] and b[0:lb] as
+ * mdt_tokens_compact writes them, of width 1 <= L <= 64 (one 64-bit word of Myers' / Hyyro's bit-vector recurrence per pair;
+ * wider rows are out of scope).  Lengths are clamped to [0, L].  Ids are expected in [0, 64): an id outside that range matches
+ * NOTHING, not even itself (the callers of the Python layer refuse such ids before any launch).  An empty row lies at the other
+ * row's length.  R == 0: nothing is launched, 0 is returned. */
+/* dist[r] (int32) = distance of row r of a to row r of b; a_packed, b_packed int32 (R,L), a_len, b_len int32 (R). */
+int mdt_edit_distance_rows(const int32_t *a_packed, const int32_t *a_len, const int32_t *b_packed, const int32_t *b_len, int32_t L,
+                           int32_t R, int32_t *dist, void *stream);
+/* The known rows that one workgroup of mdt_edit_nearest walks; the known set is split into chunks of this many over the grid. */
+#define MDT_EDIT_KNOWN_CHUNK 512
+/* Per query row r of packed (R,L): dist[r] = the smallest distance to any of the M >= 1 known rows (known_packed int32 (M,L),
+ * known_len int32 (M); any order, no keys), index[r] = the LOWEST known index that attains it.  The chunks' results are combined as
+ * the minimum of (distance << 32) | index, one unsigned 64-bit word per query, which is the same in any order: the result does not
+ * depend on how the work is split or scheduled.  best: workspace of R 64-bit words, allocated by the caller, contents irrelevant
+ * before and after.  R <= 65535 * 64. */
+int mdt_edit_nearest(const int32_t *packed, const int32_t *length, int32_t L, int32_t R, const int32_t *known_packed,
+                     const int32_t *known_len, int32_t M, uint64_t *best, int32_t *dist, int32_t *index, void *stream);
+/* mdt_screen_select with novelty and distinctness measured in edits; 1 <= L <= 64, the other limits as there.
+ *  1. Bits 1, 2, 4 as mdt_screen_select.  Bit 8 (KNOWN): the known-set test of mdt_screen_select (when M > 0), or
+ *     known_dist != NULL and known_dist[r] < min_novelty (known_dist int32 (N*G), e.g. mdt_edit_nearest's dist).
+ *  2. The eligible (status == 0) candidates of a group in ascending order of (score, c).  In that order a candidate is KEPT when its
+ *     distance to every candidate kept before it is >= min_distance, until K are kept: index[g,:] holds the kept candidates in the
+ *     order they were kept, -1 after them, count[g] their number.
+ *  3. Bit 16 (CLOSE) on every eligible candidate that was not kept and lies closer than min_distance to a kept candidate that
+ *     precedes it in the order -- wherever the K-th was kept.  Kept rows stay 0; a row with one of bits 1..8 never gets bit 16.
+ * min_distance <= 1 filters nothing (distinct rows lie 1 apart); with known_dist == NULL as well, the three outputs are
+ * mdt_screen_select's bit for bit. */
+int mdt_screen_select_diverse(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len,
+                              int32_t M, int32_t K, const int32_t *known_dist, int32_t min_novelty, int32_t min_distance,
+                              uint8_t *status, int32_t *index, int32_t *count, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

@@ -6,6 +6,7 @@
 //                      forward model's input (generative.py:425-429 on ids: tokens_to_forward_input)
 //   k_screen_score     weighted mean squared distance of the re-predicted properties from the group's target
 //   k_screen_select    per group: status bits (empty / non-finite / duplicate / known) and the K best eligible candidates
+//   k_screen_select_diverse   the same with novelty as a distance and the K best that lie min_distance edits apart
 //
 // Rows are r = c * G + g: candidate c of group g (a group is one target conditioning), the layout of guidance_sweep.
 // A molecule IS its compacted id row (the reference's string: a character-level tokenizer, id 0 skipped), so equality is decided
@@ -13,6 +14,7 @@
 //
 // Built with -ffp-contract=off: the score keeps separate fp32 multiplies and adds, so a numpy fp32 loop reproduces it.
 #include "mdt_kernels.h"
+#include "mdt_device.h"
 #include "../../include/mdt_hip.h"
 
 #include <climits>
@@ -96,6 +98,37 @@ __device__ __forceinline__ bool same_row(const int32_t* a, const int32_t* b, int
   return true;
 }
 
+// Status bits 1, 2, 4, 8 of candidate c of group g (mdt_hip.h); s_key, s_score, s_len hold the group's N candidates.
+__device__ __forceinline__ int candidate_status(int c, int g, int G, int L, const uint64_t* s_key, const float* s_score,
+                                                const int32_t* s_len, const int32_t* __restrict__ packed,
+                                                const uint64_t* __restrict__ known_key, const int32_t* __restrict__ known_packed,
+                                                const int32_t* __restrict__ known_len, int M) {
+  const uint64_t k = s_key[c];
+  const int len = s_len[c];
+  const int32_t* row = packed + ((int64_t)c * G + g) * L;
+  int st = 0;
+  if (len == 0) st |= MDT_SCREEN_EMPTY;
+  if (!isfinite(s_score[c])) st |= MDT_SCREEN_NONFINITE;
+  for (int o = 0; o < c; ++o)                                  // the first occurrence stands for the molecule
+    if (s_key[o] == k && s_len[o] == len && same_row(row, packed + ((int64_t)o * G + g) * L, len)) {
+      st |= MDT_SCREEN_DUPLICATE;
+      break;
+    }
+  if (M > 0) {
+    int lo = 0, hi = M;                                        // lower bound of k in known_key (ascending)
+    while (lo < hi) {
+      const int mid = lo + (hi - lo) / 2;
+      if (known_key[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    for (int i = lo; i < M && known_key[i] == k; ++i)          // the whole run of equal keys
+      if (known_len[i] == len && same_row(row, known_packed + (int64_t)i * L, len)) {
+        st |= MDT_SCREEN_KNOWN;
+        break;
+      }
+  }
+  return st;
+}
+
 // One workgroup of 256 per group; the group's keys, scores, lengths and status bytes sit in LDS (17 KiB at N = 1024).
 __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__ score, const uint64_t* __restrict__ key,
                                                        const int32_t* __restrict__ packed, const int32_t* __restrict__ length, int L,
@@ -123,29 +156,7 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
 
   int mine = 0;
   for (int c = tid; c < N; c += 256) {
-    const uint64_t k = s_key[c];
-    const int len = s_len[c];
-    const int32_t* row = packed + ((int64_t)c * G + g) * L;
-    int st = 0;
-    if (len == 0) st |= MDT_SCREEN_EMPTY;
-    if (!isfinite(s_score[c])) st |= MDT_SCREEN_NONFINITE;
-    for (int o = 0; o < c; ++o)                                  // the first occurrence stands for the molecule
-      if (s_key[o] == k && s_len[o] == len && same_row(row, packed + ((int64_t)o * G + g) * L, len)) {
-        st |= MDT_SCREEN_DUPLICATE;
-        break;
-      }
-    if (M > 0) {
-      int lo = 0, hi = M;                                        // lower bound of k in known_key (ascending)
-      while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (known_key[mid] < k) lo = mid + 1; else hi = mid;
-      }
-      for (int i = lo; i < M && known_key[i] == k; ++i)          // the whole run of equal keys
-        if (known_len[i] == len && same_row(row, known_packed + (int64_t)i * L, len)) {
-          st |= MDT_SCREEN_KNOWN;
-          break;
-        }
-    }
+    const int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
     s_status[c] = (uint8_t)st;
     status[(int64_t)c * G + g] = (uint8_t)st;
     mine += st == 0;
@@ -164,6 +175,102 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
   }
   for (int k = filled + tid; k < K; k += 256) index[(int64_t)g * K + k] = -1;
   if (tid == 0) count[g] = filled;
+}
+
+// k_screen_select with two filters on the edit distance (mdt_device.h; rows of at most 64 ids below 64).  Status and order as
+// above; then ONE pass over the eligible candidates in that order: a candidate closer than min_distance to a candidate kept before
+// it is CLOSE, any other is kept while slots are left.  The pass runs to the end of the order, so the CLOSE bit of a candidate does
+// not depend on where the slots ran out.  Inside a step the candidate is the pattern -- its 64 match masks in LDS, read by every
+// thread at the same address -- and the threads share out the kept rows as texts; one block-wide "any closer".
+__global__ __launch_bounds__(256) void k_screen_select_diverse(
+    const float* __restrict__ score, const uint64_t* __restrict__ key, const int32_t* __restrict__ packed,
+    const int32_t* __restrict__ length, int L, int N, int G, const uint64_t* __restrict__ known_key,
+    const int32_t* __restrict__ known_packed, const int32_t* __restrict__ known_len, int M, int K,
+    const int32_t* __restrict__ known_dist, int min_novelty, int min_distance, uint8_t* __restrict__ status,
+    int32_t* __restrict__ index, int32_t* __restrict__ count) {
+  __shared__ uint64_t s_key[kScreenMaxN];
+  __shared__ float s_score[kScreenMaxN];
+  __shared__ int32_t s_len[kScreenMaxN];
+  __shared__ uint8_t s_status[kScreenMaxN];
+  __shared__ int32_t s_order[kScreenMaxN];
+  __shared__ int32_t s_kept[kScreenMaxN];
+  __shared__ unsigned long long s_peq[64];
+  __shared__ int s_eligible;
+  const int g = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_eligible = 0;
+  for (int c = tid; c < N; c += 256) {
+    const int64_t r = (int64_t)c * G + g;
+    s_key[c] = key[r];
+    s_score[c] = score[r];
+    const int len = length[r];
+    s_len[c] = len < 0 ? 0 : (len > L ? L : len);
+  }
+  __syncthreads();
+
+  int mine = 0;
+  for (int c = tid; c < N; c += 256) {
+    int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
+    if (known_dist && known_dist[(int64_t)c * G + g] < min_novelty) st |= MDT_SCREEN_KNOWN;
+    s_status[c] = (uint8_t)st;
+    status[(int64_t)c * G + g] = (uint8_t)st;
+    mine += st == 0;
+  }
+  if (mine) atomicAdd(&s_eligible, mine);
+  __syncthreads();
+
+  const int eligible = s_eligible;
+  for (int c = tid; c < N; c += 256) {
+    if (s_status[c]) continue;
+    const float sc = s_score[c];
+    int rank = 0;
+    for (int o = 0; o < N; ++o)
+      rank += s_status[o] == 0 && (s_score[o] < sc || (s_score[o] == sc && o < c));
+    s_order[rank] = c;                                           // (the ranks of the eligible are 0 .. eligible - 1, each once)
+  }
+  __syncthreads();
+
+  int kept = 0;                                                  // (the same in every thread)
+  for (int e = 0; e < eligible; ++e) {
+    const int c = s_order[e];
+    const int m = s_len[c];                                      // >= 1: an empty row is not eligible
+    int closer = 0;
+    if (min_distance > 1 && kept > 0) {
+      const int32_t* row = packed + ((int64_t)c * G + g) * L;
+      if (tid < 64) {                                            // the mask of symbol tid
+        unsigned long long bits = 0;
+        for (int j = 0; j < m; ++j) bits |= (unsigned long long)(row[j] == tid) << j;
+        s_peq[tid] = bits;
+      }
+      __syncthreads();
+      const unsigned long long top = edit_top(m);
+      for (int t = tid; t < kept && !closer; t += 256) {
+        const int o = s_kept[t];
+        const int n = s_len[o];
+        const int32_t* text = packed + ((int64_t)o * G + g) * L;
+        unsigned long long pv = ~0ull, mv = 0;
+        int d = m;
+        for (int j = 0; j < n; ++j) {
+          const int id = text[j];
+          const unsigned long long eq = s_peq[id & 63];
+          d += edit_step(edit_has_mask(id) ? eq : 0ull, top, pv, mv);
+        }
+        closer = d < min_distance;
+      }
+    }
+    closer = __syncthreads_or(closer);                           // (also: s_peq and s_kept are free to be written again)
+    if (closer) {
+      if (tid == 0) status[(int64_t)c * G + g] = MDT_SCREEN_CLOSE;
+    } else if (kept < K) {
+      if (tid == 0) {
+        s_kept[kept] = c;
+        index[(int64_t)g * K + kept] = c;
+      }
+      ++kept;
+    }
+  }
+  for (int k = kept + tid; k < K; k += 256) index[(int64_t)g * K + k] = -1;
+  if (tid == 0) count[g] = kept;
 }
 
 }  // namespace mdt
@@ -232,6 +339,23 @@ int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* pa
   hipLaunchKernelGGL(mdt::k_screen_select, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
                      known_key, known_packed, known_len, M, K, status, index, count);
   return finish("mdt_screen_select");
+}
+
+int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
+                              int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty, int32_t min_distance,
+                              uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+  if (G <= 0) return 0;
+  if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select_diverse: need 1 <= N <= 1024 candidates per group");
+  if (K < 1 || K > N) return bad("mdt_screen_select_diverse: need 1 <= K <= N");
+  if (L < 1 || L > 64) return bad("mdt_screen_select_diverse: need 1 <= L <= 64 (the edit distance takes rows of one 64-bit word)");
+  if (M < 0) return bad("mdt_screen_select_diverse: need M >= 0");
+  if (M > 0 && (!known_key || !known_packed || !known_len))
+    return bad("mdt_screen_select_diverse: the known-set pointers may be NULL only when M == 0");
+  if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select_diverse: null pointer");
+  hipLaunchKernelGGL(mdt::k_screen_select_diverse, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length,
+                     L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, status, index, count);
+  return finish("mdt_screen_select_diverse");
 }
 
 }  // extern "C"

@@ -142,4 +142,29 @@ __device__ __forceinline__ bf16x8 row_shift(const bf16x8& v, bool keep) {
   return __builtin_bit_cast(bf16x8, r);
 }
 
+// Levenshtein distance by Hyyro's form of Myers' bit-vector recurrence (k_edit, k_screen): the pattern a[0:m], 1 <= m <= 64, is
+// the match masks Peq[s] (bit j set when a[j] == s); column after column of the dynamic programme is then one text symbol each.
+// State: pv = ~0, mv = 0, distance = m; per text symbol  distance += edit_step(Peq[symbol], edit_top(m), pv, mv).
+// An id outside [0, 64) has no mask: the caller passes eq = 0 for it (edit_has_mask), so it matches nothing, itself included.
+// Bits above m - 1 never reach the bits below them (carries and shifts go upwards), so no mask of the low m bits is needed and
+// m == 64 shifts by nothing: the only place the length enters is the probe bit.  m == 0 has no probe bit: edit_top gives 0, the
+// steps count nothing, and the caller takes the text's length as the distance.
+__device__ __forceinline__ unsigned long long edit_top(int m) { return m > 0 ? 1ull << (m - 1) : 0ull; }
+
+__device__ __forceinline__ bool edit_has_mask(int id) { return (unsigned)id < 64u; }
+
+__device__ __forceinline__ int edit_step(unsigned long long eq, unsigned long long top, unsigned long long& pv,
+                                         unsigned long long& mv) {
+  const unsigned long long xv = eq | mv;
+  const unsigned long long xh = (((eq & pv) + pv) ^ pv) | eq;
+  unsigned long long ph = mv | ~(xh | pv);
+  unsigned long long mh = pv & xh;
+  const int delta = (int)((ph & top) != 0) - (int)((mh & top) != 0);
+  ph = (ph << 1) | 1ull;                                          // (the top boundary row of a GLOBAL distance grows by one a column)
+  mh <<= 1;
+  pv = mh | ~(xv | ph);
+  mv = ph & xv;
+  return delta;
+}
+
 }  // namespace mdt

@@ -869,6 +869,8 @@ def refine_and_validate(model: "QMDiffusion", model_forward: "QMDiffusionForward
 MAX_CANDIDATES = 1024           # mdt_screen_select's limits (include/mdt_hip.h)
 MAX_SCREEN_LENGTH = 1024
 MAX_SCREEN_PROPERTIES = 64
+MAX_EDIT_LENGTH = 64            # the edit distance (csrc/k_edit.hip): one 64-bit word per row, one mask per id
+MAX_EDIT_ID = 64
 
 
 def _integer_ids(ids, name: str):
@@ -932,6 +934,7 @@ class KnownSet:
         self.lengths = np.ascontiguousarray(lengths[by_key].astype(np.int32))
         self.key = np.ascontiguousarray(key[by_key])
         self._on = {}
+        self._id_range = None
 
     def __len__(self) -> int:
         return int(self.key.shape[0])
@@ -947,6 +950,12 @@ class KnownSet:
                                 torch.from_numpy(self.lengths).to(device))
         return self._on[device]
 
+    def id_range(self):
+        """(lowest, highest) id of the set, looked up once on the host arrays; (0, 0) for an empty set."""
+        if self._id_range is None:
+            self._id_range = (int(self.packed.min()), int(self.packed.max())) if self.packed.size else (0, 0)
+        return self._id_range
+
 
 class Screened(NamedTuple):
     """screen_tokens' result, G groups (targets), K = ``keep`` slots per group in ascending order of score."""
@@ -955,7 +964,8 @@ class Screened(NamedTuple):
     score: Tensor      # (G, K): the weighted mean squared distance from the target; +inf in unfilled slots
     index: Tensor      # (G, K) int64: the candidate c (row c * G + g of the input); -1 in unfilled slots
     count: Tensor      # (G,) int64: filled slots = min(K, eligible candidates)
-    status: Tensor     # (N, G) uint8: 1 empty | 2 non-finite score | 4 duplicate of a lower c | 8 in the known set
+    status: Tensor     # (N, G) uint8: 1 empty | 2 non-finite score | 4 duplicate of a lower c | 8 in the known set (or closer to
+    #                    it than min_novelty) | 16 closer than min_distance to a better kept candidate (screen_tokens_diverse)
 
 
 def _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=None, length=None):
@@ -996,6 +1006,86 @@ def _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=N
     return weights, known_tokens
 
 
+def _edit_width(length: int, what: str) -> None:
+    if length > MAX_EDIT_LENGTH:
+        raise ValueError(f"{what} has rows of {length} positions; the edit distance takes at most {MAX_EDIT_LENGTH} "
+                         "(multi-word rows are out of scope)")
+
+
+def _edit_ids(ids, what: str):
+    """Refuses ids outside [0, MAX_EDIT_ID): one aminmax, the one host synchronisation of the edit-distance paths."""
+    t = torch.as_tensor(ids)
+    if t.numel():
+        lo, hi = (int(v) for v in torch.aminmax(t))
+        if lo < 0 or hi >= MAX_EDIT_ID:
+            raise ValueError(f"{what} holds ids from {lo} to {hi}; the edit distance takes ids in [0, {MAX_EDIT_ID})")
+    return t
+
+
+def _edit_known(known: "KnownSet") -> None:
+    lo, hi = known.id_range()
+    if lo < 0 or hi >= MAX_EDIT_ID:
+        raise ValueError(f"known_tokens holds ids from {lo} to {hi}; the edit distance takes ids in [0, {MAX_EDIT_ID})")
+
+
+def _diverse_args(min_distance, min_novelty, known, length=None, tokens=None) -> bool:
+    """The refusals of the two edit-distance filters, before anything is launched; ``length`` or the ``tokens`` themselves, as
+    _screen_args.  -> whether either filter is on (if neither is, nothing is looked at)."""
+    for name, v in (("min_distance", min_distance), ("min_novelty", min_novelty)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if min_distance == 1 and min_novelty == 1:
+        return False
+    if tokens is not None:
+        tokens = torch.as_tensor(tokens)
+        length = tokens.shape[1]
+    _edit_width(length, "tokens")
+    if min_novelty > 1:
+        if known is None or len(known) == 0:
+            raise ValueError(f"min_novelty = {min_novelty} asks for the distance to the known set: give a non-empty known_tokens")
+        _edit_known(known)
+    if tokens is not None:
+        _edit_ids(tokens, "tokens")
+    return True
+
+
+def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
+            forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
+            min_novelty=1) -> Screened:
+    """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch."""
+    weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
+    diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
+    device = torch.device(device)
+    N, K = candidates, keep
+    G, n = conditioning.shape
+    tok = torch.as_tensor(tokens).to(device)
+    if n > model_forward.max_length:
+        raise ValueError(f"conditioning holds {n} properties, the forward model predicts {model_forward.max_length} positions")
+    packed, length, key, data = torch.ops.mdt.tokens_compact(tok, model_forward.max_length, float(X_norm_factor))
+    result = model_forward.sample(data, device, cond_scale=1.0, timesteps=forward_timesteps, clamp=False, noise=forward_noise,
+                                  sampler=sampler, sigma_schedule=sigma_schedule)
+    target = conditioning.detach().to(device=device, dtype=torch.float32)
+    score = torch.ops.mdt.screen_score(result, target, None if weights is None else weights.to(device), N)
+    kk, kp, kl = known.on(device) if known is not None and len(known) else (None, None, None)
+    if not diverse:
+        status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
+    else:
+        known_dist = None
+        if min_novelty > 1:                                      # novelty as a distance: the nearest known row of every candidate
+            known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
+            kk = kp = kl = None
+        status, index, count = torch.ops.mdt.screen_select_diverse(score, key, packed, length, N, K, kk, kp, kl, known_dist,
+                                                                   min_novelty, min_distance)
+    index = index.long()
+    filled = index >= 0
+    rows = index.clamp(min=0) * G + torch.arange(G, device=device).unsqueeze(1)
+    props = result.reshape(N * G, -1)[:, :n]
+    return Screened(tokens=torch.where(filled.unsqueeze(2), tok.long()[rows], 0),
+                    props=torch.where(filled.unsqueeze(2), props[rows], float("nan")),
+                    score=torch.where(filled, score[rows], float("inf")),
+                    index=index, count=count.long(), status=status.view(N, G))
+
+
 def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int, keep: int, *,
                   known_tokens=None, weights=None, forward_timesteps: int = 100, X_norm_factor: float = 1.0, forward_noise=None,
                   sampler=None, sigma_schedule=None) -> Screened:
@@ -1014,50 +1104,102 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
     mdt::screen_score -> mdt::screen_select -> a gather.  Of equal molecules in a group the lowest c stands for all; ties in the
     score go to the lower c.  Returns Screened; the reference's "fraction of novel structures" is
     ``((status & 8) == 0).float().mean()``."""
-    weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
+    return _screen(model_forward, tokens, conditioning, device, candidates, keep, known_tokens=known_tokens, weights=weights,
+                   forward_timesteps=forward_timesteps, X_norm_factor=X_norm_factor, forward_noise=forward_noise, sampler=sampler,
+                   sigma_schedule=sigma_schedule)
+
+
+def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
+                          keep: int, *, min_distance: int = 1, min_novelty: int = 1, **screen_tokens_kwargs) -> Screened:
+    """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
+    (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings.
+
+    ``min_distance``: the K kept molecules of a target lie at least this many edits apart.  The eligible candidates are taken in
+    (score, c) order; one that is closer than ``min_distance`` to a candidate kept before it is passed over and gets status bit 16
+    (runtime.SCREEN_CLOSE), so ``count`` may stay below K although eligible candidates are left.  1: distinct rows, as screen_tokens.
+    ``min_novelty``: a candidate closer than this many edits to ANY molecule of ``known_tokens`` counts as known: status bit 8 then
+    means "within min_novelty - 1 edits of the known set" (1: "in the known set", the hash lookup of screen_tokens), and the
+    reference's "fraction of novel structures" stays ``((status & 8) == 0).float().mean()``.  Above 1 it needs a non-empty known
+    set and runs mdt::edit_nearest once over all N * G rows.
+    Both are ints >= 1; (1, 1) is screen_tokens itself, the same launches in the same order.  Either above 1 routes the selection to
+    mdt::screen_select_diverse and needs rows of at most 64 positions and ids in [0, 64), in the tokens (one aminmax: the one host
+    synchronisation added) and in the known set (checked once per KnownSet) -- all refused with ValueError before anything is
+    launched.  Rows of more than one 64-bit word are out of scope.  Returns Screened, its six fields as screen_tokens'."""
+    return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
+                   **screen_tokens_kwargs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
+# ----------------------------------------------------------------------------------------------------------------------
+def edit_distance(a_tokens, b_tokens, device) -> Tensor:
+    """The Levenshtein distance (insert, delete, substitute: 1 each) between the molecules of ``a_tokens`` and ``b_tokens``, row by
+    row: int64 (R,).  Both are raw (R, L) ids of any integer dtype and the same shape, zeros anywhere -- a molecule is its compacted
+    id row, as in screen_tokens.  L <= 64 and ids in [0, 64) (one 64-bit word per pair; wider rows are out of scope), refused
+    with ValueError before anything is launched.  Sequence: mdt::tokens_compact twice -> mdt::edit_distance."""
+    a, b = _integer_ids(a_tokens, "a_tokens"), _integer_ids(b_tokens, "b_tokens")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"a_tokens {tuple(a.shape)} and b_tokens {tuple(b.shape)} must have the same shape")
+    if a.shape[1] < 1:
+        raise ValueError("a_tokens must hold at least one position per row")
+    _edit_width(a.shape[1], "a_tokens")
+    a, b = _edit_ids(a, "a_tokens"), _edit_ids(b, "b_tokens")
     device = torch.device(device)
-    N, K = candidates, keep
-    G, n = conditioning.shape
-    tok = torch.as_tensor(tokens).to(device)
-    if n > model_forward.max_length:
-        raise ValueError(f"conditioning holds {n} properties, the forward model predicts {model_forward.max_length} positions")
-    packed, length, key, data = torch.ops.mdt.tokens_compact(tok, model_forward.max_length, float(X_norm_factor))
-    result = model_forward.sample(data, device, cond_scale=1.0, timesteps=forward_timesteps, clamp=False, noise=forward_noise,
-                                  sampler=sampler, sigma_schedule=sigma_schedule)
-    target = conditioning.detach().to(device=device, dtype=torch.float32)
-    score = torch.ops.mdt.screen_score(result, target, None if weights is None else weights.to(device), N)
-    kk, kp, kl = known.on(device) if known is not None and len(known) else (None, None, None)
-    status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
-    index = index.long()
-    filled = index >= 0
-    rows = index.clamp(min=0) * G + torch.arange(G, device=device).unsqueeze(1)
-    props = result.reshape(N * G, -1)[:, :n]
-    return Screened(tokens=torch.where(filled.unsqueeze(2), tok.long()[rows], 0),
-                    props=torch.where(filled.unsqueeze(2), props[rows], float("nan")),
-                    score=torch.where(filled, score[rows], float("inf")),
-                    index=index, count=count.long(), status=status.view(N, G))
+    ap, al, _, _ = torch.ops.mdt.tokens_compact(a.to(device), 0, 1.0)
+    bp, bl, _, _ = torch.ops.mdt.tokens_compact(b.to(device), 0, 1.0)
+    return torch.ops.mdt.edit_distance(ap, al, bp, bl).long()
+
+
+def nearest_known(tokens, known_tokens, device):
+    """How far from the known set is each molecule?  -> (distance int64 (R,), index int64 (R,)): the smallest Levenshtein distance
+    of row r of ``tokens`` (raw (R, L) ids) to any molecule of ``known_tokens`` -- a KnownSet, or raw ids, wrapped as screen_tokens
+    does -- and the lowest row of ``KnownSet.packed`` that attains it.  The result does not depend on how the device splits the
+    work.  L <= 64 and ids in [0, 64), in both (wider rows are out of scope); an empty known set has no nearest: all refused with
+    ValueError before anything is launched.  Sequence: mdt::tokens_compact -> mdt::edit_nearest."""
+    tok = _integer_ids(tokens, "tokens")
+    length = tok.shape[1]
+    if length < 1:
+        raise ValueError("tokens must hold at least one position per row")
+    _edit_width(length, "tokens")
+    known = known_tokens if isinstance(known_tokens, KnownSet) else KnownSet(known_tokens, length)
+    if known.width != length:
+        raise ValueError(f"known_tokens was built for rows of {known.width} positions, tokens has {length}")
+    if len(known) == 0:
+        raise ValueError("known_tokens is empty: there is no nearest known molecule")
+    _edit_known(known)
+    tok = _edit_ids(tok, "tokens")
+    device = torch.device(device)
+    packed, n, _, _ = torch.ops.mdt.tokens_compact(tok.to(device), 0, 1.0)
+    _, kp, kl = known.on(device)
+    dist, index = torch.ops.mdt.edit_nearest(packed, n, kp, kl)
+    return dist.long(), index.long()
 
 
 def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward", conditioning: Tensor, device, candidates: int,
                       keep: int, *, cond_scale=1.0, timesteps: int = 100, noise=None, **screen_tokens_kwargs) -> Screened:
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
-    of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes;
+    of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
+    ``min_distance`` / ``min_novelty``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
-                                         "sigma_schedule"}
+                                         "sigma_schedule", "min_distance", "min_novelty"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
                             screen_tokens_kwargs.get("weights"), length=model.max_length)
     if known is not None:
         screen_tokens_kwargs["known_tokens"] = known
+    filters = dict(min_distance=screen_tokens_kwargs.pop("min_distance", 1), min_novelty=screen_tokens_kwargs.pop("min_novelty", 1))
+    diverse = _diverse_args(filters["min_distance"], filters["min_novelty"], known, model.max_length)
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):
         scale = scale.repeat_interleave(G)
     tokens = model.sample_tokens(conditioning.repeat(N, 1), device, cond_scale=scale, timesteps=timesteps, noise=noise,
                                  sampler=screen_tokens_kwargs.get("sampler"), sigma_schedule=screen_tokens_kwargs.get("sigma_schedule"))
+    if diverse:
+        return screen_tokens_diverse(model_forward, tokens, conditioning, device, candidates, keep, **filters, **screen_tokens_kwargs)
     return screen_tokens(model_forward, tokens, conditioning, device, candidates, keep, **screen_tokens_kwargs)

@@ -16,6 +16,9 @@ fake / meta tensors).
     tokens_compact      ids -> non-zero ids left-packed, length, 64-bit key, forward input (generative.py:425-429 on ids)
     screen_score        weighted mean squared distance of re-predicted properties from the group's target
     screen_select       status (empty / non-finite / duplicate / known: is_novel, generative.py:1063) and the K best per group
+    screen_select_diverse   the same with novelty as an edit distance and the K best that lie min_distance edits apart
+    edit_distance       Levenshtein distance between compacted id rows, row by row (csrc/k_edit.hip)
+    edit_nearest        per row the nearest row of a known set: its distance and its (lowest) index
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
     aeuler_next         the whole AEulerSampler.step after its evaluation (diffusion.py:465-474)
     karras_hat / _mid / _next   the three stages of KarrasSampler.step (diffusion.py:417-435)
@@ -526,6 +529,127 @@ def _(score, key, packed, length, candidates, keep, known_key, known_packed, kno
     G = packed.shape[0] // candidates
     return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
             packed.new_empty(G, dtype=torch.int32))
+
+
+def _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len):
+    """The argument checks that mdt::screen_select_diverse shares with mdt::screen_select.  -> (rows, L, G, M, known)"""
+    rows, L = packed.shape
+    N = candidates
+    if N < 1 or rows % N:
+        raise RuntimeError(f"{op}: {rows} rows are no multiple of candidates = {N}")
+    if key.dtype != torch.int64 or packed.dtype != torch.int32 or length.dtype != torch.int32:
+        raise RuntimeError(f"{op}: key must be int64, packed and length int32 (as mdt::tokens_compact returns them)")
+    if score.numel() != rows or key.numel() != rows or length.numel() != rows:
+        raise RuntimeError(f"{op}: score, key and length must hold one value per row of packed")
+    known = (known_key, known_packed, known_len)
+    if any(k is None for k in known) != all(k is None for k in known):
+        raise RuntimeError(f"{op}: give known_key, known_packed and known_len together")
+    M = 0
+    if known_key is not None:
+        M = known_key.numel()
+        if known_key.dtype != torch.int64 or known_packed.dtype != torch.int32 or known_len.dtype != torch.int32:
+            raise RuntimeError(f"{op}: known_key must be int64, known_packed and known_len int32")
+        if tuple(known_packed.shape) != (M, L) or known_len.numel() != M:
+            raise RuntimeError(f"{op}: the known set must be (M, {L}) rows with M keys and M lengths")
+        known = tuple(k.contiguous() for k in known)
+    return rows, L, rows // N, M, known
+
+
+@custom_op("mdt::screen_select_diverse", mutates_args=())
+def screen_select_diverse(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                          known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
+                          known_dist: Optional[Tensor], min_novelty: int, min_distance: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """mdt::screen_select with the two edit-distance filters of mdt_screen_select_diverse (include/mdt_hip.h): bit 8 also where
+    known_dist (int32 (N * G), or None) < min_novelty; the K best in (score, c) order that lie >= min_distance edits apart; bit 16
+    on what a kept candidate pushed out.  Rows of at most 64 positions."""
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist)
+    lib = rt.load_library()
+    op = "mdt::screen_select_diverse"
+    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
+    if L > rt.EDIT_MAX_LENGTH:
+        raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} the edit distance takes")
+    if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
+        raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
+    kd = None if known_dist is None else known_dist.contiguous()
+    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
+    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_screen_select_diverse(rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
+                                                   *(rt.ptr(k) if M else 0 for k in known), M, keep, rt.ptr(kd), int(min_novelty),
+                                                   int(min_distance), rt.ptr(status), rt.ptr(index), rt.ptr(count),
+                                                   rt.current_stream()))
+    return status, index, count
+
+
+@screen_select_diverse.register_fake
+def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, known_dist, min_novelty, min_distance):
+    G = packed.shape[0] // candidates
+    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
+            packed.new_empty(G, dtype=torch.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# edit distance between compacted id rows (csrc/k_edit.hip): at most 64 positions, ids in [0, 64)
+def _edit_rows(op, packed, length, what):
+    if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
+        raise RuntimeError(f"{op}: {what} must be int32 rows (R, L) with one int32 length each (as mdt::tokens_compact returns them)")
+    if not 1 <= packed.shape[1] <= rt.EDIT_MAX_LENGTH:
+        raise RuntimeError(f"{op}: {what} has {packed.shape[1]} positions per row, the edit distance takes 1 to {rt.EDIT_MAX_LENGTH}")
+    return packed.contiguous(), length.contiguous()
+
+
+@custom_op("mdt::edit_distance", mutates_args=())
+def edit_distance(a_packed: Tensor, a_len: Tensor, b_packed: Tensor, b_len: Tensor) -> Tensor:
+    """-> int32 (R,): the Levenshtein distance of row r of a to row r of b."""
+    dev = _hip(a_packed, a_len, b_packed, b_len)
+    lib = rt.load_library()
+    a, al = _edit_rows("mdt::edit_distance", a_packed, a_len, "a")
+    b, bl = _edit_rows("mdt::edit_distance", b_packed, b_len, "b")
+    if a.shape != b.shape:
+        raise RuntimeError(f"mdt::edit_distance: a {tuple(a.shape)} and b {tuple(b.shape)} must have the same shape")
+    R, L = a.shape
+    dist = torch.empty(R, dtype=torch.int32, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_edit_distance_rows(rt.ptr(a), rt.ptr(al), rt.ptr(b), rt.ptr(bl), L, R, rt.ptr(dist), rt.current_stream()))
+    return dist
+
+
+@edit_distance.register_fake
+def _(a_packed, a_len, b_packed, b_len):
+    return a_packed.new_empty(a_packed.shape[0], dtype=torch.int32)
+
+
+@custom_op("mdt::edit_nearest", mutates_args=())
+def edit_nearest(packed: Tensor, length: Tensor, known_packed: Tensor, known_len: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (distance int32 (R,), index int32 (R,)): per row the smallest distance to a row of the known set (M >= 1 rows of the
+    same width) and the lowest known index that attains it."""
+    dev = _hip(packed, length, known_packed, known_len)
+    lib = rt.load_library()
+    q, ql = _edit_rows("mdt::edit_nearest", packed, length, "packed")
+    k, kl = _edit_rows("mdt::edit_nearest", known_packed, known_len, "known_packed")
+    if k.shape[1] != q.shape[1]:
+        raise RuntimeError(f"mdt::edit_nearest: the known rows have {k.shape[1]} positions, the query rows {q.shape[1]}")
+    if k.shape[0] < 1:
+        raise RuntimeError("mdt::edit_nearest: the known set is empty (need M >= 1)")
+    R, L = q.shape
+    dist = torch.empty(R, dtype=torch.int32, device=dev)
+    index = torch.empty(R, dtype=torch.int32, device=dev)
+    best = torch.empty(R, dtype=torch.int64, device=dev)            # the packed minima (distance << 32 | index), one word per row
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_edit_nearest(rt.ptr(q), rt.ptr(ql), L, R, rt.ptr(k), rt.ptr(kl), k.shape[0], rt.ptr(best), rt.ptr(dist),
+                                          rt.ptr(index), rt.current_stream()))
+    return dist, index
+
+
+@edit_nearest.register_fake
+def _(packed, length, known_packed, known_len):
+    R = packed.shape[0]
+    return packed.new_empty(R, dtype=torch.int32), packed.new_empty(R, dtype=torch.int32)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -46,6 +46,9 @@ B_KV2, B_WF32 = 11, 12
  F_KV_LSTRIDE, F_RES_KIND, F_N_RES, F_RES_PAIR1, F_RES_PAIR2, F_NFILM, F_NSPLIT, F_PAIR_STRIDE, F_WF32) = range(23)
 FF_EPS_LN, FF_SCALE, FF_EPS_GN, FF_EPS_RES, FF_SKIP_SCALE = range(5)
 SCREEN_EMPTY, SCREEN_NONFINITE, SCREEN_DUPLICATE, SCREEN_KNOWN = 1, 2, 4, 8      # enum mdt_screen_status
+SCREEN_CLOSE = 16                # ... set by mdt_screen_select_diverse only
+EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
+EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
 
 
 class MdtRef(C.Structure):
@@ -108,6 +111,9 @@ SYMBOLS = {
     "mdt_tokens_compact": (_I, [_P, _I, _I, _P, _I, C.c_double, _P, _P, _P, _P]),
     "mdt_screen_score": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P]),
     "mdt_screen_select": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mdt_screen_select_diverse": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "mdt_edit_distance_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "mdt_edit_nearest": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "mdt_timer_create": (_P, [_I]),
     "mdt_timer_destroy": (None, [_P]),
     "mdt_timer_start": (_I, [_P, _P]),
