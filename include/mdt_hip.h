@@ -602,7 +602,9 @@ enum mdt_screen_status {
   MDT_SCREEN_NONFINITE = 2, /* the score is a NaN or an infinity */
   MDT_SCREEN_DUPLICATE = 4, /* a candidate c' < c of the same group holds the same molecule (whatever the status of c') */
   MDT_SCREEN_KNOWN = 8,     /* the molecule is in the known set (mdt_screen_select_diverse: or closer to it than min_novelty) */
-  MDT_SCREEN_CLOSE = 16     /* mdt_screen_select_diverse only: closer than min_distance to a better candidate that was kept */
+  MDT_SCREEN_CLOSE = 16,    /* mdt_screen_select_diverse only: closer than min_distance to a better candidate that was kept */
+  MDT_SCREEN_MALFORMED = 32, /* mdt_smiles_check: the row breaks the grammar, or its ring / branch bookkeeping does not close */
+  MDT_SCREEN_OVERVALENT = 64 /* mdt_smiles_check: well-formed, but an unbracketed atom's bond orders exceed its maximum */
 };
 /* Per group g: status uint8 (N*G) of every candidate; index int32 (G,K): the eligible (status == 0) candidates c in ascending
  * order of (score, c) -- ties go to the lower c -- and -1 in the slots beyond count[g] = min(K, number of eligible candidates).
@@ -613,6 +615,13 @@ enum mdt_screen_status {
 int mdt_screen_select(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L, int32_t N,
                       int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len, int32_t M,
                       int32_t K, uint8_t *status, int32_t *index, int32_t *count, void *stream);
+/* mdt_screen_select with a per-row verdict from outside: reject uint8 (N*G), or NULL.  reject[r] is OR-ed into status[r] before
+ * eligibility is decided, so a rejected candidate is never kept (mdt_smiles_check's status is the intended input; any non-zero
+ * byte rejects).  DUPLICATE stays "a lower c holds the same molecule, whatever its status".  reject == NULL: mdt_screen_select. */
+int mdt_screen_select_reject(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L,
+                             int32_t N, int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len,
+                             int32_t M, int32_t K, const uint8_t *reject, uint8_t *status, int32_t *index, int32_t *count,
+                             void *stream);
 
 /* ------------------------------------------------------------------ */
 /* edit distance between molecules (csrc/k_edit.hip, csrc/k_screen.hip); additions inside ABI version 5 */
@@ -648,6 +657,62 @@ int mdt_screen_select_diverse(const float *score, const uint64_t *key, const int
                               int32_t N, int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len,
                               int32_t M, int32_t K, const int32_t *known_dist, int32_t min_novelty, int32_t min_distance,
                               uint8_t *status, int32_t *index, int32_t *count, void *stream);
+/* mdt_screen_select_diverse with reject uint8 (N*G) or NULL, as mdt_screen_select_reject: the bits are OR-ed in at step 1, so a
+ * rejected candidate is not eligible, is never kept and never pushes another out under min_distance (it gets no bit 16 either). */
+int mdt_screen_select_diverse_reject(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length,
+                                     int32_t L, int32_t N, int32_t G, const uint64_t *known_key, const int32_t *known_packed,
+                                     const int32_t *known_len, int32_t M, int32_t K, const int32_t *known_dist, int32_t min_novelty,
+                                     int32_t min_distance, const uint8_t *reject, uint8_t *status, int32_t *index, int32_t *count,
+                                     void *stream);
+
+/* ------------------------------------------------------------------ */
+/* well-formedness and valence of token rows (csrc/k_smiles.hip); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* Is the row a molecule at all?  The reference's callers ask RDKit (valid = Chem.MolFromSmiles(smi) != None, generative.py:954-994);
+ * this is a precisely defined single pass over the string instead: grammar, ring and branch bookkeeping, and the bond-order sums
+ * of unbracketed atoms.  OK means "passes this check", not "RDKit parses it".
+ *
+ * packed int32 (R,L), length int32 (R) as mdt_tokens_compact writes them (length clamped to [0, L]); 1 <= L <= 128; R >= 0
+ * (R == 0 launches nothing).  All pointers are device pointers.
+ *   classes  uint8 (256): the class of id i, which stands for ONE character:
+ *            0 other | 1 + (c - 'A') | 27 + (c - 'a') | 53 + digit | 63.. for  - = # $ : / \ ( ) . [ ] % @ + *  in this order.
+ *            An id outside [0, 256) has class 0.  Class 0 is a violation wherever the scan meets it.
+ *   max_valence uint8 (10): the maxima of B C N O P S F Cl Br I, in this order, each in [0, 15].
+ *   elements uint32 (26): bit k (< 26) of word u: (uppercase u, lowercase k) is an element symbol; bit 26: uppercase u alone is.
+ * status uint8 (R): 0, MDT_SCREEN_MALFORMED or MDT_SCREEN_OVERVALENT; position int32 (R): see below, -1 for an OK row.
+ *
+ * The rules.  n = length.  An empty row is OK.  The scan runs left to right and stops at the first token that violates a rule:
+ * MALFORMED, position = that token's index.  Violations only visible at the end have position n.  OVERVALENT is judged only for
+ * rows that are not malformed.  State: prev in {START, ATOM, BOND, DOT, OPEN, CLOSE}, the current atom, a stack of branch parents,
+ * the pending bond symbol, a ring table for the numbers 0..99 (opening atom, bond symbol or none), a bond-order sum per atom.
+ *  - Atoms outside brackets: B C N O P S F I, '*', aromatic b c n o p s; C directly followed by l is Cl, B by r is Br (two tokens,
+ *    one atom, positioned at the first).  Any other letter, H included, is a violation at that letter.  An atom is allowed after
+ *    every prev.  Unless prev is START or DOT it bonds to the current atom with the pending bond (order 1 if none); the order is
+ *    added to both atoms' sums.  The new atom becomes current; the pending bond is cleared; prev = ATOM.
+ *  - Bracket atoms: '[' isotope? symbol chiral? hcount? charge? class? ']'.  isotope: digits.  symbol: an uppercase letter -- with
+ *    the next token if that is a lowercase letter and the pair is an element, else alone if it is one, else a violation at the
+ *    uppercase letter -- or one of b c n o p s, or '*'; anything else is a violation at that token.  chiral: @ or @@.  hcount: H
+ *    and at most one digit.  charge: + or -, optionally doubled or followed by one digit.  class: ':' and one or more digits (a
+ *    non-digit after ':' is a violation at that token).  The first token that cannot continue the sequence and is not ']' is the
+ *    violation; the end of the row inside a bracket gives position n.  One atom, positioned at '[', exempt from the valence check.
+ *  - Bonds: - = # $ : / \ of orders 1 2 3 4 1 1 1, allowed when prev is ATOM, CLOSE or OPEN; prev = BOND.
+ *  - Ring closures: a digit, or '%' and exactly two digits (a non-digit in either place is the violation; a missing digit gives
+ *    position n).  Allowed when prev is ATOM or CLOSE, or BOND where that bond followed ATOM or CLOSE; otherwise the closure's
+ *    first token is the violation.  After ')' the closure belongs to the branch's parent (lenient on purpose: CC(C)1CC1 is OK).
+ *    A number that is not open is opened with (current atom, pending bond).  An open number is closed: a violation at the closure's
+ *    last token when the opening atom is the current atom, or when both ends carry a bond symbol and the symbols differ ('/' and
+ *    '\' are compatible with each other); else the order of whichever symbol is present (else 1) is added to both atoms and the number
+ *    is free again.  In both cases the pending bond is cleared and prev = ATOM.
+ *  - '(' is allowed when prev is ATOM or CLOSE: pushes the current atom, prev = OPEN.  ')' when prev is ATOM or CLOSE and the
+ *    stack is not empty: pops into the current atom, prev = CLOSE.  '.' when prev is ATOM or CLOSE and the stack is empty:
+ *    prev = DOT (rings may close across a dot).  Any other character is a violation at that token.
+ *  - End of row: a non-empty row needs prev in {ATOM, CLOSE}, an empty stack and no open ring; otherwise MALFORMED at n.
+ *  - Valence: an unbracketed, non-aromatic, non-'*' atom is overvalent when its sum exceeds its maximum; position = the atom
+ *    position of the lowest-index overvalent atom.
+ * Not checked: aromaticity and kekulisation, two bonds between the same pair of atoms, hydrogens, bracket-atom valence, stereo
+ * consistency. */
+int mdt_smiles_check(const int32_t *packed, const int32_t *length, int32_t L, int32_t R, const uint8_t *classes,
+                     const uint8_t *max_valence, const uint32_t *elements, uint8_t *status, int32_t *position, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

@@ -7,6 +7,7 @@
 //   k_screen_score     weighted mean squared distance of the re-predicted properties from the group's target
 //   k_screen_select    per group: status bits (empty / non-finite / duplicate / known) and the K best eligible candidates
 //   k_screen_select_diverse   the same with novelty as a distance and the K best that lie min_distance edits apart
+// Both selections take an optional per-row `reject` byte (mdt_smiles_check's status) that is OR-ed into the status first.
 //
 // Rows are r = c * G + g: candidate c of group g (a group is one target conditioning), the layout of guidance_sweep.
 // A molecule IS its compacted id row (the reference's string: a character-level tokenizer, id 0 skipped), so equality is decided
@@ -135,8 +136,8 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
                                                        int N, int G, const uint64_t* __restrict__ known_key,
                                                        const int32_t* __restrict__ known_packed,
                                                        const int32_t* __restrict__ known_len, int M, int K,
-                                                       uint8_t* __restrict__ status, int32_t* __restrict__ index,
-                                                       int32_t* __restrict__ count) {
+                                                       const uint8_t* __restrict__ reject, uint8_t* __restrict__ status,
+                                                       int32_t* __restrict__ index, int32_t* __restrict__ count) {
   __shared__ uint64_t s_key[kScreenMaxN];
   __shared__ float s_score[kScreenMaxN];
   __shared__ int32_t s_len[kScreenMaxN];
@@ -156,7 +157,8 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
 
   int mine = 0;
   for (int c = tid; c < N; c += 256) {
-    const int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
+    int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
+    if (reject) st |= reject[(int64_t)c * G + g];                // a verdict from outside (mdt_smiles_check): not eligible
     s_status[c] = (uint8_t)st;
     status[(int64_t)c * G + g] = (uint8_t)st;
     mine += st == 0;
@@ -186,8 +188,8 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
     const float* __restrict__ score, const uint64_t* __restrict__ key, const int32_t* __restrict__ packed,
     const int32_t* __restrict__ length, int L, int N, int G, const uint64_t* __restrict__ known_key,
     const int32_t* __restrict__ known_packed, const int32_t* __restrict__ known_len, int M, int K,
-    const int32_t* __restrict__ known_dist, int min_novelty, int min_distance, uint8_t* __restrict__ status,
-    int32_t* __restrict__ index, int32_t* __restrict__ count) {
+    const int32_t* __restrict__ known_dist, int min_novelty, int min_distance, const uint8_t* __restrict__ reject,
+    uint8_t* __restrict__ status, int32_t* __restrict__ index, int32_t* __restrict__ count) {
   __shared__ uint64_t s_key[kScreenMaxN];
   __shared__ float s_score[kScreenMaxN];
   __shared__ int32_t s_len[kScreenMaxN];
@@ -212,6 +214,7 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
   for (int c = tid; c < N; c += 256) {
     int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
     if (known_dist && known_dist[(int64_t)c * G + g] < min_novelty) st |= MDT_SCREEN_KNOWN;
+    if (reject) st |= reject[(int64_t)c * G + g];
     s_status[c] = (uint8_t)st;
     status[(int64_t)c * G + g] = (uint8_t)st;
     mine += st == 0;
@@ -325,9 +328,10 @@ int mdt_screen_score(const float* props, int64_t row_stride, const float* target
   return finish("mdt_screen_score");
 }
 
-int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L, int32_t N,
-                      int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len, int32_t M,
-                      int32_t K, uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+int mdt_screen_select_reject(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
+                             int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
+                             int32_t M, int32_t K, const uint8_t* reject, uint8_t* status, int32_t* index, int32_t* count,
+                             void* stream) {
   if (G <= 0) return 0;
   if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select: need 1 <= N <= 1024 candidates per group");
   if (K < 1 || K > N) return bad("mdt_screen_select: need 1 <= K <= N");
@@ -337,14 +341,22 @@ int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* pa
     return bad("mdt_screen_select: the known-set pointers may be NULL only when M == 0");
   if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select: null pointer");
   hipLaunchKernelGGL(mdt::k_screen_select, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
-                     known_key, known_packed, known_len, M, K, status, index, count);
+                     known_key, known_packed, known_len, M, K, reject, status, index, count);
   return finish("mdt_screen_select");
 }
 
-int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
-                              int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
-                              int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty, int32_t min_distance,
-                              uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L, int32_t N,
+                      int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len, int32_t M,
+                      int32_t K, uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+  return mdt_screen_select_reject(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, K, nullptr, status,
+                                  index, count, stream);
+}
+
+int mdt_screen_select_diverse_reject(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length,
+                                     int32_t L, int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed,
+                                     const int32_t* known_len, int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty,
+                                     int32_t min_distance, const uint8_t* reject, uint8_t* status, int32_t* index, int32_t* count,
+                                     void* stream) {
   if (G <= 0) return 0;
   if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select_diverse: need 1 <= N <= 1024 candidates per group");
   if (K < 1 || K > N) return bad("mdt_screen_select_diverse: need 1 <= K <= N");
@@ -354,8 +366,17 @@ int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int
     return bad("mdt_screen_select_diverse: the known-set pointers may be NULL only when M == 0");
   if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select_diverse: null pointer");
   hipLaunchKernelGGL(mdt::k_screen_select_diverse, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length,
-                     L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, status, index, count);
+                     L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, status, index,
+                     count);
   return finish("mdt_screen_select_diverse");
+}
+
+int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
+                              int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty, int32_t min_distance,
+                              uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+  return mdt_screen_select_diverse_reject(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, K, known_dist,
+                                          min_novelty, min_distance, nullptr, status, index, count, stream);
 }
 
 }  // extern "C"

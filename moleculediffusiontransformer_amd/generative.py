@@ -966,6 +966,7 @@ class Screened(NamedTuple):
     count: Tensor      # (G,) int64: filled slots = min(K, eligible candidates)
     status: Tensor     # (N, G) uint8: 1 empty | 2 non-finite score | 4 duplicate of a lower c | 8 in the known set (or closer to
     #                    it than min_novelty) | 16 closer than min_distance to a better kept candidate (screen_tokens_diverse)
+    #                    | 32 malformed | 64 overvalent (with ``vocabulary=``: smiles_check's verdict; never kept)
 
 
 def _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=None, length=None):
@@ -1051,10 +1052,12 @@ def _diverse_args(min_distance, min_novelty, known, length=None, tokens=None) ->
 
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
-            min_novelty=1) -> Screened:
-    """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch."""
+            min_novelty=1, vocabulary=None) -> Screened:
+    """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
+    ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
+    _vocabulary_arg(vocabulary, torch.as_tensor(tokens).shape[1])
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1067,15 +1070,25 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     target = conditioning.detach().to(device=device, dtype=torch.float32)
     score = torch.ops.mdt.screen_score(result, target, None if weights is None else weights.to(device), N)
     kk, kp, kl = known.on(device) if known is not None and len(known) else (None, None, None)
+    reject = None
+    if vocabulary is not None:                                   # is it a molecule at all?  bits 32 / 64, never kept
+        reject, _ = torch.ops.mdt.smiles_check(packed, length, *vocabulary.on(device))
     if not diverse:
-        status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
+        if reject is None:
+            status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
+        else:
+            status, index, count = torch.ops.mdt.screen_select_reject(score, key, packed, length, N, K, kk, kp, kl, reject)
     else:
         known_dist = None
         if min_novelty > 1:                                      # novelty as a distance: the nearest known row of every candidate
             known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
             kk = kp = kl = None
-        status, index, count = torch.ops.mdt.screen_select_diverse(score, key, packed, length, N, K, kk, kp, kl, known_dist,
-                                                                   min_novelty, min_distance)
+        if reject is None:
+            status, index, count = torch.ops.mdt.screen_select_diverse(score, key, packed, length, N, K, kk, kp, kl, known_dist,
+                                                                       min_novelty, min_distance)
+        else:
+            status, index, count = torch.ops.mdt.screen_select_diverse_reject(score, key, packed, length, N, K, kk, kp, kl,
+                                                                              known_dist, min_novelty, min_distance, reject)
     index = index.long()
     filled = index >= 0
     rows = index.clamp(min=0) * G + torch.arange(G, device=device).unsqueeze(1)
@@ -1110,9 +1123,18 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 
 
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
-                          keep: int, *, min_distance: int = 1, min_novelty: int = 1, **screen_tokens_kwargs) -> Screened:
+                          keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None,
+                          **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
-    (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings.
+    (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
+    ``vocabulary=``, with "is it a molecule at all?" asked of every candidate.
+
+    ``vocabulary``: a SmilesVocabulary (None: not asked; the call makes the launches it made before, in the same order).  One
+    mdt::smiles_check (see smiles_check() for what it does and does not check) runs over the N * G compacted rows and the selection
+    takes its status as `reject`: a malformed candidate gets status bit 32 (runtime.SCREEN_MALFORMED), an overvalent one bit 64
+    (runtime.SCREEN_OVERVALENT); neither is kept, and neither pushes another candidate out under ``min_distance``.  The valid
+    fraction is ``((status & 96) == 0).float().mean()``.  It works with both filters at 1 as well (screen_tokens plus validity)
+    and needs rows of at most 128 positions, refused with ValueError before anything is launched.
 
     ``min_distance``: the K kept molecules of a target lie at least this many edits apart.  The eligible candidates are taken in
     (score, c) order; one that is closer than ``min_distance`` to a candidate kept before it is passed over and gets status bit 16
@@ -1126,7 +1148,177 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     synchronisation added) and in the known set (checked once per KnownSet) -- all refused with ValueError before anything is
     launched.  Rows of more than one 64-bit word are out of scope.  Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
-                   **screen_tokens_kwargs)
+                   vocabulary=vocabulary, **screen_tokens_kwargs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# is it a molecule at all?  well-formedness and valence of the strings behind the ids (csrc/k_smiles.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_SMILES_LENGTH = 128         # mdt_smiles_check's limits (include/mdt_hip.h)
+MAX_SMILES_ID = 256
+VALENCE_SYMBOLS = ("B", "C", "N", "O", "P", "S", "F", "Cl", "Br", "I")
+DEFAULT_MAX_VALENCE = dict(zip(VALENCE_SYMBOLS, (3, 4, 3, 2, 5, 6, 1, 1, 1, 1)))
+ELEMENT_SYMBOLS = (
+    "H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr Nb Mo Tc Ru Rh Pd "
+    "Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt Au Hg Tl Pb Bi Po At Rn Fr Ra "
+    "Ac Th Pa U Np Pu Am Cm Bk Cf Es Fm Md No Lr Rf Db Sg Bh Hs Mt Ds Rg Cn Nh Fl Mc Lv Ts Og").split()
+_SMILES_SYMBOLS = "-=#$:/\\().[]%@+*"           # classes 63 .. 78, in this order (include/mdt_hip.h, mdt_smiles_check)
+
+
+def smiles_class(ch: str) -> int:
+    """The class byte of one character (include/mdt_hip.h, mdt_smiles_check): 0 other | 1 + (c - 'A') | 27 + (c - 'a') |
+    53 + digit | 63 + its place in ``- = # $ : / \\ ( ) . [ ] % @ + *``.  Only ASCII letters and digits count as such."""
+    if len(ch) == 1 and ch.isascii():
+        if ch.isupper():
+            return 1 + ord(ch) - ord("A")
+        if ch.islower():
+            return 27 + ord(ch) - ord("a")
+        if ch.isdigit():
+            return 53 + int(ch)
+        if ch in _SMILES_SYMBOLS:
+            return 63 + _SMILES_SYMBOLS.index(ch)
+    return 0
+
+
+def element_masks():
+    """The element table of mdt_smiles_check: numpy int32 (26,), bit k of word u set when (uppercase u, lowercase k) is one of the
+    118 element symbols, bit 26 when the uppercase letter alone is."""
+    import numpy as np
+    masks = np.zeros(26, np.int64)
+    for sym in ELEMENT_SYMBOLS:
+        masks[ord(sym[0]) - ord("A")] |= 1 << (26 if len(sym) == 1 else ord(sym[1]) - ord("a"))
+    return masks.astype(np.int32)
+
+
+class SmilesVocabulary:
+    """Which character each token id stands for -- what smiles_check() and the ``vocabulary=`` of the screening calls need to read
+    an id row as a string.
+
+    ``chars``: a sequence, ``chars[i]`` the character of id i (index 0 is ignored: id 0 is padding; ``None`` / ``""`` = unused),
+    or a dict ``{id: char}`` such as a keras tokenizer's ``index_word``.  Characters are taken as given (no case folding).
+    Entries of more than one character, ids outside [1, 256) and non-integer keys are refused with ValueError.
+    ``max_valence``: overrides of the default maxima B 3, C 4, N 3, O 2, P 5, S 6, F 1, Cl 1, Br 1, I 1, e.g. ``{"N": 5}``; other
+    keys, or values outside 0..8, are refused.
+    ``classes`` uint8 (256), ``max_valence`` uint8 (10), ``elements`` int32 (26): numpy, the tables of mdt_smiles_check
+    (include/mdt_hip.h).  The device copy is made on first use and cached, one per device."""
+
+    def __init__(self, chars, max_valence=None):
+        import numpy as np
+        if isinstance(chars, dict):
+            items = list(chars.items())
+        elif isinstance(chars, (str, bytes)) or not hasattr(chars, "__len__"):
+            raise ValueError("chars must be a sequence of characters indexed by id, or a dict {id: character}")
+        else:
+            items = list(enumerate(chars))[1:]
+        self.chars = {}
+        for i, ch in items:
+            if isinstance(i, (bool, float)) or not isinstance(i, (int, np.integer)):
+                raise ValueError(f"token ids must be integers, got {i!r}")
+            if ch is None or ch == "":
+                continue
+            if not isinstance(ch, str) or len(ch) != 1:
+                raise ValueError(f"id {i} stands for {ch!r}: every id stands for exactly one character")
+            if not 1 <= int(i) < MAX_SMILES_ID:
+                raise ValueError(f"id {i} lies outside [1, {MAX_SMILES_ID})")
+            self.chars[int(i)] = ch
+        limits = dict(DEFAULT_MAX_VALENCE)
+        for sym, v in (max_valence or {}).items():
+            if sym not in limits:
+                raise ValueError(f"max_valence: {sym!r} is none of {', '.join(VALENCE_SYMBOLS)}")
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 8:
+                raise ValueError(f"max_valence[{sym!r}] must be an int in 0..8, got {v!r}")
+            limits[sym] = int(v)
+        self.classes = np.zeros(MAX_SMILES_ID, np.uint8)
+        for i, ch in self.chars.items():
+            self.classes[i] = smiles_class(ch)
+        self.max_valence = np.array([limits[sym] for sym in VALENCE_SYMBOLS], np.uint8)
+        self.elements = element_masks()
+        self._ids = {}
+        for i in sorted(self.chars):
+            self._ids.setdefault(self.chars[i], i)                         # (of two ids for one character the lower encodes)
+        self._on = {}
+
+    def __len__(self) -> int:
+        return len(self.chars)
+
+    def encode(self, strings, length: int) -> Tensor:
+        """-> int64 (R, length): one id per character, zero-padded at the end.  A character without an id, or a string of more
+        than ``length`` characters, raises ValueError."""
+        if isinstance(strings, str):
+            strings = [strings]
+        if isinstance(length, bool) or not isinstance(length, int) or length < 1:
+            raise ValueError(f"length must be an int >= 1, got {length!r}")
+        out = torch.zeros(len(strings), length, dtype=torch.int64)
+        for r, s in enumerate(strings):
+            if len(s) > length:
+                raise ValueError(f"{s!r} has {len(s)} characters, the rows {length} positions")
+            for j, ch in enumerate(s):
+                if ch not in self._ids:
+                    raise ValueError(f"{s!r}: the vocabulary has no id for {ch!r}")
+                out[r, j] = self._ids[ch]
+        return out
+
+    def decode(self, ids):
+        """-> list of str: the compacted rows (zeros anywhere are skipped) as strings.  An id without a character raises ValueError."""
+        ids = _integer_ids(ids, "ids")
+        rows = ids.detach().cpu().tolist() if isinstance(ids, Tensor) else ids.tolist()
+        out = []
+        for row in rows:
+            try:
+                out.append("".join(self.chars[t] for t in row if t != 0))
+            except KeyError as e:
+                raise ValueError(f"the vocabulary has no character for id {e.args[0]}") from None
+        return out
+
+    def on(self, device):
+        """(classes uint8 (256), max_valence uint8 (10), elements int32 (26)) on ``device``."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._on:
+            self._on[device] = tuple(torch.from_numpy(a).to(device) for a in (self.classes, self.max_valence, self.elements))
+        return self._on[device]
+
+
+def _vocabulary_arg(vocabulary, length: int) -> None:
+    """The refusals of ``vocabulary=``, before anything is launched."""
+    if vocabulary is None:
+        return
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if length > MAX_SMILES_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; smiles_check takes at most {MAX_SMILES_LENGTH} "
+                         "(wider rows are out of scope)")
+
+
+def smiles_check(tokens, vocabulary: "SmilesVocabulary", device):
+    """Is each row a molecule at all?  -> (status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer dtype, zeros
+    anywhere (a molecule is its compacted id row, as in screen_tokens), read as strings through ``vocabulary``.
+
+    status 0: passes; 32 (runtime.SCREEN_MALFORMED): the string breaks the grammar -- atoms, bracket atoms, bonds, ring closures,
+    branches, dots -- or leaves a ring or a branch open, ``position`` = the index of the first offending token in the compacted
+    row, or the row's length where only the end shows it; 64 (runtime.SCREEN_OVERVALENT): well-formed, but the bond orders at an
+    unbracketed atom exceed its maximum (``vocabulary.max_valence``), ``position`` = the lowest such atom.  An OK row (an empty
+    one included) has position -1.  The rule set is written out at mdt_smiles_check in include/mdt_hip.h.
+
+    This is a single pass over the string, not RDKit's MolFromSmiles (which the reference's draw_and_save asks,
+    generative.py:954-994).  Not checked: aromaticity and kekulisation, two bonds between the same pair of atoms, hydrogens,
+    bracket-atom valence, stereo consistency.  So 0 means "passes this check", not "RDKit parses it"; the intent is that what this
+    check rejects RDKit rejects too (two known departures: '.' inside a branch, and %(nnn)) -- an intent that is unverified: it
+    was never run against RDKit.
+    L <= 128 and ids below 256 (an id outside [0, 256), or one without a character, is malformed where it stands); non-integer
+    ids, L < 1 and L > 128 are refused with ValueError before anything is launched.  Sequence: mdt::tokens_compact ->
+    mdt::smiles_check."""
+    tok = _integer_ids(tokens, "tokens")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if tok.shape[1] < 1:
+        raise ValueError("tokens must hold at least one position per row")
+    _vocabulary_arg(vocabulary, tok.shape[1])
+    device = torch.device(device)
+    packed, n, _, _ = torch.ops.mdt.tokens_compact(torch.as_tensor(tok).to(device), 0, 1.0)
+    status, position = torch.ops.mdt.smiles_check(packed, n, *vocabulary.on(device))
+    return status.long(), position.long()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1179,13 +1371,13 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
                       keep: int, *, cond_scale=1.0, timesteps: int = 100, noise=None, **screen_tokens_kwargs) -> Screened:
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
-    ``min_distance`` / ``min_novelty``, with which the tokens go to screen_tokens_diverse instead;
+    ``min_distance`` / ``min_novelty`` / ``vocabulary``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
-                                         "sigma_schedule", "min_distance", "min_novelty"}
+                                         "sigma_schedule", "min_distance", "min_novelty", "vocabulary"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -1194,6 +1386,10 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
         screen_tokens_kwargs["known_tokens"] = known
     filters = dict(min_distance=screen_tokens_kwargs.pop("min_distance", 1), min_novelty=screen_tokens_kwargs.pop("min_novelty", 1))
     diverse = _diverse_args(filters["min_distance"], filters["min_novelty"], known, model.max_length)
+    vocabulary = screen_tokens_kwargs.pop("vocabulary", None)
+    _vocabulary_arg(vocabulary, model.max_length)
+    if vocabulary is not None:
+        diverse, filters["vocabulary"] = True, vocabulary
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

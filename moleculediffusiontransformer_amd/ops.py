@@ -17,6 +17,8 @@ fake / meta tensors).
     screen_score        weighted mean squared distance of re-predicted properties from the group's target
     screen_select       status (empty / non-finite / duplicate / known: is_novel, generative.py:1063) and the K best per group
     screen_select_diverse   the same with novelty as an edit distance and the K best that lie min_distance edits apart
+    screen_select_reject / screen_select_diverse_reject   the two selections with a per-row `reject` byte OR-ed into the status
+    smiles_check        well-formedness and valence of compacted id rows: status 0 / 32 / 64 and a position (csrc/k_smiles.hip)
     edit_distance       Levenshtein distance between compacted id rows, row by row (csrc/k_edit.hip)
     edit_nearest        per row the nearest row of a known set: its distance and its (lowest) index
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
@@ -589,6 +591,127 @@ def _(score, key, packed, length, candidates, keep, known_key, known_packed, kno
     G = packed.shape[0] // candidates
     return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
             packed.new_empty(G, dtype=torch.int32))
+
+
+def _reject_rows(op, reject, rows):
+    if reject is None:
+        return None
+    if reject.dtype != torch.uint8 or reject.numel() != rows:
+        raise RuntimeError(f"{op}: reject must hold one uint8 per row of packed")
+    return reject.contiguous()
+
+
+@custom_op("mdt::screen_select_reject", mutates_args=())
+def screen_select_reject(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                         known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
+                         reject: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """mdt::screen_select with ``reject`` (uint8 (N * G), e.g. mdt::smiles_check's status, or None): its bits are OR-ed into the
+    status before eligibility is decided.  None: mdt::screen_select's launch, bit for bit."""
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, reject)
+    lib = rt.load_library()
+    op = "mdt::screen_select_reject"
+    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
+    rej = _reject_rows(op, reject, rows)
+    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
+    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        with torch.cuda.device(dev):
+            head = (rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
+                    *(rt.ptr(k) if M else 0 for k in known), M, keep)
+            tail = (rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream())
+            if rej is None:
+                rt.check(lib.mdt_screen_select(*head, *tail))
+            else:
+                rt.check(lib.mdt_screen_select_reject(*head, rt.ptr(rej), *tail))
+    return status, index, count
+
+
+@screen_select_reject.register_fake
+def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, reject):
+    G = packed.shape[0] // candidates
+    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
+            packed.new_empty(G, dtype=torch.int32))
+
+
+@custom_op("mdt::screen_select_diverse_reject", mutates_args=())
+def screen_select_diverse_reject(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                                 known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
+                                 known_dist: Optional[Tensor], min_novelty: int, min_distance: int,
+                                 reject: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """mdt::screen_select_diverse with ``reject`` as mdt::screen_select_reject takes it: a rejected candidate is not eligible, so
+    it is never kept and never pushes another out under min_distance.  None: mdt::screen_select_diverse's launch, bit for bit."""
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject)
+    lib = rt.load_library()
+    op = "mdt::screen_select_diverse_reject"
+    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
+    if L > rt.EDIT_MAX_LENGTH:
+        raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} the edit distance takes")
+    if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
+        raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
+    kd = None if known_dist is None else known_dist.contiguous()
+    rej = _reject_rows(op, reject, rows)
+    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
+    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        with torch.cuda.device(dev):
+            head = (rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
+                    *(rt.ptr(k) if M else 0 for k in known), M, keep, rt.ptr(kd), int(min_novelty), int(min_distance))
+            tail = (rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream())
+            if rej is None:
+                rt.check(lib.mdt_screen_select_diverse(*head, *tail))
+            else:
+                rt.check(lib.mdt_screen_select_diverse_reject(*head, rt.ptr(rej), *tail))
+    return status, index, count
+
+
+@screen_select_diverse_reject.register_fake
+def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, known_dist, min_novelty, min_distance,
+      reject):
+    G = packed.shape[0] // candidates
+    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
+            packed.new_empty(G, dtype=torch.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# well-formedness and valence of compacted id rows (csrc/k_smiles.hip): at most 128 positions, ids in [0, 256)
+@custom_op("mdt::smiles_check", mutates_args=())
+def smiles_check(packed: Tensor, length: Tensor, classes: Tensor, max_valence: Tensor, elements: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (status uint8 (R,): 0 | 32 malformed | 64 overvalent, position int32 (R,): -1 for an OK row).  packed int32 (R, L) and
+    length int32 (R) as mdt::tokens_compact returns them; classes uint8 (256), max_valence uint8 (10), elements int32 (26): the
+    tables of mdt_smiles_check (include/mdt_hip.h), which SmilesVocabulary builds."""
+    dev = _hip(packed, length, classes, max_valence, elements)
+    lib = rt.load_library()
+    op = "mdt::smiles_check"
+    if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
+        raise RuntimeError(f"{op}: packed must be int32 rows (R, L) with one int32 length each (as mdt::tokens_compact returns them)")
+    R, L = packed.shape
+    if not 1 <= L <= rt.SMILES_MAX_LENGTH:
+        raise RuntimeError(f"{op}: packed has {L} positions per row, the check takes 1 to {rt.SMILES_MAX_LENGTH}")
+    if classes.dtype != torch.uint8 or tuple(classes.shape) != (256,):
+        raise RuntimeError(f"{op}: classes must be uint8 (256,)")
+    if max_valence.dtype != torch.uint8 or tuple(max_valence.shape) != (10,):
+        raise RuntimeError(f"{op}: max_valence must be uint8 (10,): B C N O P S F Cl Br I")
+    if elements.dtype != torch.int32 or tuple(elements.shape) != (26,):
+        raise RuntimeError(f"{op}: elements must be int32 (26,): one mask per uppercase letter")
+    packed, length = packed.contiguous(), length.contiguous()
+    classes, max_valence, elements = classes.contiguous(), max_valence.contiguous(), elements.contiguous()
+    status = torch.zeros(R, dtype=torch.uint8, device=dev)
+    position = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_smiles_check(rt.ptr(packed), rt.ptr(length), L, R, rt.ptr(classes), rt.ptr(max_valence),
+                                          rt.ptr(elements), rt.ptr(status), rt.ptr(position), rt.current_stream()))
+    return status, position
+
+
+@smiles_check.register_fake
+def _(packed, length, classes, max_valence, elements):
+    R = packed.shape[0]
+    return packed.new_empty(R, dtype=torch.uint8), packed.new_empty(R, dtype=torch.int32)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

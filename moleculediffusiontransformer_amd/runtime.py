@@ -47,6 +47,8 @@ B_KV2, B_WF32 = 11, 12
 FF_EPS_LN, FF_SCALE, FF_EPS_GN, FF_EPS_RES, FF_SKIP_SCALE = range(5)
 SCREEN_EMPTY, SCREEN_NONFINITE, SCREEN_DUPLICATE, SCREEN_KNOWN = 1, 2, 4, 8      # enum mdt_screen_status
 SCREEN_CLOSE = 16                # ... set by mdt_screen_select_diverse only
+SCREEN_MALFORMED, SCREEN_OVERVALENT = 32, 64     # ... set by mdt_smiles_check, handed to the selections as `reject`
+SMILES_MAX_LENGTH = 128          # mdt_smiles_check takes rows of at most 128 positions, ids in [0, 256)
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
 
@@ -112,6 +114,9 @@ SYMBOLS = {
     "mdt_screen_score": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P]),
     "mdt_screen_select": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mdt_screen_select_diverse": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "mdt_screen_select_reject": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "mdt_screen_select_diverse_reject": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "mdt_smiles_check": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mdt_edit_distance_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "mdt_edit_nearest": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "mdt_timer_create": (_P, [_I]),
