@@ -715,6 +715,61 @@ int mdt_smiles_check(const int32_t *packed, const int32_t *length, int32_t L, in
                      const uint8_t *max_valence, const uint32_t *elements, uint8_t *status, int32_t *position, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* graph identity of token rows (csrc/k_molgraph.hip); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* Which molecule is the row?  A SMILES string is one of many spellings of a molecule (OCC and CCO are ethanol twice), so equality of
+ * compacted rows is equality of spellings.  The reference's callers go through RDKit (Chem.MolFromSmiles, generative.py:954-994);
+ * this is a precisely defined answer instead: the molecular graph the scan of mdt_smiles_check sees, and a 64-bit key of that graph
+ * that does not depend on how the row spells it.
+ *
+ * The graph of a row (mdt_mol_graph).  packed, length, L, R, classes, max_valence, elements, status, position: as mdt_smiles_check,
+ * the same scan, rules, classes and tables, the same status and position -- but 1 <= L <= 64: with at most 64 tokens there are at
+ * most 64 atoms and at most 63 bonds (a ring bond costs two tokens); wider rows are refused before any launch.  For a row of
+ * status 0 the scan also yields
+ *  - atoms, in order of appearance: natoms int32 (R), atoms uint32 (R,L), one descriptor per atom:
+ *      bits 0..4   the symbol's first letter, 0..25 for A..Z in either case; 26 for '*'
+ *      bits 5..9   0, or 1 + (the symbol's second letter - 'a'): Cl and Br outside brackets, any two-letter element inside
+ *      bit  10     aromatic: the symbol is one of b c n o p s in lower case (bracketed or not)
+ *      bit  11     the atom is a bracket atom
+ *      bits 12..16 formal charge + 9: '+' 1, '++' 2, '+d' d, '-' -1, '--' -2, '-d' -d; no charge, or unbracketed: 0
+ *      bits 17..20 bracket H count: 'H' 1, 'Hd' d; absent, or unbracketed: 0
+ *      bits 21..31 isotope number modulo 2048 (absent, or unbracketed: 0) -- the fields above take 21 bits, so 11 are left
+ *    Chirality marks and the atom class are ignored.
+ *  - bonds, in order of creation: nbonds int32 (R), bonds uint32 (R,L), a | b << 8 | order << 16 with a, b atom indices.  An atom
+ *    that bonds to the current atom makes (current atom, new atom); a ring closure makes (opening atom, closing atom).  Orders:
+ *    '-' '/' '\' 1, '=' 2, '#' 3, '$' 4, ':' 5, no symbol: 5 when both atoms are aromatic, else 1.  A ring closure takes
+ *    whichever end's symbol is present.
+ * Words beyond the counts are 0.  A row of status != 0, and an empty row, has natoms = nbonds = 0 and all-zero words.
+ *
+ * The key (mdt_mol_key).  mix = the splitmix64 step of mdt_tokens_compact.  n = natoms, E = the bonds, seed[a] = mix(atoms[a]),
+ * ROOT = 0xA5A5A5A5A5A5A5A5, K = 0x100000001B3, all arithmetic mod 2^64.  For every root r in 0..n-1:
+ *   1. lab = seed, then lab[r] = mix(seed[r] ^ ROOT).
+ *   2. n rounds.  Each round: acc[a] = the sum, over the bonds at a to neighbour b (a bond listed twice counts twice), of
+ *      mix(lab[b] + order * K); then lab[a] = mix(lab[a] ^ mix(acc[a])) for all a at once.
+ *   3. H_r = the sum over a of mix(lab[a]).
+ * key = mix(sum over r of mix(H_r) + n + (|E| << 32)); if that is 0, the key is 1.  KEY 0 MEANS "NO MOLECULE": natoms == 0, i.e. an
+ * empty row or a row whose status is not 0 (and any row whose counts lie outside [0, L] or whose bonds name an atom >= natoms,
+ * which mdt_mol_graph never writes).  Every combination over atoms, bonds and roots is a sum mod 2^64, so the key cannot depend on
+ * atom numbering, branch order, ring numbers or which end of a closure carries the bond symbol.
+ * Limits.  Equal graphs always give equal keys.  Unequal graphs can collide in principle: the key is a refinement hash, not a
+ * canonical form (none was found among 2,100 random graphs of up to 20 atoms and the 684 graphs of up to 7 nodes and degree 4; the
+ * rooting is what separates cubane from cuneane, decalin from bicyclopentyl, two cyclopropanes from cyclohexane).  It is not
+ * RDKit's canonical SMILES: no hydrogen or bracket normalisation ([CH4] and C differ), no aromaticity perception (C1=CC=CC=C1 and
+ * c1ccccc1 differ), and stereo is ignored (F/C=C/F equals F/C=C\F).
+ * mdt_mol_key takes the graph arrays (device pointers), so the graph is computed once.  R == 0 launches nothing. */
+int mdt_mol_graph(const int32_t *packed, const int32_t *length, int32_t L, int32_t R, const uint8_t *classes,
+                  const uint8_t *max_valence, const uint32_t *elements, int32_t *natoms, uint32_t *atoms, int32_t *nbonds,
+                  uint32_t *bonds, uint8_t *status, int32_t *position, void *stream);
+int mdt_mol_key(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+                uint64_t *key, void *stream);
+/* flags uint8 (N*G), row r = c * G + g as in the selections: MDT_SCREEN_DUPLICATE when a candidate c' < c of the same group has the
+ * same non-zero key, whatever the status of c' (the first occurrence stands for all); MDT_SCREEN_KNOWN when the key is non-zero and
+ * is found, by binary search, in known_key: uint64 (M), ASCENDING as unsigned.  Key 0 gets neither bit.  1 <= N <= 1024, G >= 0
+ * (G == 0 launches nothing), M >= 0; known_key may be NULL only when M == 0.  The flags are meant to be OR-ed into the `reject`
+ * byte of the mdt_screen_select*_reject calls. */
+int mdt_key_flags(const uint64_t *key, int32_t N, int32_t G, const uint64_t *known_key, int32_t M, uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */
 /* ------------------------------------------------------------------ */
 typedef struct mdt_timer mdt_timer;

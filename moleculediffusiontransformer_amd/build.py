@@ -43,6 +43,7 @@ SOURCES = [
     ("k_screen.hip", ["-ffp-contract=off"]),      # the score keeps separate fp32 multiplies and adds as well
     ("k_edit.hip", []),
     ("k_smiles.hip", []),
+    ("k_molgraph.hip", []),
     ("mdt_api.cpp", ["-x", "hip"]),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

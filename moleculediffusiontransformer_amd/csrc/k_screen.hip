@@ -31,12 +31,6 @@ __device__ __forceinline__ uint64_t key_word(uint32_t j, uint32_t id) {
   return z ^ (z >> 31);
 }
 
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int off) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 // One 64-lane wave per row, four rows per block.  Positions in chunks of 64: ballot the non-zero lanes, the popcount of the lanes
 // below is the slot, a running base carries over the chunks.  No LDS.  tokens and packed must not overlap.
 __global__ __launch_bounds__(256) void k_tokens_compact(const int32_t* __restrict__ tokens, int B, int L, float* __restrict__ fwd_in,

@@ -142,6 +142,13 @@ __device__ __forceinline__ bf16x8 row_shift(const bf16x8& v, bool keep) {
   return __builtin_bit_cast(bf16x8, r);
 }
 
+// 64-bit butterfly exchange over the wave as two 32-bit shuffles (k_screen: the row key; k_molgraph: the sum over the roots)
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int off) {
+  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, off, 64);
+  const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // Levenshtein distance by Hyyro's form of Myers' bit-vector recurrence (k_edit, k_screen): the pattern a[0:m], 1 <= m <= 64, is
 // the match masks Peq[s] (bit j set when a[j] == s); column after column of the dynamic programme is then one text symbol each.
 // State: pv = ~0, mv = 0, distance = m; per text symbol  distance += edit_step(Peq[symbol], edit_top(m), pv, mv).

@@ -1,0 +1,343 @@
+// The single-pass scanner of SMILES token rows that k_smiles.hip (the verdict) and k_molgraph.hip (the verdict and the molecular
+// graph) share, and the graph key's per-root hash.  The rules: include/mdt_hip.h, mdt_smiles_check and mdt_mol_graph / mdt_mol_key.
+// Everything here is __host__ __device__ and touches only the arrays it is handed, so the rules can be run, and their array bounds
+// checked, in a host program without a device.  Included by the two .hip files only (mdt_api.cpp does not see it).
+#pragma once
+
+#include <cstdint>
+#include <hip/hip_runtime.h>
+
+namespace mdt {
+
+// The class bytes (mdt_hip.h, mdt_smiles_check): 0 other | 1 + (c - 'A') | 27 + (c - 'a') | 53 + digit | then  - = # $ : / \ ( ) . [ ] % @ + *
+constexpr int kClsUpper = 1, kClsLower = 27, kClsDigit = 53, kClsBond = 63, kClsOpen = 70, kClsClose = 71, kClsDot = 72,
+              kClsLBracket = 73, kClsRBracket = 74, kClsPercent = 75, kClsAt = 76, kClsPlus = 77, kClsStar = 78;
+constexpr int kClsMinus = kClsBond, kClsColon = kClsBond + 4;
+enum { kPrevStart = 0, kPrevAtom, kPrevBond, kPrevDot, kPrevOpen, kPrevClose };
+constexpr int kSmilesMaxL = 128, kSmilesRings = 100, kSmilesLanes = 64;
+constexpr int kExempt = 127;                                   // capacity of an atom that is not judged (bracket, aromatic, '*')
+constexpr int kNoPosition = 1 << 20;
+
+__host__ __device__ __forceinline__ bool is_upper(int c) { return (unsigned)(c - kClsUpper) < 26u; }
+__host__ __device__ __forceinline__ bool is_lower(int c) { return (unsigned)(c - kClsLower) < 26u; }
+__host__ __device__ __forceinline__ bool is_digit(int c) { return (unsigned)(c - kClsDigit) < 10u; }
+__host__ __device__ __forceinline__ bool is_bond(int c) { return (unsigned)(c - kClsBond) < 7u; }
+// b c n o p s, as letters 0..25
+__host__ __device__ __forceinline__ bool is_aromatic(int k) { return (unsigned)k < 26u && ((0x4E006u >> k) & 1u); }
+// bond code 1..7 = - = # $ : / \ ; 0 = none, which bonds once
+__host__ __device__ __forceinline__ int bond_order(int b) { return b >= 2 && b <= 4 ? b : 1; }
+// The slot of an unbracketed uppercase atom in the max-valence table (B C N O P S F Cl Br I), -1: not an atom outside brackets.
+__host__ __device__ __forceinline__ int organic_slot(int u) {
+  switch (u) {
+    case 'B' - 'A': return 0;
+    case 'C' - 'A': return 1;
+    case 'N' - 'A': return 2;
+    case 'O' - 'A': return 3;
+    case 'P' - 'A': return 4;
+    case 'S' - 'A': return 5;
+    case 'F' - 'A': return 6;
+    case 'I' - 'A': return 9;
+    default: return -1;
+  }
+}
+
+// The per-lane bytes of LDS of k_smiles_check (see the top of k_smiles.hip) for rows of L positions: 4 * odd.
+__host__ __device__ inline int smiles_lane_stride(int L) {
+  const int bytes = L + L + (L + 1) / 2 + 2 * kSmilesRings;
+  const int words = (bytes + 3) / 4;
+  return 4 * (words | 1);
+}
+
+// ---- the atom descriptor and the bond word of the molecular graph (mdt_hip.h, mdt_mol_graph) ----
+constexpr int kMolMaxL = 64;                                   // at most 64 tokens: at most 64 atoms, at most 63 bonds
+constexpr int kMolStar = 26;                                   // '*' in the first-letter field
+constexpr uint32_t kMolAromatic = 1u << 10, kMolBracket = 1u << 11;
+// first: letter 0..25 (either case) or kMolStar; second: 0 none, else 1 + (lowercase letter); charge in [-9, 9]; h in [0, 9];
+// isotope already reduced modulo 2048
+__host__ __device__ __forceinline__ uint32_t mol_descriptor(int first, int second, bool aromatic, bool bracket, int charge, int h,
+                                                            int isotope) {
+  return (uint32_t)first | (uint32_t)second << 5 | (aromatic ? kMolAromatic : 0u) | (bracket ? kMolBracket : 0u) |
+         (uint32_t)(charge + 9) << 12 | (uint32_t)h << 17 | (uint32_t)isotope << 21;
+}
+// bond code (0 none, 1..7 = - = # $ : / \) -> the graph's order: - / \ 1, = 2, # 3, $ 4, ':' 5, none: 5 between two aromatic atoms, else 1
+__host__ __device__ __forceinline__ int mol_bond_order(int code, bool both_aromatic) {
+  if (code == 0) return both_aromatic ? 5 : 1;
+  return code >= 2 && code <= 5 ? code : 1;
+}
+
+// The emitter of the scan that only judges: nothing is recorded, and what the scan computes for it alone is dead code.
+struct SmilesNoEmit {
+  static constexpr bool kEmits = false;
+  __host__ __device__ __forceinline__ void atom(int, uint32_t) {}
+  __host__ __device__ __forceinline__ void bond(int, int, int) {}
+};
+
+// The emitter that records the graph: atoms (descriptors, in order of appearance) and bonds (a | b << 8 | order << 16, in order
+// of creation) into two arrays of L words, and per token position one byte -- the atom's index, bit 7: aromatic -- into `index`
+// (L bytes).  An atom takes at least one token and a bond is made by an atom token or a closing ring token, so the counts stay
+// <= L and <= L - 1.
+struct MolGraphEmit {
+  static constexpr bool kEmits = true;
+  uint32_t* atoms;
+  uint32_t* bonds;
+  uint8_t* index;
+  int natoms = 0, nbonds = 0;
+  __host__ __device__ __forceinline__ void atom(int pos, uint32_t desc) {
+    index[pos] = (uint8_t)(natoms | ((desc & kMolAromatic) ? 0x80 : 0));
+    atoms[natoms++] = desc;
+  }
+  __host__ __device__ __forceinline__ void bond(int pos_a, int pos_b, int code) {
+    const int a = index[pos_a], b = index[pos_b];
+    const int order = mol_bond_order(code, (a & b & 0x80) != 0);
+    bonds[nbonds++] = (uint32_t)(a & 63) | (uint32_t)(b & 63) << 8 | (uint32_t)order << 16;
+  }
+};
+
+// The scan of one row (the rules: mdt_hip.h, mdt_smiles_check).  tok: its n <= L class bytes; cap (L), stack ((L + 1) / 2) and ring
+// (2 * 100) are this row's work arrays, contents irrelevant before and after; limits: the ten maxima, one nibble each.
+// -> the violation (>= 0: MALFORMED there) or -1, and `over`: the lowest overvalent atom or kNoPosition.  emit: told every atom
+// (its token position and descriptor) as it appears, then every bond (the two atoms' positions and the bond code) as it is made;
+// what it was told about a row that turns out malformed or overvalent is the caller's to discard.
+template <class Emit>
+__host__ __device__ inline int smiles_scan(const uint8_t* tok, int8_t* cap, uint8_t* stack, uint8_t* ring, int L, int n,
+                                           uint64_t limits, const uint32_t* __restrict__ elements, int& over_out, Emit& emit) {
+  const int depth_max = (L + 1) / 2;
+  int prev = kPrevStart, bond_prev = kPrevStart, cur = 0, depth = 0, pending = 0;
+  uint64_t open_lo = 0, open_hi = 0;
+  int over = kNoPosition, viol = -1;
+
+  // order `o` more on atom `a`: the capacity goes down; below zero the atom is overvalent, and stays so
+  auto bond_to = [&](int a, int o) {
+    int v = cap[a];
+    if (v == kExempt) return;
+    v -= o;
+    if (v < -100) v = -100;
+    cap[a] = (int8_t)v;
+    if (v < 0 && a < over) over = a;
+  };
+
+  int j = 0;
+  while (j < n && viol < 0) {
+    const int c = tok[j];
+    int atom_cap = -1;                                          // >= 0: tokens [j, next) are an atom of this capacity
+    uint32_t desc = 0;                                          // ... and of this descriptor (used by an emitting scan only)
+    int next = j + 1;
+    if (is_upper(c)) {
+      const int u = c - kClsUpper;
+      int slot = organic_slot(u), second = 0;
+      if (j + 1 < n) {
+        const int d = tok[j + 1];
+        if (u == 'C' - 'A' && d == kClsLower + ('l' - 'a')) { slot = 7; next = j + 2; second = 1 + ('l' - 'a'); }
+        if (u == 'B' - 'A' && d == kClsLower + ('r' - 'a')) { slot = 8; next = j + 2; second = 1 + ('r' - 'a'); }
+      }
+      if (slot < 0) viol = j;
+      else {
+        atom_cap = (int)((limits >> (4 * slot)) & 15u);
+        if constexpr (Emit::kEmits) desc = mol_descriptor(u, second, false, false, 0, 0, 0);
+      }
+    } else if (is_lower(c)) {
+      if (is_aromatic(c - kClsLower)) {
+        atom_cap = kExempt;
+        if constexpr (Emit::kEmits) desc = mol_descriptor(c - kClsLower, 0, true, false, 0, 0, 0);
+      } else {
+        viol = j;
+      }
+    } else if (c == kClsStar) {
+      atom_cap = kExempt;
+      if constexpr (Emit::kEmits) desc = mol_descriptor(kMolStar, 0, false, false, 0, 0, 0);
+    } else if (c == kClsLBracket) {
+      int k = j + 1;
+      int isotope = 0, first = 0, second = 0, charge = 0, hcount = 0;
+      bool aromatic = false;
+      while (k < n && is_digit(tok[k])) {                       // isotope
+        if constexpr (Emit::kEmits) isotope = (isotope * 10 + (tok[k] - kClsDigit)) & 2047;
+        ++k;
+      }
+      if (k >= n) viol = n;
+      else {
+        const int t = tok[k];
+        if (is_upper(t)) {
+          const uint32_t w = elements[t - kClsUpper];
+          const int d = k + 1 < n ? tok[k + 1] : 0;
+          first = t - kClsUpper;
+          if (is_lower(d) && ((w >> (d - kClsLower)) & 1u)) { second = 1 + (d - kClsLower); k += 2; }
+          else if ((w >> 26) & 1u) k += 1;
+          else viol = k;
+        } else if ((is_lower(t) && is_aromatic(t - kClsLower)) || t == kClsStar) {
+          aromatic = t != kClsStar;
+          first = aromatic ? t - kClsLower : kMolStar;
+          k += 1;
+        } else {
+          viol = k;
+        }
+      }
+      if (viol < 0) {
+        if (k < n && tok[k] == kClsAt) {                        // chiral
+          ++k;
+          if (k < n && tok[k] == kClsAt) ++k;
+        }
+        if (k < n && tok[k] == kClsUpper + ('H' - 'A')) {       // hcount
+          ++k;
+          hcount = 1;
+          if (k < n && is_digit(tok[k])) { hcount = tok[k] - kClsDigit; ++k; }
+        }
+        if (k < n && (tok[k] == kClsPlus || tok[k] == kClsMinus)) {   // charge
+          const int sign = tok[k];
+          ++k;
+          charge = 1;
+          if (k < n && (tok[k] == sign || is_digit(tok[k]))) { charge = tok[k] == sign ? 2 : tok[k] - kClsDigit; ++k; }
+          if (sign == kClsMinus) charge = -charge;
+        }
+        if (k < n && tok[k] == kClsColon) {                     // class
+          ++k;
+          if (k >= n) viol = n;
+          else if (!is_digit(tok[k])) viol = k;
+          else
+            while (k < n && is_digit(tok[k])) ++k;
+        }
+        if (viol < 0) {
+          if (k >= n) viol = n;
+          else if (tok[k] != kClsRBracket) viol = k;
+          else {
+            atom_cap = kExempt;
+            next = k + 1;
+            if constexpr (Emit::kEmits) desc = mol_descriptor(first, second, aromatic, true, charge, hcount, isotope);
+          }
+        }
+      }
+    } else if (is_bond(c)) {
+      if (prev == kPrevAtom || prev == kPrevClose || prev == kPrevOpen) {
+        bond_prev = prev;
+        pending = c - kClsBond + 1;
+        prev = kPrevBond;
+      } else {
+        viol = j;
+      }
+    } else if (is_digit(c) || c == kClsPercent) {
+      const bool after_atom = prev == kPrevAtom || prev == kPrevClose;
+      if (!(after_atom || (prev == kPrevBond && (bond_prev == kPrevAtom || bond_prev == kPrevClose)))) {
+        viol = j;
+      } else {
+        int number = c - kClsDigit, last = j;
+        if (c == kClsPercent) {
+          if (j + 1 >= n) viol = n;
+          else if (!is_digit(tok[j + 1])) viol = j + 1;
+          else if (j + 2 >= n) viol = n;
+          else if (!is_digit(tok[j + 2])) viol = j + 2;
+          else {
+            number = 10 * (tok[j + 1] - kClsDigit) + (tok[j + 2] - kClsDigit);
+            last = j + 2;
+          }
+        }
+        if (viol < 0) {                                         // 0 <= number <= 99
+          const bool high = number >= 64;
+          const uint64_t bit = (uint64_t)1 << (number & 63);
+          if (!((high ? open_hi : open_lo) & bit)) {
+            ring[2 * number] = (uint8_t)cur;
+            ring[2 * number + 1] = (uint8_t)pending;
+          } else {
+            const int a = ring[2 * number], b = ring[2 * number + 1];
+            if (a == cur || (b && pending && b != pending && !(b >= 6 && pending >= 6))) {
+              viol = last;
+            } else {
+              const int o = bond_order(b ? b : pending);
+              bond_to(a, o);
+              bond_to(cur, o);
+              emit.bond(a, cur, b ? b : pending);
+            }
+          }
+          if (high) open_hi ^= bit; else open_lo ^= bit;
+          pending = 0;
+          prev = kPrevAtom;
+          next = last + 1;
+        }
+      }
+    } else if (c == kClsOpen) {
+      if ((prev == kPrevAtom || prev == kPrevClose) && depth < depth_max) {   // (depth < depth_max always: two tokens per level)
+        stack[depth++] = (uint8_t)cur;
+        prev = kPrevOpen;
+      } else {
+        viol = j;
+      }
+    } else if (c == kClsClose) {
+      if ((prev == kPrevAtom || prev == kPrevClose) && depth > 0) {
+        cur = stack[--depth];
+        prev = kPrevClose;
+      } else {
+        viol = j;
+      }
+    } else if (c == kClsDot) {
+      if ((prev == kPrevAtom || prev == kPrevClose) && depth == 0) prev = kPrevDot;
+      else viol = j;
+    } else {
+      viol = j;
+    }
+    if (atom_cap >= 0) {                                        // a new atom at position j
+      cap[j] = (int8_t)atom_cap;
+      emit.atom(j, desc);
+      if (prev != kPrevStart && prev != kPrevDot) {
+        const int o = bond_order(pending);
+        bond_to(cur, o);
+        bond_to(j, o);
+        emit.bond(cur, j, pending);
+      }
+      pending = 0;
+      cur = j;
+      prev = kPrevAtom;
+    }
+    j = next;
+  }
+  if (viol < 0 && n > 0 && (!(prev == kPrevAtom || prev == kPrevClose) || depth > 0 || (open_lo | open_hi) != 0)) viol = n;
+
+  over_out = over;
+  return viol;
+}
+
+// ---- the graph key (mdt_hip.h, mdt_mol_key) ----
+constexpr uint64_t kMolRoot = 0xA5A5A5A5A5A5A5A5ull, kMolBondK = 0x100000001B3ull;
+
+// one splitmix64 step, as mdt_tokens_compact's
+__host__ __device__ __forceinline__ uint64_t mol_mix(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// H_root of the graph (atoms[0:n], bonds[0:nb]): n rounds of refinement from the labelling that marks atom `root`.  lab and acc
+// are this root's columns, element a at [a * stride] (n elements each; contents irrelevant before and after).  root >= n marks
+// no atom; the caller discards that result.  Control flow and every bond depend on the graph alone, never on the root: on the
+// device 64 roots walk in step, one per lane, with stride 64.
+__host__ __device__ inline uint64_t mol_root_hash(const uint32_t* __restrict__ atoms, const uint32_t* __restrict__ bonds, int n,
+                                                  int nb, int root, uint64_t* lab, uint64_t* acc, int stride) {
+  for (int a = 0; a < n; ++a) {
+    const uint64_t seed = mol_mix((uint64_t)atoms[a]);
+    lab[a * stride] = a == root ? mol_mix(seed ^ kMolRoot) : seed;
+    acc[a * stride] = 0;
+  }
+  for (int round = 0; round < n; ++round) {
+    for (int e = 0; e < nb; ++e) {
+      const uint32_t w = bonds[e];
+      const int a = (int)(w & 255u), b = (int)((w >> 8) & 255u);
+      const uint64_t ok = (uint64_t)(w >> 16) * kMolBondK;
+      const uint64_t la = lab[a * stride], lb = lab[b * stride];
+      acc[a * stride] += mol_mix(lb + ok);
+      acc[b * stride] += mol_mix(la + ok);
+    }
+    for (int a = 0; a < n; ++a) {
+      lab[a * stride] = mol_mix(lab[a * stride] ^ mol_mix(acc[a * stride]));
+      acc[a * stride] = 0;
+    }
+  }
+  uint64_t h = 0;
+  for (int a = 0; a < n; ++a) h += mol_mix(lab[a * stride]);
+  return h;
+}
+
+// the key from the sum over the roots of mix(H_root); never 0 for a molecule
+__host__ __device__ __forceinline__ uint64_t mol_key_final(uint64_t sum, int n, int nb) {
+  const uint64_t key = mol_mix(sum + (uint64_t)n + ((uint64_t)nb << 32));
+  return key ? key : 1;
+}
+
+}  // namespace mdt

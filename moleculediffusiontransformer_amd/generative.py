@@ -871,6 +871,8 @@ MAX_SCREEN_LENGTH = 1024
 MAX_SCREEN_PROPERTIES = 64
 MAX_EDIT_LENGTH = 64            # the edit distance (csrc/k_edit.hip): one 64-bit word per row, one mask per id
 MAX_EDIT_ID = 64
+MAX_MOL_LENGTH = 64             # the molecular graph and its key (csrc/k_molgraph.hip): at most 64 atoms, one root per lane
+IDENTITIES = ("string", "graph")
 
 
 def _integer_ids(ids, name: str):
@@ -934,6 +936,7 @@ class KnownSet:
         self.lengths = np.ascontiguousarray(lengths[by_key].astype(np.int32))
         self.key = np.ascontiguousarray(key[by_key])
         self._on = {}
+        self._mol_keys = {}
         self._id_range = None
 
     def __len__(self) -> int:
@@ -949,6 +952,30 @@ class KnownSet:
             self._on[device] = (torch.from_numpy(self.key.view(np.int64)).to(device), torch.from_numpy(self.packed).to(device),
                                 torch.from_numpy(self.lengths).to(device))
         return self._on[device]
+
+    def mol_keys(self, vocabulary: "SmilesVocabulary", device) -> Tensor:
+        """The graph keys of the known molecules (mol_key()): int64 (M',) on ``device`` holding the uint64 bits of the sorted unique
+        NON-ZERO keys of the known rows -- rows that are no molecule under ``vocabulary`` (key 0) drop out, respellings of one
+        molecule count once.  Computed once by mdt::mol_graph -> mdt::mol_key and cached per (vocabulary, device).  Sorted ascending
+        AS UNSIGNED, which is what mdt::key_flags' binary search needs: on int64 storage that is a signed sort of (key ^ 2^63) --
+        flipping the top bit maps unsigned order onto signed order -- flipped back afterwards.  ``width`` > 64 raises ValueError."""
+        if not isinstance(vocabulary, SmilesVocabulary):
+            raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+        if self.width > MAX_MOL_LENGTH:
+            raise ValueError(f"known_tokens has rows of {self.width} positions; the graph key takes at most {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        at = (id(vocabulary), device)
+        if at not in self._mol_keys:
+            _, packed, lengths = self.on(device)
+            natoms, atoms, nbonds, bonds, _, _ = torch.ops.mdt.mol_graph(packed, lengths, *vocabulary.on(device))
+            key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+            top = -2 ** 63                                                     # the bit pattern 1 << 63
+            key = torch.unique(key[key != 0] ^ top) ^ top                      # unique() sorts ascending (signed)
+            self._mol_keys[at] = (vocabulary, key)                             # (the vocabulary is held: its id stays its own)
+        return self._mol_keys[at][1]
 
     def id_range(self):
         """(lowest, highest) id of the set, looked up once on the host arrays; (0, 0) for an empty set."""
@@ -1052,12 +1079,14 @@ def _diverse_args(min_distance, min_novelty, known, length=None, tokens=None) ->
 
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
-            min_novelty=1, vocabulary=None) -> Screened:
+            min_novelty=1, vocabulary=None, identity="string") -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
-    ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`."""
+    ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
+    with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     _vocabulary_arg(vocabulary, torch.as_tensor(tokens).shape[1])
+    _identity_arg(identity, vocabulary, torch.as_tensor(tokens).shape[1])
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1073,6 +1102,11 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     reject = None
     if vocabulary is not None:                                   # is it a molecule at all?  bits 32 / 64, never kept
         reject, _ = torch.ops.mdt.smiles_check(packed, length, *vocabulary.on(device))
+    if identity == "graph":                                      # which molecule is it?  bits 4 / 8 by the graph key
+        natoms, atoms, nbonds, bonds, _, _ = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))
+        graph_key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+        known_graph = known.mol_keys(vocabulary, device) if known is not None and len(known) else None
+        reject = reject | torch.ops.mdt.key_flags(graph_key, N, known_graph)
     if not diverse:
         if reject is None:
             status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
@@ -1123,7 +1157,7 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 
 
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
-                          keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None,
+                          keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
                           **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
@@ -1146,9 +1180,20 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     Both are ints >= 1; (1, 1) is screen_tokens itself, the same launches in the same order.  Either above 1 routes the selection to
     mdt::screen_select_diverse and needs rows of at most 64 positions and ids in [0, 64), in the tokens (one aminmax: the one host
     synchronisation added) and in the known set (checked once per KnownSet) -- all refused with ValueError before anything is
-    launched.  Rows of more than one 64-bit word are out of scope.  Returns Screened, its six fields as screen_tokens'."""
+    launched.  Rows of more than one 64-bit word are out of scope.
+
+    ``identity``: what "the same molecule" means for status bits 4 (duplicate) and 8 (known).  ``"string"`` (the default): equality
+    of the compacted id rows, exactly the launches made without the keyword, in the same order.  ``"graph"``: equality of the graph
+    key of mol_key() as well, so OCC after CCO is a duplicate, and known when the known set spells it C(O)C -- see mol_key() for
+    what the key is and is not (a refinement hash, not a canonical form; no hydrogen, aromaticity or stereo normalisation).  It needs
+    a ``vocabulary`` and rows of at most 64 positions, refused with ValueError before anything is launched.  After
+    mdt::smiles_check it runs mdt::mol_graph -> mdt::mol_key -> mdt::key_flags (the known set's keys: KnownSet.mol_keys(), computed
+    once) and ORs the flags into the `reject` byte of the selection.  Equal strings are equal graphs, so graph mode only adds bits;
+    of the spellings of one molecule in a group the lowest c stands for all.  ``min_distance`` and ``min_novelty`` stay measured
+    in edits on the STRINGS in both modes, and the novel fraction stays ``((status & 8) == 0).float().mean()``.
+    Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
-                   vocabulary=vocabulary, **screen_tokens_kwargs)
+                   vocabulary=vocabulary, identity=identity, **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1322,6 +1367,77 @@ def smiles_check(tokens, vocabulary: "SmilesVocabulary", device):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# which molecule is it?  the graph behind a row and its spelling-invariant key (csrc/k_molgraph.hip): at most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+def _identity_arg(identity, vocabulary, length: int) -> None:
+    """The refusals of ``identity=``, before anything is launched."""
+    if identity not in IDENTITIES:
+        raise ValueError(f"identity must be one of {IDENTITIES}, got {identity!r}")
+    if identity == "graph":
+        if vocabulary is None:
+            raise ValueError('identity="graph" reads the rows as strings: give a vocabulary')
+        if length > MAX_MOL_LENGTH:
+            raise ValueError(f"tokens has rows of {length} positions; the graph key takes at most {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+
+
+def _mol_rows(tokens, vocabulary, device):
+    """The refusals of mol_graph() / mol_key(), then the compacted rows on the device."""
+    tok = _integer_ids(tokens, "tokens")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if tok.shape[1] < 1:
+        raise ValueError("tokens must hold at least one position per row")
+    if tok.shape[1] > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {tok.shape[1]} positions; the graph key takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    packed, n, _, _ = torch.ops.mdt.tokens_compact(torch.as_tensor(tok).to(torch.device(device)), 0, 1.0)
+    return packed, n
+
+
+def mol_graph(tokens, vocabulary: "SmilesVocabulary", device):
+    """The molecular graph behind each row -> (natoms int64 (R,), atoms int64 (R, L), nbonds int64 (R,), bonds int64 (R, L),
+    status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer dtype, zeros anywhere, read through ``vocabulary``.
+
+    ``status`` / ``position`` are smiles_check()'s.  For a row of status 0: ``atoms[r, :natoms[r]]`` are the atoms in order of
+    appearance, one 32-bit descriptor each -- bits 0..4 the symbol's first letter (0..25; 26 for ``*``), 5..9 its second letter + 1
+    (0: none), 10 aromatic (lower case), 11 bracket atom, 12..16 formal charge + 9, 17..20 bracket H count, 21..31 isotope modulo
+    2048; chirality and atom class are ignored -- and ``bonds[r, :nbonds[r]]`` the bonds in order of creation,
+    ``a | b << 8 | order << 16`` with ``- / \\`` 1, ``=`` 2, ``#`` 3, ``$`` 4, ``:`` 5, no symbol 5 between two aromatic atoms and
+    1 otherwise.  A row of status != 0 and an empty row have no atoms; words beyond the counts are 0.  Atom and bond counts are what
+    one filters on next.  The definition is written out at mdt_mol_graph in include/mdt_hip.h; it sees what smiles_check() sees and
+    nothing more: no hydrogens beyond the bracket count, no aromaticity perception, no stereo.
+    L <= 64 (64 tokens: at most 64 atoms, 63 bonds); the refusals are smiles_check()'s and L > 64, with ValueError before anything
+    is launched.  Sequence: mdt::tokens_compact -> mdt::mol_graph."""
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    out = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    natoms, atoms, nbonds, bonds, status, position = out
+    return natoms.long(), atoms.long() & 0xFFFFFFFF, nbonds.long(), bonds.long(), status.long(), position.long()
+
+
+def mol_key(tokens, vocabulary: "SmilesVocabulary", device):
+    """Which molecule is each row?  -> (key int64 (R,): the uint64 bits, status int64 (R,), position int64 (R,)) for raw (R, L) ids
+    of any integer dtype, zeros anywhere.  ``key`` is a 64-bit key of the molecular graph behind the row (mol_graph()) that does not
+    depend on how the row spells it: start atom, branch order, ring numbers (``%nn`` included), which end of a ring closure carries
+    the bond symbol, an explicit ``-``, the order of dotted components.  OCC and CCO have one key; so have C1CC1C and CC1CC1.
+    KEY 0 MEANS "NO MOLECULE": an empty row, or a row whose ``status`` (smiles_check()'s, with its ``position``) is not 0.
+
+    The key is a rooted refinement hash (mdt_mol_key in include/mdt_hip.h has every step): for each atom as root, n rounds of
+    neighbourhood hashing from the atom descriptors, all combinations sums mod 2^64.  Its limits:
+    equal graphs always give equal keys; unequal graphs can collide in principle -- the key is a refinement hash, not a canonical
+    form (none was found among 2,100 random graphs and the 684 small graphs it was tried on, and the rooting separates cubane from
+    cuneane); and it is not RDKit's canonical SMILES, which the reference's callers would get (Chem.MolFromSmiles,
+    generative.py:954-994).  These count as different molecules: [CH4] and C (no hydrogen or bracket normalisation);
+    C1=CC=CC=C1 and c1ccccc1 (no aromaticity perception).  Stereo is ignored: F/C=C/F equals F/C=C\\F.
+    L <= 64; the refusals are smiles_check()'s and L > 64, with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_key."""
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+    return key, status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:
@@ -1371,13 +1487,13 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
                       keep: int, *, cond_scale=1.0, timesteps: int = 100, noise=None, **screen_tokens_kwargs) -> Screened:
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
-    ``min_distance`` / ``min_novelty`` / ``vocabulary``, with which the tokens go to screen_tokens_diverse instead;
+    ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
-                                         "sigma_schedule", "min_distance", "min_novelty", "vocabulary"}
+                                         "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -1390,6 +1506,10 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     _vocabulary_arg(vocabulary, model.max_length)
     if vocabulary is not None:
         diverse, filters["vocabulary"] = True, vocabulary
+    identity = screen_tokens_kwargs.pop("identity", "string")
+    _identity_arg(identity, vocabulary, model.max_length)
+    if identity != "string":                                     # ("string": the calls made without the keyword)
+        diverse, filters["identity"] = True, identity
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

@@ -19,6 +19,8 @@ fake / meta tensors).
     screen_select_diverse   the same with novelty as an edit distance and the K best that lie min_distance edits apart
     screen_select_reject / screen_select_diverse_reject   the two selections with a per-row `reject` byte OR-ed into the status
     smiles_check        well-formedness and valence of compacted id rows: status 0 / 32 / 64 and a position (csrc/k_smiles.hip)
+    mol_graph / mol_key / key_flags   the molecular graph behind a row, its spelling-invariant 64-bit key, and the duplicate / known
+                        flags by that key (csrc/k_molgraph.hip)
     edit_distance       Levenshtein distance between compacted id rows, row by row (csrc/k_edit.hip)
     edit_nearest        per row the nearest row of a known set: its distance and its (lowest) index
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
@@ -712,6 +714,112 @@ def smiles_check(packed: Tensor, length: Tensor, classes: Tensor, max_valence: T
 def _(packed, length, classes, max_valence, elements):
     R = packed.shape[0]
     return packed.new_empty(R, dtype=torch.uint8), packed.new_empty(R, dtype=torch.int32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# graph identity of compacted id rows (csrc/k_molgraph.hip): at most 64 positions, ids in [0, 256)
+@custom_op("mdt::mol_graph", mutates_args=())
+def mol_graph(packed: Tensor, length: Tensor, classes: Tensor, max_valence: Tensor,
+              elements: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (natoms int32 (R,), atoms int32 (R, L): the uint32 descriptors' bits, nbonds int32 (R,), bonds int32 (R, L):
+    a | b << 8 | order << 16, status uint8 (R,), position int32 (R,)): the molecular graph of every row that passes
+    mdt::smiles_check's rules (status and position are that op's), as mdt_mol_graph defines it (include/mdt_hip.h).  Rows of status
+    != 0 and empty rows have no atoms; words beyond the counts are 0.  Arguments as mdt::smiles_check, rows of at most 64 positions."""
+    dev = _hip(packed, length, classes, max_valence, elements)
+    lib = rt.load_library()
+    op = "mdt::mol_graph"
+    if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
+        raise RuntimeError(f"{op}: packed must be int32 rows (R, L) with one int32 length each (as mdt::tokens_compact returns them)")
+    R, L = packed.shape
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: packed has {L} positions per row, the graph takes 1 to {rt.MOL_MAX_LENGTH}")
+    if classes.dtype != torch.uint8 or tuple(classes.shape) != (256,):
+        raise RuntimeError(f"{op}: classes must be uint8 (256,)")
+    if max_valence.dtype != torch.uint8 or tuple(max_valence.shape) != (10,):
+        raise RuntimeError(f"{op}: max_valence must be uint8 (10,): B C N O P S F Cl Br I")
+    if elements.dtype != torch.int32 or tuple(elements.shape) != (26,):
+        raise RuntimeError(f"{op}: elements must be int32 (26,): one mask per uppercase letter")
+    packed, length = packed.contiguous(), length.contiguous()
+    classes, max_valence, elements = classes.contiguous(), max_valence.contiguous(), elements.contiguous()
+    natoms = torch.zeros(R, dtype=torch.int32, device=dev)
+    atoms = torch.zeros(R, L, dtype=torch.int32, device=dev)
+    nbonds = torch.zeros(R, dtype=torch.int32, device=dev)
+    bonds = torch.zeros(R, L, dtype=torch.int32, device=dev)
+    status = torch.zeros(R, dtype=torch.uint8, device=dev)
+    position = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_graph(rt.ptr(packed), rt.ptr(length), L, R, rt.ptr(classes), rt.ptr(max_valence), rt.ptr(elements),
+                                       rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), rt.ptr(status),
+                                       rt.ptr(position), rt.current_stream()))
+    return natoms, atoms, nbonds, bonds, status, position
+
+
+@mol_graph.register_fake
+def _(packed, length, classes, max_valence, elements):
+    R, L = packed.shape
+    return (packed.new_empty(R, dtype=torch.int32), packed.new_empty(R, L, dtype=torch.int32),
+            packed.new_empty(R, dtype=torch.int32), packed.new_empty(R, L, dtype=torch.int32),
+            packed.new_empty(R, dtype=torch.uint8), packed.new_empty(R, dtype=torch.int32))
+
+
+@custom_op("mdt::mol_key", mutates_args=())
+def mol_key(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor) -> Tensor:
+    """-> key int64 (R,): the uint64 bits of mdt_mol_key's graph key (include/mdt_hip.h) for the graph arrays of mdt::mol_graph;
+    0 where natoms is 0 (no molecule)."""
+    dev = _hip(natoms, atoms, nbonds, bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_key"
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the key takes 1 to {rt.MOL_MAX_LENGTH}")
+    natoms, atoms, nbonds, bonds = natoms.contiguous(), atoms.contiguous(), nbonds.contiguous(), bonds.contiguous()
+    key = torch.zeros(R, dtype=torch.int64, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_key(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, rt.ptr(key),
+                                     rt.current_stream()))
+    return key
+
+
+@mol_key.register_fake
+def _(natoms, atoms, nbonds, bonds):
+    return atoms.new_empty(atoms.shape[0], dtype=torch.int64)
+
+
+@custom_op("mdt::key_flags", mutates_args=())
+def key_flags(key: Tensor, candidates: int, known_key: Optional[Tensor]) -> Tensor:
+    """-> flags uint8 (N * G,), row c * G + g: 4 (duplicate) where a candidate c' < c of the same group has the same non-zero key,
+    8 (known) where the non-zero key is in ``known_key`` (int64 (M,): uint64 bits ASCENDING as unsigned, or None).  Key 0: neither."""
+    dev = _hip(key, known_key)
+    lib = rt.load_library()
+    op = "mdt::key_flags"
+    N = candidates
+    if key.dim() != 1 or key.dtype != torch.int64:
+        raise RuntimeError(f"{op}: key must be int64 (N * G,)")
+    rows = key.numel()
+    if not 1 <= N <= rt.MAX_KEY_CANDIDATES or rows % N:
+        raise RuntimeError(f"{op}: candidates = {N} must lie in [1, {rt.MAX_KEY_CANDIDATES}] and divide the {rows} rows")
+    M = 0
+    if known_key is not None:
+        if known_key.dim() != 1 or known_key.dtype != torch.int64:
+            raise RuntimeError(f"{op}: known_key must be int64 (M,)")
+        M, known_key = known_key.numel(), known_key.contiguous()
+    key = key.contiguous()
+    flags = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    if rows:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_key_flags(rt.ptr(key), N, rows // N, rt.ptr(known_key) if M else 0, M, rt.ptr(flags), rt.current_stream()))
+    return flags
+
+
+@key_flags.register_fake
+def _(key, candidates, known_key):
+    return key.new_empty(key.shape[0], dtype=torch.uint8)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -49,6 +49,8 @@ SCREEN_EMPTY, SCREEN_NONFINITE, SCREEN_DUPLICATE, SCREEN_KNOWN = 1, 2, 4, 8     
 SCREEN_CLOSE = 16                # ... set by mdt_screen_select_diverse only
 SCREEN_MALFORMED, SCREEN_OVERVALENT = 32, 64     # ... set by mdt_smiles_check, handed to the selections as `reject`
 SMILES_MAX_LENGTH = 128          # mdt_smiles_check takes rows of at most 128 positions, ids in [0, 256)
+MAX_KEY_CANDIDATES = 1024        # mdt_key_flags: candidates per group
+MOL_MAX_LENGTH = 64              # mdt_mol_graph / mdt_mol_key: at most 64 positions (64 atoms, one root per lane)
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
 
@@ -117,6 +119,9 @@ SYMBOLS = {
     "mdt_screen_select_reject": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mdt_screen_select_diverse_reject": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "mdt_smiles_check": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mdt_mol_graph": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mdt_mol_key": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "mdt_key_flags": (_I, [_P, _I, _I, _P, _I, _P, _P]),
     "mdt_edit_distance_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "mdt_edit_nearest": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "mdt_timer_create": (_P, [_I]),
