@@ -770,6 +770,61 @@ int mdt_mol_key(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbo
 int mdt_key_flags(const uint64_t *key, int32_t N, int32_t G, const uint64_t *known_key, int32_t M, uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* Tanimoto similarity on graph fingerprints (csrc/k_molfp.hip, csrc/k_screen.hip); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* How similar are two molecules?  The edit distance above measures how two STRINGS are written (OCC lies two edits from CCO, the
+ * same molecule); the reference's callers compare graphs (view_difference, generative.py:932-945: a maximum common substructure).
+ * This is a precisely defined answer on the graph of mdt_mol_graph: a circular fingerprint of MDT_FP_BITS bits and the Tanimoto
+ * similarity of two fingerprints.  Everything is integer arithmetic mod 2^64 and every result is exact.
+ *
+ * The fingerprint (mdt_mol_fp).  Inputs: the graph arrays natoms, atoms, nbonds, bonds of mdt_mol_graph (device pointers), rows of
+ * width 1 <= L <= 64.  mix and K = 0x100000001B3 as in mdt_mol_key; there is no root.
+ *  - Degree: deg[a] = the number of bond-list entries that name atom a, counted per END: a bond listed twice counts twice, and an
+ *    entry (a, a), which mdt_mol_graph never writes, counts twice at a.
+ *  - Round 0: id_0[a] = mix(atoms[a] | (uint64)deg[a] << 32).
+ *  - Rounds r = 1..radius: acc[a] = the sum, over the bonds at a to neighbour b, of mix(id_{r-1}[b] + order * K) (an entry (a, a)
+ *    adds its term twice); then id_r[a] = mix(id_{r-1}[a] ^ mix(acc[a])) for all atoms at once.
+ *  - The fingerprint: MDT_FP_BITS = 1024 bits as 16 uint64 words.  For every atom a < natoms and every r in 0..radius bit
+ *    id_r[a] & 1023 is set: word bit >> 6, bit bit & 63 of that word.  count = the number of set bits.  0 <= radius <= 3.
+ *  - Rows without a molecule: natoms == 0 (an empty row, a row of status != 0) gives an all-zero fingerprint and count 0; so does a
+ *    row whose counts lie outside [0, L] or whose bonds name an atom >= natoms (the rule of mdt_mol_key).
+ * Tanimoto: inter = popcount(A & B), union = |A| + |B| - inter; the similarity is inter / union, and 0 when union == 0.  Fractions
+ * are compared exactly, by cross-multiplication, never as floats.  A threshold crosses this interface as an integer sim_num in
+ * [1, MDT_FP_SIM_DEN]: "at least as similar as the threshold" means union > 0 && inter * 65536 >= sim_num * union (32 bits suffice).
+ * What this is NOT.  It is not RDKit's Morgan or ECFP fingerprint, and bits are not comparable with either.  The round-0 invariant
+ * holds no implicit hydrogens (only what the descriptor holds).  Duplicate substructures are not removed (every atom sets a bit in
+ * every round).  There is no aromaticity perception (C1=CC=CC=C1 and c1ccccc1 differ) and no stereo.  Folding to 1024 bits can make
+ * unequal environments share a bit, so unequal molecules can have similarity 1.  Equal graphs always give equal fingerprints: every
+ * combination over the bonds is a sum mod 2^64 and the bit set does not depend on atom numbering.
+ * fp uint64 (R,16), count int32 (R).  R == 0 launches nothing. */
+#define MDT_FP_BITS 1024
+#define MDT_FP_SIM_DEN 65536
+int mdt_mol_fp(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+               int32_t radius, uint64_t *fp, int32_t *count, void *stream);
+/* inter[r], uni[r] (int32) of row r of a_fp against row r of b_fp, both uint64 (R,16); the popcounts are taken from the words. */
+int mdt_fp_tanimoto_rows(const uint64_t *a_fp, const uint64_t *b_fp, int32_t R, int32_t *inter, int32_t *uni, void *stream);
+/* The known rows that one workgroup of mdt_fp_nearest walks; the known set is split into chunks of this many over the grid. */
+#define MDT_FP_KNOWN_CHUNK 512
+/* Per query row r of fp (R,16): index[r] = the LOWEST of the M >= 1 rows of known_fp uint64 (M,16) that attains the largest
+ * similarity to it, inter[r] and uni[r] the counts of that pair (similarity 0 everywhere, e.g. an all-zero query: index 0).  The
+ * chunks' results are combined as the maximum of (floor(inter * 2^31 / union) << 32) | (0xFFFFFFFF - index), one unsigned 64-bit
+ * word per query: for unions up to 2048 distinct fractions differ by at least 2^-22, so the quotient orders them strictly and maps
+ * equal fractions to equal values, and the result does not depend on how the work is split or scheduled.  best: workspace of R
+ * 64-bit words, allocated by the caller, contents irrelevant before and after.  R <= 65535 * 64. */
+int mdt_fp_nearest(const uint64_t *fp, int32_t R, const uint64_t *known_fp, int32_t M, uint64_t *best, int32_t *inter, int32_t *uni,
+                   int32_t *index, void *stream);
+/* mdt_screen_select_diverse_reject with similarity as a second way to be CLOSE: fp uint64 (N*G,16) and fp_count int32 (N*G) as
+ * mdt_mol_fp writes them, 1 <= sim_num <= MDT_FP_SIM_DEN.  In step 2 a candidate is kept when, to every candidate kept before it,
+ * its edit distance is >= min_distance (as there; min_distance <= 1 filters nothing) AND its similarity is not "at least
+ * sim_num / 65536"; bit 16 goes to what either test passed over.  A row without a molecule has an all-zero fingerprint and is
+ * similar to nothing.  fp == NULL and fp_count == NULL: mdt_screen_select_diverse_reject itself, the same launch, sim_num ignored. */
+int mdt_screen_select_similar(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len,
+                              int32_t M, int32_t K, const int32_t *known_dist, int32_t min_novelty, int32_t min_distance,
+                              const uint8_t *reject, const uint64_t *fp, const int32_t *fp_count, int32_t sim_num, uint8_t *status,
+                              int32_t *index, int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */
 /* ------------------------------------------------------------------ */
 typedef struct mdt_timer mdt_timer;

@@ -178,12 +178,17 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
 // it is CLOSE, any other is kept while slots are left.  The pass runs to the end of the order, so the CLOSE bit of a candidate does
 // not depend on where the slots ran out.  Inside a step the candidate is the pattern -- its 64 match masks in LDS, read by every
 // thread at the same address -- and the threads share out the kept rows as texts; one block-wide "any closer".
+// kFp (mdt_screen_select_similar): "closer" also when the candidate's fingerprint (fp (N*G,16), its popcount fp_count) is at least
+// sim_num / 65536 Tanimoto-similar to a kept one's; the threads share out the kept rows in the same way, 16 words per pair.
+// Without kFp the fingerprint arguments are not looked at and the code is the one that ran before the switch existed.
+template <bool kFp>
 __global__ __launch_bounds__(256) void k_screen_select_diverse(
     const float* __restrict__ score, const uint64_t* __restrict__ key, const int32_t* __restrict__ packed,
     const int32_t* __restrict__ length, int L, int N, int G, const uint64_t* __restrict__ known_key,
     const int32_t* __restrict__ known_packed, const int32_t* __restrict__ known_len, int M, int K,
     const int32_t* __restrict__ known_dist, int min_novelty, int min_distance, const uint8_t* __restrict__ reject,
-    uint8_t* __restrict__ status, int32_t* __restrict__ index, int32_t* __restrict__ count) {
+    const uint64_t* __restrict__ fp, const int32_t* __restrict__ fp_count, uint32_t sim_num, uint8_t* __restrict__ status,
+    int32_t* __restrict__ index, int32_t* __restrict__ count) {
   __shared__ uint64_t s_key[kScreenMaxN];
   __shared__ float s_score[kScreenMaxN];
   __shared__ int32_t s_len[kScreenMaxN];
@@ -232,6 +237,19 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
     const int c = s_order[e];
     const int m = s_len[c];                                      // >= 1: an empty row is not eligible
     int closer = 0;
+    if constexpr (kFp) {
+      __syncthreads();                                           // (s_kept as thread 0 left it in the step before)
+      const uint64_t* mine = fp + ((int64_t)c * G + g) * 16;
+      const int mine_count = fp_count[(int64_t)c * G + g];
+      for (int t = tid; t < kept && !closer; t += 256) {
+        const int64_t o = (int64_t)s_kept[t] * G + g;
+        const uint64_t* other = fp + o * 16;
+        int inter = 0;
+        for (int w = 0; w < 16; ++w) inter += __popcll(mine[w] & other[w]);
+        const int uni = mine_count + fp_count[o] - inter;
+        closer = uni > 0 && (uint32_t)inter * (uint32_t)MDT_FP_SIM_DEN >= sim_num * (uint32_t)uni;
+      }
+    }
     if (min_distance > 1 && kept > 0) {
       const int32_t* row = packed + ((int64_t)c * G + g) * L;
       if (tid < 64) {                                            // the mask of symbol tid
@@ -241,7 +259,7 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
       }
       __syncthreads();
       const unsigned long long top = edit_top(m);
-      for (int t = tid; t < kept && !closer; t += 256) {
+      for (int t = tid; t < kept && !closer; t += 256) {      // (kFp: a thread that found a similar one skips this)
         const int o = s_kept[t];
         const int n = s_len[o];
         const int32_t* text = packed + ((int64_t)o * G + g) * L;
@@ -359,10 +377,34 @@ int mdt_screen_select_diverse_reject(const float* score, const uint64_t* key, co
   if (M > 0 && (!known_key || !known_packed || !known_len))
     return bad("mdt_screen_select_diverse: the known-set pointers may be NULL only when M == 0");
   if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select_diverse: null pointer");
-  hipLaunchKernelGGL(mdt::k_screen_select_diverse, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length,
-                     L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, status, index,
-                     count);
+  hipLaunchKernelGGL(mdt::k_screen_select_diverse<false>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed,
+                     length, L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject,
+                     (const uint64_t*)nullptr, (const int32_t*)nullptr, 0u, status, index, count);
   return finish("mdt_screen_select_diverse");
+}
+
+int mdt_screen_select_similar(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
+                              int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty, int32_t min_distance,
+                              const uint8_t* reject, const uint64_t* fp, const int32_t* fp_count, int32_t sim_num, uint8_t* status,
+                              int32_t* index, int32_t* count, void* stream) {
+  if (!fp && !fp_count)                                         // no fingerprints: the selection as it was, the same launch
+    return mdt_screen_select_diverse_reject(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, K,
+                                            known_dist, min_novelty, min_distance, reject, status, index, count, stream);
+  if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select_similar: need 1 <= N <= 1024 candidates per group");
+  if (K < 1 || K > N) return bad("mdt_screen_select_similar: need 1 <= K <= N");
+  if (L < 1 || L > 64) return bad("mdt_screen_select_similar: need 1 <= L <= 64 positions per row");
+  if (M < 0) return bad("mdt_screen_select_similar: need M >= 0");
+  if (sim_num < 1 || sim_num > MDT_FP_SIM_DEN) return bad("mdt_screen_select_similar: need 1 <= sim_num <= 65536");
+  if (G <= 0) return 0;
+  if (M > 0 && (!known_key || !known_packed || !known_len))
+    return bad("mdt_screen_select_similar: the known-set pointers may be NULL only when M == 0");
+  if (!score || !key || !packed || !length || !status || !index || !count || !fp || !fp_count)
+    return bad("mdt_screen_select_similar: null pointer");
+  hipLaunchKernelGGL(mdt::k_screen_select_diverse<true>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed,
+                     length, L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, fp,
+                     fp_count, (uint32_t)sim_num, status, index, count);
+  return finish("mdt_screen_select_similar");
 }
 
 int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,

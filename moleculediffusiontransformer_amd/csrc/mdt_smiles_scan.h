@@ -340,4 +340,87 @@ __host__ __device__ __forceinline__ uint64_t mol_key_final(uint64_t sum, int n, 
   return key ? key : 1;
 }
 
+// ---- the graph fingerprint and its Tanimoto similarity (mdt_hip.h, mdt_mol_fp / mdt_fp_nearest) ----
+constexpr int kFpBits = 1024, kFpWords = kFpBits / 64, kFpDwords = kFpBits / 32, kFpMaxRadius = 3;
+constexpr uint32_t kFpSimDen = 65536;
+
+__host__ __device__ __forceinline__ uint64_t fp_seed(uint32_t atom, int deg) { return mol_mix((uint64_t)atom | (uint64_t)deg << 32); }
+// what a bond of this order adds to the sum of the atom at its one end, given the label of the atom at its other end
+__host__ __device__ __forceinline__ uint64_t fp_bond_term(uint64_t other, uint32_t order) {
+  return mol_mix(other + (uint64_t)order * kMolBondK);
+}
+__host__ __device__ __forceinline__ uint64_t fp_next(uint64_t id, uint64_t acc) { return mol_mix(id ^ mol_mix(acc)); }
+__host__ __device__ __forceinline__ int fp_bit(uint64_t id) { return (int)(id & (uint64_t)(kFpBits - 1)); }
+__host__ __device__ __forceinline__ int fp_popc64(uint64_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __popcll(w);
+#else
+  return __builtin_popcountll(w);
+#endif
+}
+// Is (n, nb, bonds[0:nb]) the graph of a row of width L?  Counts inside [1, L] x [0, L], every bond end below n.
+__host__ __device__ inline bool fp_graph_ok(const uint32_t* bonds, int n, int nb, int L) {
+  if (n < 1 || n > L || nb < 0 || nb > L) return false;
+  for (int e = 0; e < nb; ++e)
+    if ((int)(bonds[e] & 255u) >= n || (int)((bonds[e] >> 8) & 255u) >= n) return false;
+  return true;
+}
+// The fingerprint of one row, atom after atom: fp[0:16], returns the number of set bits.  This is the definition in the order it is
+// written down; k_mol_fp computes the same with one atom per lane.  atoms[0:n], bonds[0:nb] are read, nothing beyond.
+__host__ __device__ inline int fp_row(const uint32_t* atoms, const uint32_t* bonds, int n, int nb, int L, int radius, uint64_t* fp) {
+  for (int w = 0; w < kFpWords; ++w) fp[w] = 0;
+  if (!fp_graph_ok(bonds, n, nb, L)) return 0;
+  uint64_t id[kMolMaxL], acc[kMolMaxL];
+  int deg[kMolMaxL];
+  for (int a = 0; a < n; ++a) deg[a] = 0;
+  for (int e = 0; e < nb; ++e) {
+    ++deg[bonds[e] & 255u];
+    ++deg[(bonds[e] >> 8) & 255u];
+  }
+  for (int a = 0; a < n; ++a) id[a] = fp_seed(atoms[a], deg[a]);
+  for (int r = 0;; ++r) {
+    for (int a = 0; a < n; ++a) fp[fp_bit(id[a]) >> 6] |= 1ull << (fp_bit(id[a]) & 63);
+    if (r == radius) break;
+    for (int a = 0; a < n; ++a) acc[a] = 0;
+    for (int e = 0; e < nb; ++e) {
+      const uint32_t w = bonds[e];
+      const int a = (int)(w & 255u), b = (int)((w >> 8) & 255u);
+      const uint64_t ta = fp_bond_term(id[b], w >> 16), tb = fp_bond_term(id[a], w >> 16);
+      acc[a] += ta;
+      acc[b] += tb;
+    }
+    for (int a = 0; a < n; ++a) id[a] = fp_next(id[a], acc[a]);
+  }
+  int count = 0;
+  for (int w = 0; w < kFpWords; ++w) count += fp_popc64(fp[w]);
+  return count;
+}
+// inter = |A & B|, uni = |A| + |B| - inter for two fingerprints of 16 words
+__host__ __device__ inline void fp_counts(const uint64_t* a, const uint64_t* b, int& inter, int& uni) {
+  int i = 0, ca = 0, cb = 0;
+  for (int w = 0; w < kFpWords; ++w) {
+    i += fp_popc64(a[w] & b[w]);
+    ca += fp_popc64(a[w]);
+    cb += fp_popc64(b[w]);
+  }
+  inter = i;
+  uni = ca + cb - i;
+}
+// "at least as similar as sim_num / 65536": exact, inside 32 bits (inter <= 1024, uni <= 2048, sim_num <= 65536)
+__host__ __device__ __forceinline__ bool fp_at_least(int inter, int uni, uint32_t sim_num) {
+  return uni > 0 && (uint32_t)inter * kFpSimDen >= sim_num * (uint32_t)uni;
+}
+// inter_a / uni_a > inter_b / uni_b, exact by cross-multiplication.  b is a running best that starts at (0, 1); a may be (0, 0) --
+// two empty fingerprints, similarity 0 -- which is never greater.
+__host__ __device__ __forceinline__ bool fp_greater(uint32_t inter_a, uint32_t uni_a, uint32_t inter_b, uint32_t uni_b) {
+  return inter_a * uni_b > inter_b * uni_a;
+}
+// One word per (similarity, known index) whose unsigned maximum is "the largest similarity, the lowest index": the quotient
+// floor(inter * 2^31 / uni) orders distinct fractions of denominators <= 2048 strictly (they differ by >= 2^-22) and maps equal
+// fractions to equal values.
+__host__ __device__ __forceinline__ uint64_t fp_pack(int inter, int uni, uint32_t index) {
+  const uint64_t q = uni > 0 ? ((uint64_t)inter << 31) / (uint64_t)uni : 0;
+  return q << 32 | (uint64_t)(0xFFFFFFFFu - index);
+}
+
 }  // namespace mdt

@@ -873,6 +873,8 @@ MAX_EDIT_LENGTH = 64            # the edit distance (csrc/k_edit.hip): one 64-bi
 MAX_EDIT_ID = 64
 MAX_MOL_LENGTH = 64             # the molecular graph and its key (csrc/k_molgraph.hip): at most 64 atoms, one root per lane
 IDENTITIES = ("string", "graph")
+FP_SIM_DEN = 65536              # a similarity threshold crosses into the kernels as sim_num / 65536 (MDT_FP_SIM_DEN)
+MAX_FP_RADIUS = 3               # the fingerprint (csrc/k_molfp.hip): rounds 0 .. radius, radius in [0, 3]
 
 
 def _integer_ids(ids, name: str):
@@ -937,6 +939,7 @@ class KnownSet:
         self.key = np.ascontiguousarray(key[by_key])
         self._on = {}
         self._mol_keys = {}
+        self._fingerprints = {}
         self._id_range = None
 
     def __len__(self) -> int:
@@ -976,6 +979,27 @@ class KnownSet:
             key = torch.unique(key[key != 0] ^ top) ^ top                      # unique() sorts ascending (signed)
             self._mol_keys[at] = (vocabulary, key)                             # (the vocabulary is held: its id stays its own)
         return self._mol_keys[at][1]
+
+    def fingerprints(self, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+        """The fingerprints of the known molecules (mol_fingerprint()): (fp int64 (M, 16): the uint64 bits, count int32 (M,)) on
+        ``device`` for ALL rows of ``packed``, in that order, so an index into them is an index into ``packed``.  Rows that are no
+        molecule under ``vocabulary`` have an all-zero fingerprint (similarity 0 to everything).  Computed once by mdt::mol_graph ->
+        mdt::mol_fp and cached per (vocabulary, device, radius).  ``width`` > 64 raises ValueError."""
+        if not isinstance(vocabulary, SmilesVocabulary):
+            raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+        if self.width > MAX_MOL_LENGTH:
+            raise ValueError(f"known_tokens has rows of {self.width} positions; the fingerprint takes at most {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+        radius = _radius_arg(radius)
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        at = (id(vocabulary), device, radius)
+        if at not in self._fingerprints:
+            _, packed, lengths = self.on(device)
+            natoms, atoms, nbonds, bonds, _, _ = torch.ops.mdt.mol_graph(packed, lengths, *vocabulary.on(device))
+            self._fingerprints[at] = (vocabulary, torch.ops.mdt.mol_fp(natoms, atoms, nbonds, bonds, radius))
+        return self._fingerprints[at][1]
 
     def id_range(self):
         """(lowest, highest) id of the set, looked up once on the host arrays; (0, 0) for an empty set."""
@@ -1077,9 +1101,43 @@ def _diverse_args(min_distance, min_novelty, known, length=None, tokens=None) ->
     return True
 
 
+def _radius_arg(radius) -> int:
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_FP_RADIUS:
+        raise ValueError(f"the fingerprint radius must be an int in [0, {MAX_FP_RADIUS}], got {radius!r}")
+    return radius
+
+
+def _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known, length: int):
+    """The refusals of the two similarity thresholds, before anything is launched.  -> (sim_num or None, known sim_num or None)."""
+    nums = []
+    for name, t in (("max_similarity", max_similarity), ("max_known_similarity", max_known_similarity)):
+        if t is None:
+            nums.append(None)
+            continue
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0 < t <= 1:
+            raise ValueError(f"{name} must be a float in (0, 1], got {t!r}")
+        num = int(round(t * FP_SIM_DEN))
+        if not 1 <= num <= FP_SIM_DEN:
+            raise ValueError(f"{name} = {t!r} is sim_num = {num} of {FP_SIM_DEN}, outside [1, {FP_SIM_DEN}]")
+        nums.append(num)
+    if nums == [None, None]:
+        return None, None
+    _radius_arg(fingerprint_radius)
+    if vocabulary is None:
+        raise ValueError("max_similarity / max_known_similarity read the rows as strings: give a vocabulary")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the fingerprint takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    if nums[1] is not None and (known is None or len(known) == 0):
+        raise ValueError(f"max_known_similarity = {max_known_similarity} asks for the similarity to the known set: give a non-empty "
+                         "known_tokens")
+    return nums[0], nums[1]
+
+
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
-            min_novelty=1, vocabulary=None, identity="string") -> Screened:
+            min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
+            fingerprint_radius=2) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
     with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`."""
@@ -1087,6 +1145,8 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     _vocabulary_arg(vocabulary, torch.as_tensor(tokens).shape[1])
     _identity_arg(identity, vocabulary, torch.as_tensor(tokens).shape[1])
+    sim_num, known_sim_num = _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known,
+                                              torch.as_tensor(tokens).shape[1])
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1102,12 +1162,30 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     reject = None
     if vocabulary is not None:                                   # is it a molecule at all?  bits 32 / 64, never kept
         reject, _ = torch.ops.mdt.smiles_check(packed, length, *vocabulary.on(device))
+    graph = None
     if identity == "graph":                                      # which molecule is it?  bits 4 / 8 by the graph key
-        natoms, atoms, nbonds, bonds, _, _ = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))
-        graph_key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+        graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
+        graph_key = torch.ops.mdt.mol_key(*graph)
         known_graph = known.mol_keys(vocabulary, device) if known is not None and len(known) else None
         reject = reject | torch.ops.mdt.key_flags(graph_key, N, known_graph)
-    if not diverse:
+    fp = fp_count = None
+    if sim_num is not None or known_sim_num is not None:         # how similar is it?  fingerprints of the graph, computed once
+        if graph is None:
+            graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
+        fp, fp_count = torch.ops.mdt.mol_fp(*graph, fingerprint_radius)
+    if known_sim_num is not None:                                # bit 8 where the nearest known molecule is at least that similar
+        known_fp, _ = known.fingerprints(vocabulary, device, fingerprint_radius)
+        _, inter, union = torch.ops.mdt.fp_nearest(fp, known_fp)
+        near = (union > 0) & (inter.long() * FP_SIM_DEN >= known_sim_num * union.long())     # the integer rule of mdt_hip.h
+        reject = reject | (near.to(torch.uint8) * rt.SCREEN_KNOWN)
+    if sim_num is not None:
+        known_dist = None
+        if min_novelty > 1:
+            known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
+            kk = kp = kl = None
+        status, index, count = torch.ops.mdt.screen_select_similar(score, key, packed, length, N, K, kk, kp, kl, known_dist,
+                                                                   min_novelty, min_distance, reject, fp, fp_count, sim_num)
+    elif not diverse:
         if reject is None:
             status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
         else:
@@ -1158,6 +1236,7 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
+                          max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2,
                           **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
@@ -1191,9 +1270,22 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     once) and ORs the flags into the `reject` byte of the selection.  Equal strings are equal graphs, so graph mode only adds bits;
     of the spellings of one molecule in a group the lowest c stands for all.  ``min_distance`` and ``min_novelty`` stay measured
     in edits on the STRINGS in both modes, and the novel fraction stays ``((status & 8) == 0).float().mean()``.
+
+    ``max_similarity`` / ``max_known_similarity``: "distinct" and "novel" measured on the GRAPHS instead, as the Tanimoto similarity
+    of the fingerprints of mol_fingerprint() (radius ``fingerprint_radius``, 0..3) -- see there for what the fingerprint is and is
+    not: not RDKit's Morgan or ECFP, no implicit hydrogens, no aromaticity perception, no stereo, and folding can make unequal
+    molecules look alike.  Each is None (off) or a float in (0, 1], handed to the kernels as ``sim_num = int(round(t * 65536))``
+    and compared exactly (``inter * 65536 >= sim_num * union``); both need a ``vocabulary`` and rows of at most 64 positions.
+    ``max_similarity``: a candidate at least that similar to a candidate kept before it is passed over and gets status bit 16; the
+    selection is routed to mdt::screen_select_similar and combines with ``min_distance`` (either test passes a candidate over).
+    ``max_known_similarity``: needs a non-empty known set; mdt::fp_nearest runs once over the N * G rows against
+    KnownSet.fingerprints() and bit 8 is OR-ed into `reject` where the nearest known molecule is at least that similar.  A row that
+    is no molecule has an all-zero fingerprint, similar to nothing.  With both at None nothing new is launched; refusals come
+    with ValueError before anything is launched.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
-                   vocabulary=vocabulary, identity=identity, **screen_tokens_kwargs)
+                   vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
+                   max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1438,6 +1530,85 @@ def mol_key(tokens, vocabulary: "SmilesVocabulary", device):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# how similar are two molecules?  Tanimoto similarity of graph fingerprints (csrc/k_molfp.hip): rows of at most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+def _fp_of(tokens, vocabulary, device, radius):
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    fp, count = torch.ops.mdt.mol_fp(natoms, atoms, nbonds, bonds, radius)
+    return fp, count, status, position
+
+
+def mol_fingerprint(tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+    """A circular fingerprint of the molecule behind each row -> (fp int64 (R, 16): the uint64 bits of 1024 bits, count int64 (R,):
+    the set bits, status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer dtype, zeros anywhere.  ``status`` /
+    ``position`` are smiles_check()'s.  A row that is no molecule (empty, or status != 0) has an all-zero fingerprint and count 0.
+
+    On the graph of mol_graph(): every atom starts from its descriptor and its degree, and in each of ``radius`` rounds (0..3) takes
+    in the labels of its neighbours with the bond orders -- the neighbourhood hash of mol_key() without a root; every atom sets one
+    bit (label mod 1024) per round 0..radius.  mdt_mol_fp in include/mdt_hip.h has every step.  Equal graphs always give equal
+    fingerprints, whatever the spelling: OCC and CCO have one fingerprint.  What it is NOT: it is not RDKit's Morgan or ECFP
+    fingerprint, and its bits compare with neither; the round-0 invariant holds no implicit hydrogens; duplicate substructures are not
+    removed; there is no aromaticity perception (C1=CC=CC=C1 and c1ccccc1 differ) and no stereo; and folding to 1024 bits can make
+    unequal environments share a bit, so unequal molecules can reach similarity 1.
+    L <= 64; the refusals are mol_key()'s and a radius outside [0, 3], with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp."""
+    radius = _radius_arg(radius)
+    fp, count, status, position = _fp_of(tokens, vocabulary, device, radius)
+    return fp, count.long(), status.long(), position.long()
+
+
+def tanimoto(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+    """How similar are the molecules of ``a_tokens`` and ``b_tokens``, row by row?  -> (similarity float32 (R,), inter int64 (R,),
+    union int64 (R,)): the Tanimoto similarity of their mol_fingerprint()s, ``inter = popcount(A & B)``, ``union = |A| + |B| -
+    inter``, ``similarity = inter / max(union, 1)`` computed in torch from the exact counts (compare the counts, not the floats,
+    where exactness matters).  1 for two spellings of one molecule; 0 when either row is no molecule.  It is not RDKit's Morgan or
+    ECFP similarity: no implicit hydrogens, no aromaticity perception, no stereo, duplicate substructures are not removed, and
+    folding can make unequal molecules share bits (see mol_fingerprint()).  Both are raw (R, L) ids of the same shape, L <= 64.
+    Sequence: per side mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp, then mdt::fp_tanimoto."""
+    radius = _radius_arg(radius)
+    a, b = _integer_ids(a_tokens, "a_tokens"), _integer_ids(b_tokens, "b_tokens")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"a_tokens {tuple(a.shape)} and b_tokens {tuple(b.shape)} must have the same shape")
+    fa, fb = _fp_of(a, vocabulary, device, radius)[0], _fp_of(b, vocabulary, device, radius)[0]
+    inter, union = torch.ops.mdt.fp_tanimoto(fa, fb)
+    inter, union = inter.long(), union.long()
+    return inter.float() / union.clamp(min=1).float(), inter, union
+
+
+def nearest_known_tanimoto(tokens, known_tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+    """Which known molecule is each molecule most similar to?  -> (similarity float32 (R,), index int64 (R,), inter int64 (R,),
+    union int64 (R,)): the largest Tanimoto similarity (mol_fingerprint(), tanimoto()) of row r of ``tokens`` to any molecule of
+    ``known_tokens`` -- a KnownSet, or raw ids, wrapped as screen_tokens does -- the LOWEST row of ``KnownSet.packed`` that attains
+    it, and the exact counts of that pair (``similarity = inter / max(union, 1)``).  A row that is no molecule has similarity 0 and
+    index 0.  The result does not depend on how the device splits the work.  It is not RDKit's Morgan or ECFP similarity (no
+    implicit hydrogens, no aromaticity perception, no stereo; duplicate substructures are not removed; folding can make unequal
+    molecules share bits).  L <= 64 in both; an empty known set has no nearest: refused with ValueError before anything is
+    launched.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp -> mdt::fp_nearest (the known set's fingerprints:
+    KnownSet.fingerprints(), computed once)."""
+    radius = _radius_arg(radius)
+    tok = _integer_ids(tokens, "tokens")
+    length = tok.shape[1]
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if length < 1:
+        raise ValueError("tokens must hold at least one position per row")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the fingerprint takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    known = known_tokens if isinstance(known_tokens, KnownSet) else KnownSet(known_tokens, length)
+    if known.width != length:
+        raise ValueError(f"known_tokens was built for rows of {known.width} positions, tokens has {length}")
+    if len(known) == 0:
+        raise ValueError("known_tokens is empty: there is no nearest known molecule")
+    fp = _fp_of(tok, vocabulary, device, radius)[0]
+    known_fp, _ = known.fingerprints(vocabulary, device, radius)
+    index, inter, union = torch.ops.mdt.fp_nearest(fp, known_fp)
+    inter, union = inter.long(), union.long()
+    return inter.float() / union.clamp(min=1).float(), index.long(), inter, union
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:
@@ -1487,13 +1658,15 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
                       keep: int, *, cond_scale=1.0, timesteps: int = 100, noise=None, **screen_tokens_kwargs) -> Screened:
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
-    ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity``, with which the tokens go to screen_tokens_diverse instead;
+    ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
+    ``fingerprint_radius``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
-                                         "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity"}
+                                         "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
+                                         "max_known_similarity", "fingerprint_radius"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -1510,6 +1683,13 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     _identity_arg(identity, vocabulary, model.max_length)
     if identity != "string":                                     # ("string": the calls made without the keyword)
         diverse, filters["identity"] = True, identity
+    similar = {k: screen_tokens_kwargs.pop(k) for k in ("max_similarity", "max_known_similarity", "fingerprint_radius")
+               if k in screen_tokens_kwargs}
+    if any(similar.get(k) is not None for k in ("max_similarity", "max_known_similarity")):     # (both None: the calls made without)
+        _similarity_args(similar.get("max_similarity"), similar.get("max_known_similarity"), similar.get("fingerprint_radius", 2),
+                         vocabulary, known, model.max_length)
+        diverse = True
+        filters.update(similar)
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

@@ -823,6 +823,147 @@ def _(key, candidates, known_key):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Tanimoto similarity on graph fingerprints (csrc/k_molfp.hip): 1024 bits as 16 int64 words (the uint64 bits) per row
+def _fp_rows(op, fp, what):
+    if fp.dim() != 2 or fp.dtype != torch.int64 or fp.shape[1] != rt.FP_WORDS:
+        raise RuntimeError(f"{op}: {what} must be int64 (R, {rt.FP_WORDS}): the uint64 words of mdt::mol_fp")
+    return fp.contiguous()
+
+
+@custom_op("mdt::mol_fp", mutates_args=())
+def mol_fp(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, radius: int) -> Tuple[Tensor, Tensor]:
+    """-> (fp int64 (R, 16): the uint64 bits of mdt_mol_fp's 1024-bit circular fingerprint (include/mdt_hip.h) for the graph arrays
+    of mdt::mol_graph, count int32 (R,): its set bits); all zero where natoms is 0 (no molecule).  0 <= radius <= 3.  Not RDKit's
+    Morgan / ECFP."""
+    dev = _hip(natoms, atoms, nbonds, bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_fp"
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the fingerprint takes 1 to {rt.MOL_MAX_LENGTH}")
+    if not 0 <= radius <= rt.FP_MAX_RADIUS:
+        raise RuntimeError(f"{op}: radius = {radius} must lie in [0, {rt.FP_MAX_RADIUS}]")
+    natoms, atoms, nbonds, bonds = natoms.contiguous(), atoms.contiguous(), nbonds.contiguous(), bonds.contiguous()
+    fp = torch.zeros(R, rt.FP_WORDS, dtype=torch.int64, device=dev)
+    count = torch.zeros(R, dtype=torch.int32, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_fp(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, int(radius), rt.ptr(fp),
+                                    rt.ptr(count), rt.current_stream()))
+    return fp, count
+
+
+@mol_fp.register_fake
+def _(natoms, atoms, nbonds, bonds, radius):
+    R = atoms.shape[0]
+    return atoms.new_empty(R, rt.FP_WORDS, dtype=torch.int64), atoms.new_empty(R, dtype=torch.int32)
+
+
+@custom_op("mdt::fp_tanimoto", mutates_args=())
+def fp_tanimoto(a_fp: Tensor, b_fp: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (inter int32 (R,), union int32 (R,)): popcount(A & B) and |A| + |B| - inter of row r of a against row r of b; the Tanimoto
+    similarity is inter / union, 0 where union is 0."""
+    dev = _hip(a_fp, b_fp)
+    lib = rt.load_library()
+    a, b = _fp_rows("mdt::fp_tanimoto", a_fp, "a_fp"), _fp_rows("mdt::fp_tanimoto", b_fp, "b_fp")
+    if a.shape != b.shape:
+        raise RuntimeError(f"mdt::fp_tanimoto: a_fp {tuple(a.shape)} and b_fp {tuple(b.shape)} must have the same shape")
+    R = a.shape[0]
+    inter = torch.zeros(R, dtype=torch.int32, device=dev)
+    union = torch.zeros(R, dtype=torch.int32, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_fp_tanimoto_rows(rt.ptr(a), rt.ptr(b), R, rt.ptr(inter), rt.ptr(union), rt.current_stream()))
+    return inter, union
+
+
+@fp_tanimoto.register_fake
+def _(a_fp, b_fp):
+    R = a_fp.shape[0]
+    return a_fp.new_empty(R, dtype=torch.int32), a_fp.new_empty(R, dtype=torch.int32)
+
+
+@custom_op("mdt::fp_nearest", mutates_args=())
+def fp_nearest(fp: Tensor, known_fp: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (index int32 (R,), inter int32 (R,), union int32 (R,)): per row the LOWEST row of ``known_fp`` (M >= 1 fingerprints) that
+    attains the largest Tanimoto similarity to it, and the counts of that pair.  Exact, and independent of how the work is split."""
+    dev = _hip(fp, known_fp)
+    lib = rt.load_library()
+    q, k = _fp_rows("mdt::fp_nearest", fp, "fp"), _fp_rows("mdt::fp_nearest", known_fp, "known_fp")
+    if k.shape[0] < 1:
+        raise RuntimeError("mdt::fp_nearest: the known set is empty (need M >= 1)")
+    R = q.shape[0]
+    index = torch.zeros(R, dtype=torch.int32, device=dev)
+    inter = torch.zeros(R, dtype=torch.int32, device=dev)
+    union = torch.zeros(R, dtype=torch.int32, device=dev)
+    best = torch.empty(R, dtype=torch.int64, device=dev)            # the packed maxima (quotient << 32 | ~index), one word per row
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_fp_nearest(rt.ptr(q), R, rt.ptr(k), k.shape[0], rt.ptr(best), rt.ptr(inter), rt.ptr(union),
+                                        rt.ptr(index), rt.current_stream()))
+    return index, inter, union
+
+
+@fp_nearest.register_fake
+def _(fp, known_fp):
+    R = fp.shape[0]
+    return tuple(fp.new_empty(R, dtype=torch.int32) for _ in range(3))
+
+
+@custom_op("mdt::screen_select_similar", mutates_args=())
+def screen_select_similar(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                          known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
+                          known_dist: Optional[Tensor], min_novelty: int, min_distance: int, reject: Optional[Tensor],
+                          fp: Optional[Tensor], fp_count: Optional[Tensor], sim_num: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """mdt::screen_select_diverse_reject with similarity as a second way to be passed over (mdt_screen_select_similar,
+    include/mdt_hip.h): a candidate whose fingerprint (``fp`` int64 (N * G, 16), ``fp_count`` int32 (N * G), as mdt::mol_fp returns
+    them) is at least sim_num / 65536 Tanimoto-similar to a candidate kept before it gets bit 16, as one closer than min_distance
+    edits does.  fp and fp_count None: mdt::screen_select_diverse_reject's kernel on the same inputs, bit for bit."""
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject, fp, fp_count)
+    lib = rt.load_library()
+    op = "mdt::screen_select_similar"
+    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
+    if L > rt.EDIT_MAX_LENGTH:
+        raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} the edit distance and the fingerprint take")
+    if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
+        raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
+    if (fp is None) != (fp_count is None):
+        raise RuntimeError(f"{op}: fp and fp_count come together")
+    if fp is not None:
+        fp = _fp_rows(op, fp, "fp")
+        if fp.shape[0] != rows or fp_count.dtype != torch.int32 or fp_count.numel() != rows:
+            raise RuntimeError(f"{op}: fp and fp_count must hold one fingerprint and one int32 per row of packed")
+        fp_count = fp_count.contiguous()
+        if not 1 <= sim_num <= rt.FP_SIM_DEN:
+            raise RuntimeError(f"{op}: sim_num = {sim_num} must lie in [1, {rt.FP_SIM_DEN}]")
+    kd = None if known_dist is None else known_dist.contiguous()
+    rej = _reject_rows(op, reject, rows)
+    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
+    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_screen_select_similar(rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
+                                                   *(rt.ptr(k) if M else 0 for k in known), M, keep, rt.ptr(kd), int(min_novelty),
+                                                   int(min_distance), rt.ptr(rej), rt.ptr(fp), rt.ptr(fp_count), int(sim_num),
+                                                   rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream()))
+    return status, index, count
+
+
+@screen_select_similar.register_fake
+def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, known_dist, min_novelty, min_distance,
+      reject, fp, fp_count, sim_num):
+    G = packed.shape[0] // candidates
+    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
+            packed.new_empty(G, dtype=torch.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between compacted id rows (csrc/k_edit.hip): at most 64 positions, ids in [0, 64)
 def _edit_rows(op, packed, length, what):
     if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
