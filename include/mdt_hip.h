@@ -604,7 +604,8 @@ enum mdt_screen_status {
   MDT_SCREEN_KNOWN = 8,     /* the molecule is in the known set (mdt_screen_select_diverse: or closer to it than min_novelty) */
   MDT_SCREEN_CLOSE = 16,    /* mdt_screen_select_diverse only: closer than min_distance to a better candidate that was kept */
   MDT_SCREEN_MALFORMED = 32, /* mdt_smiles_check: the row breaks the grammar, or its ring / branch bookkeeping does not close */
-  MDT_SCREEN_OVERVALENT = 64 /* mdt_smiles_check: well-formed, but an unbracketed atom's bond orders exceed its maximum */
+  MDT_SCREEN_OVERVALENT = 64, /* mdt_smiles_check: well-formed, but an unbracketed atom's bond orders exceed its maximum */
+  MDT_SCREEN_SUBSTRUCTURE = 128 /* mdt_sub_match: a required pattern is missing or undecided, or a forbidden one present or undecided */
 };
 /* Per group g: status uint8 (N*G) of every candidate; index int32 (G,K): the eligible (status == 0) candidates c in ascending
  * order of (score, c) -- ties go to the lower c -- and -1 in the slots beyond count[g] = min(K, number of eligible candidates).
@@ -823,6 +824,58 @@ int mdt_screen_select_similar(const float *score, const uint64_t *key, const int
                               int32_t M, int32_t K, const int32_t *known_dist, int32_t min_novelty, int32_t min_distance,
                               const uint8_t *reject, const uint64_t *fp, const int32_t *fp_count, int32_t sim_num, uint8_t *status,
                               int32_t *index, int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* Graph substructure match (csrc/k_molsub.hip, csrc/mdt_molsub.h); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* Does the molecule contain this fragment?  OCC contains CO; a string search says no.  This is a precisely defined answer on the
+ * graph of mdt_mol_graph.  It is not RDKit's HasSubstructMatch and not SMARTS: patterns are written in the same SMILES dialect and
+ * parsed by the same scan.
+ *
+ * Inputs.  Target rows: natoms, atoms, nbonds, bonds of mdt_mol_graph, R rows of width 1 <= L <= 64.  Pattern rows: the same four
+ * arrays for 1 <= P <= MDT_SUB_MAX_PATTERNS patterns of width 1 <= LP <= MDT_SUB_MAX_WIDTH.  n and m are the atom counts of target
+ * and pattern.
+ * Atom rule.  Pattern atom p accepts target atom t when ((p ^ t) & mask(p)) == 0, mask(p) = (bracket(p) ? 0xFFFFF000 : 0) |
+ * (first letter of p == 26 ? 0 : 0x7FF): symbol and aromatic bit must be equal unless the pattern atom is '*'; a bracketed pattern
+ * atom also wants equal charge, H-count and isotope fields (an unbracketed target atom has all three 0, so [N] accepts N); the bracket
+ * bit itself never counts.
+ * Bond rule.  A pattern bond (a, b, order) is satisfied under a map f when the target's bond list holds an entry between f(a) and
+ * f(b), in either direction, with the same order (the orders of mdt_mol_graph: cc is 5, CC is 1).  A pattern entry listed twice asks
+ * the same thing twice.
+ * Match.  Pattern q occurs in a row when an injective f: pattern atoms -> target atoms satisfies both rules: subgraph monomorphism,
+ * not the induced kind (extra target bonds between mapped atoms are fine).  A disconnected pattern ('.') needs all its parts on
+ * distinct atoms.
+ * The search is part of the definition, because its cap is.  Pattern atoms are taken in index order (order of appearance; the scan
+ * guarantees that every atom after the first of a component has a bond to an earlier atom).  Back-bonds of p: the pattern entries
+ * with max(a, b) == p, other end min(a, b) (the scan can write a > b, as in C(C1)1).  Candidates of p under a partial map, taken in
+ * ascending target index: compat[p] & ~used & AND over the back-bonds (e, o) of p of adj_o[f(e)], where compat[p] is the 64-bit set
+ * of target atoms that p accepts and adj_o[u] the set of atoms joined to u by an entry of order o.
+ * Decided before any search: a pattern or target with no molecule gives no match -- natoms == 0, counts outside [0, width], or a
+ * bond naming an atom >= natoms (the rule of mdt_mol_key); m > n gives no match; some compat[p] == 0 gives no match; m == 1 matches
+ * iff compat[0] != 0.  Otherwise every root r in compat[0] runs a depth-first search with f(0) = r.  One STEP is one assignment
+ * f(p) = t for p >= 1; the search succeeds when atom m - 1 is assigned; a root about to make step number MDT_SUB_MAX_STEPS + 1 is
+ * abandoned (capped).  Per (row, pattern): MATCH if any root succeeds, UNDECIDED if none succeeds and at least one was capped, NO
+ * MATCH otherwise.  The result does not depend on scheduling: a root may stop early once another has succeeded, and for no other
+ * reason.  The cap is a definition, not a measurement: *.*.*.*.*.*.*.* against 64 atoms is 64^8 maps, and a kernel without a cap
+ * would be a hang.
+ * What no scan writes: a target entry of an order outside 1..5 joins nothing; a pattern with such an entry gives no match; a
+ * pattern entry (p, p) is part of what p accepts -- only a target atom with an entry (t, t) of that order is in compat[p].
+ * What this is and is NOT.  A decided answer (match or no match) does not depend on how target or pattern is spelled; which rows
+ * come out undecided can depend on the spelling.  There are no implicit hydrogens, so [CH4] does not accept C; no aromaticity
+ * perception, so c1ccccc1 is not found in C1=CC=CC=C1; no stereo, no recursive or logical atom expressions, and no mapping is
+ * returned.  The fingerprint of mdt_mol_fp is no pre-filter for this: the atom's degree enters its round 0, so a fragment's bits
+ * are not a subset of its host's bits.
+ * Outputs: bit q of match[r] / undecided[r] (uint32 (R)) is the verdict for pattern q; the two words never share a bit.  flags uint8
+ * (R) or NULL: MDT_SCREEN_SUBSTRUCTURE when (match[r] & need) != need or ((match[r] | undecided[r]) & ban) != 0, else 0 --
+ * conservative both ways: an undecided required pattern counts as missing, an undecided forbidden one as present.  need and ban
+ * may only have bits below P and may not overlap.  R == 0 launches nothing. */
+#define MDT_SUB_MAX_PATTERNS 32
+#define MDT_SUB_MAX_WIDTH 32
+#define MDT_SUB_MAX_STEPS 4096
+int mdt_sub_match(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+                  const int32_t *p_natoms, const uint32_t *p_atoms, const int32_t *p_nbonds, const uint32_t *p_bonds,
+                  int32_t LP, int32_t P, uint32_t need, uint32_t ban,
+                  uint32_t *match, uint32_t *undecided, uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

@@ -874,6 +874,8 @@ MAX_EDIT_ID = 64
 MAX_MOL_LENGTH = 64             # the molecular graph and its key (csrc/k_molgraph.hip): at most 64 atoms, one root per lane
 IDENTITIES = ("string", "graph")
 FP_SIM_DEN = 65536              # a similarity threshold crosses into the kernels as sim_num / 65536 (MDT_FP_SIM_DEN)
+MAX_SUB_PATTERNS = 32           # the substructure match (csrc/k_molsub.hip): patterns a call, one bit of a 32-bit word each
+MAX_SUB_LENGTH = 32             # ... and characters a pattern
 MAX_FP_RADIUS = 3               # the fingerprint (csrc/k_molfp.hip): rounds 0 .. radius, radius in [0, 3]
 
 
@@ -1137,16 +1139,18 @@ def _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, v
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
             min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
-            fingerprint_radius=2) -> Screened:
+            fingerprint_radius=2, require=None, forbid=None) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
-    with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`."""
+    with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`;
+    with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     _vocabulary_arg(vocabulary, torch.as_tensor(tokens).shape[1])
     _identity_arg(identity, vocabulary, torch.as_tensor(tokens).shape[1])
     sim_num, known_sim_num = _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known,
                                               torch.as_tensor(tokens).shape[1])
+    fragments = _substructure_args(require, forbid, vocabulary, torch.as_tensor(tokens).shape[1])
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1168,6 +1172,10 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
         graph_key = torch.ops.mdt.mol_key(*graph)
         known_graph = known.mol_keys(vocabulary, device) if known is not None and len(known) else None
         reject = reject | torch.ops.mdt.key_flags(graph_key, N, known_graph)
+    if fragments is not None:                                    # does it contain the fragment?  bit 128, never kept
+        if graph is None:
+            graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
+        reject = reject | torch.ops.mdt.sub_match(*graph, *_joined_patterns(fragments[0], device), fragments[1], fragments[2])[2]
     fp = fp_count = None
     if sim_num is not None or known_sim_num is not None:         # how similar is it?  fingerprints of the graph, computed once
         if graph is None:
@@ -1236,7 +1244,7 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
-                          max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2,
+                          max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2, require=None, forbid=None,
                           **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
@@ -1282,10 +1290,21 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     KnownSet.fingerprints() and bit 8 is OR-ed into `reject` where the nearest known molecule is at least that similar.  A row that
     is no molecule has an all-zero fingerprint, similar to nothing.  With both at None nothing new is launched; refusals come
     with ValueError before anything is launched.
+
+    ``require`` / ``forbid``: fragments a kept candidate must contain / may not contain, as GRAPHS (has_substructure(), see there
+    for the definition and its limits: subgraph monomorphism on the graph of mol_graph() under a step cap; not SMARTS and not
+    RDKit's HasSubstructMatch, no implicit hydrogens, no aromaticity perception, no stereo).  Each is a SubstructureSet, a list of
+    SMILES strings (wrapped; build the set once when calling repeatedly) or None; together they hold at most 32 patterns; both need
+    a ``vocabulary`` and rows of at most 64 positions.  One mdt::sub_match over the N * G rows -- on the graph that
+    ``identity="graph"`` and the fingerprints use, computed once -- ORs status bit 128 (runtime.SCREEN_SUBSTRUCTURE) into `reject`
+    where a required pattern is not found or a forbidden one is; an undecided verdict counts against the candidate both ways.  A
+    candidate with bit 128 is never kept and pushes nothing out; ``((status & 128) == 0).float().mean()`` is the fraction that meets
+    the constraint.  With both at None nothing new is launched.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
                    vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
-                   max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, **screen_tokens_kwargs)
+                   max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, require=require, forbid=forbid,
+                   **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1609,6 +1628,148 @@ def nearest_known_tanimoto(tokens, known_tokens, vocabulary: "SmilesVocabulary",
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# does the molecule contain this fragment?  graph substructure match (csrc/k_molsub.hip): rows of at most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+class SubstructureSet:
+    """1 to 32 fragments to look for in molecules (has_substructure(), ``require=`` / ``forbid=`` of the screening calls): SMILES
+    strings of at most 32 characters each, written in the dialect of smiles_check() and read through ``vocabulary`` -- not SMARTS.
+    ``*`` accepts any atom; a bracket atom also wants its charge, H count and isotope; everything else wants its symbol and case.
+    ``patterns`` (a tuple of str), ``vocabulary`` and ``len()`` are what it was built from.  An empty pattern, one of more than 32
+    characters, a character without an id, no pattern or more than 32 raise ValueError here; a pattern that does not pass
+    smiles_check() raises ValueError, naming the pattern and the position, on the first ``on(device)``."""
+
+    def __init__(self, patterns, vocabulary: "SmilesVocabulary"):
+        if not isinstance(vocabulary, SmilesVocabulary):
+            raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+        if isinstance(patterns, str):
+            patterns = [patterns]
+        patterns = tuple(patterns)
+        if not 1 <= len(patterns) <= MAX_SUB_PATTERNS:
+            raise ValueError(f"a SubstructureSet holds 1 to {MAX_SUB_PATTERNS} patterns, got {len(patterns)}")
+        for q, s in enumerate(patterns):
+            if not isinstance(s, str):
+                raise ValueError(f"pattern {q} is {s!r}: every pattern is a SMILES string")
+            if s == "":
+                raise ValueError(f"pattern {q} is empty at position 0: an empty fragment is in no molecule")
+            if len(s) > MAX_SUB_LENGTH:
+                raise ValueError(f"pattern {q} {s!r} has {len(s)} characters; a pattern takes at most {MAX_SUB_LENGTH} "
+                                 "(wider patterns are out of scope)")
+        self.patterns, self.vocabulary = patterns, vocabulary
+        self.width = max(len(s) for s in patterns)
+        self._tokens = vocabulary.encode(list(patterns), self.width)
+        self._on = {}
+        self._joined = {}
+
+    def __len__(self) -> int:
+        return len(self.patterns)
+
+    def on(self, device):
+        """The graphs of the patterns, (natoms int32 (P,), atoms int32 (P, LP), nbonds int32 (P,), bonds int32 (P, LP)) on
+        ``device``: computed once per device by mdt::tokens_compact -> mdt::mol_graph and cached.  The first call per device
+        costs one host synchronisation: a pattern that is malformed or overvalent raises ValueError with its position."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._on:
+            packed, n, _, _ = torch.ops.mdt.tokens_compact(self._tokens.to(device), 0, 1.0)
+            natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *self.vocabulary.on(device))
+            status, position = status.cpu().tolist(), position.cpu().tolist()
+            for q, (st, pos) in enumerate(zip(status, position)):
+                if st != 0:
+                    kind = "overvalent" if st == rt.SCREEN_OVERVALENT else "malformed"
+                    raise ValueError(f"pattern {q} {self.patterns[q]!r} does not pass smiles_check(): {kind} at position {pos}")
+            self._on[device] = (natoms, atoms, nbonds, bonds)
+        return self._on[device]
+
+
+def _substructure_set(patterns, vocabulary, what: str) -> "SubstructureSet":
+    if isinstance(patterns, SubstructureSet):
+        return patterns
+    if isinstance(patterns, str) or not hasattr(patterns, "__len__"):
+        raise ValueError(f"{what} must be a SubstructureSet or a list of SMILES strings, got {type(patterns).__name__}")
+    return SubstructureSet(patterns, vocabulary)
+
+
+def _substructure_args(require, forbid, vocabulary, length: int):
+    """The refusals of ``require=`` / ``forbid=``, before anything is launched.  -> None when both are None, else (the sets in
+    the order of their bits, need, ban)."""
+    if require is None and forbid is None:
+        return None
+    if vocabulary is None:
+        raise ValueError("require / forbid read the rows as strings: give a vocabulary")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the substructure match takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    sets, masks, at = [], [0, 0], 0
+    for i, (what, given) in enumerate((("require", require), ("forbid", forbid))):
+        if given is None:
+            continue
+        one = _substructure_set(given, vocabulary, what)
+        sets.append(one)
+        masks[i] = ((1 << len(one)) - 1) << at
+        at += len(one)
+    if at > MAX_SUB_PATTERNS:
+        raise ValueError(f"require and forbid hold {at} patterns together; one call takes at most {MAX_SUB_PATTERNS}")
+    return sets, masks[0], masks[1]
+
+
+def _joined_patterns(sets, device):
+    """The pattern graphs of one or two SubstructureSets as one set of arrays, the narrower padded with zeros; the joined arrays
+    of a pair of sets are kept with the first of them, one per (second set, device)."""
+    if len(sets) == 1:
+        return sets[0].on(device)
+    parts = [one.on(device) for one in sets]
+    at = (id(sets[1]), parts[1][1].device)
+    if at not in sets[0]._joined:
+        width = max(p[1].shape[1] for p in parts)
+        wide = lambda t: torch.nn.functional.pad(t, (0, width - t.shape[1]))  # noqa: E731
+        joined = (torch.cat([p[0] for p in parts]), torch.cat([wide(p[1]) for p in parts]), torch.cat([p[2] for p in parts]),
+                  torch.cat([wide(p[3]) for p in parts]))
+        sets[0]._joined[at] = (sets[1], joined)                               # (the second set is held: its id stays its own)
+    return sets[0]._joined[at][1]
+
+
+def has_substructure(tokens, patterns, vocabulary: "SmilesVocabulary", device):
+    """Does the molecule behind each row contain each fragment?  -> (match bool (R, P), undecided bool (R, P), status int64 (R,),
+    position int64 (R,)) for raw (R, L) ids of any integer dtype, zeros anywhere, and ``patterns``, a SubstructureSet or a list
+    of 1 to 32 SMILES strings of at most 32 characters (wrapped; build the set once when calling repeatedly).  ``status`` /
+    ``position`` are smiles_check()'s; a row that is no molecule (empty, or status != 0) contains nothing, decided.
+
+    On the graph of mol_graph(): pattern q occurs in a row when its atoms can be mapped to distinct atoms of the row so that every
+    pattern atom accepts its image (equal symbol and case, ``*`` accepts all, a bracket atom also wants equal charge, H count and
+    isotope) and every pattern bond finds a bond of the same order between the images -- subgraph monomorphism, so OCC contains CO,
+    C1CC1 contains CCC, and a dotted pattern needs all its parts on distinct atoms.  mdt_sub_match in include/mdt_hip.h has every
+    step, the order of the depth-first search included, because a root of the search that would take more than 4096 steps is
+    abandoned: where no root succeeds and one was abandoned the pair is ``undecided`` (never together with ``match``).  A decided
+    answer does not depend on how row or pattern is spelled; which pairs come out undecided can.  No pair was undecided among 54,000
+    of small patterns and random molecules of up to 20 atoms; ``C.C.C.C.C.C.CN`` against 62 carbons and a lone N is.
+    What it is NOT: not SMARTS and not RDKit's HasSubstructMatch.  There are no implicit hydrogens, so [CH4] does not accept C; no
+    aromaticity perception, so c1ccccc1 is not found in C1=CC=CC=C1; no stereo, no recursive or logical atom expressions, and no
+    mapping is returned.  The fingerprint of mol_fingerprint() is no pre-filter for this: an atom's degree enters its first
+    round, so a fragment's bits are not a subset of its host's.
+    L <= 64; non-integer ids, L < 1, L > 64, a vocabulary that is no SmilesVocabulary and patterns that SubstructureSet refuses
+    raise ValueError before anything is launched.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::sub_match (the
+    patterns' graphs: SubstructureSet.on(), computed once)."""
+    tok = _integer_ids(tokens, "tokens")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if tok.shape[1] < 1:
+        raise ValueError("tokens must hold at least one position per row")
+    if tok.shape[1] > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {tok.shape[1]} positions; the substructure match takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    fragments = _substructure_set(patterns, vocabulary, "patterns")
+    packed, n = _mol_rows(tok, vocabulary, device)
+    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    match, undecided, _ = torch.ops.mdt.sub_match(natoms, atoms, nbonds, bonds, *fragments.on(device), 0, 0)
+    bit = torch.arange(len(fragments), device=match.device)
+    spread = lambda word: ((word.long().unsqueeze(1) >> bit) & 1).bool()  # noqa: E731
+    return spread(match), spread(undecided), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:
@@ -1659,14 +1820,14 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
     ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
-    ``fingerprint_radius``, with which the tokens go to screen_tokens_diverse instead;
+    ``fingerprint_radius`` / ``require`` / ``forbid``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
                                          "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
-                                         "max_known_similarity", "fingerprint_radius"}
+                                         "max_known_similarity", "fingerprint_radius", "require", "forbid"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -1690,6 +1851,12 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
                          vocabulary, known, model.max_length)
         diverse = True
         filters.update(similar)
+    fragments = {k: screen_tokens_kwargs.pop(k) for k in ("require", "forbid") if k in screen_tokens_kwargs}
+    fragments = {k: f for k, f in fragments.items() if f is not None}                         # (None: the calls made without)
+    if fragments:
+        _substructure_args(fragments.get("require"), fragments.get("forbid"), vocabulary, model.max_length)
+        diverse = True
+        filters.update(fragments)
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

@@ -964,6 +964,54 @@ def _(score, key, packed, length, candidates, keep, known_key, known_packed, kno
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# graph substructure match (csrc/k_molsub.hip): up to 32 patterns of up to 32 positions against rows of up to 64
+@custom_op("mdt::sub_match", mutates_args=())
+def sub_match(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, p_natoms: Tensor, p_atoms: Tensor, p_nbonds: Tensor,
+              p_bonds: Tensor, need: int, ban: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (match int32 (R,), undecided int32 (R,): the uint32 bits, bit q = the verdict for pattern q of mdt_sub_match
+    (include/mdt_hip.h) on the graph arrays of mdt::mol_graph -- targets (R, L <= 64), patterns (P <= 32, LP <= 32); flags uint8
+    (R,): 128 where a pattern of the mask ``need`` is not matched or one of ``ban`` is matched or undecided).  Subgraph
+    monomorphism under a step cap; not SMARTS, not RDKit's HasSubstructMatch."""
+    dev = _hip(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds)
+    lib = rt.load_library()
+    op = "mdt::sub_match"
+    for what, n_, a_, nb_, b_ in (("", natoms, atoms, nbonds, bonds), ("p_", p_natoms, p_atoms, p_nbonds, p_bonds)):
+        if a_.dim() != 2 or tuple(b_.shape) != tuple(a_.shape) or any(t.dtype != torch.int32 for t in (n_, a_, nb_, b_)):
+            raise RuntimeError(f"{op}: {what}atoms and {what}bonds must be int32 (rows, width), {what}natoms and {what}nbonds int32 "
+                               "(as mdt::mol_graph returns them)")
+        if n_.numel() != a_.shape[0] or nb_.numel() != a_.shape[0]:
+            raise RuntimeError(f"{op}: {what}natoms and {what}nbonds must hold one value per row of {what}atoms")
+    (R, L), (P, LP) = atoms.shape, p_atoms.shape
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the match takes 1 to {rt.MOL_MAX_LENGTH}")
+    if not 1 <= LP <= rt.SUB_MAX_WIDTH:
+        raise RuntimeError(f"{op}: p_atoms has {LP} positions per pattern, the match takes 1 to {rt.SUB_MAX_WIDTH}")
+    if not 1 <= P <= rt.SUB_MAX_PATTERNS:
+        raise RuntimeError(f"{op}: {P} patterns, the match takes 1 to {rt.SUB_MAX_PATTERNS} a call")
+    if not (0 <= need < 1 << P and 0 <= ban < 1 << P):
+        raise RuntimeError(f"{op}: need = {need:#x} and ban = {ban:#x} may only have bits below P = {P}")
+    if need & ban:
+        raise RuntimeError(f"{op}: need = {need:#x} and ban = {ban:#x} overlap")
+    natoms, atoms, nbonds, bonds = natoms.contiguous(), atoms.contiguous(), nbonds.contiguous(), bonds.contiguous()
+    p_natoms, p_atoms, p_nbonds, p_bonds = p_natoms.contiguous(), p_atoms.contiguous(), p_nbonds.contiguous(), p_bonds.contiguous()
+    match = torch.zeros(R, dtype=torch.int32, device=dev)
+    undecided = torch.zeros(R, dtype=torch.int32, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_sub_match(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, rt.ptr(p_natoms),
+                                       rt.ptr(p_atoms), rt.ptr(p_nbonds), rt.ptr(p_bonds), LP, P, int(need), int(ban),
+                                       rt.ptr(match), rt.ptr(undecided), rt.ptr(flags), rt.current_stream()))
+    return match, undecided, flags
+
+
+@sub_match.register_fake
+def _(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds, need, ban):
+    R = atoms.shape[0]
+    return (atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between compacted id rows (csrc/k_edit.hip): at most 64 positions, ids in [0, 64)
 def _edit_rows(op, packed, length, what):
     if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
