@@ -135,48 +135,29 @@ __global__ __launch_bounds__(256) void k_edit_unpack(const unsigned long long* _
 // ------------------------------------------------------------------------------------------------
 // C ABI entry points of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
-namespace {
-inline int finish(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    mdt_set_error(buf);
-    return 1;
-  }
-  return 0;
-}
-inline int bad(const char* msg) {
-  mdt_set_error(msg);
-  return 2;
-}
-}  // namespace
-
 extern "C" {
 
 int mdt_edit_distance_rows(const int32_t* a_packed, const int32_t* a_len, const int32_t* b_packed, const int32_t* b_len, int32_t L,
                            int32_t R, int32_t* dist, void* stream) {
   if (R == 0) return 0;
-  if (R < 0) return bad("mdt_edit_distance_rows: need R >= 0 rows");
-  if (L < 1 || L > 64) return bad("mdt_edit_distance_rows: need 1 <= L <= 64 positions per row");
-  if (!a_packed || !a_len || !b_packed || !b_len || !dist) return bad("mdt_edit_distance_rows: null pointer");
+  if (R < 0) return mdt_bad("mdt_edit_distance_rows: need R >= 0 rows");
+  if (L < 1 || L > 64) return mdt_bad("mdt_edit_distance_rows: need 1 <= L <= 64 positions per row");
+  if (!a_packed || !a_len || !b_packed || !b_len || !dist) return mdt_bad("mdt_edit_distance_rows: null pointer");
   const unsigned blocks = (unsigned)(((int64_t)R + mdt::kEditTile - 1) / mdt::kEditTile);
   hipLaunchKernelGGL(mdt::k_edit_rows, dim3(blocks), dim3(mdt::kEditTile), 0, (hipStream_t)stream, a_packed, a_len, b_packed, b_len,
                      L, R, dist);
-  return finish("mdt_edit_distance_rows");
+  return mdt_finish("mdt_edit_distance_rows");
 }
 
 int mdt_edit_nearest(const int32_t* packed, const int32_t* length, int32_t L, int32_t R, const int32_t* known_packed,
                      const int32_t* known_len, int32_t M, uint64_t* best, int32_t* dist, int32_t* index, void* stream) {
   if (R == 0) return 0;
-  if (R < 0) return bad("mdt_edit_nearest: need R >= 0 rows");
-  if (L < 1 || L > 64) return bad("mdt_edit_nearest: need 1 <= L <= 64 positions per row");
-  if (M < 1) return bad("mdt_edit_nearest: need M >= 1 known rows");
-  if (!packed || !length || !known_packed || !known_len || !best || !dist || !index) return bad("mdt_edit_nearest: null pointer");
+  if (R < 0) return mdt_bad("mdt_edit_nearest: need R >= 0 rows");
+  if (L < 1 || L > 64) return mdt_bad("mdt_edit_nearest: need 1 <= L <= 64 positions per row");
+  if (M < 1) return mdt_bad("mdt_edit_nearest: need M >= 1 known rows");
+  if (!packed || !length || !known_packed || !known_len || !best || !dist || !index) return mdt_bad("mdt_edit_nearest: null pointer");
   const int64_t tiles = ((int64_t)R + mdt::kEditTile - 1) / mdt::kEditTile;
-  if (tiles > 65535) return bad("mdt_edit_nearest: R exceeds 65535 * 64 rows");
+  if (tiles > 65535) return mdt_bad("mdt_edit_nearest: R exceeds 65535 * 64 rows");
   const unsigned chunks = (unsigned)(((int64_t)M + mdt::kEditChunk - 1) / mdt::kEditChunk);
   const unsigned blocks = (unsigned)(((int64_t)R + 255) / 256);
   unsigned long long* word = reinterpret_cast<unsigned long long*>(best);
@@ -184,7 +165,7 @@ int mdt_edit_nearest(const int32_t* packed, const int32_t* length, int32_t L, in
   hipLaunchKernelGGL(mdt::k_edit_nearest, dim3(chunks, (unsigned)tiles), dim3(mdt::kEditTile * mdt::kEditWaves), 0,
                      (hipStream_t)stream, packed, length, L, R, known_packed, known_len, M, word);
   hipLaunchKernelGGL(mdt::k_edit_unpack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, word, R, dist, index);
-  return finish("mdt_edit_nearest");
+  return mdt_finish("mdt_edit_nearest");
 }
 
 }  // extern "C"

@@ -860,28 +860,7 @@ hipError_t launch_time_embed(const float* cn, const float* w, float* out, int ro
 // ------------------------------------------------------------------------------------------------
 // C ABI entry points of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
 namespace {
-inline int finish(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    mdt_set_error(buf);
-    return 1;
-  }
-  return 0;
-}
-inline int bad(const char* msg) {
-  mdt_set_error(msg);
-  return 2;
-}
-inline int bad(const char* name, const char* msg) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s%s", name, msg);
-  return bad(buf);
-}
 inline size_t tile_bytes(int L, int Cp) { return (size_t)L * (Cp + 1) * sizeof(float); }
 
 // Launch of a kernel that holds one sample in dynamic LDS, one workgroup of 256 per sample: up to the CU's 160 KiB (the default limit
@@ -892,16 +871,16 @@ int launch_lds(const char* name, int B, size_t lds, void* stream, A... args) {
   static mdt::DevOnce once;
   if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
   hipLaunchKernelGGL(Kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, args...);
-  return finish(name);
+  return mdt_finish(name);
 }
 // The entry of every tile kernel: an empty batch is no error, the tile's shape is checked (max_length = 1024, the reference
 // constructors' default, at 16 padded channels is 68 KiB), then `refuse` -- what this entry point excludes beyond that, or nullptr.
 template <auto Kernel, class... A>
 int launch_tile(const char* name, const char* refuse, int B, int C, int L, int Cp, void* stream, A... args) {
   if (B <= 0) return 0;
-  if (L % 4 || Cp % 16 || Cp < C) return bad(name, ": need L % 4 == 0, Cp % 16 == 0, Cp >= C");
-  if (tile_bytes(L, Cp) > kMaxLds) return bad(name, ": (L, Cp) tile exceeds the 160 KiB of LDS of a compute unit");
-  if (refuse) return bad(name, refuse);
+  if (L % 4 || Cp % 16 || Cp < C) return mdt_bad(name, ": need L % 4 == 0, Cp % 16 == 0, Cp >= C");
+  if (tile_bytes(L, Cp) > kMaxLds) return mdt_bad(name, ": (L, Cp) tile exceeds the 160 KiB of LDS of a compute unit");
+  if (refuse) return mdt_bad(name, refuse);
   return launch_lds<Kernel>(name, B, tile_bytes(L, Cp), stream, args...);
 }
 // mdt_dyn_scale / mdt_dyn_scale_rows: the coefficients as float or as const float* per sample; `refuse` as launch_tile's
@@ -909,12 +888,12 @@ template <auto Kernel, class Coef>
 int launch_dyn_scale(const char* name, const char* refuse, const float* x, const float* pred, float* scale, Coef c_skip, Coef c_out, float q,
                      int B, int C, int L, int Cp, void* stream) {
   if (B <= 0) return 0;
-  if (refuse) return bad(name, refuse);
-  if (!(q > 0.0f && q <= 1.0f)) return bad(name, ": the quantile must lie in (0, 1]");
-  if (C <= 0 || L <= 0 || Cp < C) return bad(name, ": bad dims");
+  if (refuse) return mdt_bad(name, refuse);
+  if (!(q > 0.0f && q <= 1.0f)) return mdt_bad(name, ": the quantile must lie in (0, 1]");
+  if (C <= 0 || L <= 0 || Cp < C) return mdt_bad(name, ": bad dims");
   int npad = 1;
   while (npad < C * L) npad <<= 1;
-  if ((size_t)npad * sizeof(float) > kMaxLds) return bad(name, ": C * L exceeds 32768 values (the sort runs in one compute unit's LDS)");
+  if ((size_t)npad * sizeof(float) > kMaxLds) return mdt_bad(name, ": C * L exceeds 32768 values (the sort runs in one compute unit's LDS)");
   return launch_lds<Kernel>(name, B, (size_t)npad * sizeof(float), stream, x, pred, scale, c_skip, c_out, q, C, L, Cp, npad);
 }
 }  // namespace
@@ -924,20 +903,20 @@ extern "C" {
 int mdt_cond_embed(const float* seq, const float* fc1_w, const float* fc1_b, const float* inv_freq, float* out,
                    int32_t B, int32_t n, int32_t D1, int32_t D2, void* stream) {
   if (B <= 0) return 0;
-  if (D2 % 2) return bad("mdt_cond_embed: D2 must be even");
+  if (D2 % 2) return mdt_bad("mdt_cond_embed: D2 must be even");
   hipLaunchKernelGGL(mdt::k_cond_embed, dim3(mdt::grid_for((int64_t)B * n * (D1 + D2))), dim3(256), 0,
                      (hipStream_t)stream, seq, fc1_w, fc1_b, inv_freq, out, B, n, D1, D2, 0);
-  return finish("mdt_cond_embed");
+  return mdt_finish("mdt_cond_embed");
 }
 
 int mdt_cond_embed_add(const float* seq, const float* fc1_w, const float* fc1_b, const float* inv_freq, float* out,
                        int32_t B, int32_t n, int32_t D1, int32_t D2, void* stream) {
-  if (!seq || !fc1_w || !fc1_b || !inv_freq || !out) return bad("mdt_cond_embed_add: null pointer");
+  if (!seq || !fc1_w || !fc1_b || !inv_freq || !out) return mdt_bad("mdt_cond_embed_add: null pointer");
   if (B <= 0) return 0;
-  if (D1 <= 0 || D2 <= 0 || D2 % 2 || D1 > D2) return bad("mdt_cond_embed_add: need 0 < D1 <= D2, D2 even");
+  if (D1 <= 0 || D2 <= 0 || D2 % 2 || D1 > D2) return mdt_bad("mdt_cond_embed_add: need 0 < D1 <= D2, D2 even");
   hipLaunchKernelGGL(mdt::k_cond_embed, dim3(mdt::grid_for((int64_t)B * n * D1)), dim3(256), 0, (hipStream_t)stream, seq,
                      fc1_w, fc1_b, inv_freq, out, B, n, D1, D2, 1);
-  return finish("mdt_cond_embed_add");
+  return mdt_finish("mdt_cond_embed_add");
 }
 
 int mdt_precond_in(const float* x, float* xin, float c_in, int32_t B, int32_t C, int32_t L, int32_t Cp,
@@ -1048,31 +1027,31 @@ int mdt_karras_next(const float* x_hat, const float* x_next, const float* d, con
 int mdt_init_noise(float* x, const float* noise, float sigma0, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
                    int32_t C, int32_t L, void* stream) {
   if (B <= 0) return 0;
-  if (L % 4) return bad("mdt_init_noise: L % 4 != 0");
+  if (L % 4) return mdt_bad("mdt_init_noise: L % 4 != 0");
   const int64_t n4 = (int64_t)B * C * L / 4;
   hipLaunchKernelGGL(mdt::k_init_noise, dim3(mdt::grid_for(n4)), dim3(256), 0, (hipStream_t)stream, x, noise, sigma0,
                      seed, step, sample0 * C * L, n4);
-  return finish("mdt_init_noise");
+  return mdt_finish("mdt_init_noise");
 }
 
 int mdt_add_noise(float* x, const float* noise, float s, uint64_t seed, uint32_t step, int64_t sample0, int32_t B,
                   int32_t C, int32_t L, void* stream) {
   if (B <= 0) return 0;
-  if (L % 4) return bad("mdt_add_noise: L % 4 != 0");
+  if (L % 4) return mdt_bad("mdt_add_noise: L % 4 != 0");
   const int64_t n4 = (int64_t)B * C * L / 4;
   hipLaunchKernelGGL(mdt::k_add_noise, dim3(mdt::grid_for(n4)), dim3(256), 0, (hipStream_t)stream, x, noise, s, seed,
                      step, sample0 * C * L, n4);
-  return finish("mdt_add_noise");
+  return mdt_finish("mdt_add_noise");
 }
 
 int mdt_inpaint_merge(float* x, const float* src, const uint8_t* mask, const float* noise, float sigma, uint64_t seed,
                       uint32_t step, int64_t sample0, int32_t B, int32_t C, int32_t L, void* stream) {
   if (B <= 0) return 0;
-  if (L % 4) return bad("mdt_inpaint_merge: L % 4 != 0");
+  if (L % 4) return mdt_bad("mdt_inpaint_merge: L % 4 != 0");
   const int64_t n4 = (int64_t)B * C * L / 4;
   hipLaunchKernelGGL(mdt::k_inpaint_merge, dim3(mdt::grid_for(n4)), dim3(256), 0, (hipStream_t)stream, x, src, mask,
                      noise, sigma, seed, step, sample0 * C * L, n4);
-  return finish("mdt_inpaint_merge");
+  return mdt_finish("mdt_inpaint_merge");
 }
 
 int mdt_inpaint_enter(float* x, float* xin, const float* src, const int32_t* draft, const uint8_t* keep,
@@ -1109,63 +1088,63 @@ int mdt_refine_keep_enter(float* x, float* xin, const int32_t* start, int32_t st
 int mdt_inpaint_finish(float* x, const float* src, const int32_t* draft, const uint8_t* keep, int32_t keep_per_token,
                        int32_t* tokens, int32_t B, int32_t C, int32_t L, void* stream) {
   if (B <= 0) return 0;
-  if (!x || !keep) return bad("mdt_inpaint_finish: null pointer");
-  if (!src == !draft) return bad("mdt_inpaint_finish: give the source either dense (src) or as draft ids (draft)");
-  if (C <= 0 || L <= 0) return bad("mdt_inpaint_finish: bad dims");
+  if (!x || !keep) return mdt_bad("mdt_inpaint_finish: null pointer");
+  if (!src == !draft) return mdt_bad("mdt_inpaint_finish: give the source either dense (src) or as draft ids (draft)");
+  if (C <= 0 || L <= 0) return mdt_bad("mdt_inpaint_finish: bad dims");
   const int64_t n = (int64_t)B * L;
   hipLaunchKernelGGL(mdt::k_inpaint_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, src, draft,
                      keep, keep_per_token ? 1 : 0, tokens, B, C, L);
-  return finish("mdt_inpaint_finish");
+  return mdt_finish("mdt_inpaint_finish");
 }
 
 int mdt_adpm2_euler(const float* x_base, const float* x_from, const float* denoised, const float* noise, float* out,
                     float sigma, float dt, float sigma_up, int32_t noise_mode, uint64_t seed, uint32_t step,
                     int64_t sample0, int32_t B, int32_t C, int32_t L, void* stream) {
   if (B <= 0) return 0;
-  if (L % 4) return bad("mdt_adpm2_euler: L % 4 != 0");
-  if (noise_mode < 0 || noise_mode > 2 || (noise_mode == 1 && !noise)) return bad("mdt_adpm2_euler: bad noise mode");
+  if (L % 4) return mdt_bad("mdt_adpm2_euler: L % 4 != 0");
+  if (noise_mode < 0 || noise_mode > 2 || (noise_mode == 1 && !noise)) return mdt_bad("mdt_adpm2_euler: bad noise mode");
   const int64_t n4 = (int64_t)B * C * L / 4;
   hipLaunchKernelGGL(mdt::k_adpm2_euler, dim3(mdt::grid_for(n4)), dim3(256), 0, (hipStream_t)stream, x_base, x_from,
                      denoised, noise, out, sigma, dt, sigma_up, noise_mode, seed, step, sample0 * C * L, n4);
-  return finish("mdt_adpm2_euler");
+  return mdt_finish("mdt_adpm2_euler");
 }
 
 int mdt_copy_f32(float* dst, const float* src, int64_t n, void* stream) {
   if (n <= 0) return 0;
-  if (!dst || !src) return bad("mdt_copy_f32: null pointer");
+  if (!dst || !src) return mdt_bad("mdt_copy_f32: null pointer");
   const bool vec = n % 4 == 0 && ((reinterpret_cast<size_t>(dst) | reinterpret_cast<size_t>(src)) & 15) == 0;
   const int64_t items = vec ? n / 4 : (n < 65536 ? n : 65536);
   hipLaunchKernelGGL(mdt::k_copy_f32, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dst, src, n, vec ? 1 : 0);
-  return finish("mdt_copy_f32");
+  return mdt_finish("mdt_copy_f32");
 }
 
 int mdt_clamp(float* x, float lo, float hi, int64_t n, void* stream) {
   if (n <= 0) return 0;
-  if (n % 4) return bad("mdt_clamp: n % 4 != 0");
+  if (n % 4) return mdt_bad("mdt_clamp: n % 4 != 0");
   hipLaunchKernelGGL(mdt::k_clamp, dim3(mdt::grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, x, lo, hi, n / 4);
-  return finish("mdt_clamp");
+  return mdt_finish("mdt_clamp");
 }
 
 int mdt_cfg_mix(const float* cond, const float* uncond, float* out, float scale, int64_t n, void* stream) {
   if (n <= 0) return 0;
-  if (n % 4) return bad("mdt_cfg_mix: n % 4 != 0");
+  if (n % 4) return mdt_bad("mdt_cfg_mix: n % 4 != 0");
   hipLaunchKernelGGL(mdt::k_cfg_mix, dim3(mdt::grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, cond, uncond, out,
                      scale, n / 4);
-  return finish("mdt_cfg_mix");
+  return mdt_finish("mdt_cfg_mix");
 }
 
 int mdt_cfg_mix_rows(const float* cond, const float* uncond, float* out, const float* scale, int32_t B, int64_t row_elems,
                      void* stream) {
   if (B <= 0) return 0;
-  if (!cond || !uncond || !out || !scale) return bad("mdt_cfg_mix_rows: null pointer");
-  if (row_elems <= 0 || row_elems % 4) return bad("mdt_cfg_mix_rows: row_elems must be a positive multiple of 4");
+  if (!cond || !uncond || !out || !scale) return mdt_bad("mdt_cfg_mix_rows: null pointer");
+  if (row_elems <= 0 || row_elems % 4) return mdt_bad("mdt_cfg_mix_rows: row_elems must be a positive multiple of 4");
   const int64_t row4 = row_elems / 4;
   int G = 256;                                          // lanes of a segment: the power of two that covers a short row
   while (G > 1 && G / 2 >= row4) G /= 2;
   const int64_t segs = (row4 + G - 1) / G, units = (int64_t)B * segs;
   hipLaunchKernelGGL(mdt::k_cfg_mix_rows, dim3(mdt::grid_for(units * G)), dim3(256), 0, (hipStream_t)stream, cond, uncond, out,
                      scale, row4, segs, units, G);
-  return finish("mdt_cfg_mix_rows");
+  return mdt_finish("mdt_cfg_mix_rows");
 }
 
 int mdt_argmax_tokens(const float* x, int32_t* tokens, int32_t B, int32_t C, int32_t L, void* stream) {
@@ -1173,7 +1152,7 @@ int mdt_argmax_tokens(const float* x, int32_t* tokens, int32_t B, int32_t C, int
   const int64_t n = (int64_t)B * L;
   hipLaunchKernelGGL(mdt::k_argmax, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, tokens, B,
                      C, L);
-  return finish("mdt_argmax_tokens");
+  return mdt_finish("mdt_argmax_tokens");
 }
 
 }  // extern "C"

@@ -32,13 +32,6 @@ constexpr int kFpChunk = MDT_FP_KNOWN_CHUNK;                   // ... its known 
 static_assert(kFpChunk % kFpWaves == 0, "a wave takes a whole share of the chunk");
 static_assert(kFpBits == MDT_FP_BITS && kFpSimDen == MDT_FP_SIM_DEN, "mdt_hip.h and mdt_smiles_scan.h agree");
 
-// What one lane wrote to LDS is read by other lanes of the SAME wave: order the accesses, no workgroup barrier.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(64 * kFpRowsPerBlock) void k_mol_fp(const int32_t* __restrict__ natoms,
                                                                  const uint32_t* __restrict__ atoms,
                                                                  const int32_t* __restrict__ nbonds,
@@ -53,16 +46,7 @@ __global__ __launch_bounds__(64 * kFpRowsPerBlock) void k_mol_fp(const int32_t* 
   uint32_t* out = reinterpret_cast<uint32_t*>(fp + row * kFpWords);      // dword d = bits 32 d .. 32 d + 31 (little-endian words)
   const int n = natoms[row], nb = nbonds[row];
   const uint32_t* row_bonds = bonds + row * L;
-  bool ok = !(n < 1 || n > L || nb < 0 || nb > L);              // the rule of k_mol_key: such a row is no molecule
-  if (ok) {
-    bool bad = false;
-    if (lane < nb) {
-      const uint32_t w = row_bonds[lane];
-      bad = (int)(w & 255u) >= n || (int)((w >> 8) & 255u) >= n;
-    }
-    ok = !__any(bad);
-  }
-  if (!ok) {
+  if (!mol_graph_ok_wave(row_bonds, n, nb, L, lane)) {          // the rule of k_mol_key: such a row is no molecule
     if (lane < kFpDwords) out[lane] = 0;
     if (lane == 0) count[row] = 0;
     return;
@@ -71,7 +55,7 @@ __global__ __launch_bounds__(64 * kFpRowsPerBlock) void k_mol_fp(const int32_t* 
   int deg = 0;
   for (int e = 0; e < nb; ++e) {
     const uint32_t w = row_bonds[e];
-    deg += (int)((int)(w & 255u) == lane) + (int)((int)((w >> 8) & 255u) == lane);
+    deg += (int)(mol_a(w) == lane) + (int)(mol_b(w) == lane);
   }
   uint64_t id = lane < n ? fp_seed(atoms[row * L + lane], deg) : 0;
   wave_lds_sync();                                              // (s_fp is zero before the first bit is set)
@@ -87,10 +71,10 @@ __global__ __launch_bounds__(64 * kFpRowsPerBlock) void k_mol_fp(const int32_t* 
     uint64_t acc = 0;
     for (int e = 0; e < nb; ++e) {
       const uint32_t w = row_bonds[e];
-      const int a = (int)(w & 255u), b = (int)((w >> 8) & 255u);               // (< n <= 64: inside the labels)
+      const int a = mol_a(w), b = mol_b(w);                                    // (< n <= 64: inside the labels)
       const uint64_t la = cur[a], lb = cur[b];                               // the same address in every lane
       const int times = (int)(a == lane) + (int)(b == lane);                 // (a bond of an atom to itself counts at both ends)
-      const uint64_t term = fp_bond_term(a == lane ? lb : la, w >> 16);
+      const uint64_t term = fp_bond_term(a == lane ? lb : la, mol_order(w));
       acc += times == 2 ? 2 * term : (times ? term : 0);
     }
     id = fp_next(id, acc);
@@ -180,66 +164,47 @@ __global__ __launch_bounds__(256) void k_fp_finish(const unsigned long long* __r
 // ------------------------------------------------------------------------------------------------
 // C ABI entry points of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
-namespace {
-inline int finish(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    mdt_set_error(buf);
-    return 1;
-  }
-  return 0;
-}
-inline int bad(const char* msg) {
-  mdt_set_error(msg);
-  return 2;
-}
-}  // namespace
-
 extern "C" {
 
 int mdt_mol_fp(const int32_t* natoms, const uint32_t* atoms, const int32_t* nbonds, const uint32_t* bonds, int32_t L, int32_t R,
                int32_t radius, uint64_t* fp, int32_t* count, void* stream) {
-  if (R < 0) return bad("mdt_mol_fp: need R >= 0");
-  if (L < 1 || L > mdt::kMolMaxL) return bad("mdt_mol_fp: need 1 <= L <= 64");
-  if (radius < 0 || radius > mdt::kFpMaxRadius) return bad("mdt_mol_fp: need 0 <= radius <= 3");
+  if (R < 0) return mdt_bad("mdt_mol_fp: need R >= 0");
+  if (L < 1 || L > mdt::kMolMaxL) return mdt_bad("mdt_mol_fp: need 1 <= L <= 64");
+  if (radius < 0 || radius > mdt::kFpMaxRadius) return mdt_bad("mdt_mol_fp: need 0 <= radius <= 3");
   if (R == 0) return 0;
-  if (!natoms || !atoms || !nbonds || !bonds || !fp || !count) return bad("mdt_mol_fp: null pointer");
+  if (!natoms || !atoms || !nbonds || !bonds || !fp || !count) return mdt_bad("mdt_mol_fp: null pointer");
   const unsigned blocks = (unsigned)(((int64_t)R + mdt::kFpRowsPerBlock - 1) / mdt::kFpRowsPerBlock);
   hipLaunchKernelGGL(mdt::k_mol_fp, dim3(blocks), dim3(64 * mdt::kFpRowsPerBlock), 0, (hipStream_t)stream, natoms, atoms, nbonds,
                      bonds, L, R, radius, fp, count);
-  return finish("mdt_mol_fp");
+  return mdt_finish("mdt_mol_fp");
 }
 
 int mdt_fp_tanimoto_rows(const uint64_t* a_fp, const uint64_t* b_fp, int32_t R, int32_t* inter, int32_t* uni, void* stream) {
-  if (R < 0) return bad("mdt_fp_tanimoto_rows: need R >= 0");
+  if (R < 0) return mdt_bad("mdt_fp_tanimoto_rows: need R >= 0");
   if (R == 0) return 0;
-  if (!a_fp || !b_fp || !inter || !uni) return bad("mdt_fp_tanimoto_rows: null pointer");
+  if (!a_fp || !b_fp || !inter || !uni) return mdt_bad("mdt_fp_tanimoto_rows: null pointer");
   hipLaunchKernelGGL(mdt::k_fp_rows, dim3((unsigned)(((int64_t)R + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a_fp, b_fp, R,
                      inter, uni);
-  return finish("mdt_fp_tanimoto_rows");
+  return mdt_finish("mdt_fp_tanimoto_rows");
 }
 
 int mdt_fp_nearest(const uint64_t* fp, int32_t R, const uint64_t* known_fp, int32_t M, uint64_t* best, int32_t* inter, int32_t* uni,
                    int32_t* index, void* stream) {
-  if (R < 0) return bad("mdt_fp_nearest: need R >= 0");
-  if (M < 1) return bad("mdt_fp_nearest: need M >= 1 known rows");
+  if (R < 0) return mdt_bad("mdt_fp_nearest: need R >= 0");
+  if (M < 1) return mdt_bad("mdt_fp_nearest: need M >= 1 known rows");
   if (R == 0) return 0;
-  if (!fp || !known_fp || !best || !inter || !uni || !index) return bad("mdt_fp_nearest: null pointer");
+  if (!fp || !known_fp || !best || !inter || !uni || !index) return mdt_bad("mdt_fp_nearest: null pointer");
   const int64_t tiles = ((int64_t)R + mdt::kFpTile - 1) / mdt::kFpTile;
-  if (tiles > 65535) return bad("mdt_fp_nearest: R exceeds 65535 * 64 rows");
+  if (tiles > 65535) return mdt_bad("mdt_fp_nearest: R exceeds 65535 * 64 rows");
   const unsigned chunks = (unsigned)(((int64_t)M + mdt::kFpChunk - 1) / mdt::kFpChunk);
   const unsigned blocks = (unsigned)(((int64_t)R + 255) / 256);
   unsigned long long* word = reinterpret_cast<unsigned long long*>(best);
   if (hipMemsetAsync(word, 0, (size_t)R * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
-    return finish("mdt_fp_nearest");
+    return mdt_finish("mdt_fp_nearest");
   hipLaunchKernelGGL(mdt::k_fp_nearest, dim3(chunks, (unsigned)tiles), dim3(mdt::kFpTile * mdt::kFpWaves), 0, (hipStream_t)stream,
                      reinterpret_cast<const uint32_t*>(fp), R, reinterpret_cast<const uint32_t*>(known_fp), M, word);
   hipLaunchKernelGGL(mdt::k_fp_finish, dim3(blocks), dim3(256), 0, (hipStream_t)stream, word, fp, R, known_fp, M, inter, uni, index);
-  return finish("mdt_fp_nearest");
+  return mdt_finish("mdt_fp_nearest");
 }
 
 }  // extern "C"

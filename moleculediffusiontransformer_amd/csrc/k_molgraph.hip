@@ -118,19 +118,11 @@ __global__ __launch_bounds__(64) void k_mol_key(const int32_t* __restrict__ nato
   const int64_t row = blockIdx.x;
   const int lane = threadIdx.x;
   const int n = natoms[row], nb = nbonds[row];
-  if (n < 1 || n > L || nb < 0 || nb > L) {                     // no molecule (or counts no graph of this width can have)
-    if (lane == 0) key[row] = 0;
-    return;
-  }
   const uint32_t* row_atoms = atoms + row * L;
   const uint32_t* row_bonds = bonds + row * L;
-  // a bond that names an atom the row does not have would index past the columns: such a row has no key
-  bool bad = false;
-  if (lane < nb) {
-    const uint32_t w = row_bonds[lane];
-    bad = (int)(w & 255u) >= n || (int)((w >> 8) & 255u) >= n;
-  }
-  if (__any(bad)) {
+  // No molecule, counts no graph of this width can have, or a bond that names an atom the row does not have (it would index past
+  // the columns): such a row has no key.
+  if (!mol_graph_ok_wave(row_bonds, n, nb, L, lane)) {
     if (lane == 0) key[row] = 0;
     return;
   }
@@ -174,77 +166,39 @@ __global__ __launch_bounds__(256) void k_key_flags(const uint64_t* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 // C ABI entry points of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
-static int molgraph_launched(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s: %s", who, hipGetErrorString(e));
-  mdt_set_error(buf);
-  return 1;
-}
-
 extern "C" int mdt_mol_graph(const int32_t* packed, const int32_t* length, int32_t L, int32_t R, const uint8_t* classes,
                              const uint8_t* max_valence, const uint32_t* elements, int32_t* natoms, uint32_t* atoms,
                              int32_t* nbonds, uint32_t* bonds, uint8_t* status, int32_t* position, void* stream) {
-  if (R < 0) {
-    mdt_set_error("mdt_mol_graph: need R >= 0");
-    return 2;
-  }
-  if (L < 1 || L > mdt::kMolMaxL) {
-    mdt_set_error("mdt_mol_graph: need 1 <= L <= 64");
-    return 2;
-  }
+  if (R < 0) return mdt_bad("mdt_mol_graph: need R >= 0");
+  if (L < 1 || L > mdt::kMolMaxL) return mdt_bad("mdt_mol_graph: need 1 <= L <= 64");
   if (R == 0) return 0;
-  if (!packed || !length || !classes || !max_valence || !elements || !natoms || !atoms || !nbonds || !bonds || !status ||
-      !position) {
-    mdt_set_error("mdt_mol_graph: null pointer");
-    return 2;
-  }
+  if (!packed || !length || !classes || !max_valence || !elements || !natoms || !atoms || !nbonds || !bonds || !status || !position)
+    return mdt_bad("mdt_mol_graph: null pointer");
   const int stride = mdt::molgraph_lane_stride(L);
   const unsigned blocks = (unsigned)(((int64_t)R + mdt::kSmilesLanes - 1) / mdt::kSmilesLanes);
   hipLaunchKernelGGL(mdt::k_mol_graph, dim3(blocks), dim3(mdt::kSmilesLanes), (size_t)stride * mdt::kSmilesLanes,
                      (hipStream_t)stream, packed, length, R, L, stride, classes, max_valence, elements, natoms, atoms, nbonds, bonds,
                      status, position);
-  return molgraph_launched("mdt_mol_graph");
+  return mdt_finish("mdt_mol_graph");
 }
 
 extern "C" int mdt_mol_key(const int32_t* natoms, const uint32_t* atoms, const int32_t* nbonds, const uint32_t* bonds, int32_t L,
                            int32_t R, uint64_t* key, void* stream) {
-  if (R < 0) {
-    mdt_set_error("mdt_mol_key: need R >= 0");
-    return 2;
-  }
-  if (L < 1 || L > mdt::kMolMaxL) {
-    mdt_set_error("mdt_mol_key: need 1 <= L <= 64");
-    return 2;
-  }
+  if (R < 0) return mdt_bad("mdt_mol_key: need R >= 0");
+  if (L < 1 || L > mdt::kMolMaxL) return mdt_bad("mdt_mol_key: need 1 <= L <= 64");
   if (R == 0) return 0;
-  if (!natoms || !atoms || !nbonds || !bonds || !key) {
-    mdt_set_error("mdt_mol_key: null pointer");
-    return 2;
-  }
+  if (!natoms || !atoms || !nbonds || !bonds || !key) return mdt_bad("mdt_mol_key: null pointer");
   hipLaunchKernelGGL(mdt::k_mol_key, dim3((unsigned)R), dim3(64), (size_t)2 * L * 64 * sizeof(uint64_t), (hipStream_t)stream, natoms,
                      atoms, nbonds, bonds, L, key);
-  return molgraph_launched("mdt_mol_key");
+  return mdt_finish("mdt_mol_key");
 }
 
 extern "C" int mdt_key_flags(const uint64_t* key, int32_t N, int32_t G, const uint64_t* known_key, int32_t M, uint8_t* flags,
                              void* stream) {
-  if (N < 1 || N > mdt::kKeyFlagsMaxN) {
-    mdt_set_error("mdt_key_flags: need 1 <= N <= 1024");
-    return 2;
-  }
-  if (G < 0 || M < 0) {
-    mdt_set_error("mdt_key_flags: need G >= 0 and M >= 0");
-    return 2;
-  }
+  if (N < 1 || N > mdt::kKeyFlagsMaxN) return mdt_bad("mdt_key_flags: need 1 <= N <= 1024");
+  if (G < 0 || M < 0) return mdt_bad("mdt_key_flags: need G >= 0 and M >= 0");
   if (G == 0) return 0;
-  if (!key || !flags || (M > 0 && !known_key)) {
-    mdt_set_error("mdt_key_flags: null pointer");
-    return 2;
-  }
+  if (!key || !flags || (M > 0 && !known_key)) return mdt_bad("mdt_key_flags: null pointer");
   hipLaunchKernelGGL(mdt::k_key_flags, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, key, N, G, known_key, M, flags);
-  return molgraph_launched("mdt_key_flags");
+  return mdt_finish("mdt_key_flags");
 }

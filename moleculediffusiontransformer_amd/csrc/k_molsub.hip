@@ -27,13 +27,6 @@ static_assert(kSubMaxPatterns == MDT_SUB_MAX_PATTERNS && kSubMaxWidth == MDT_SUB
               "mdt_hip.h and mdt_molsub.h agree");
 static_assert(kSubFStride >= kSubMaxWidth && (kSubFStride / 4) % 2 == 1, "a map fits and its stride is an odd number of dwords");
 
-// What one lane wrote to LDS is read by other lanes of the SAME wave: order the accesses, no workgroup barrier.
-__device__ __forceinline__ void sub_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // "another root of this row has succeeded": the only reason for which a root may stop early
 struct SubWaveSignal {
   uint32_t* word;
@@ -42,7 +35,7 @@ struct SubWaveSignal {
 };
 
 __device__ __forceinline__ int sub_key(uint32_t w) {            // the later atom of an entry; 255 for an entry (p, p)
-  const int a = sub_a(w), b = sub_b(w);
+  const int a = mol_a(w), b = mol_b(w);
   return a == b ? 255 : (a > b ? a : b);
 }
 
@@ -67,10 +60,10 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_match(
   for (int q = wave; q < P; q += kSubRowsPerBlock) {
     const int m = p_natoms[q], mb = p_nbonds[q];
     const uint32_t* q_bonds = p_bonds + q * LP;
-    bool ok = sub_counts_ok(m, mb, LP);
+    bool ok = mol_counts_ok(m, mb, LP);
     const bool mine = ok && lane < mb;                          // (mb <= LP <= 32 lanes own an entry)
     const uint32_t w = mine ? q_bonds[lane] : 0u;
-    ok = ok && !__any(mine && (sub_a(w) >= m || sub_b(w) >= m || !sub_order_ok(sub_order(w))));
+    ok = ok && !__any(mine && (mol_a(w) >= m || mol_b(w) >= m || !mol_order_ok(mol_order(w))));
     if (lane == 0) s_pm[q] = ok ? m : 0;
     if (!ok) continue;                                          // (wave-uniform)
     if (lane < m) s_patom[q][lane] = p_atoms[q * LP + lane];
@@ -81,10 +74,10 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_match(
       const int kk = sub_key(wk);
       pos += (int)(kk < key || (kk == key && k < lane));        // entries sorted by later atom, then by index
       start += (int)(kk < lane);                                // lane as pattern atom: the entries of the atoms before it
-      if (kk == 255 && sub_a(wk) == lane) self |= 1 << (sub_order(wk) - 1);
+      if (kk == 255 && mol_a(wk) == lane) self |= 1 << (mol_order(wk) - 1);
     }
     if (mine && key != 255)                                     // (pos < the entries that are no (p, p): inside the row)
-      s_back[q][pos] = (uint16_t)((sub_a(w) < sub_b(w) ? sub_a(w) : sub_b(w)) | sub_order(w) << 8);
+      s_back[q][pos] = (uint16_t)((mol_a(w) < mol_b(w) ? mol_a(w) : mol_b(w)) | mol_order(w) << 8);
     if (lane <= m) s_bstart[q][lane] = (uint8_t)start;          // (m <= 32 < kSubFStride)
     if (lane < m) s_selfneed[q][lane] = (uint8_t)self;
   }
@@ -96,19 +89,19 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_match(
   // ---- the rows: bounded by R ----
   for (int64_t row = (int64_t)blockIdx.x * kSubRowsPerBlock + wave; row < R; row += (int64_t)gridDim.x * kSubRowsPerBlock) {
     const int n = natoms[row], nb = nbonds[row];
-    bool ok = sub_counts_ok(n, nb, L);                          // the rule of k_mol_key: such a row is no molecule
+    bool ok = mol_counts_ok(n, nb, L);                          // the rule of k_mol_key: such a row is no molecule
     const bool mine = ok && lane < nb;                          // (nb <= L <= 64 lanes own an entry)
     const uint32_t w = mine ? bonds[row * L + lane] : 0u;
-    ok = ok && !__any(mine && (sub_a(w) >= n || sub_b(w) >= n));
+    ok = ok && !__any(mine && (mol_a(w) >= n || mol_b(w) >= n));
     uint32_t mt = 0, und = 0;
     if (ok) {
       for (int o = 0; o < kSubOrders; ++o) adj[o * 64 + lane] = 0;
-      sub_wave_sync();
-      if (mine && sub_order_ok(sub_order(w))) {                 // (a, b < n <= 64, order in 1..5: inside the five columns)
-        atomicOr(&adj[(sub_order(w) - 1) * 64 + sub_a(w)], 1ull << sub_b(w));
-        atomicOr(&adj[(sub_order(w) - 1) * 64 + sub_b(w)], 1ull << sub_a(w));
+      wave_lds_sync();
+      if (mine && mol_order_ok(mol_order(w))) {                 // (a, b < n <= 64, order in 1..5: inside the five columns)
+        atomicOr(&adj[(mol_order(w) - 1) * 64 + mol_a(w)], 1ull << mol_b(w));
+        atomicOr(&adj[(mol_order(w) - 1) * 64 + mol_b(w)], 1ull << mol_a(w));
       }
-      sub_wave_sync();
+      wave_lds_sync();
       const uint32_t desc = lane < n ? atoms[row * L + lane] : 0u;
       uint32_t have = 0;                                        // the orders of this atom's entries (t, t)
       for (int o = 0; o < kSubOrders; ++o) have |= (uint32_t)((adj[o * 64 + lane] >> lane) & 1ull) << o;
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_match(
           continue;
         }
         if (lane == 0) s_found[wave] = 0;
-        sub_wave_sync();
+        wave_lds_sync();
         int code = kSubNone;
         if ((roots >> lane) & 1ull) {
           // every loop inside is bounded by the back-bonds of one atom (<= LP) or by the step cap (see sub_root_search)
@@ -141,7 +134,7 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_match(
         const bool found = __any(code == kSubFound), capped = __any(code == kSubCapped);
         if (found) mt |= 1u << q;
         else if (capped) und |= 1u << q;
-        sub_wave_sync();                                        // (the next pattern writes compat and the found word again)
+        wave_lds_sync();                                        // (the next pattern writes compat and the found word again)
       }
     }
     if (lane == 0) {
@@ -157,39 +150,23 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_match(
 // ------------------------------------------------------------------------------------------------
 // C ABI entry point of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
-namespace {
-inline int bad(const char* msg) {
-  mdt_set_error(msg);
-  return 2;
-}
-}  // namespace
-
 extern "C" int mdt_sub_match(const int32_t* natoms, const uint32_t* atoms, const int32_t* nbonds, const uint32_t* bonds, int32_t L,
                              int32_t R, const int32_t* p_natoms, const uint32_t* p_atoms, const int32_t* p_nbonds,
                              const uint32_t* p_bonds, int32_t LP, int32_t P, uint32_t need, uint32_t ban, uint32_t* match,
                              uint32_t* undecided, uint8_t* flags, void* stream) {
-  if (R < 0) return bad("mdt_sub_match: need R >= 0");
-  if (L < 1 || L > mdt::kMolMaxL) return bad("mdt_sub_match: need 1 <= L <= 64");
-  if (LP < 1 || LP > mdt::kSubMaxWidth) return bad("mdt_sub_match: need 1 <= LP <= 32");
-  if (P < 1 || P > mdt::kSubMaxPatterns) return bad("mdt_sub_match: need 1 <= P <= 32");
+  if (R < 0) return mdt_bad("mdt_sub_match: need R >= 0");
+  if (L < 1 || L > mdt::kMolMaxL) return mdt_bad("mdt_sub_match: need 1 <= L <= 64");
+  if (LP < 1 || LP > mdt::kSubMaxWidth) return mdt_bad("mdt_sub_match: need 1 <= LP <= 32");
+  if (P < 1 || P > mdt::kSubMaxPatterns) return mdt_bad("mdt_sub_match: need 1 <= P <= 32");
   const uint32_t all = P == 32 ? 0xFFFFFFFFu : (1u << P) - 1u;
-  if ((need | ban) & ~all) return bad("mdt_sub_match: need and ban may only have bits below P");
-  if (need & ban) return bad("mdt_sub_match: need and ban may not overlap");
+  if ((need | ban) & ~all) return mdt_bad("mdt_sub_match: need and ban may only have bits below P");
+  if (need & ban) return mdt_bad("mdt_sub_match: need and ban may not overlap");
   if (R == 0) return 0;
   if (!natoms || !atoms || !nbonds || !bonds || !p_natoms || !p_atoms || !p_nbonds || !p_bonds || !match || !undecided)
-    return bad("mdt_sub_match: null pointer");
+    return mdt_bad("mdt_sub_match: null pointer");
   const int64_t want = ((int64_t)R + mdt::kSubRowsPerBlock - 1) / mdt::kSubRowsPerBlock;
   const unsigned blocks = (unsigned)(want < mdt::kSubMaxBlocks ? want : mdt::kSubMaxBlocks);
   hipLaunchKernelGGL(mdt::k_sub_match, dim3(blocks), dim3(64 * mdt::kSubRowsPerBlock), 0, (hipStream_t)stream, natoms, atoms, nbonds,
                      bonds, L, R, p_natoms, p_atoms, p_nbonds, p_bonds, LP, P, need, ban, match, undecided, flags);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "mdt_sub_match: %s", hipGetErrorString(e));
-    mdt_set_error(buf);
-    return 1;
-  }
-  return 0;
+  return mdt_finish("mdt_sub_match");
 }

@@ -7,7 +7,8 @@
 //   k_screen_score     weighted mean squared distance of the re-predicted properties from the group's target
 //   k_screen_select    per group: status bits (empty / non-finite / duplicate / known) and the K best eligible candidates
 //   k_screen_select_diverse   the same with novelty as a distance and the K best that lie min_distance edits apart
-// Both selections take an optional per-row `reject` byte (mdt_smiles_check's status) that is OR-ed into the status first.
+// Both selections take an optional per-row `reject` byte (mdt_smiles_check's status) that is OR-ed into the status first; they
+// open with the same select_prologue, and their five entry points check and launch through one select_launch.
 //
 // Rows are r = c * G + g: candidate c of group g (a group is one target conditioning), the layout of guidance_sweep.
 // A molecule IS its compacted id row (the reference's string: a character-level tokenizer, id 0 skipped), so equality is decided
@@ -124,6 +125,43 @@ __device__ __forceinline__ int candidate_status(int c, int g, int G, int L, cons
   return st;
 }
 
+// The opening of both selections, by the group's whole workgroup: the keys, scores and lengths of its N candidates into LDS; every
+// candidate's status -- candidate_status, KNOWN also where known_dist (or nullptr) is below min_novelty, then the `reject` byte (or
+// nullptr: a verdict from outside such as mdt_smiles_check's, never eligible) -- into s_status and `status`.  Ends behind a
+// barrier; -> the number of eligible candidates (status 0), the same in every thread.
+__device__ __forceinline__ int select_prologue(const float* __restrict__ score, const uint64_t* __restrict__ key,
+                                               const int32_t* __restrict__ packed, const int32_t* __restrict__ length, int L, int N,
+                                               int G, const uint64_t* __restrict__ known_key,
+                                               const int32_t* __restrict__ known_packed, const int32_t* __restrict__ known_len, int M,
+                                               const int32_t* __restrict__ known_dist, int min_novelty,
+                                               const uint8_t* __restrict__ reject, uint8_t* __restrict__ status, uint64_t* s_key,
+                                               float* s_score, int32_t* s_len, uint8_t* s_status, int* s_eligible) {
+  const int g = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) *s_eligible = 0;
+  for (int c = tid; c < N; c += 256) {
+    const int64_t r = (int64_t)c * G + g;
+    s_key[c] = key[r];
+    s_score[c] = score[r];
+    const int len = length[r];
+    s_len[c] = len < 0 ? 0 : (len > L ? L : len);                // (never read a row past its L ids, whatever length holds)
+  }
+  __syncthreads();
+
+  int mine = 0;
+  for (int c = tid; c < N; c += 256) {
+    int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
+    if (known_dist && known_dist[(int64_t)c * G + g] < min_novelty) st |= MDT_SCREEN_KNOWN;
+    if (reject) st |= reject[(int64_t)c * G + g];
+    s_status[c] = (uint8_t)st;
+    status[(int64_t)c * G + g] = (uint8_t)st;
+    mine += st == 0;
+  }
+  if (mine) atomicAdd(s_eligible, mine);
+  __syncthreads();
+  return *s_eligible;
+}
+
 // One workgroup of 256 per group; the group's keys, scores, lengths and status bytes sit in LDS (17 KiB at N = 1024).
 __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__ score, const uint64_t* __restrict__ key,
                                                        const int32_t* __restrict__ packed, const int32_t* __restrict__ length, int L,
@@ -139,28 +177,9 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
   __shared__ int s_eligible;
   const int g = blockIdx.x;
   const int tid = threadIdx.x;
-  if (tid == 0) s_eligible = 0;
-  for (int c = tid; c < N; c += 256) {
-    const int64_t r = (int64_t)c * G + g;
-    s_key[c] = key[r];
-    s_score[c] = score[r];
-    const int len = length[r];
-    s_len[c] = len < 0 ? 0 : (len > L ? L : len);                // (never read a row past its L ids, whatever length holds)
-  }
-  __syncthreads();
-
-  int mine = 0;
-  for (int c = tid; c < N; c += 256) {
-    int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
-    if (reject) st |= reject[(int64_t)c * G + g];                // a verdict from outside (mdt_smiles_check): not eligible
-    s_status[c] = (uint8_t)st;
-    status[(int64_t)c * G + g] = (uint8_t)st;
-    mine += st == 0;
-  }
-  if (mine) atomicAdd(&s_eligible, mine);
-  __syncthreads();
-
-  const int filled = s_eligible < K ? s_eligible : K;
+  const int eligible = select_prologue(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, nullptr, 0, reject,
+                                       status, s_key, s_score, s_len, s_status, &s_eligible);
+  const int filled = eligible < K ? eligible : K;
   for (int c = tid; c < N; c += 256) {
     if (s_status[c]) continue;
     const float sc = s_score[c];
@@ -199,29 +218,8 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
   __shared__ int s_eligible;
   const int g = blockIdx.x;
   const int tid = threadIdx.x;
-  if (tid == 0) s_eligible = 0;
-  for (int c = tid; c < N; c += 256) {
-    const int64_t r = (int64_t)c * G + g;
-    s_key[c] = key[r];
-    s_score[c] = score[r];
-    const int len = length[r];
-    s_len[c] = len < 0 ? 0 : (len > L ? L : len);
-  }
-  __syncthreads();
-
-  int mine = 0;
-  for (int c = tid; c < N; c += 256) {
-    int st = candidate_status(c, g, G, L, s_key, s_score, s_len, packed, known_key, known_packed, known_len, M);
-    if (known_dist && known_dist[(int64_t)c * G + g] < min_novelty) st |= MDT_SCREEN_KNOWN;
-    if (reject) st |= reject[(int64_t)c * G + g];
-    s_status[c] = (uint8_t)st;
-    status[(int64_t)c * G + g] = (uint8_t)st;
-    mine += st == 0;
-  }
-  if (mine) atomicAdd(&s_eligible, mine);
-  __syncthreads();
-
-  const int eligible = s_eligible;
+  const int eligible = select_prologue(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, known_dist,
+                                       min_novelty, reject, status, s_key, s_score, s_len, s_status, &s_eligible);
   for (int c = tid; c < N; c += 256) {
     if (s_status[c]) continue;
     const float sc = s_score[c];
@@ -293,22 +291,44 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
 // ------------------------------------------------------------------------------------------------
 // C ABI entry points of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
 namespace {
-inline int finish(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    mdt_set_error(buf);
-    return 1;
-  }
-  return 0;
-}
-inline int bad(const char* msg) {
-  mdt_set_error(msg);
-  return 2;
+// Every selection's checks and its launch.  name: what the messages start with; L_max: 1024 takes k_screen_select, 64 the diverse
+// kernel (rows of one 64-bit word), which looks at the fingerprints iff with_fp.  Two things here are as callers have come to know
+// them, and the host tests pin both: the entry points with `reject` report under the name of the one without (they were added as
+// its extension and share its messages), and with fingerprints the ranges are checked BEFORE an empty batch (G <= 0) returns 0,
+// without them after.
+int select_launch(const char* name, int L_max, bool with_fp, const float* score, const uint64_t* key, const int32_t* packed,
+                  const int32_t* length, int32_t L, int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed,
+                  const int32_t* known_len, int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty,
+                  int32_t min_distance, const uint8_t* reject, const uint64_t* fp, const int32_t* fp_count, int32_t sim_num,
+                  uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+  if (!with_fp && G <= 0) return 0;
+  if (N < 1 || N > mdt::kScreenMaxN) return mdt_bad(name, ": need 1 <= N <= 1024 candidates per group");
+  if (K < 1 || K > N) return mdt_bad(name, ": need 1 <= K <= N");
+  if (L < 1 || L > L_max)
+    return mdt_bad(name, L_max == 1024 ? ": need 1 <= L <= 1024"
+                         : with_fp      ? ": need 1 <= L <= 64 positions per row"
+                                        : ": need 1 <= L <= 64 (the edit distance takes rows of one 64-bit word)");
+  if (M < 0) return mdt_bad(name, ": need M >= 0");
+  if (with_fp && (sim_num < 1 || sim_num > MDT_FP_SIM_DEN)) return mdt_bad(name, ": need 1 <= sim_num <= 65536");
+  if (G <= 0) return 0;
+  if (M > 0 && (!known_key || !known_packed || !known_len))
+    return mdt_bad(name, ": the known-set pointers may be NULL only when M == 0");
+  if (!score || !key || !packed || !length || !status || !index || !count || (with_fp && (!fp || !fp_count)))
+    return mdt_bad(name, ": null pointer");
+  const dim3 grid((unsigned)G), block(256);
+  if (L_max == 1024)
+    hipLaunchKernelGGL(mdt::k_screen_select, grid, block, 0, (hipStream_t)stream, score, key, packed, length, L, N, G, known_key,
+                       known_packed, known_len, M, K, reject, status, index, count);
+  else if (with_fp)
+    hipLaunchKernelGGL(mdt::k_screen_select_diverse<true>, grid, block, 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
+                       known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count,
+                       (uint32_t)sim_num, status, index, count);
+  else
+    hipLaunchKernelGGL(mdt::k_screen_select_diverse<false>, grid, block, 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
+                       known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject,
+                       (const uint64_t*)nullptr, (const int32_t*)nullptr, 0u, status, index, count);
+  return mdt_finish(name);
 }
 }  // namespace
 
@@ -317,44 +337,35 @@ extern "C" {
 int mdt_tokens_compact(const int32_t* tokens, int32_t B, int32_t L, float* fwd_in, int32_t Lf, double x_norm, int32_t* packed,
                        int32_t* length, uint64_t* key, void* stream) {
   if (B <= 0) return 0;
-  if (!tokens || !packed || !length || !key) return bad("mdt_tokens_compact: null pointer");
-  if (tokens == packed) return bad("mdt_tokens_compact: packed must not be the tokens themselves");
-  if (L < 1) return bad("mdt_tokens_compact: need L >= 1");
-  if (fwd_in && Lf < 1) return bad("mdt_tokens_compact: need Lf >= 1 with fwd_in");
-  if (fwd_in && !(std::isfinite(x_norm) && x_norm != 0.0)) return bad("mdt_tokens_compact: x_norm must be finite and non-zero");
+  if (!tokens || !packed || !length || !key) return mdt_bad("mdt_tokens_compact: null pointer");
+  if (tokens == packed) return mdt_bad("mdt_tokens_compact: packed must not be the tokens themselves");
+  if (L < 1) return mdt_bad("mdt_tokens_compact: need L >= 1");
+  if (fwd_in && Lf < 1) return mdt_bad("mdt_tokens_compact: need Lf >= 1 with fwd_in");
+  if (fwd_in && !(std::isfinite(x_norm) && x_norm != 0.0)) return mdt_bad("mdt_tokens_compact: x_norm must be finite and non-zero");
   hipLaunchKernelGGL(mdt::k_tokens_compact, dim3(((unsigned)B + 3) / 4), dim3(256), 0, (hipStream_t)stream, tokens, B, L, fwd_in,
                      Lf, x_norm, packed, length, key);
-  return finish("mdt_tokens_compact");
+  return mdt_finish("mdt_tokens_compact");
 }
 
 int mdt_screen_score(const float* props, int64_t row_stride, const float* target, const float* weights, int32_t N, int32_t G,
                      int32_t n, float* score, void* stream) {
   if (N <= 0 || G <= 0) return 0;
-  if (!props || !target || !score) return bad("mdt_screen_score: null pointer");
-  if (n < 1 || n > 64) return bad("mdt_screen_score: need 1 <= n <= 64 properties");
-  if (row_stride < n) return bad("mdt_screen_score: row_stride must be at least n");
-  if ((int64_t)N * G > INT_MAX) return bad("mdt_screen_score: N * G exceeds 2^31 - 1 rows");
+  if (!props || !target || !score) return mdt_bad("mdt_screen_score: null pointer");
+  if (n < 1 || n > 64) return mdt_bad("mdt_screen_score: need 1 <= n <= 64 properties");
+  if (row_stride < n) return mdt_bad("mdt_screen_score: row_stride must be at least n");
+  if ((int64_t)N * G > INT_MAX) return mdt_bad("mdt_screen_score: N * G exceeds 2^31 - 1 rows");
   const int rows = N * G;
   hipLaunchKernelGGL(mdt::k_screen_score, dim3(((unsigned)rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, props, row_stride,
                      target, weights, rows, G, n, score);
-  return finish("mdt_screen_score");
+  return mdt_finish("mdt_screen_score");
 }
 
 int mdt_screen_select_reject(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
                              int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
                              int32_t M, int32_t K, const uint8_t* reject, uint8_t* status, int32_t* index, int32_t* count,
                              void* stream) {
-  if (G <= 0) return 0;
-  if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select: need 1 <= N <= 1024 candidates per group");
-  if (K < 1 || K > N) return bad("mdt_screen_select: need 1 <= K <= N");
-  if (L < 1 || L > 1024) return bad("mdt_screen_select: need 1 <= L <= 1024");
-  if (M < 0) return bad("mdt_screen_select: need M >= 0");
-  if (M > 0 && (!known_key || !known_packed || !known_len))
-    return bad("mdt_screen_select: the known-set pointers may be NULL only when M == 0");
-  if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select: null pointer");
-  hipLaunchKernelGGL(mdt::k_screen_select, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
-                     known_key, known_packed, known_len, M, K, reject, status, index, count);
-  return finish("mdt_screen_select");
+  return select_launch("mdt_screen_select", 1024, false, score, key, packed, length, L, N, G, known_key, known_packed, known_len, M,
+                       K, nullptr, 0, 0, reject, nullptr, nullptr, 0, status, index, count, stream);
 }
 
 int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L, int32_t N,
@@ -369,18 +380,9 @@ int mdt_screen_select_diverse_reject(const float* score, const uint64_t* key, co
                                      const int32_t* known_len, int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty,
                                      int32_t min_distance, const uint8_t* reject, uint8_t* status, int32_t* index, int32_t* count,
                                      void* stream) {
-  if (G <= 0) return 0;
-  if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select_diverse: need 1 <= N <= 1024 candidates per group");
-  if (K < 1 || K > N) return bad("mdt_screen_select_diverse: need 1 <= K <= N");
-  if (L < 1 || L > 64) return bad("mdt_screen_select_diverse: need 1 <= L <= 64 (the edit distance takes rows of one 64-bit word)");
-  if (M < 0) return bad("mdt_screen_select_diverse: need M >= 0");
-  if (M > 0 && (!known_key || !known_packed || !known_len))
-    return bad("mdt_screen_select_diverse: the known-set pointers may be NULL only when M == 0");
-  if (!score || !key || !packed || !length || !status || !index || !count) return bad("mdt_screen_select_diverse: null pointer");
-  hipLaunchKernelGGL(mdt::k_screen_select_diverse<false>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed,
-                     length, L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject,
-                     (const uint64_t*)nullptr, (const int32_t*)nullptr, 0u, status, index, count);
-  return finish("mdt_screen_select_diverse");
+  return select_launch("mdt_screen_select_diverse", 64, false, score, key, packed, length, L, N, G, known_key, known_packed,
+                       known_len, M, K, known_dist, min_novelty, min_distance, reject, nullptr, nullptr, 0, status, index, count,
+                       stream);
 }
 
 int mdt_screen_select_similar(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
@@ -391,20 +393,8 @@ int mdt_screen_select_similar(const float* score, const uint64_t* key, const int
   if (!fp && !fp_count)                                         // no fingerprints: the selection as it was, the same launch
     return mdt_screen_select_diverse_reject(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, K,
                                             known_dist, min_novelty, min_distance, reject, status, index, count, stream);
-  if (N < 1 || N > mdt::kScreenMaxN) return bad("mdt_screen_select_similar: need 1 <= N <= 1024 candidates per group");
-  if (K < 1 || K > N) return bad("mdt_screen_select_similar: need 1 <= K <= N");
-  if (L < 1 || L > 64) return bad("mdt_screen_select_similar: need 1 <= L <= 64 positions per row");
-  if (M < 0) return bad("mdt_screen_select_similar: need M >= 0");
-  if (sim_num < 1 || sim_num > MDT_FP_SIM_DEN) return bad("mdt_screen_select_similar: need 1 <= sim_num <= 65536");
-  if (G <= 0) return 0;
-  if (M > 0 && (!known_key || !known_packed || !known_len))
-    return bad("mdt_screen_select_similar: the known-set pointers may be NULL only when M == 0");
-  if (!score || !key || !packed || !length || !status || !index || !count || !fp || !fp_count)
-    return bad("mdt_screen_select_similar: null pointer");
-  hipLaunchKernelGGL(mdt::k_screen_select_diverse<true>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, score, key, packed,
-                     length, L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, fp,
-                     fp_count, (uint32_t)sim_num, status, index, count);
-  return finish("mdt_screen_select_similar");
+  return select_launch("mdt_screen_select_similar", 64, true, score, key, packed, length, L, N, G, known_key, known_packed, known_len,
+                       M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count, sim_num, status, index, count, stream);
 }
 
 int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,

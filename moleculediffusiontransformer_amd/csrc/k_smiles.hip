@@ -80,34 +80,17 @@ __global__ __launch_bounds__(kSmilesLanes) void k_smiles_check(const int32_t* __
 // ------------------------------------------------------------------------------------------------
 // C ABI entry point of this translation unit (declared in include/mdt_hip.h)
 // ------------------------------------------------------------------------------------------------
-extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);  // mdt_api.cpp (not exported)
-
 extern "C" int mdt_smiles_check(const int32_t* packed, const int32_t* length, int32_t L, int32_t R, const uint8_t* classes,
                                 const uint8_t* max_valence, const uint32_t* elements, uint8_t* status, int32_t* position,
                                 void* stream) {
-  if (R < 0) {
-    mdt_set_error("mdt_smiles_check: need R >= 0");
-    return 2;
-  }
-  if (L < 1 || L > mdt::kSmilesMaxL) {
-    mdt_set_error("mdt_smiles_check: need 1 <= L <= 128");
-    return 2;
-  }
+  if (R < 0) return mdt_bad("mdt_smiles_check: need R >= 0");
+  if (L < 1 || L > mdt::kSmilesMaxL) return mdt_bad("mdt_smiles_check: need 1 <= L <= 128");
   if (R == 0) return 0;
-  if (!packed || !length || !classes || !max_valence || !elements || !status || !position) {
-    mdt_set_error("mdt_smiles_check: null pointer");
-    return 2;
-  }
+  if (!packed || !length || !classes || !max_valence || !elements || !status || !position)
+    return mdt_bad("mdt_smiles_check: null pointer");
   const int stride = mdt::smiles_lane_stride(L);
   const unsigned blocks = (unsigned)(((int64_t)R + mdt::kSmilesLanes - 1) / mdt::kSmilesLanes);
   hipLaunchKernelGGL(mdt::k_smiles_check, dim3(blocks), dim3(mdt::kSmilesLanes), (size_t)stride * mdt::kSmilesLanes,
                      (hipStream_t)stream, packed, length, R, L, stride, classes, max_valence, elements, status, position);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "mdt_smiles_check: %s", hipGetErrorString(e));
-    mdt_set_error(buf);
-    return 1;
-  }
-  return 0;
+  return mdt_finish("mdt_smiles_check");
 }

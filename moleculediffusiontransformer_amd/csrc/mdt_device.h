@@ -1,5 +1,7 @@
 // Device primitives shared by the ring and block kernels (k_tblock_lw, k_tblock32, k_tf128, k_tf256, k_rconv, k_res256, k_proj,
-// k_resblock, k_attn): vector types, MFMA names, lane-group exchanges, operand splits, counted LDS reads and their waits.
+// k_resblock, k_attn): vector types, MFMA names, lane-group exchanges, operand splits, counted LDS reads and their waits; and by the
+// screening kernels (k_screen, k_edit, k_molgraph, k_molfp, k_molsub): the 64-bit shuffle, the edit-distance recurrence, the
+// wave-local LDS ordering.
 // Device code only; included by the .hip files that use it, never through mdt_kernels.h (mdt_api.cpp does not see it).
 // Everything is __forceinline__: a kernel's code object does not depend on whether a primitive is defined here or in its file.
 // The rule: a primitive used by two kernels lives here, once, with its rationale; what one kernel alone uses stays in its file.
@@ -140,6 +142,16 @@ __device__ __forceinline__ bf16x8 row_shift(const bf16x8& v, bool keep) {
     r[k] = keep ? t : 0;
   }
   return __builtin_bit_cast(bf16x8, r);
+}
+
+// What one lane wrote to LDS is read by other lanes of the SAME wave (k_molfp: the labels and the fingerprint of a row; k_molsub:
+// the adjacency columns, the compat words and the found word of a row): order the accesses.  The waves of these workgroups each
+// own a row and its slice of LDS, so a workgroup barrier would couple waves that share nothing -- and could not be reached from
+// their wave-uniform, per-row control flow.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // 64-bit butterfly exchange over the wave as two 32-bit shuffles (k_screen: the row key; k_molgraph: the sum over the roots)

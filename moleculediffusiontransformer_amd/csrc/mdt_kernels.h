@@ -29,6 +29,31 @@ static inline const char* mdt_tuning_env(const char* name) {
 #endif
 }
 
+// The tail of a C entry point that lives next to its kernels (k_elem, k_screen, k_edit, k_smiles, k_molgraph, k_molfp, k_molsub):
+// the message goes to mdt_last_error() through mdt_set_error (mdt_api.cpp; hidden, so not part of the exported C ABI).
+#include <cstdio>
+extern "C" __attribute__((visibility("hidden"))) void mdt_set_error(const char* msg);
+// an argument the entry point refuses: nothing was launched
+static inline int mdt_bad(const char* msg) {
+  mdt_set_error(msg);
+  return 2;
+}
+// ... by a launcher that serves several entry points (k_elem's tile launchers, k_screen's selections): `name` and what follows it
+static inline int mdt_bad(const char* name, const char* msg) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s%s", name, msg);
+  return mdt_bad(buf);
+}
+// after the last launch of entry point `who`: 0, or 1 with "<who>: <the HIP error>"
+static inline int mdt_finish(const char* who) {
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s: %s", who, hipGetErrorString(e));
+  mdt_set_error(buf);
+  return 1;
+}
+
 // priority of the loader waves of the ring kernels (s_setprio): 3 = their few instructions issue ahead of the MFMA waves
 #ifndef MDT_LOADER_PRIO
 #define MDT_LOADER_PRIO 3

@@ -1,7 +1,7 @@
-// Graph substructure match (mdt_hip.h, mdt_sub_match): the atom rule, the checks made before any search and the depth-first search
-// of one root with its step count.  Like mdt_smiles_scan.h everything here is __host__ __device__ and touches only the arrays it is
-// handed, so the kernel (k_molsub.hip: tables in LDS, one root per lane) and a host program (tools/molsub_host_check.cpp: tables in
-// arrays of exactly their size) run the same search.
+// Graph substructure match (mdt_hip.h, mdt_sub_match): the atom rule and the depth-first search of one root with its step count;
+// the bond word and the check made before any search (mol_graph_ok) are mdt_smiles_scan.h's.  Like that header everything here is
+// __host__ __device__ and touches only the arrays it is handed, so the kernel (k_molsub.hip: tables in LDS, one root per lane) and
+// a host program (tools/molsub_host_check.cpp: tables in arrays of exactly their size) run the same search.
 #pragma once
 
 #include <cstdint>
@@ -11,7 +11,7 @@
 
 namespace mdt {
 
-constexpr int kSubMaxPatterns = 32, kSubMaxWidth = 32, kSubMaxSteps = 4096, kSubOrders = 5;
+constexpr int kSubMaxPatterns = 32, kSubMaxWidth = 32, kSubMaxSteps = 4096, kSubOrders = kMolOrders;
 enum { kSubNone = 0, kSubFound = 1, kSubCapped = 2, kSubStopped = 3 };   // what one root's search ends with
 
 // which bits of the descriptor pattern atom p compares: symbol and aromatic bit unless it is '*', charge, H count and isotope when it
@@ -20,12 +20,6 @@ __host__ __device__ __forceinline__ uint32_t sub_atom_mask(uint32_t p) {
   return ((p & kMolBracket) ? 0xFFFFF000u : 0u) | ((p & 31u) == (uint32_t)kMolStar ? 0u : 0x7FFu);
 }
 __host__ __device__ __forceinline__ bool sub_accepts(uint32_t p, uint32_t t) { return ((p ^ t) & sub_atom_mask(p)) == 0; }
-// the bond word a | b << 8 | order << 16
-__host__ __device__ __forceinline__ int sub_a(uint32_t w) { return (int)(w & 255u); }
-__host__ __device__ __forceinline__ int sub_b(uint32_t w) { return (int)((w >> 8) & 255u); }
-__host__ __device__ __forceinline__ int sub_order(uint32_t w) { return (int)(w >> 16); }
-__host__ __device__ __forceinline__ bool sub_order_ok(int o) { return (unsigned)(o - 1) < (unsigned)kSubOrders; }
-__host__ __device__ __forceinline__ bool sub_counts_ok(int n, int nb, int width) { return !(n < 1 || n > width || nb < 0 || nb > width); }
 // the bits above bit t
 __host__ __device__ __forceinline__ uint64_t sub_above(int t) { return ~(((uint64_t)2 << t) - 1); }
 __host__ __device__ __forceinline__ int sub_lowest(uint64_t w) {
@@ -101,16 +95,6 @@ struct SubNoSignal {
   __host__ __device__ __forceinline__ void found() const {}
 };
 
-// Is (n, nb, bonds[0:nb]) a graph of this width that can take part?  Counts inside [1, width] x [0, width], every bond end below n
-// (the rule of mdt_mol_key); with `orders`, also every order in 1..5 (asked of a pattern: an entry of any other order, which
-// mdt_mol_graph never writes, could not be satisfied).
-__host__ __device__ inline bool sub_graph_ok(const uint32_t* bonds, int n, int nb, int width, bool orders) {
-  if (!sub_counts_ok(n, nb, width)) return false;
-  for (int e = 0; e < nb; ++e)
-    if (sub_a(bonds[e]) >= n || sub_b(bonds[e]) >= n || (orders && !sub_order_ok(sub_order(bonds[e])))) return false;
-  return true;
-}
-
 // One (row, pattern) pair, root after root, in the order the definition is written down: -> kSubFound (match), kSubCapped
 // (undecided) or kSubNone.  root_code[0:n] / root_steps[0:n], when given, take every root's own end and step count (-1 / 0 for a
 // target atom that is no root); no root stops for another.  Reads atoms[0:n], bonds[0:nb], p_atoms[0:m], p_bonds[0:mb] and nothing
@@ -120,14 +104,14 @@ __host__ __device__ inline int sub_match_pair(const uint32_t* atoms, const uint3
                                               int* root_steps) {
   if (root_code)
     for (int r = 0; r < n && r < L; ++r) root_code[r] = -1, root_steps[r] = 0;
-  if (!sub_graph_ok(bonds, n, nb, L, false) || !sub_graph_ok(p_bonds, m, mb, LP, true) || m > n) return kSubNone;
+  if (!mol_graph_ok(bonds, n, nb, L, false) || !mol_graph_ok(p_bonds, m, mb, LP, true) || m > n) return kSubNone;
   uint64_t adj[kSubOrders * 64], compat[kSubMaxWidth];
   uint8_t back_start[kSubMaxWidth + 1], f[kSubMaxWidth], self_have[64], self_need[kSubMaxWidth];
   uint16_t back[kSubMaxWidth];
   for (int i = 0; i < kSubOrders * 64; ++i) adj[i] = 0;
   for (int e = 0; e < nb; ++e) {
-    const int a = sub_a(bonds[e]), b = sub_b(bonds[e]), o = sub_order(bonds[e]);
-    if (!sub_order_ok(o)) continue;                             // (no pattern entry asks for such an order)
+    const int a = mol_a(bonds[e]), b = mol_b(bonds[e]), o = mol_order(bonds[e]);
+    if (!mol_order_ok(o)) continue;                             // (no pattern entry asks for such an order)
     adj[(o - 1) * 64 + a] |= (uint64_t)1 << b;
     adj[(o - 1) * 64 + b] |= (uint64_t)1 << a;
   }
@@ -140,7 +124,7 @@ __host__ __device__ inline int sub_match_pair(const uint32_t* atoms, const uint3
     back_start[p] = (uint8_t)k;
     self_need[p] = 0;
     for (int e = 0; e < mb; ++e) {
-      const int a = sub_a(p_bonds[e]), b = sub_b(p_bonds[e]), o = sub_order(p_bonds[e]);
+      const int a = mol_a(p_bonds[e]), b = mol_b(p_bonds[e]), o = mol_order(p_bonds[e]);
       if ((a > b ? a : b) != p) continue;
       if (a == b) self_need[p] |= (uint8_t)(1u << (o - 1));     // an entry (p, p): part of what p accepts
       else back[k++] = (uint16_t)((a < b ? a : b) | o << 8);

@@ -1,7 +1,9 @@
 // The single-pass scanner of SMILES token rows that k_smiles.hip (the verdict) and k_molgraph.hip (the verdict and the molecular
-// graph) share, and the graph key's per-root hash.  The rules: include/mdt_hip.h, mdt_smiles_check and mdt_mol_graph / mdt_mol_key.
-// Everything here is __host__ __device__ and touches only the arrays it is handed, so the rules can be run, and their array bounds
-// checked, in a host program without a device.  Included by the two .hip files only (mdt_api.cpp does not see it).
+// graph) share, the graph row itself -- the bond word's accessors and "is this a graph row?", for k_molgraph.hip, k_molfp.hip and
+// (through mdt_molsub.h) k_molsub.hip -- and the graph key's per-root hash.  The rules: include/mdt_hip.h, mdt_smiles_check and
+// mdt_mol_graph / mdt_mol_key.  Everything here but mol_graph_ok_wave is __host__ __device__ and touches only the arrays it is handed,
+// so the rules can be run, and their array bounds checked, in a host program without a device.  Included by .hip files only
+// (mdt_api.cpp does not see it).
 #pragma once
 
 #include <cstdint>
@@ -63,6 +65,31 @@ __host__ __device__ __forceinline__ uint32_t mol_descriptor(int first, int secon
 __host__ __device__ __forceinline__ int mol_bond_order(int code, bool both_aromatic) {
   if (code == 0) return both_aromatic ? 5 : 1;
   return code >= 2 && code <= 5 ? code : 1;
+}
+// the bond word a | b << 8 | order << 16, for every reader of the graph arrays
+constexpr int kMolOrders = 5;                                  // the orders mol_bond_order writes: 1..5
+__host__ __device__ __forceinline__ int mol_a(uint32_t w) { return (int)(w & 255u); }
+__host__ __device__ __forceinline__ int mol_b(uint32_t w) { return (int)((w >> 8) & 255u); }
+__host__ __device__ __forceinline__ int mol_order(uint32_t w) { return (int)(w >> 16); }
+__host__ __device__ __forceinline__ bool mol_order_ok(int o) { return (unsigned)(o - 1) < (unsigned)kMolOrders; }
+__host__ __device__ __forceinline__ bool mol_counts_ok(int n, int nb, int L) { return !(n < 1 || n > L || nb < 0 || nb > L); }
+// Is (n, nb, bonds[0:nb]) the graph of a row of width L?  Counts inside [1, L] x [0, L], every bond end below n; with `orders`, also
+// every order in 1..5 (asked of a substructure pattern: an entry of any other order, which mdt_mol_graph never writes, could not be
+// satisfied).  A row that fails has no key, no fingerprint and matches nothing.  Reads bonds[0:nb] and nothing beyond.
+__host__ __device__ inline bool mol_graph_ok(const uint32_t* bonds, int n, int nb, int L, bool orders) {
+  if (!mol_counts_ok(n, nb, L)) return false;
+  for (int e = 0; e < nb; ++e)
+    if (mol_a(bonds[e]) >= n || mol_b(bonds[e]) >= n || (orders && !mol_order_ok(mol_order(bonds[e])))) return false;
+  return true;
+}
+// mol_graph_ok (without `orders`) by one wave that looks at one row, lane e owning bond e (nb <= L <= 64): the wave-uniform
+// verdict of k_mol_key and k_mol_fp.  Nothing is read when the counts already fail.  (k_sub_match spells the same check out with
+// these accessors: it keeps the bond word, and through this helper its search came out 1-3 % slower on eight patterns.)
+__device__ __forceinline__ bool mol_graph_ok_wave(const uint32_t* __restrict__ bonds, int n, int nb, int L, int lane) {
+  const bool counts = mol_counts_ok(n, nb, L);
+  const bool mine = counts && lane < nb;
+  const uint32_t w = mine ? bonds[lane] : 0u;
+  return counts && !__any(mine && (mol_a(w) >= n || mol_b(w) >= n));
 }
 
 // The emitter of the scan that only judges: nothing is recorded, and what the scan computes for it alone is dead code.
@@ -318,8 +345,8 @@ __host__ __device__ inline uint64_t mol_root_hash(const uint32_t* __restrict__ a
   for (int round = 0; round < n; ++round) {
     for (int e = 0; e < nb; ++e) {
       const uint32_t w = bonds[e];
-      const int a = (int)(w & 255u), b = (int)((w >> 8) & 255u);
-      const uint64_t ok = (uint64_t)(w >> 16) * kMolBondK;
+      const int a = mol_a(w), b = mol_b(w);
+      const uint64_t ok = (uint64_t)mol_order(w) * kMolBondK;
       const uint64_t la = lab[a * stride], lb = lab[b * stride];
       acc[a * stride] += mol_mix(lb + ok);
       acc[b * stride] += mol_mix(la + ok);
@@ -358,24 +385,17 @@ __host__ __device__ __forceinline__ int fp_popc64(uint64_t w) {
   return __builtin_popcountll(w);
 #endif
 }
-// Is (n, nb, bonds[0:nb]) the graph of a row of width L?  Counts inside [1, L] x [0, L], every bond end below n.
-__host__ __device__ inline bool fp_graph_ok(const uint32_t* bonds, int n, int nb, int L) {
-  if (n < 1 || n > L || nb < 0 || nb > L) return false;
-  for (int e = 0; e < nb; ++e)
-    if ((int)(bonds[e] & 255u) >= n || (int)((bonds[e] >> 8) & 255u) >= n) return false;
-  return true;
-}
 // The fingerprint of one row, atom after atom: fp[0:16], returns the number of set bits.  This is the definition in the order it is
 // written down; k_mol_fp computes the same with one atom per lane.  atoms[0:n], bonds[0:nb] are read, nothing beyond.
 __host__ __device__ inline int fp_row(const uint32_t* atoms, const uint32_t* bonds, int n, int nb, int L, int radius, uint64_t* fp) {
   for (int w = 0; w < kFpWords; ++w) fp[w] = 0;
-  if (!fp_graph_ok(bonds, n, nb, L)) return 0;
+  if (!mol_graph_ok(bonds, n, nb, L, false)) return 0;
   uint64_t id[kMolMaxL], acc[kMolMaxL];
   int deg[kMolMaxL];
   for (int a = 0; a < n; ++a) deg[a] = 0;
   for (int e = 0; e < nb; ++e) {
-    ++deg[bonds[e] & 255u];
-    ++deg[(bonds[e] >> 8) & 255u];
+    ++deg[mol_a(bonds[e])];
+    ++deg[mol_b(bonds[e])];
   }
   for (int a = 0; a < n; ++a) id[a] = fp_seed(atoms[a], deg[a]);
   for (int r = 0;; ++r) {
@@ -384,8 +404,8 @@ __host__ __device__ inline int fp_row(const uint32_t* atoms, const uint32_t* bon
     for (int a = 0; a < n; ++a) acc[a] = 0;
     for (int e = 0; e < nb; ++e) {
       const uint32_t w = bonds[e];
-      const int a = (int)(w & 255u), b = (int)((w >> 8) & 255u);
-      const uint64_t ta = fp_bond_term(id[b], w >> 16), tb = fp_bond_term(id[a], w >> 16);
+      const int a = mol_a(w), b = mol_b(w);
+      const uint64_t ta = fp_bond_term(id[b], mol_order(w)), tb = fp_bond_term(id[a], mol_order(w));
       acc[a] += ta;
       acc[b] += tb;
     }

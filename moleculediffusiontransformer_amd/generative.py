@@ -1146,11 +1146,11 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
-    _vocabulary_arg(vocabulary, torch.as_tensor(tokens).shape[1])
-    _identity_arg(identity, vocabulary, torch.as_tensor(tokens).shape[1])
-    sim_num, known_sim_num = _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known,
-                                              torch.as_tensor(tokens).shape[1])
-    fragments = _substructure_args(require, forbid, vocabulary, torch.as_tensor(tokens).shape[1])
+    width = torch.as_tensor(tokens).shape[1]
+    _vocabulary_arg(vocabulary, width)
+    _identity_arg(identity, vocabulary, width)
+    sim_num, known_sim_num = _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known, width)
+    fragments = _substructure_args(require, forbid, vocabulary, width)
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1186,29 +1186,22 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
         _, inter, union = torch.ops.mdt.fp_nearest(fp, known_fp)
         near = (union > 0) & (inter.long() * FP_SIM_DEN >= known_sim_num * union.long())     # the integer rule of mdt_hip.h
         reject = reject | (near.to(torch.uint8) * rt.SCREEN_KNOWN)
+    distances = diverse or sim_num is not None                   # the selections that take known_dist and the two minima
+    known_dist = None
+    if distances and min_novelty > 1:                            # novelty as a distance: the nearest known row of every candidate
+        known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
+        kk = kp = kl = None
+    args = (score, key, packed, length, N, K, kk, kp, kl)
+    if distances:
+        args += (known_dist, min_novelty, min_distance)
     if sim_num is not None:
-        known_dist = None
-        if min_novelty > 1:
-            known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
-            kk = kp = kl = None
-        status, index, count = torch.ops.mdt.screen_select_similar(score, key, packed, length, N, K, kk, kp, kl, known_dist,
-                                                                   min_novelty, min_distance, reject, fp, fp_count, sim_num)
-    elif not diverse:
-        if reject is None:
-            status, index, count = torch.ops.mdt.screen_select(score, key, packed, length, N, K, kk, kp, kl)
-        else:
-            status, index, count = torch.ops.mdt.screen_select_reject(score, key, packed, length, N, K, kk, kp, kl, reject)
+        status, index, count = torch.ops.mdt.screen_select_similar(*args, reject, fp, fp_count, sim_num)
+    elif reject is not None:
+        select = torch.ops.mdt.screen_select_diverse_reject if diverse else torch.ops.mdt.screen_select_reject
+        status, index, count = select(*args, reject)
     else:
-        known_dist = None
-        if min_novelty > 1:                                      # novelty as a distance: the nearest known row of every candidate
-            known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
-            kk = kp = kl = None
-        if reject is None:
-            status, index, count = torch.ops.mdt.screen_select_diverse(score, key, packed, length, N, K, kk, kp, kl, known_dist,
-                                                                       min_novelty, min_distance)
-        else:
-            status, index, count = torch.ops.mdt.screen_select_diverse_reject(score, key, packed, length, N, K, kk, kp, kl,
-                                                                              known_dist, min_novelty, min_distance, reject)
+        select = torch.ops.mdt.screen_select_diverse if diverse else torch.ops.mdt.screen_select
+        status, index, count = select(*args)
     index = index.long()
     filled = index >= 0
     rows = index.clamp(min=0) * G + torch.arange(G, device=device).unsqueeze(1)

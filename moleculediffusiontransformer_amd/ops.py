@@ -488,59 +488,21 @@ def _(props, target, weights, candidates):
     return props.new_empty(candidates * target.shape[0], dtype=torch.float32)
 
 
-@custom_op("mdt::screen_select", mutates_args=())
-def screen_select(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
-                  known_key: Optional[Tensor], known_packed: Optional[Tensor],
-                  known_len: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (status uint8 (N * G), index int32 (G, K), count int32 (G)).  The known set: keys int64 (the uint64 bits, ascending AS
-    uint64), packed rows int32 (M, L), lengths int32 (M) -- all three or none."""
-    dev = _hip(score, key, packed, length, known_key, known_packed, known_len)
+def _screen_select(op, score, key, packed, length, candidates, keep, known_key, known_packed, known_len, *, diverse=None,
+                   reject=None, similar=None):
+    """The one body of the five selection ops: the argument checks, the three outputs, the call.  diverse: (known_dist, min_novelty,
+    min_distance) of the ops that take them -- their rows have at most the 64 positions of the edit distance; reject: the byte per
+    row, or None; similar: (fp, fp_count, sim_num) of mdt::screen_select_similar.  The C symbol is the op's own, except that a
+    ..._reject op whose reject is None calls the symbol without it: that op's launch, bit for bit."""
+    known_dist, min_novelty, min_distance = diverse if diverse is not None else (None, 0, 0)
+    fp, fp_count, sim_num = similar if similar is not None else (None, None, 0)
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject, fp, fp_count)
     lib = rt.load_library()
-    rows, L = packed.shape
-    N, K = candidates, keep
-    if N < 1 or rows % N:
-        raise RuntimeError(f"mdt::screen_select: {rows} rows are no multiple of candidates = {N}")
-    G = rows // N
-    if key.dtype != torch.int64 or packed.dtype != torch.int32 or length.dtype != torch.int32:
-        raise RuntimeError("mdt::screen_select: key must be int64, packed and length int32 (as mdt::tokens_compact returns them)")
-    if score.numel() != rows or key.numel() != rows or length.numel() != rows:
-        raise RuntimeError("mdt::screen_select: score, key and length must hold one value per row of packed")
-    known = (known_key, known_packed, known_len)
-    if any(k is None for k in known) != all(k is None for k in known):
-        raise RuntimeError("mdt::screen_select: give known_key, known_packed and known_len together")
-    M = 0
-    if known_key is not None:
-        M = known_key.numel()
-        if known_key.dtype != torch.int64 or known_packed.dtype != torch.int32 or known_len.dtype != torch.int32:
-            raise RuntimeError("mdt::screen_select: known_key must be int64, known_packed and known_len int32")
-        if tuple(known_packed.shape) != (M, L) or known_len.numel() != M:
-            raise RuntimeError(f"mdt::screen_select: the known set must be (M, {L}) rows with M keys and M lengths")
-        known = tuple(k.contiguous() for k in known)
-    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
-    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    index = torch.full((G, K), -1, dtype=torch.int32, device=dev)
-    count = torch.zeros(G, dtype=torch.int32, device=dev)
-    if G:
-        with torch.cuda.device(dev):
-            rt.check(lib.mdt_screen_select(rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, N, G,
-                                           *(rt.ptr(k) if M else 0 for k in known), M, K, rt.ptr(status), rt.ptr(index),
-                                           rt.ptr(count), rt.current_stream()))
-    return status, index, count
-
-
-@screen_select.register_fake
-def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len):
-    G = packed.shape[0] // candidates
-    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
-            packed.new_empty(G, dtype=torch.int32))
-
-
-def _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len):
-    """The argument checks that mdt::screen_select_diverse shares with mdt::screen_select.  -> (rows, L, G, M, known)"""
     rows, L = packed.shape
     N = candidates
     if N < 1 or rows % N:
         raise RuntimeError(f"{op}: {rows} rows are no multiple of candidates = {N}")
+    G = rows // N
     if key.dtype != torch.int64 or packed.dtype != torch.int32 or length.dtype != torch.int32:
         raise RuntimeError(f"{op}: key must be int64, packed and length int32 (as mdt::tokens_compact returns them)")
     if score.numel() != rows or key.numel() != rows or length.numel() != rows:
@@ -556,7 +518,59 @@ def _screen_select_checks(op, score, key, packed, length, candidates, known_key,
         if tuple(known_packed.shape) != (M, L) or known_len.numel() != M:
             raise RuntimeError(f"{op}: the known set must be (M, {L}) rows with M keys and M lengths")
         known = tuple(k.contiguous() for k in known)
-    return rows, L, rows // N, M, known
+    if diverse is not None:
+        if L > rt.EDIT_MAX_LENGTH:
+            takes = "the edit distance takes" if similar is None else "the edit distance and the fingerprint take"
+            raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} {takes}")
+        if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
+            raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
+        known_dist = None if known_dist is None else known_dist.contiguous()
+    if (fp is None) != (fp_count is None):
+        raise RuntimeError(f"{op}: fp and fp_count come together")
+    if fp is not None:
+        fp = _fp_rows(op, fp, "fp")
+        if fp.shape[0] != rows or fp_count.dtype != torch.int32 or fp_count.numel() != rows:
+            raise RuntimeError(f"{op}: fp and fp_count must hold one fingerprint and one int32 per row of packed")
+        fp_count = fp_count.contiguous()
+        if not 1 <= sim_num <= rt.FP_SIM_DEN:
+            raise RuntimeError(f"{op}: sim_num = {sim_num} must lie in [1, {rt.FP_SIM_DEN}]")
+    if reject is not None:
+        if reject.dtype != torch.uint8 or reject.numel() != rows:
+            raise RuntimeError(f"{op}: reject must hold one uint8 per row of packed")
+        reject = reject.contiguous()
+    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
+    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
+    count = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        symbol = "mdt_" + op[len("mdt::"):]
+        args = [rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, N, G, *(rt.ptr(k) if M else 0 for k in known), M, keep]
+        if diverse is not None:
+            args += [rt.ptr(known_dist), int(min_novelty), int(min_distance)]
+        if similar is not None:
+            args += [rt.ptr(reject), rt.ptr(fp), rt.ptr(fp_count), int(sim_num)]
+        elif reject is not None:
+            args += [rt.ptr(reject)]
+        else:
+            symbol = symbol.removesuffix("_reject")
+        with torch.cuda.device(dev):
+            rt.check(getattr(lib, symbol)(*args, rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream()))
+    return status, index, count
+
+
+def _screen_select_fake(score, key, packed, length, candidates, keep, *optional):
+    G = packed.shape[0] // candidates
+    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
+            packed.new_empty(G, dtype=torch.int32))
+
+
+@custom_op("mdt::screen_select", mutates_args=())
+def screen_select(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                  known_key: Optional[Tensor], known_packed: Optional[Tensor],
+                  known_len: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (status uint8 (N * G), index int32 (G, K), count int32 (G)).  The known set: keys int64 (the uint64 bits, ascending AS
+    uint64), packed rows int32 (M, L), lengths int32 (M) -- all three or none."""
+    return _screen_select("mdt::screen_select", score, key, packed, length, candidates, keep, known_key, known_packed, known_len)
 
 
 @custom_op("mdt::screen_select_diverse", mutates_args=())
@@ -566,41 +580,8 @@ def screen_select_diverse(score: Tensor, key: Tensor, packed: Tensor, length: Te
     """mdt::screen_select with the two edit-distance filters of mdt_screen_select_diverse (include/mdt_hip.h): bit 8 also where
     known_dist (int32 (N * G), or None) < min_novelty; the K best in (score, c) order that lie >= min_distance edits apart; bit 16
     on what a kept candidate pushed out.  Rows of at most 64 positions."""
-    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist)
-    lib = rt.load_library()
-    op = "mdt::screen_select_diverse"
-    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
-    if L > rt.EDIT_MAX_LENGTH:
-        raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} the edit distance takes")
-    if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
-        raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
-    kd = None if known_dist is None else known_dist.contiguous()
-    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
-    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
-    count = torch.zeros(G, dtype=torch.int32, device=dev)
-    if G:
-        with torch.cuda.device(dev):
-            rt.check(lib.mdt_screen_select_diverse(rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
-                                                   *(rt.ptr(k) if M else 0 for k in known), M, keep, rt.ptr(kd), int(min_novelty),
-                                                   int(min_distance), rt.ptr(status), rt.ptr(index), rt.ptr(count),
-                                                   rt.current_stream()))
-    return status, index, count
-
-
-@screen_select_diverse.register_fake
-def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, known_dist, min_novelty, min_distance):
-    G = packed.shape[0] // candidates
-    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
-            packed.new_empty(G, dtype=torch.int32))
-
-
-def _reject_rows(op, reject, rows):
-    if reject is None:
-        return None
-    if reject.dtype != torch.uint8 or reject.numel() != rows:
-        raise RuntimeError(f"{op}: reject must hold one uint8 per row of packed")
-    return reject.contiguous()
+    return _screen_select("mdt::screen_select_diverse", score, key, packed, length, candidates, keep, known_key, known_packed,
+                          known_len, diverse=(known_dist, min_novelty, min_distance))
 
 
 @custom_op("mdt::screen_select_reject", mutates_args=())
@@ -609,32 +590,8 @@ def screen_select_reject(score: Tensor, key: Tensor, packed: Tensor, length: Ten
                          reject: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
     """mdt::screen_select with ``reject`` (uint8 (N * G), e.g. mdt::smiles_check's status, or None): its bits are OR-ed into the
     status before eligibility is decided.  None: mdt::screen_select's launch, bit for bit."""
-    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, reject)
-    lib = rt.load_library()
-    op = "mdt::screen_select_reject"
-    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
-    rej = _reject_rows(op, reject, rows)
-    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
-    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
-    count = torch.zeros(G, dtype=torch.int32, device=dev)
-    if G:
-        with torch.cuda.device(dev):
-            head = (rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
-                    *(rt.ptr(k) if M else 0 for k in known), M, keep)
-            tail = (rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream())
-            if rej is None:
-                rt.check(lib.mdt_screen_select(*head, *tail))
-            else:
-                rt.check(lib.mdt_screen_select_reject(*head, rt.ptr(rej), *tail))
-    return status, index, count
-
-
-@screen_select_reject.register_fake
-def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, reject):
-    G = packed.shape[0] // candidates
-    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
-            packed.new_empty(G, dtype=torch.int32))
+    return _screen_select("mdt::screen_select_reject", score, key, packed, length, candidates, keep, known_key, known_packed,
+                          known_len, reject=reject)
 
 
 @custom_op("mdt::screen_select_diverse_reject", mutates_args=())
@@ -644,39 +601,25 @@ def screen_select_diverse_reject(score: Tensor, key: Tensor, packed: Tensor, len
                                  reject: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
     """mdt::screen_select_diverse with ``reject`` as mdt::screen_select_reject takes it: a rejected candidate is not eligible, so
     it is never kept and never pushes another out under min_distance.  None: mdt::screen_select_diverse's launch, bit for bit."""
-    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject)
-    lib = rt.load_library()
-    op = "mdt::screen_select_diverse_reject"
-    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
-    if L > rt.EDIT_MAX_LENGTH:
-        raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} the edit distance takes")
-    if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
-        raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
-    kd = None if known_dist is None else known_dist.contiguous()
-    rej = _reject_rows(op, reject, rows)
-    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
-    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
-    count = torch.zeros(G, dtype=torch.int32, device=dev)
-    if G:
-        with torch.cuda.device(dev):
-            head = (rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
-                    *(rt.ptr(k) if M else 0 for k in known), M, keep, rt.ptr(kd), int(min_novelty), int(min_distance))
-            tail = (rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream())
-            if rej is None:
-                rt.check(lib.mdt_screen_select_diverse(*head, *tail))
-            else:
-                rt.check(lib.mdt_screen_select_diverse_reject(*head, rt.ptr(rej), *tail))
-    return status, index, count
+    return _screen_select("mdt::screen_select_diverse_reject", score, key, packed, length, candidates, keep, known_key, known_packed,
+                          known_len, diverse=(known_dist, min_novelty, min_distance), reject=reject)
 
 
-@screen_select_diverse_reject.register_fake
-def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, known_dist, min_novelty, min_distance,
-      reject):
-    G = packed.shape[0] // candidates
-    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
-            packed.new_empty(G, dtype=torch.int32))
+@custom_op("mdt::screen_select_similar", mutates_args=())
+def screen_select_similar(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                          known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
+                          known_dist: Optional[Tensor], min_novelty: int, min_distance: int, reject: Optional[Tensor],
+                          fp: Optional[Tensor], fp_count: Optional[Tensor], sim_num: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """mdt::screen_select_diverse_reject with similarity as a second way to be passed over (mdt_screen_select_similar,
+    include/mdt_hip.h): a candidate whose fingerprint (``fp`` int64 (N * G, 16), ``fp_count`` int32 (N * G), as mdt::mol_fp returns
+    them) is at least sim_num / 65536 Tanimoto-similar to a candidate kept before it gets bit 16, as one closer than min_distance
+    edits does.  fp and fp_count None: mdt::screen_select_diverse_reject's kernel on the same inputs, bit for bit."""
+    return _screen_select("mdt::screen_select_similar", score, key, packed, length, candidates, keep, known_key, known_packed,
+                          known_len, diverse=(known_dist, min_novelty, min_distance), reject=reject, similar=(fp, fp_count, sim_num))
 
+
+for _op in (screen_select, screen_select_diverse, screen_select_reject, screen_select_diverse_reject, screen_select_similar):
+    _op.register_fake(_screen_select_fake)
 
 # ----------------------------------------------------------------------------------------------------------------------
 # well-formedness and valence of compacted id rows (csrc/k_smiles.hip): at most 128 positions, ids in [0, 256)
@@ -912,55 +855,6 @@ def fp_nearest(fp: Tensor, known_fp: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
 def _(fp, known_fp):
     R = fp.shape[0]
     return tuple(fp.new_empty(R, dtype=torch.int32) for _ in range(3))
-
-
-@custom_op("mdt::screen_select_similar", mutates_args=())
-def screen_select_similar(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
-                          known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
-                          known_dist: Optional[Tensor], min_novelty: int, min_distance: int, reject: Optional[Tensor],
-                          fp: Optional[Tensor], fp_count: Optional[Tensor], sim_num: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """mdt::screen_select_diverse_reject with similarity as a second way to be passed over (mdt_screen_select_similar,
-    include/mdt_hip.h): a candidate whose fingerprint (``fp`` int64 (N * G, 16), ``fp_count`` int32 (N * G), as mdt::mol_fp returns
-    them) is at least sim_num / 65536 Tanimoto-similar to a candidate kept before it gets bit 16, as one closer than min_distance
-    edits does.  fp and fp_count None: mdt::screen_select_diverse_reject's kernel on the same inputs, bit for bit."""
-    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject, fp, fp_count)
-    lib = rt.load_library()
-    op = "mdt::screen_select_similar"
-    rows, L, G, M, known = _screen_select_checks(op, score, key, packed, length, candidates, known_key, known_packed, known_len)
-    if L > rt.EDIT_MAX_LENGTH:
-        raise RuntimeError(f"{op}: rows of {L} positions exceed the {rt.EDIT_MAX_LENGTH} the edit distance and the fingerprint take")
-    if known_dist is not None and (known_dist.dtype != torch.int32 or known_dist.numel() != rows):
-        raise RuntimeError(f"{op}: known_dist must hold one int32 per row of packed")
-    if (fp is None) != (fp_count is None):
-        raise RuntimeError(f"{op}: fp and fp_count come together")
-    if fp is not None:
-        fp = _fp_rows(op, fp, "fp")
-        if fp.shape[0] != rows or fp_count.dtype != torch.int32 or fp_count.numel() != rows:
-            raise RuntimeError(f"{op}: fp and fp_count must hold one fingerprint and one int32 per row of packed")
-        fp_count = fp_count.contiguous()
-        if not 1 <= sim_num <= rt.FP_SIM_DEN:
-            raise RuntimeError(f"{op}: sim_num = {sim_num} must lie in [1, {rt.FP_SIM_DEN}]")
-    kd = None if known_dist is None else known_dist.contiguous()
-    rej = _reject_rows(op, reject, rows)
-    score, key, packed, length = _f32c(score), key.contiguous(), packed.contiguous(), length.contiguous()
-    status = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    index = torch.full((G, keep), -1, dtype=torch.int32, device=dev)
-    count = torch.zeros(G, dtype=torch.int32, device=dev)
-    if G:
-        with torch.cuda.device(dev):
-            rt.check(lib.mdt_screen_select_similar(rt.ptr(score), rt.ptr(key), rt.ptr(packed), rt.ptr(length), L, candidates, G,
-                                                   *(rt.ptr(k) if M else 0 for k in known), M, keep, rt.ptr(kd), int(min_novelty),
-                                                   int(min_distance), rt.ptr(rej), rt.ptr(fp), rt.ptr(fp_count), int(sim_num),
-                                                   rt.ptr(status), rt.ptr(index), rt.ptr(count), rt.current_stream()))
-    return status, index, count
-
-
-@screen_select_similar.register_fake
-def _(score, key, packed, length, candidates, keep, known_key, known_packed, known_len, known_dist, min_novelty, min_distance,
-      reject, fp, fp_count, sim_num):
-    G = packed.shape[0] // candidates
-    return (packed.new_empty(packed.shape[0], dtype=torch.uint8), packed.new_empty(G, keep, dtype=torch.int32),
-            packed.new_empty(G, dtype=torch.int32))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

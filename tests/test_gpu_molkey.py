@@ -115,6 +115,31 @@ def test_full_width_rows(vocab):
     assert natoms.tolist() == [64, 4] and nbonds.tolist() == [63, 33]
 
 
+def test_mol_key_of_graph_arrays_no_scan_writes():
+    """Counts outside [1, L] x [0, L] and a bond that names an atom the row does not have -> key 0 (nothing beyond the counts is
+    read); a bond listed twice and a bond of an atom to itself count at both ends, as tests/molkey_ref.py's key counts them."""
+    c = K.descriptor("C")
+    natoms = torch.tensor([3, 9, 2, -1, 2, 2, 2], dtype=torch.int32, device=DEV)
+    nbonds = torch.tensor([2, 0, 9, 0, -1, 2, 1], dtype=torch.int32, device=DEV)
+    atoms = torch.full((7, 8), c, dtype=torch.int32, device=DEV)
+    bonds = torch.zeros(7, 8, dtype=torch.int32, device=DEV)
+    bonds[0, :2] = torch.tensor([0 | 3 << 8 | 1 << 16, 1 | 2 << 8 | 1 << 16])
+    bonds[5, :2] = 0 | 1 << 8 | 1 << 16
+    bonds[6, 0] = 0 | 0 << 8 | 2 << 16
+    key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+    torch.cuda.synchronize()
+    want = [0] * 5 + [K.key([c, c], [(0, 1, 1)] * 2), K.key([c, c], [(0, 0, 2)])]
+    assert want[5] and want[6] and want[5] != want[6]
+    assert key.dtype == torch.int64 and key.cpu().numpy().view(np.uint64).tolist() == want
+    # full width: 64 atoms are a graph of L = 64, a bond end of 64 is not
+    wide = torch.zeros(1, 64, dtype=torch.int32, device=DEV)
+    wide[0, 0] = 0 | 64 << 8 | 1 << 16
+    key = torch.ops.mdt.mol_key(torch.tensor([64], dtype=torch.int32, device=DEV), torch.full((1, 64), c, dtype=torch.int32, device=DEV),
+                                torch.tensor([1], dtype=torch.int32, device=DEV), wide)
+    torch.cuda.synchronize()
+    assert key.tolist() == [0]
+
+
 def test_zeros_scattered_through_a_row(vocab):
     rng = np.random.default_rng(7)
     strings = [s for s, _, _ in S.TABLES] + [s for pair in EQUAL for s in pair]
