@@ -67,7 +67,8 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ buffers
     def reserve(self, B: int) -> None:
-        """(Re)allocate per-batch buffers.  Invalidates captured graphs when B changes."""
+        """(Re)allocate per-batch buffers.  Invalidates captured graphs when B changes.  `act`, `film` and `xbuf` come from
+        torch.empty and arena slots are reused: callers and kernels must not assume anything about their contents."""
         if B == self.B:
             return
         c = self.c
