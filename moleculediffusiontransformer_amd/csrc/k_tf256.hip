@@ -42,9 +42,11 @@
 // the probe).
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "mdt_kernels.h"
 #include "mdt_device.h"
+#include "mdt_ring_sched.h"
 
 // Compiled twice: as is (split-bf16 products, launch_tf256) and through k_tf256_f32.hip with MDT_TF_F32 = 1 (exact fp32 MFMA
 // products, launch_tf256_f32) -- two translation units that build in parallel.
@@ -72,6 +74,13 @@ __device__ __forceinline__ void frag_wait() {
 #else
   lgkm_wait<N>();
 #endif
+}
+
+// f(integral_constant<int, Q>) for Q = 0 .. N - 1 WITHOUT a loop: the index of a register array is a constant from the first
+// optimisation pass on (a `#pragma unroll` loop is a loop with a variable index until it is unrolled, late)
+template <class F, int... Q>
+__device__ __forceinline__ void for_const(F&& f, std::integer_sequence<int, Q...>) {
+  (f(std::integral_constant<int, Q>{}), ...);
 }
 
 constexpr int C = 256;          // channels
@@ -103,6 +112,16 @@ constexpr int VEC_BYTES = VEC_FLOATS * 4;
 #ifndef MDT_RING_AHEAD
 #define MDT_RING_AHEAD 2     // tiles the loader waves run ahead of the one being consumed (2 or 3; NS = 4 slots)
 #endif
+// 1 (tuning builds, for A/B): the loader waves run HALF a tile further ahead where the slot's previous tile has a half that only
+// units 0 and 1 read (mdt_ring_sched.h; checked by tools/ring_sched_check.cpp and tests/test_gpu_ring_halfahead.py).  Measured and
+// NOT the default: the landing wait of a streamed turn falls from 136 to 112 cycles, the turn's bookkeeping grows the issue from
+// 504 to 648 (profiles/ring_halfahead_stamps.txt).  0: every tile whole behind B(k), two tiles in flight.
+#ifndef MDT_RING_HALF
+#define MDT_RING_HALF 0
+#endif
+#if MDT_RING_HALF != 0 && !defined(MDT_TUNING)
+#error "MDT_RING_HALF=1 is the A/B schedule of tuning builds: add -DMDT_TUNING"
+#endif
 #ifndef MDT_XH_ADDR
 #define MDT_XH_ADDR 1        // 1: whole address in the VECTOR offset (scalar offset 0), as tools/ubench/pair_handoff.hip does
 #endif
@@ -110,6 +129,11 @@ constexpr int AUX_ST = MDT_XH_MODE == 1 ? 17 : (MDT_XH_MODE == 3 ? 18 : (MDT_XH_
 constexpr int AUX_LD = MDT_XH_MODE == 0 ? 16 : (MDT_XH_MODE == 3 ? 18 : (MDT_XH_MODE == 4 ? 19 : 17));
 constexpr unsigned XBLOCK = 32 * C * 4;            // bytes one workgroup hands over per round
 constexpr unsigned long long POLL_TIMEOUT = 30000000ull;   // s_memrealtime ticks (100 MHz): 0.3 s
+#ifdef MDT_STAMPS
+constexpr int STAMP_LDS = 4096;   // the loader's per-turn stamps (tuning build)
+#else
+constexpr int STAMP_LDS = 0;
+#endif
 
 }  // namespace
 
@@ -152,14 +176,14 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
     const int xO = (lane & 7) ^ (lane >> 4);
     const int baseO = (lane >> 3) * 128;
     unsigned voffP[IPT], voffO[IPT];
-#pragma unroll
-    for (int q = 0; q < IPT; ++q) {
+    for_const([&](auto qc) __attribute__((always_inline)) {
+      constexpr int q = decltype(qc)::value;
       const int inst = iw + 4 * q;
       const int U = 2 * inst;
       voffP[q] = F32 ? (unsigned)(inst * 1024 + lane * 16) : (unsigned)(U * (2 * CS) + ((xP ^ (U & 15)) << 4) + baseP);
       voffO[q] = F32 ? (unsigned)(inst * 1024 + lane * 16)
                      : (unsigned)(((inst * 8) / CS) * (128 * CS) + ((inst * 8) % CS) * 128 + ((xO ^ (4 * (inst & 1))) << 4) + baseO);
-    }
+    }, std::make_integer_sequence<int, IPT>{});
     const int sample0 = rb * (32 / a.T);
     const bool second = a.kv2 && sample0 >= a.nsamples / 2;      // dual batch: shared K / V rows for the second half
     unsigned voffKV[8];
@@ -174,55 +198,93 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         voffKV[q] = (unsigned)(((sm * bstr + key) * a.ldkv + 4 * ((lane & 15) ^ (R & 15))) * 4);
       }
     }
+    // The loader's lambdas are inlined BEFORE anything else is done to them (always_inline): optimised on their own, with the
+    // offset arrays behind the closure pointer, hipcc merges the straight-line piece sets of issue_w into one block with a VARIABLE
+    // array index (or selects between the two arrays' addresses) and both arrays end up in scratch memory -- 32..80 bytes per
+    // lane, and every scratch load in a loader wave is waited for with vmcnt(0) in the middle of the DMA stream (measured: 2000
+    // cycles per loader turn instead of 500; tests/test_host_logic.py bounds the scratch of every instantiation)
+#define MDT_INLINE_L __attribute__((always_inline))
     // vector-memory operations THIS wave issues for a tile (the counted waits below are per wave)
-    auto pieces_of = [&](unsigned d) -> int {
-      const unsigned kind = d & 7u;
-      if (kind == D_SCRATCH) return 0;
-      if (kind == D_SCRATCH_VEC) return iw < VEC_BYTES / 1024 ? 1 : 0;
-      if (kind >= D_K) return NPW;
-      return IPT;
-    };
-    auto issue_vec = [&](unsigned aux) {             // aux = (float offset / 256) << 1 | parity
+    // -- a nibble per kind, looked up with two shifts: the loader's turn is a chain of scalar instructions at ~5 cycles each, a
+    // branch per kind costs more than the whole look-up
+    const unsigned piece_tab = (unsigned)ring::pieces_of(D_P, iw, NPW, VEC_BYTES / 1024) | (unsigned)ring::pieces_of(D_O, iw, NPW, VEC_BYTES / 1024) << 4 |
+                               (unsigned)ring::pieces_of(D_K, iw, NPW, VEC_BYTES / 1024) << 8 | (unsigned)ring::pieces_of(D_V, iw, NPW, VEC_BYTES / 1024) << 12 |
+                               (unsigned)ring::pieces_of(D_SCRATCH_VEC, iw, NPW, VEC_BYTES / 1024) << 20;
+    auto pieces_of = [&](unsigned d) MDT_INLINE_L -> int { return (int)((piece_tab >> ((d & 7u) * 4u)) & 15u); };
+    auto issue_vec = [&](unsigned aux) MDT_INLINE_L {             // aux = (float offset / 256) << 1 | parity
       if (iw < VEC_BYTES / 1024)
         __builtin_amdgcn_global_load_lds(reinterpret_cast<const unsigned char*>(a.vec) + (aux >> 1) * 1024 + iw * 1024 + lane * 16,
                                          (__attribute__((address_space(3))) void*)(vec_b + (aux & 1u) * VEC_BYTES + iw * 1024), 16, 0, 0);
     };
-    auto issue_tile = [&](int tau, unsigned d) {
+    // the pieces q in `mask` of a weight sub-tile (ring::WHOLE, or the early / late pieces of mdt_ring_sched.h); every piece set is
+    // compile-time, straight-line code
+    auto issue_w = [&](int tau, unsigned d, unsigned mask) MDT_INLINE_L {
       unsigned char* slot = smem + MDT_SLOT_IDX(tau) * SLOT + iw * 1024;
-      const unsigned kind = d & 7u, aux = d >> 3;
-      if (kind == D_SCRATCH) return;
-      if (kind == D_SCRATCH_VEC) { issue_vec(aux); return; }
-      if (kind >= D_K) {
-        if constexpr (NPW > 0) {
-          const int layer = (int)(aux >> 4), head = (int)(aux & 15u);
-          const float* lb = second ? a.kv2 + (int64_t)layer * a.kv2_lstride
-                                   : a.kv + (int64_t)layer * a.kv_lstride + (int64_t)sample0 * a.kv_bstride * a.ldkv;
-          const unsigned char* base = reinterpret_cast<const unsigned char*>(lb + 64 * head + (kind == D_V ? 64 * a.nheads : 0));
-#pragma unroll
-          for (int q = 0; q < NPW; ++q)
-            __builtin_amdgcn_global_load_lds(base + voffKV[q], (__attribute__((address_space(3))) void*)(slot + q * 4096), 16, 0, MDT_KV_CPOL);
-        }
-        return;
-      }
-      const unsigned char* tile = wsrc + (int64_t)aux * SLOT;   // wave-uniform
-      const bool ptile = kind == D_P;
-#pragma unroll
-      for (int q = 0; q < IPT; ++q) {
-        const unsigned off = ptile ? voffP[q] : voffO[q];
-        __builtin_amdgcn_global_load_lds(tile + off, (__attribute__((address_space(3))) void*)(slot + q * 4096), 16, 0, 0);
+      const unsigned char* tile = wsrc + (int64_t)(d >> 3) * SLOT;   // wave-uniform
+      // (a bit select, not `ptile ? voffP[q] : voffO[q]`: with several inlined copies of this function hipcc turns that into a
+      //  select of the two ARRAYS' addresses and moves both to scratch memory -- 80 bytes per lane, every scratch load waited for
+      //  with vmcnt(0) in the middle of the DMA stream: 2000 cycles per loader turn instead of 500)
+      const unsigned pmask = (d & 7u) == D_P ? ~0u : 0u;
+      auto pieces = [&](auto mc) MDT_INLINE_L {
+        constexpr unsigned M = decltype(mc)::value;
+        // (an assembly comment that names the piece set, in front and behind: the blocks of two piece sets are then not the same
+        //  instruction sequence, and hipcc cannot fold them into one block that indexes the offset arrays with a variable)
+        asm volatile("; pieces %0" ::"n"(M));
+        for_const([&](auto qc) MDT_INLINE_L {
+          constexpr int q = decltype(qc)::value;
+          if constexpr ((M & (1u << q)) != 0) {
+            const unsigned off = F32 ? voffP[q] : ((voffP[q] & pmask) | (voffO[q] & ~pmask));
+            __builtin_amdgcn_global_load_lds(tile + off, (__attribute__((address_space(3))) void*)(slot + q * 4096), 16, 0, 0);
+          }
+        }, std::make_integer_sequence<int, IPT>{});
+        asm volatile("; pieces %0 issued" ::"n"(M));
+      };
+      using ring::WHOLE;
+      if (mask == WHOLE) { pieces(std::integral_constant<unsigned, WHOLE>{}); return; }
+      if constexpr (F32) {
+        constexpr unsigned EP = ring::DEAD_P_F32, EO = ring::DEAD_O_F32;
+        if (mask == EP) pieces(std::integral_constant<unsigned, EP>{});
+        else if (mask == (WHOLE & ~EP)) pieces(std::integral_constant<unsigned, (WHOLE & ~EP)>{});
+        else if (mask == EO) pieces(std::integral_constant<unsigned, EO>{});
+        else pieces(std::integral_constant<unsigned, (WHOLE & ~EO)>{});
+      } else {
+        constexpr unsigned EO = ring::DEAD_O_BF16;   // (a P tile of this form has no dead half)
+        if (mask == EO) pieces(std::integral_constant<unsigned, EO>{});
+        else pieces(std::integral_constant<unsigned, (WHOLE & ~EO)>{});
       }
     };
-    auto wait_vm = [&](int allow) {
+    auto issue_tile = [&](int tau, unsigned d) MDT_INLINE_L {     // a whole tile of any kind; the common kind first
+      const unsigned kind = d & 7u, aux = d >> 3;
+      if (kind < D_K) { issue_w(tau, d, ring::WHOLE); return; }
+      if (kind == D_SCRATCH) return;
+      if (kind == D_SCRATCH_VEC) { issue_vec(aux); return; }
+      if constexpr (NPW > 0) {
+        unsigned char* slot = smem + MDT_SLOT_IDX(tau) * SLOT + iw * 1024;
+        const int layer = (int)(aux >> 4), head = (int)(aux & 15u);
+        const float* lb = second ? a.kv2 + (int64_t)layer * a.kv2_lstride
+                                 : a.kv + (int64_t)layer * a.kv_lstride + (int64_t)sample0 * a.kv_bstride * a.ldkv;
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(lb + 64 * head + (kind == D_V ? 64 * a.nheads : 0));
+#pragma unroll
+        for (int q = 0; q < NPW; ++q)
+          __builtin_amdgcn_global_load_lds(base + voffKV[q], (__attribute__((address_space(3))) void*)(slot + q * 4096), 16, 0, MDT_KV_CPOL);
+      }
+    };
+    // The counted wait in front of B(k): at most `allow` of this wave's operations may stay in flight.  s_waitcnt takes an
+    // immediate, so the count is ROUNDED DOWN to one of a few values tested most-common first (a smaller count only waits for
+    // more): 12 = a whole tile and the early half of the next, 8 = a whole tile (or late + early halves), a K / V tile, 4 = a late
+    // half.  (Round 5 put two exact fast paths in front of a 17-way switch; as compiled both ended up inside the switch's
+    // cascade of scalar branches, ~300 cycles of a loader turn by the stamps of the same loader in k_res256.hip.)
+    auto wait_landed = [&](int allow) MDT_INLINE_L {
 #ifdef MDT_ABL_VMWAIT   // ablation (WRONG results, timing only): a tile is published whether or not its DMA has landed
       return;
 #endif
-      switch (allow) {
-#define MDT_VMW(n) case n: asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); break;
-        MDT_VMW(0) MDT_VMW(1) MDT_VMW(2) MDT_VMW(3) MDT_VMW(4) MDT_VMW(5) MDT_VMW(6) MDT_VMW(7) MDT_VMW(8) MDT_VMW(9) MDT_VMW(10)
-        MDT_VMW(11) MDT_VMW(12) MDT_VMW(13) MDT_VMW(14) MDT_VMW(15)
-#undef MDT_VMW
-        default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-      }
+      constexpr int KV = NPW > 0 ? NPW : 1;
+      if (MDT_RING_HALF && allow >= IPT + IPT / 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else if (allow >= IPT) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else if (NPW > 4 && allow >= KV) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KV) : "memory");
+      else if (allow >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else if (NPW > 0 && NPW < 4 && allow >= KV) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KV) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     // Tile k + AHEAD is issued behind B(k): the compute waves are past tile k - 1 there, and with AHEAD = 3 its slot is tile
     // k - 1's (NS = 4).  The only accesses to that slot that may still be in flight are fragment reads issued BEFORE the barrier
@@ -249,46 +311,106 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
     const int pf_mine = (int)blockIdx.x / (8 * NSPLIT);
     int pf_turn = MDT_STREAM_PF % pf_groups;                             // (k + MDT_STREAM_PF) % pf_groups, kept without a division per tile
     unsigned char* pf_sink_b = vec_b + 2 * VEC_BYTES;                     // 1 KB behind the vector areas (launch_tf2 sizes it)
-    int pf1 = 0, pf2 = 0;                                                // prefetch loads issued one / two turns ago
-    for (int k = 0; k < NT; ++k) {
-      const unsigned dnew = k + AHEAD < NT ? tiles[k + AHEAD] : 0u;
-      int allow = 0;
-#pragma unroll
-      for (int j = 0; j < AHEAD - 1; ++j) allow += k + 1 + j < NT ? pieces_of(dq[j]) : 0;
-      if (PF_ON && k + 1 < NT) allow += pf1 + pf2;
-      // tile k landed; tiles k + 1 .. may be in flight.  Round 5: the common cases -- a weight sub-tile or a K / V tile next, no
-      // touch of this workgroup in flight -- are tested first: as compiled, the 17-way switch of wait_vm is a cascade of ~27
-      // scalar branches, ~300 cycles of a loader turn (stamps of the same loader in k_res256.hip, where the loader IS what a
-      // sub-tile waits for: 1100 -> 890 cycles per sub-tile).  Here the compute waves arrive at the barrier last: same-box A/B of
-      // this change on the headline 4506 / 4487 -> 4519 / 4526 molecules/s, evaluation 1.766 ms either way (profiles/r5_res256_ab.txt)
-      if (allow == IPT) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (NPW > 0 && allow == NPW) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPW > 0 ? NPW : 1) : "memory");      // a K / V tile next
-      else wait_vm(allow);
-      MDT_BARRIER();                                      // B(k)
-      if (k + AHEAD < NT) issue_tile(k + AHEAD, dnew);
-      if constexpr (PF_ON) {
-        pf2 = pf1;
-        pf1 = 0;
-        const bool mine = pf_turn == pf_mine;
-        if (++pf_turn == pf_groups) pf_turn = 0;
-        if (mine && k + MDT_STREAM_PF < NT) {
-          const unsigned dp = tiles[k + MDT_STREAM_PF];
-          const unsigned kp = dp & 7u;
-          if (kp != D_SCRATCH && kp != D_SCRATCH_VEC && kp < D_K) {      // a weight sub-tile
-            const unsigned char* t = wsrc + (int64_t)(dp >> 3) * SLOT + (iw * 64 + lane) * 128;
-            // one dword per lane by LDS-DMA into a sink nothing reads: no landing REGISTER at all (an inline-asm global_load with
-            // a live "+v" register is the hazard class of mdt_kernels.h: prefetch_next_weights, and a load whose value the
-            // compiler can see is waited for with vmcnt(0) on the spot -- HBM latency in the loader's per-tile turn).  Counts in
-            // vmcnt like the DMA pieces and completes in order with them.
-            __builtin_amdgcn_global_load_lds(t, (__attribute__((address_space(3))) void*)(pf_sink_b + iw * 256), 4, 0, 0);
-            pf1 = 1;
-          }
+    // this wave's touch of tile k + MDT_STREAM_PF, if it is this workgroup's turn: 1 if a load was issued
+    auto pf_touch = [&](int k) MDT_INLINE_L -> int {
+      if constexpr (!PF_ON) return 0;
+      const bool mine = pf_turn == pf_mine;
+      if (++pf_turn == pf_groups) pf_turn = 0;
+      if (!(mine && k + MDT_STREAM_PF < NT)) return 0;
+      const unsigned dp = tiles[k + MDT_STREAM_PF];
+      if ((dp & 7u) >= D_K) return 0;                                  // not a weight sub-tile
+      const unsigned char* t = wsrc + (int64_t)(dp >> 3) * SLOT + (iw * 64 + lane) * 128;
+      // one dword per lane by LDS-DMA into a sink nothing reads: no landing REGISTER at all (an inline-asm global_load with
+      // a live "+v" register is the hazard class of mdt_kernels.h: prefetch_next_weights, and a load whose value the
+      // compiler can see is waited for with vmcnt(0) on the spot -- HBM latency in the loader's per-tile turn).  Counts in
+      // vmcnt like the DMA pieces and completes in order with them.
+      __builtin_amdgcn_global_load_lds(t, (__attribute__((address_space(3))) void*)(pf_sink_b + iw * 256), 4, 0, 0);
+      return 1;
+    };
+#ifdef MDT_STAMPS   // tuning build: loader wave 4 of the workgroups of row block 0 keeps four shader-clock stamps per turn (before the
+                    // landing wait, behind it, behind B(k), behind the issue) of turns LS0 .. LS0 + LSN - 1 in LDS behind the prefetch
+                    // sink (launch_tf2 adds the room) and copies them out behind the loop: xflags[64 + 64 nrb + 1024 + 1024 hh ...]
+    constexpr int LS0 = 8, LSN = 120;
+    unsigned long long* lst = reinterpret_cast<unsigned long long*>(pf_sink_b + 1024);
+    unsigned long long lt[4] = {0, 0, 0, 0};
+    // (the clock reads are not waited for where they are taken: one wait and four LDS writes at the end of the turn)
+#define MDT_LSTAMP(k_, j_)                                                                                    \
+  do {                                                                                                        \
+    if (NSPLIT == 2 && rb == 0 && iw == 0 && (k_) >= LS0 && (k_) < LS0 + LSN) {                               \
+      asm volatile("s_memtime %0" : "=s"(lt[j_])::"memory");                                                  \
+      if ((j_) == 3) {                                                                                        \
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[0]), "+s"(lt[1]), "+s"(lt[2]), "+s"(lt[3])::"memory");  \
+        if (lane == 0) {                                                                                      \
+          lst[4 * ((k_) - LS0)] = lt[0]; lst[4 * ((k_) - LS0) + 1] = lt[1];                                   \
+          lst[4 * ((k_) - LS0) + 2] = lt[2]; lst[4 * ((k_) - LS0) + 3] = lt[3];                               \
+        }                                                                                                     \
+      }                                                                                                       \
+    }                                                                                                         \
+  } while (0)
+#else
+#define MDT_LSTAMP(k_, j_) do {} while (0)
+#endif
+    if constexpr (MDT_RING_HALF != 0 && AHEAD == 2) {
+      // Half a tile further ahead (mdt_ring_sched.h states the schedule, its one rule and the allowance; tools/ring_sched_check.cpp
+      // replays descriptor streams against the byte ranges phase() reads): behind B(k) the late pieces of tile k + 2 (or all of
+      // it), then the early pieces of tile k + 3 into the half of tile k - 1's slot that only its units 0 and 1 read.
+      ring::Allowance al;
+      al.prev_total = NT > 1 ? pieces_of(dq[0]) : 0;                     // tile 1: the last operations in front of the loop
+      unsigned d2 = NT > 2 ? tiles[2] : 0u;                              // descriptor of tile k + 2
+      unsigned em2 = 0u;                                                 // ... its early pieces, issued one turn ago
+      unsigned km1 = D_SCRATCH, kk0 = tiles[0] & 7u, kk1 = dq[0] & 7u;   // kinds of tiles k - 1, k, k + 1
+      for (int k = 0; k < NT; ++k) {
+        const unsigned d3 = k + 3 < NT ? tiles[k + 3] : 0u;
+        const int allow = k + 1 < NT ? al.at_barrier() : 0;
+        MDT_LSTAMP(k, 0);
+        wait_landed(allow);
+        MDT_LSTAMP(k, 1);
+        MDT_BARRIER();                                      // B(k)
+        MDT_LSTAMP(k, 2);
+        const unsigned em3 = k + 3 < NT ? ring::early_mask(F32, k + 3, d3 & 7u, km1) : 0u;
+        int n_late = 0;
+        if (em2) {                                          // (tile k + 2 has early pieces: it exists and is a weight tile)
+          issue_w(k + 2, d2, ring::late_mask(em2));
+          n_late = IPT - ring::NEARLY;
+        } else if (k + 2 < NT) {
+          issue_tile(k + 2, d2);
+          n_late = pieces_of(d2);
         }
+        if (em3) issue_w(k + 3, d3, em3);
+        al.turn(n_late, em3 ? ring::NEARLY : 0, pf_touch(k));
+        MDT_LSTAMP(k, 3);
+        km1 = kk0; kk0 = kk1; kk1 = d2 & 7u;
+        d2 = d3; em2 = em3;
       }
+    } else {
+      int pf1 = 0, pf2 = 0;                                              // prefetch loads issued one / two turns ago
+      for (int k = 0; k < NT; ++k) {
+        const unsigned dnew = k + AHEAD < NT ? tiles[k + AHEAD] : 0u;
+        int allow = 0;
 #pragma unroll
-      for (int j = 0; j + 1 < AHEAD - 1; ++j) dq[j] = dq[j + 1];
-      dq[AHEAD - 2] = dnew;
+        for (int j = 0; j < AHEAD - 1; ++j) allow += k + 1 + j < NT ? pieces_of(dq[j]) : 0;
+        if (PF_ON && k + 1 < NT) allow += pf1 + pf2;
+        MDT_LSTAMP(k, 0);
+        wait_landed(allow);
+        MDT_LSTAMP(k, 1);
+        MDT_BARRIER();                                      // B(k)
+        MDT_LSTAMP(k, 2);
+        if (k + AHEAD < NT) issue_tile(k + AHEAD, dnew);
+        pf2 = pf1;
+        pf1 = pf_touch(k);
+        MDT_LSTAMP(k, 3);
+#pragma unroll
+        for (int j = 0; j + 1 < AHEAD - 1; ++j) dq[j] = dq[j + 1];
+        dq[AHEAD - 2] = dnew;
+      }
     }
+#ifdef MDT_STAMPS
+    if (NSPLIT == 2 && rb == 0 && iw == 0) {
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      unsigned long long* out = reinterpret_cast<unsigned long long*>(a.xflags + 64 + 64 * nrb + 1024 + 1024 * hh);
+      for (int e = lane; e < 4 * LSN; e += 64) out[e] = (e >> 2) + LS0 < NT ? lst[e] : 0ull;
+    }
+#endif
     prefetch_next_weights(a.pf_ptr, a.pf_lines, iw * 64 + lane);
     return;
   }
@@ -1175,7 +1297,7 @@ int g_pair_capacity_override = 0;     // tests (mdt_set_tuning("pair_capacity", 
 
 template <int NPW, int NSPLIT, bool F32>
 static hipError_t launch_tf2(const TFArgs& a, hipStream_t s) {
-  const size_t smem = (size_t)NS * SLOT + RED_BYTES + 2 * VEC_BYTES + 1024;   // ring, S^T exchange, vectors, prefetch sink
+  const size_t smem = (size_t)NS * SLOT + RED_BYTES + 2 * VEC_BYTES + 1024 + STAMP_LDS;   // ring, S^T exchange, vectors, prefetch sink
   static DevOnce attr_once;                          // per device (mdt_kernels.h)
   if (attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tf256<NPW, NSPLIT, F32>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1245,7 +1367,7 @@ int tf256_pair_capacity() {
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  const size_t smem = (size_t)NS * SLOT + RED_BYTES + 2 * VEC_BYTES + 1024;
+  const size_t smem = (size_t)NS * SLOT + RED_BYTES + 2 * VEC_BYTES + 1024 + STAMP_LDS;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tf256<6, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_tf256<6, 2, false>), 512, smem) != hipSuccess) return 0;
   return cus * per_cu;

@@ -58,4 +58,25 @@ for form, stride in (("whole", 0), ("pair", 8), ("pair", 1)):
             d = [(st[0][k + 1], st[1][k + 1] - st[1][k]) for k in range(len(st[0]) - 1)]
             print(f"  half {hh}: total {st[1][-1] - st[1][0]} cycles; (source line of the stamp : cycles since the previous stamp)")
             print("   " + " ".join(f"{ln}:{c}" for ln, c in d))
+        # loader wave 4 of the same workgroups: four stamps per turn (before the landing wait, behind it, behind B(k), behind the
+        # issue) of turns 8 .. 127.  A barrier wait near zero = the loader arrived last at B(k), a long one = the compute waves did.
+        nt = op.i[rt.F_NT]
+        words = comp.W.pack()[op.p0.off: op.p0.off + 2 * nt].contiguous().view(torch.int32).tolist()
+        for hh in range(2):
+            o = 64 + 64 * nrb + 1024 + 1024 * hh
+            raw = flags.cpu()[o: o + 960].view(torch.int64).view(-1, 4).tolist()
+            rows = [(8 + n, r) for n, r in enumerate(raw) if all(r)]
+            print(f"  loader, half {hh}: turn kind(k) kind(k+2) | landing wait, barrier wait, issue, period (cycles)")
+            stats = {}
+            for (k, r), (_, nx) in zip(rows, rows[1:]):
+                kd, kd2 = words[hh * nt + k] & 7, words[hh * nt + k + 2] & 7 if k + 2 < nt else 4
+                rec = (r[1] - r[0], r[2] - r[1], r[3] - r[2], nx[2] - r[2])
+                print(f"   {k:4d} {'POKVSs'[kd]} {'POKVSs'[kd2]} | {rec[0]:5d} {rec[1]:5d} {rec[2]:5d} {rec[3]:5d}")
+                if kd < 2 and kd2 < 2 and (words[hh * nt + k + 1] & 7) < 2 and (words[hh * nt + k - 1] & 7) < 2:
+                    stats.setdefault("streamed", []).append(rec)
+            for name, v in stats.items():
+                med = [sorted(c)[len(c) // 2] for c in zip(*v)]
+                mean = [sum(c) / len(c) for c in zip(*v)]
+                print(f"   {name} turns (weight tiles k-1 .. k+2), n = {len(v)}: median landing {med[0]}, barrier {med[1]}, issue {med[2]}, "
+                      f"period {med[3]}; mean landing {mean[0]:.0f}, barrier {mean[1]:.0f}, issue {mean[2]:.0f}, period {mean[3]:.0f}")
 lib.mdt_set_tuning(b"pair_stride", 0)
