@@ -604,7 +604,8 @@ enum mdt_screen_status {
   MDT_SCREEN_KNOWN = 8,     /* the molecule is in the known set (mdt_screen_select_diverse: or closer to it than min_novelty) */
   MDT_SCREEN_CLOSE = 16,    /* mdt_screen_select_diverse only: closer than min_distance to a better candidate that was kept */
   MDT_SCREEN_MALFORMED = 32, /* mdt_smiles_check: the row breaks the grammar, or its ring / branch bookkeeping does not close */
-  MDT_SCREEN_OVERVALENT = 64, /* mdt_smiles_check: well-formed, but an unbracketed atom's bond orders exceed its maximum */
+  MDT_SCREEN_OVERVALENT = 64, /* mdt_smiles_check: well-formed, but an unbracketed atom's bond orders exceed its maximum; the
+                                 screening call's kekulize: also a verdict != 0 of mdt_mol_hydrogens (no status bit is free) */
   MDT_SCREEN_SUBSTRUCTURE = 128 /* mdt_sub_match: a required pattern is missing or undecided, or a forbidden one present or undecided */
 };
 /* Per group g: status uint8 (N*G) of every candidate; index int32 (G,K): the eligible (status == 0) candidates c in ascending
@@ -876,6 +877,59 @@ int mdt_sub_match(const int32_t *natoms, const uint32_t *atoms, const int32_t *n
                   const int32_t *p_natoms, const uint32_t *p_atoms, const int32_t *p_nbonds, const uint32_t *p_bonds,
                   int32_t LP, int32_t P, uint32_t need, uint32_t ban,
                   uint32_t *match, uint32_t *undecided, uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* Implicit hydrogens and a Kekule check (csrc/k_molh.hip, csrc/mdt_molh.h); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* How many hydrogens does each atom carry, and is the row, where it is written with lower-case atoms, a molecule at all?
+ * mdt_smiles_check exempts aromatic atoms from every valence rule, so c1cccc1 passes it; the reference's callers would see RDKit
+ * refuse it (Chem.MolFromSmiles(smi) is None, generative.py:954-994).  This is a precisely defined answer on the graph of
+ * mdt_mol_graph: per atom its hydrogens and whether it still needs a double bond, per row whether those double bonds can be placed
+ * (a Kekule structure exists), and the molecular formula.  It is not RDKit's sanitisation.
+ *
+ * Inputs.  natoms, atoms, nbonds, bonds of mdt_mol_graph (device pointers), R rows of width 1 <= L <= 64; 1 <= max_steps <=
+ * MDT_MOLH_MAX_STEPS.  A row that is no molecule -- natoms == 0, counts outside [0, L], a bond naming an atom >= natoms (the rule of
+ * mdt_mol_key) -- has verdict 0, atom -1 and all-zero outputs.
+ * Per atom.  sum1(a) = the sum over the bond entries at a of the order, an entry of order 5 counted as 1; an entry listed twice
+ * counts twice; an entry (a, a), which mdt_mol_graph never writes, counts twice at a and is never an edge below.  Normal valences:
+ * B {3}, C {4}, N {3, 5}, O {2}, P {3, 5}, S {2, 4, 6}, F Cl Br I {1}; every other symbol and '*' has none.  "v for s" is the
+ * smallest normal valence >= s.
+ *  - Unbracketed, not aromatic: H = v - sum1 for v for sum1; H = 0 if there is none.  The atom wants nothing.
+ *  - Unbracketed, aromatic (b c n o p s, with the lists of B C N O P S; any other symbol has no list): if there is no v for sum1 the
+ *    atom is AROMATIC-OVERVALENT, H = 0, it wants nothing.  Otherwise rem = v - sum1, the atom WANTS a double bond iff rem >= 1, and
+ *    H = rem - (1 if it wants).  So c of benzene has H 1 and wants; the n of pyridine H 0 and wants; n with three neighbours, o, s
+ *    want nothing; c(=O) of a pyridone wants nothing.
+ *  - Bracket atom: H = the bracket's H count, as SMILES says.  It is never overvalent.  It wants nothing unless it is aromatic:
+ *    group g = b 13, c 14, n 15, o 16, p 15, s 16 (another symbol: wants nothing), g' = g - charge, lists by g': 13 {3}, 14 {4},
+ *    15 {3, 5}, 16 {2, 4, 6} (any other g': wants nothing), s' = sum1 + H; it wants iff a v for s' exists in that list and
+ *    v - s' >= 1.  So [nH], [n-], [cH-] want nothing; [n+] with three neighbours, [nH+], [o+], [s+] want.
+ * Per row.  W = the wanting atoms.  An EDGE is a bond entry of order 5 between two distinct atoms of W: an explicit '-' between two
+ * rings is never a double bond, a bare cc bond is an edge.  Verdict, first rule that applies:
+ *   MDT_MOLH_AROMATIC_OVERVALENT (1)  some atom is aromatic-overvalent; atom = the lowest such index; no search runs.
+ *   MDT_MOLH_NO_KEKULE (2)            |W| is odd (zero steps).
+ *   otherwise the search decides: it looks for a perfect matching of W over the edges, AND ITS ORDER IS PART OF THE DEFINITION,
+ *   because its cap is.  M = the unmatched atoms of W.  M empty: verdict MDT_MOLH_OK (0).  Else u = the atom of M with the fewest
+ *   neighbours in M, ties to the lowest index.  The neighbours of u in M are tried in ascending index (none: go back); each try is
+ *   one STEP and removes u and that neighbour from M; a try that would be step max_steps + 1 ends the search: MDT_MOLH_UNDECIDED
+ *   (3).  Going back restores the last pair (u, v) and goes on with the candidates of u above v; with nothing to restore the verdict
+ *   is MDT_MOLH_NO_KEKULE.  atom = -1 for verdicts 0, 2 and 3.
+ * Outputs, every word defined, zero beyond natoms.  hydrogens uint8 (R,L).  partner uint8 (R,L): 1 + the atom matched to this one
+ * when the verdict is 0 and the atom is in W, else 0 -- WHICH matching is found depends on how the row is spelled; the verdict of a
+ * decided row (0 or 2) does not, and neither do hydrogens, formula or verdict 1.  verdict uint8 (R), atom int32 (R).  formula int32
+ * (R,13): the counts of H B C N O F P S Cl Br I, of every other symbol ('*' included), then the net formal charge; H = the sum of
+ * hydrogens plus one for every atom whose symbol is H (only a bracket atom can be; it is not "other").  The formula is written for
+ * every verdict.
+ * What this is and is NOT.  Not RDKit's sanitisation.  Ring membership is not checked: cc is kekulisable as ethene, and an aromatic
+ * atom outside any ring is judged like one inside.  No aromaticity perception the other way (C1=CC=CC=C1 stays as written).  No
+ * radicals: an atom's free valences are filled with hydrogens.  Bracket atoms are taken at their word.  max_steps is the bound
+ * every loop needs on a shared machine, and a definition, not a measurement: no row of the reference pools comes near it.
+ * R == 0 launches nothing. */
+#define MDT_MOLH_MAX_STEPS 4096
+#define MDT_MOLH_FORMULA 13
+enum mdt_molh_verdict { MDT_MOLH_OK = 0, MDT_MOLH_AROMATIC_OVERVALENT = 1, MDT_MOLH_NO_KEKULE = 2, MDT_MOLH_UNDECIDED = 3 };
+int mdt_mol_hydrogens(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+                      int32_t max_steps, uint8_t *hydrogens, uint8_t *partner, uint8_t *verdict, int32_t *atom, int32_t *formula,
+                      void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

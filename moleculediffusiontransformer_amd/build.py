@@ -46,6 +46,7 @@ SOURCES = [
     ("k_molgraph.hip", []),
     ("k_molfp.hip", []),
     ("k_molsub.hip", []),
+    ("k_molh.hip", []),
     ("mdt_api.cpp", ["-x", "hip"]),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

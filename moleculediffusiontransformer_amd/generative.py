@@ -877,6 +877,7 @@ FP_SIM_DEN = 65536              # a similarity threshold crosses into the kernel
 MAX_SUB_PATTERNS = 32           # the substructure match (csrc/k_molsub.hip): patterns a call, one bit of a 32-bit word each
 MAX_SUB_LENGTH = 32             # ... and characters a pattern
 MAX_FP_RADIUS = 3               # the fingerprint (csrc/k_molfp.hip): rounds 0 .. radius, radius in [0, 3]
+MOLH_MAX_STEPS = 4096           # the Kekule check (csrc/k_molh.hip): tries of a row's matching search (MDT_MOLH_MAX_STEPS)
 
 
 def _integer_ids(ids, name: str):
@@ -1139,11 +1140,12 @@ def _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, v
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
             min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
-            fingerprint_radius=2, require=None, forbid=None) -> Screened:
+            fingerprint_radius=2, require=None, forbid=None, kekulize=False) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
     with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`;
-    with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in."""
+    with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in; with ``kekulize`` one mdt::mol_hydrogens on the
+    same graph, right after mdt::mol_graph, ORs bit 64 in where its verdict is not 0."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     width = torch.as_tensor(tokens).shape[1]
@@ -1151,6 +1153,7 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     _identity_arg(identity, vocabulary, width)
     sim_num, known_sim_num = _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known, width)
     fragments = _substructure_args(require, forbid, vocabulary, width)
+    _kekulize_arg(kekulize, vocabulary, width)
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1167,8 +1170,13 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     if vocabulary is not None:                                   # is it a molecule at all?  bits 32 / 64, never kept
         reject, _ = torch.ops.mdt.smiles_check(packed, length, *vocabulary.on(device))
     graph = None
-    if identity == "graph":                                      # which molecule is it?  bits 4 / 8 by the graph key
+    if kekulize:                                                 # can its aromatic atoms be satisfied?  bit 64, never kept
         graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
+        verdict = torch.ops.mdt.mol_hydrogens(*graph, MOLH_MAX_STEPS)[2]
+        reject = reject | ((verdict != 0).to(torch.uint8) * rt.SCREEN_OVERVALENT)
+    if identity == "graph":                                      # which molecule is it?  bits 4 / 8 by the graph key
+        if graph is None:
+            graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
         graph_key = torch.ops.mdt.mol_key(*graph)
         known_graph = known.mol_keys(vocabulary, device) if known is not None and len(known) else None
         reject = reject | torch.ops.mdt.key_flags(graph_key, N, known_graph)
@@ -1238,7 +1246,7 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
                           max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2, require=None, forbid=None,
-                          **screen_tokens_kwargs) -> Screened:
+                          kekulize: bool = False, **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
     ``vocabulary=``, with "is it a molecule at all?" asked of every candidate.
@@ -1293,11 +1301,22 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     where a required pattern is not found or a forbidden one is; an undecided verdict counts against the candidate both ways.  A
     candidate with bit 128 is never kept and pushes nothing out; ``((status & 128) == 0).float().mean()`` is the fraction that meets
     the constraint.  With both at None nothing new is launched.
+
+    ``kekulize``: with True, "is it a molecule at all?" is also asked of the lower-case atoms, which mdt::smiles_check exempts from
+    every valence rule (c1cccc1 passes it).  It needs a ``vocabulary`` and rows of at most 64 positions, refused with ValueError
+    before anything is launched.  One mdt::mol_hydrogens (mol_hydrogens(), see there for the definition and its limits: not RDKit's
+    sanitisation, ring membership is not checked, bracket atoms are taken at their word) runs over the N * G rows right after
+    mdt::mol_graph -- the graph that ``identity="graph"``, the fingerprints and ``require`` / ``forbid`` share, computed once -- and
+    rows whose verdict is not 0 get status bit 64 (runtime.SCREEN_OVERVALENT) OR-ed into `reject`.  No status bit is free, so under
+    ``kekulize=True`` bit 64 also means "an aromatic atom's valence cannot be satisfied": an aromatic atom is overvalent, or no
+    Kekule structure exists, or the search was undecided after 4096 steps, which counts against the row.  Such a row is never kept
+    and pushes nothing out; the valid fraction stays ``((status & 96) == 0).float().mean()``.  With False (the default) the call
+    makes exactly the launches it makes without the keyword, in the same order.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
                    vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
                    max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, require=require, forbid=forbid,
-                   **screen_tokens_kwargs)
+                   kekulize=kekulize, **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1763,6 +1782,114 @@ def has_substructure(tokens, patterns, vocabulary: "SmilesVocabulary", device):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# how many hydrogens, and do the lower-case atoms add up?  implicit hydrogens, the Kekule check and the formula
+# (csrc/k_molh.hip): rows of at most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+FORMULA_SLOTS = ("H", "B", "C", "N", "O", "F", "P", "S", "Cl", "Br", "I", "other", "charge")      # the columns of mol_formula()
+ATOMIC_WEIGHTS = dict(H=1.008, B=10.81, C=12.011, N=14.007, O=15.999, F=18.998403163, P=30.973761998, S=32.06, Cl=35.45, Br=79.904,
+                      I=126.90447)                                # standard atomic weights (IUPAC abridged values)
+
+
+def _kekulize_arg(kekulize, vocabulary, length: int) -> None:
+    """The refusals of ``kekulize=``, before anything is launched."""
+    if not isinstance(kekulize, bool):
+        raise ValueError(f"kekulize must be True or False, got {kekulize!r}")
+    if kekulize:
+        if vocabulary is None:
+            raise ValueError("kekulize=True reads the rows as strings: give a vocabulary")
+        if length > MAX_MOL_LENGTH:
+            raise ValueError(f"tokens has rows of {length} positions; the Kekule check takes at most {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+
+
+def _max_steps_arg(max_steps) -> int:
+    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or not 1 <= max_steps <= MOLH_MAX_STEPS:
+        raise ValueError(f"max_steps must be an int in [1, {MOLH_MAX_STEPS}], got {max_steps!r}")
+    return max_steps
+
+
+def _hydrogens_of(tokens, vocabulary, device, max_steps):
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    return torch.ops.mdt.mol_hydrogens(natoms, atoms, nbonds, bonds, max_steps) + (status, position)
+
+
+def mol_hydrogens(tokens, vocabulary: "SmilesVocabulary", device, max_steps: int = MOLH_MAX_STEPS):
+    """How many hydrogens does each atom carry, and can the double bonds of the lower-case atoms be placed?  -> (hydrogens int64
+    (R, L), partner int64 (R, L), verdict int64 (R,), atom int64 (R,), status int64 (R,), position int64 (R,)) for raw (R, L) ids of
+    any integer dtype, zeros anywhere.  ``status`` / ``position`` are smiles_check()'s; the rest is indexed like mol_graph()'s atoms.
+
+    ``hydrogens[r, a]``: the hydrogens of atom a -- a bracket atom's own count; for any other atom what fills its smallest normal
+    valence (B 3, C 4, N 3 5, O 2, P 3 5, S 2 4 6, halogens 1) above its bonds, an aromatic bond counted as 1, less the one
+    double bond an aromatic atom may still want.  ``verdict``: 0 the row adds up; 1 (runtime.MOLH_AROMATIC_OVERVALENT) an
+    unbracketed aromatic atom has more bonds than any normal valence, ``atom`` = the lowest such atom (-1 otherwise); 2
+    (runtime.MOLH_NO_KEKULE) the atoms that want a double bond cannot be paired along the aromatic bonds -- c1cccc1, n1cccc1
+    (pyrrole without its H); 3 (runtime.MOLH_UNDECIDED) the pairing search made ``max_steps`` (1..4096) tries without an answer.
+    ``partner[r, a]``: where the verdict is 0 and atom a wants a double bond, 1 + the atom it goes to, else 0 -- one Kekule
+    structure; which one can depend on how the row is spelled, the verdict of a decided row, the hydrogens and the formula do not.
+    A row that is no molecule (empty, or status != 0) has verdict 0, atom -1 and zeros.  mdt_mol_hydrogens in include/mdt_hip.h has
+    every rule, the order of the search included, because its cap is part of the definition.
+    What it is NOT: not RDKit's sanitisation.  Ring membership is not checked (cc is kekulisable as ethene), there is no
+    aromaticity perception the other way (C1=CC=CC=C1 stays as written), no radicals, and bracket atoms are taken at their word.
+    L <= 64; the refusals are mol_key()'s and a max_steps outside [1, 4096], with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens."""
+    max_steps = _max_steps_arg(max_steps)
+    hydrogens, partner, verdict, atom, _, status, position = _hydrogens_of(tokens, vocabulary, device, max_steps)
+    return hydrogens.long(), partner.long(), verdict.long(), atom.long(), status.long(), position.long()
+
+
+def mol_formula(tokens, vocabulary: "SmilesVocabulary", device):
+    """The molecular formula behind each row -> (counts int64 (R, 13), verdict int64 (R,), status int64 (R,), position int64 (R,))
+    for raw (R, L) ids: the atoms of H B C N O F P S Cl Br I, of any other symbol (``*`` included), and the net formal charge
+    (FORMULA_SLOTS), with the hydrogens of mol_hydrogens() -- see there for the rules and for ``verdict``, under which the counts are
+    written whatever it is.  ``counts[:, 1:12].sum(1)`` is the heavy-atom count (a bracket atom [H] counts as a hydrogen); a row that
+    is no molecule has all zeros.  formula_strings() and mol_weight() read the counts on the host.  Not RDKit's CalcMolFormula:
+    no isotopes in the formula, no radicals.  L <= 64; the refusals are mol_key()'s.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens."""
+    _, _, verdict, _, formula, status, position = _hydrogens_of(tokens, vocabulary, device, MOLH_MAX_STEPS)
+    return formula.long(), verdict.long(), status.long(), position.long()
+
+
+def _formula_counts(counts):
+    counts = torch.as_tensor(counts).detach().cpu()
+    if counts.dim() != 2 or counts.shape[1] != len(FORMULA_SLOTS) or counts.is_floating_point():
+        raise ValueError(f"counts must be integers of shape (R, {len(FORMULA_SLOTS)}) as mol_formula() returns them, got "
+                         f"{counts.dtype} {tuple(counts.shape)}")
+    return counts.long()
+
+
+def formula_strings(counts):
+    """The rows of mol_formula()'s ``counts`` as text, on the host: Hill order (C, H, then the other symbols alphabetically; without
+    carbon all alphabetically), a count of 1 not written, the net charge as ``+`` / ``-`` / ``+2`` / ``-2``, a ``?`` at the end when
+    atoms of other symbols are present (they are not in the text), and ``""`` for a row without atoms.  C2H6O, H4N+, CH3?."""
+    out = []
+    for row in _formula_counts(counts).tolist():
+        count = dict(zip(FORMULA_SLOTS, row))
+        if not any(row[:12]):
+            out.append("")
+            continue
+        symbols = sorted(FORMULA_SLOTS[:11])
+        if count["C"]:
+            symbols = ["C", "H"] + [s for s in symbols if s not in ("C", "H")]
+        text = "".join(s + (str(count[s]) if count[s] != 1 else "") for s in symbols if count[s])
+        q = count["charge"]
+        if q:
+            text += ("+" if q > 0 else "-") + (str(abs(q)) if abs(q) > 1 else "")
+        out.append(text + ("?" if count["other"] else ""))
+    return out
+
+
+def mol_weight(counts) -> Tensor:
+    """The molecular weight of the rows of mol_formula()'s ``counts``, on the host: float64 (R,), the standard atomic weights
+    (ATOMIC_WEIGHTS) times the counts; NaN where atoms of other symbols are present, 0 for a row without atoms.  Isotopes and the
+    charge do not enter."""
+    counts = _formula_counts(counts)
+    w = torch.tensor([ATOMIC_WEIGHTS[s] for s in FORMULA_SLOTS[:11]], dtype=torch.float64)
+    weight = counts[:, :11].double() @ w
+    return torch.where(counts[:, 11] > 0, torch.full_like(weight, float("nan")), weight)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:
@@ -1813,14 +1940,14 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
     ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
-    ``fingerprint_radius`` / ``require`` / ``forbid``, with which the tokens go to screen_tokens_diverse instead;
+    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
                                          "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
-                                         "max_known_similarity", "fingerprint_radius", "require", "forbid"}
+                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -1850,6 +1977,10 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
         _substructure_args(fragments.get("require"), fragments.get("forbid"), vocabulary, model.max_length)
         diverse = True
         filters.update(fragments)
+    kekulize = screen_tokens_kwargs.pop("kekulize", False)
+    _kekulize_arg(kekulize, vocabulary, model.max_length)
+    if kekulize:                                                 # (False: the calls made without the keyword)
+        diverse, filters["kekulize"] = True, True
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

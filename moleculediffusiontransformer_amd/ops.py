@@ -906,6 +906,48 @@ def _(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds, need, 
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# implicit hydrogens, the Kekule check and the formula (csrc/k_molh.hip): rows of at most 64 positions
+@custom_op("mdt::mol_hydrogens", mutates_args=())
+def mol_hydrogens(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, max_steps: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (hydrogens uint8 (R, L), partner uint8 (R, L), verdict uint8 (R,), atom int32 (R,), formula int32 (R, 13)) of
+    mdt_mol_hydrogens (include/mdt_hip.h) for the graph arrays of mdt::mol_graph: per atom the hydrogens it carries and, where the
+    verdict is 0, 1 + the atom its double bond goes to (0: none); verdict 0 ok, 1 an aromatic atom is overvalent (``atom``), 2 no
+    Kekule structure, 3 undecided after ``max_steps`` (1..4096) tries; formula: H B C N O F P S Cl Br I other charge.  All zero
+    (atom -1) where natoms is 0 (no molecule).  Not RDKit's sanitisation."""
+    dev = _hip(natoms, atoms, nbonds, bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_hydrogens"
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the hydrogens take 1 to {rt.MOL_MAX_LENGTH}")
+    if not 1 <= max_steps <= rt.MOLH_MAX_STEPS:
+        raise RuntimeError(f"{op}: max_steps = {max_steps} must lie in [1, {rt.MOLH_MAX_STEPS}]")
+    natoms, atoms, nbonds, bonds = natoms.contiguous(), atoms.contiguous(), nbonds.contiguous(), bonds.contiguous()
+    hydrogens = torch.zeros(R, L, dtype=torch.uint8, device=dev)
+    partner = torch.zeros(R, L, dtype=torch.uint8, device=dev)
+    verdict = torch.zeros(R, dtype=torch.uint8, device=dev)
+    atom = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    formula = torch.zeros(R, rt.MOLH_FORMULA, dtype=torch.int32, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_hydrogens(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, int(max_steps),
+                                           rt.ptr(hydrogens), rt.ptr(partner), rt.ptr(verdict), rt.ptr(atom), rt.ptr(formula),
+                                           rt.current_stream()))
+    return hydrogens, partner, verdict, atom, formula
+
+
+@mol_hydrogens.register_fake
+def _(natoms, atoms, nbonds, bonds, max_steps):
+    R, L = atoms.shape
+    return (atoms.new_empty(R, L, dtype=torch.uint8), atoms.new_empty(R, L, dtype=torch.uint8), atoms.new_empty(R, dtype=torch.uint8),
+            atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, rt.MOLH_FORMULA, dtype=torch.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between compacted id rows (csrc/k_edit.hip): at most 64 positions, ids in [0, 64)
 def _edit_rows(op, packed, length, what):
     if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
