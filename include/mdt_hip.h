@@ -606,7 +606,9 @@ enum mdt_screen_status {
   MDT_SCREEN_MALFORMED = 32, /* mdt_smiles_check: the row breaks the grammar, or its ring / branch bookkeeping does not close */
   MDT_SCREEN_OVERVALENT = 64, /* mdt_smiles_check: well-formed, but an unbracketed atom's bond orders exceed its maximum; the
                                  screening call's kekulize: also a verdict != 0 of mdt_mol_hydrogens (no status bit is free) */
-  MDT_SCREEN_SUBSTRUCTURE = 128 /* mdt_sub_match: a required pattern is missing or undecided, or a forbidden one present or undecided */
+  MDT_SCREEN_SUBSTRUCTURE = 128 /* mdt_sub_match: a required pattern is missing or undecided, or a forbidden one present or undecided;
+                                   the screening call's limits: also "a descriptor of mdt_mol_rings lies outside its bounds" (no
+                                   status bit is free) */
 };
 /* Per group g: status uint8 (N*G) of every candidate; index int32 (G,K): the eligible (status == 0) candidates c in ascending
  * order of (score, c) -- ties go to the lower c -- and -1 in the slots beyond count[g] = min(K, number of eligible candidates).
@@ -920,7 +922,8 @@ int mdt_sub_match(const int32_t *natoms, const uint32_t *atoms, const int32_t *n
  * hydrogens plus one for every atom whose symbol is H (only a bracket atom can be; it is not "other").  The formula is written for
  * every verdict.
  * What this is and is NOT.  Not RDKit's sanitisation.  Ring membership is not checked: cc is kekulisable as ethene, and an aromatic
- * atom outside any ring is judged like one inside.  No aromaticity perception the other way (C1=CC=CC=C1 stays as written).  No
+ * atom outside any ring is judged like one inside (mdt_mol_rings counts such atoms: MDT_MOLR_AROMATIC_OUTSIDE_RING).  No aromaticity
+ * perception the other way (C1=CC=CC=C1 stays as written).  No
  * radicals: an atom's free valences are filled with hydrogens.  Bracket atoms are taken at their word.  max_steps is the bound
  * every loop needs on a shared machine, and a definition, not a measurement: no row of the reference pools comes near it.
  * R == 0 launches nothing. */
@@ -930,6 +933,73 @@ enum mdt_molh_verdict { MDT_MOLH_OK = 0, MDT_MOLH_AROMATIC_OVERVALENT = 1, MDT_M
 int mdt_mol_hydrogens(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
                       int32_t max_steps, uint8_t *hydrogens, uint8_t *partner, uint8_t *verdict, int32_t *atom, int32_t *formula,
                       void *stream);
+
+/* ------------------------------------------------------------------ */
+/* Ring perception and descriptors (csrc/k_molring.hip, csrc/mdt_molring.h); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* Which bonds and atoms lie in a ring, how small is the smallest ring through them, and is the molecule inside the caller's bounds
+ * on sixteen integer descriptors?  Everything the layers before this one answer about a row is local to an atom or a bond; "no
+ * three- or four-membered ring", "no macrocycle", "at most 10 rotatable bonds", "inside Lipinski's weight / donor / acceptor
+ * limits" are not.  This is a precisely defined answer on the graph of mdt_mol_graph and the hydrogens of mdt_mol_hydrogens.
+ *
+ * Inputs.  natoms, atoms, nbonds, bonds of mdt_mol_graph and hydrogens uint8 (R,L) of mdt_mol_hydrogens (device pointers; hydrogens
+ * is required, and mdt_mol_hydrogens defines it for every verdict), R rows of width 1 <= L <= 64.  lo, hi: int32 (MDT_MOLR_DESC)
+ * device pointers, both given or both NULL.  flags: uint8 (R) or NULL.  A row that is no molecule -- natoms == 0, counts outside
+ * [0, L], a bond naming an atom >= natoms (the rule of mdt_mol_key) -- has all-zero outputs and flag 0.
+ * The ring graph.  The simple graph on the row's atoms whose edges are the distinct unordered pairs {a, b}, a != b, named by at
+ * least one bond entry, whatever the entry's order: an order outside 1..5 is an edge like any other, entries listed twice collapse
+ * to one edge (C12CC12 is a row the scan accepts), an entry (a, a) is never an edge.  E = its edges, n = natoms.
+ * Outputs, every word defined.
+ *  bond_ring uint8 (R,L), per bond entry: for an entry (a, b), a != b: 1 + the length of a shortest path from a to b in the ring
+ *   graph with the edge {a, b} removed, 0 if there is none (the bond is a bridge); for an entry (a, a): 0; 0 beyond nbonds.
+ *  atom_ring uint8 (R,L), per atom: the smallest non-zero bond_ring over the entries at the atom, 0 if none, 0 beyond natoms: the
+ *   size of the smallest cycle through the atom.
+ *  desc int32 (R, MDT_MOLR_DESC = 16); "symbol X" means the atom's letters, in either case, bracketed or not:
+ *    0 MDT_MOLR_HEAVY_ATOMS            atoms whose symbol is not H.
+ *    1 MDT_MOLR_HETERO_ATOMS           heavy atoms whose symbol is not C; '*' counts.
+ *    2 MDT_MOLR_DONORS                 atoms of symbol N or O with hydrogens >= 1.
+ *    3 MDT_MOLR_ACCEPTORS              atoms of symbol N or O: Lipinski's N + O count.
+ *    4 MDT_MOLR_ROTATABLE_BONDS        entries (a, b) of order 1 with bond_ring == 0 and a != b whose two ends each have at least 2
+ *                                      distinct heavy neighbours in the ring graph and no entry of order 3 or 4 (an entry (x, x)
+ *                                      included).  An entry listed twice counts twice.  AN ORDER-5 ENTRY IS NEVER ROTATABLE: a
+ *                                      stated limit, which misses the axis of a biphenyl written without '-'.
+ *    5 MDT_MOLR_RINGS                  E - n + components (the cycle rank).
+ *    6 MDT_MOLR_RING_ATOMS             atoms with atom_ring > 0.
+ *    7 MDT_MOLR_RING_BONDS             entries with bond_ring > 0.
+ *    8 MDT_MOLR_SMALLEST_RING          the minimum non-zero bond_ring, 0 if there is none.
+ *    9 MDT_MOLR_LARGEST_RING           the maximum bond_ring: naphthalene gives 6, not 10.
+ *   10 MDT_MOLR_AROMATIC_ATOMS         atoms with descriptor bit 10.
+ *   11 MDT_MOLR_AROMATIC_OUTSIDE_RING  atoms with bit 10 and atom_ring == 0: the cc that mdt_mol_hydrogens kekulises as ethene, as
+ *                                      a number a bound can reject.
+ *   12 MDT_MOLR_SP3_CARBONS            atoms of symbol C without bit 10 whose every entry ((x, x) included) has order 1.
+ *   13 MDT_MOLR_CARBONS                atoms of symbol C.
+ *   14 MDT_MOLR_COMPONENTS             the connected components of the ring graph.
+ *   15 MDT_MOLR_WEIGHT                 milli-dalton: the sum over the formula slots of mdt_mol_hydrogens, H B C N O F P S Cl Br I,
+ *                                      of count times 1008 10810 12011 14007 15999 18998 30974 32060 35450 79904 126904 (the
+ *                                      standard atomic weights of mol_weight(), each rounded to the nearest milli-dalton); H = the
+ *                                      sum of hydrogens plus the atoms of symbol H, as the formula counts it; "other" weighs 0.
+ *  flags[r]: MDT_SCREEN_SUBSTRUCTURE (128) when the row is a molecule, lo and hi are given and some k has desc[k] < lo[k] or
+ *   desc[k] > hi[k]; otherwise 0.  Nothing is written when flags is NULL.
+ * What this is and is NOT.  Not RDKit's ring info and not an SSSR: a bond knows the smallest cycle through it, nobody lists rings,
+ * and MDT_MOLR_RINGS is the cycle rank (cubane: 5, though it has six faces).  No envelope rings: the 10-ring
+ * around naphthalene is nobody's smallest cycle.  No logP, so Lipinski's fourth rule is not here.  Aromaticity is as written (bit
+ * 10), not perceived: C1=CC=CC=C1 has no aromatic atom.  Donors and weight rest on hydrogens as handed in.  Nothing here depends
+ * on how the row is spelled but the order of the per-entry and per-atom outputs, which follow the graph row's numbering.
+ * Every loop of the kernel is bounded by nbonds, natoms or both (at most nbonds searches of at most natoms levels), so there is no
+ * step cap and no undecided answer.  R == 0 launches nothing.
+ * Cost (131,072 mutated rows of L = 32, half of them molecules, 21 % with a ring; one MI355X, 2026-10-20): 0.0952
+ * ms a call, 0.0967 ms with bounds and flags, beside 0.0649 ms for mdt_mol_hydrogens and 0.0827 ms for mdt_mol_fp on the same rows;
+ * the estimate written before the first run (instruction issue, 10.1 ballot levels a molecule row) said 0.0628 ms: ratio 1.51. */
+#define MDT_MOLR_DESC 16
+enum mdt_molr_slot {
+  MDT_MOLR_HEAVY_ATOMS = 0, MDT_MOLR_HETERO_ATOMS = 1, MDT_MOLR_DONORS = 2, MDT_MOLR_ACCEPTORS = 3, MDT_MOLR_ROTATABLE_BONDS = 4,
+  MDT_MOLR_RINGS = 5, MDT_MOLR_RING_ATOMS = 6, MDT_MOLR_RING_BONDS = 7, MDT_MOLR_SMALLEST_RING = 8, MDT_MOLR_LARGEST_RING = 9,
+  MDT_MOLR_AROMATIC_ATOMS = 10, MDT_MOLR_AROMATIC_OUTSIDE_RING = 11, MDT_MOLR_SP3_CARBONS = 12, MDT_MOLR_CARBONS = 13,
+  MDT_MOLR_COMPONENTS = 14, MDT_MOLR_WEIGHT = 15
+};
+int mdt_mol_rings(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, const uint8_t *hydrogens,
+                  int32_t L, int32_t R, const int32_t *lo, const int32_t *hi, uint8_t *bond_ring, uint8_t *atom_ring, int32_t *desc,
+                  uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

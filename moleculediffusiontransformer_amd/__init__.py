@@ -10,9 +10,9 @@ hand-written gfx950 kernels (csrc/, C ABI in include/mdt_hip.h).  So does the VA
 """
 from .diffusion import (ADPM2Sampler, AEulerSampler, DiffusionInpainter, DiffusionSampler, KarrasSampler,  # noqa: F401
                         KarrasSchedule, LogNormalDistribution, NoiseSource, Sampler, guidance_rows, refine_start)
-from .generative import (KDiffusion_mod, KnownSet, QMDiffusion, QMDiffusionForward, Screened, SmilesVocabulary, SubstructureSet,  # noqa: F401
+from .generative import (DESCRIPTOR_NAMES, DescriptorLimits, KDiffusion_mod, KnownSet, QMDiffusion, QMDiffusionForward, Screened, SmilesVocabulary, SubstructureSet,  # noqa: F401
                          XDiffusion_x, complete_and_validate, edit_distance, formula_strings, generate_and_validate, guidance_sweep,
-                         has_substructure, mol_fingerprint, mol_formula, mol_graph, mol_hydrogens, mol_key, mol_weight, nearest_known, nearest_known_tanimoto, one_hot_draft, predict_properties_from_tokens, refine_and_validate, screen_candidates,
+                         has_substructure, mol_fingerprint, mol_descriptors, mol_formula, mol_graph, mol_hydrogens, mol_key, mol_rings, mol_weight, nearest_known, nearest_known_tanimoto, one_hot_draft, predict_properties_from_tokens, refine_and_validate, screen_candidates,
                          screen_tokens,
                          screen_tokens_diverse, smiles_check, strength_sweep, tanimoto, tokens_to_forward_input)
 from .graphmodel import AnalogDiffusionFull, AnalogDiffusionSparse  # noqa: F401

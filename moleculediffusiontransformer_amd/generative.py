@@ -1140,12 +1140,13 @@ def _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, v
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
             min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
-            fingerprint_radius=2, require=None, forbid=None, kekulize=False) -> Screened:
+            fingerprint_radius=2, require=None, forbid=None, kekulize=False, limits=None) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
     with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`;
     with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in; with ``kekulize`` one mdt::mol_hydrogens on the
-    same graph, right after mdt::mol_graph, ORs bit 64 in where its verdict is not 0."""
+    same graph, right after mdt::mol_graph, ORs bit 64 in where its verdict is not 0; with ``limits`` one mdt::mol_rings after that
+    mdt::mol_hydrogens (made once when both are asked for) ORs bit 128 in where a descriptor lies outside its bounds."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     width = torch.as_tensor(tokens).shape[1]
@@ -1154,6 +1155,7 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     sim_num, known_sim_num = _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, vocabulary, known, width)
     fragments = _substructure_args(require, forbid, vocabulary, width)
     _kekulize_arg(kekulize, vocabulary, width)
+    _limits_arg(limits, vocabulary, width)
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1170,10 +1172,13 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     if vocabulary is not None:                                   # is it a molecule at all?  bits 32 / 64, never kept
         reject, _ = torch.ops.mdt.smiles_check(packed, length, *vocabulary.on(device))
     graph = None
-    if kekulize:                                                 # can its aromatic atoms be satisfied?  bit 64, never kept
+    if kekulize or limits is not None:                           # the hydrogens: one launch for the Kekule check and the descriptors
         graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
-        verdict = torch.ops.mdt.mol_hydrogens(*graph, MOLH_MAX_STEPS)[2]
+        hydrogens, _, verdict, _, _ = torch.ops.mdt.mol_hydrogens(*graph, MOLH_MAX_STEPS)
+    if kekulize:                                                 # can its aromatic atoms be satisfied?  bit 64, never kept
         reject = reject | ((verdict != 0).to(torch.uint8) * rt.SCREEN_OVERVALENT)
+    if limits is not None:                                       # is it inside the descriptor bounds?  bit 128, never kept
+        reject = reject | torch.ops.mdt.mol_rings(*graph, hydrogens, *limits.on(device))[3]
     if identity == "graph":                                      # which molecule is it?  bits 4 / 8 by the graph key
         if graph is None:
             graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
@@ -1246,7 +1251,7 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
                           max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2, require=None, forbid=None,
-                          kekulize: bool = False, **screen_tokens_kwargs) -> Screened:
+                          kekulize: bool = False, limits=None, **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
     ``vocabulary=``, with "is it a molecule at all?" asked of every candidate.
@@ -1312,11 +1317,21 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     Kekule structure exists, or the search was undecided after 4096 steps, which counts against the row.  Such a row is never kept
     and pushes nothing out; the valid fraction stays ``((status & 96) == 0).float().mean()``.  With False (the default) the call
     makes exactly the launches it makes without the keyword, in the same order.
+
+    ``limits``: a DescriptorLimits (None: not asked) -- bounds on the sixteen integer descriptors of mol_descriptors(): ring count
+    and ring sizes, rotatable bonds, donors, acceptors, weight, ... (see there and mol_rings() for the definitions and their
+    limits: not RDKit's ring info, not an SSSR, no logP, aromaticity as written).  It needs a ``vocabulary`` and rows of at most 64
+    positions, refused with ValueError before anything is launched.  One mdt::mol_rings runs over the N * G rows after the shared
+    mdt::mol_graph and after the mdt::mol_hydrogens launch that ``kekulize=True`` also uses -- that launch is made once when both
+    are on -- and ORs status bit 128 (runtime.SCREEN_SUBSTRUCTURE) into `reject` where a descriptor of a molecule row lies outside
+    its bounds.  No status bit is free, so under ``limits=`` bit 128 also means "a descriptor lies outside its bounds".  Such a
+    candidate is never kept and pushes nothing out.  ``DescriptorLimits.lipinski()`` is weight <= 500, donors <= 5, acceptors <=
+    10.  With None the call makes exactly the launches it makes without the keyword, in the same order.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
                    vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
                    max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, require=require, forbid=forbid,
-                   kekulize=kekulize, **screen_tokens_kwargs)
+                   kekulize=kekulize, limits=limits, **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1890,6 +1905,112 @@ def mol_weight(counts) -> Tensor:
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# which bonds and atoms lie in a ring, and is the molecule inside the bounds?  ring perception and descriptors
+# (csrc/k_molring.hip): rows of at most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+DESCRIPTOR_NAMES = ("heavy_atoms", "hetero_atoms", "donors", "acceptors", "rotatable_bonds", "rings", "ring_atoms", "ring_bonds",
+                    "smallest_ring", "largest_ring", "aromatic_atoms", "aromatic_outside_ring", "sp3_carbons", "carbons", "components",
+                    "weight")                                    # the columns of mol_descriptors() (enum mdt_molr_slot)
+_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+class DescriptorLimits:
+    """Bounds on the descriptors of mol_descriptors() for ``limits=`` of the screening calls: ``DescriptorLimits(max_rings=4,
+    min_smallest_ring=5, max_rotatable_bonds=10, max_weight=500.0)``.  Every name of DESCRIPTOR_NAMES takes a ``min_<name>`` and a
+    ``max_<name>`` keyword; both ends are inclusive, an unset bound is no bound (int32 min in ``lo``, int32 max in ``hi``), any other
+    keyword raises ValueError.  The counts are ints; ``min_weight`` / ``max_weight`` are in dalton (int or float) and are handed to
+    the kernel in milli-dalton, ``int(round(1000 * x))``, compared with the integer weight of mdt_mol_rings.  ``lo`` / ``hi``: int32
+    (16,) on the host; ``on(device)`` keeps one copy per device.  Note ``min_smallest_ring=5`` also rejects a molecule without rings
+    (its smallest ring is 0): "no three- or four-membered ring, rings or not" is not one pair of bounds."""
+
+    def __init__(self, **bounds):
+        lo, hi = [_INT32_MIN] * len(DESCRIPTOR_NAMES), [_INT32_MAX] * len(DESCRIPTOR_NAMES)
+        for key, value in bounds.items():
+            side, _, name = key.partition("_")
+            if side not in ("min", "max") or name not in DESCRIPTOR_NAMES:
+                raise ValueError(f"DescriptorLimits got {key!r}; the bounds are min_<name> / max_<name> for <name> in {DESCRIPTOR_NAMES}")
+            if name == "weight":
+                if isinstance(value, bool) or not isinstance(value, (int, float)) or value != value or abs(value) > 2.0e6:
+                    raise ValueError(f"{key} must be a number of dalton in [-2e6, 2e6], got {value!r}")
+                value = int(round(1000 * value))
+            elif isinstance(value, bool) or not isinstance(value, int) or not _INT32_MIN <= value <= _INT32_MAX:
+                raise ValueError(f"{key} must be an int (a count) inside int32, got {value!r}")
+            (lo if side == "min" else hi)[DESCRIPTOR_NAMES.index(name)] = value
+        self.bounds = dict(bounds)
+        self.lo, self.hi = torch.tensor(lo, dtype=torch.int32), torch.tensor(hi, dtype=torch.int32)
+        self._on = {}
+
+    @classmethod
+    def lipinski(cls) -> "DescriptorLimits":
+        """Three of Lipinski's four rules: weight <= 500 dalton, donors <= 5 (N or O with a hydrogen), acceptors <= 10 (N + O).
+        The fourth rule, logP <= 5, is not built: there is no logP here."""
+        return cls(max_weight=500.0, max_donors=5, max_acceptors=10)
+
+    def on(self, device):
+        """(lo, hi) on ``device``, copied there once."""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = (self.lo.to(device), self.hi.to(device))
+        return self._on[device]
+
+    def __repr__(self):
+        return "DescriptorLimits(%s)" % ", ".join(f"{k}={v!r}" for k, v in self.bounds.items())
+
+
+def _limits_arg(limits, vocabulary, length: int) -> None:
+    """The refusals of ``limits=``, before anything is launched."""
+    if limits is None:
+        return
+    if not isinstance(limits, DescriptorLimits):
+        raise ValueError(f"limits must be a DescriptorLimits or None, got {type(limits).__name__}")
+    if vocabulary is None:
+        raise ValueError("limits= reads the rows as strings: give a vocabulary")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the descriptors take at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+
+
+def _rings_of(tokens, vocabulary, device):
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    *graph, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    hydrogens, _, verdict, _, _ = torch.ops.mdt.mol_hydrogens(*graph, MOLH_MAX_STEPS)
+    bond_ring, atom_ring, desc, _ = torch.ops.mdt.mol_rings(*graph, hydrogens, None, None)
+    return atom_ring, bond_ring, desc, verdict, status, position
+
+
+def mol_rings(tokens, vocabulary: "SmilesVocabulary", device):
+    """Which atoms and bonds lie in a ring, and how small is it?  -> (atom_ring int64 (R, L), bond_ring int64 (R, L), descriptors
+    int64 (R, 16), verdict int64 (R,), status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer dtype, zeros
+    anywhere.  ``status`` / ``position`` are smiles_check()'s; ``verdict`` is mol_hydrogens()'s, because donors and weight rest on
+    its hydrogens (they are defined for every verdict); atoms and bonds are indexed like mol_graph()'s.
+
+    ``bond_ring[r, e]``: the size of the smallest cycle through bond e -- 1 + the shortest path between its ends that avoids it --
+    or 0 where there is none (a bridge).  ``atom_ring[r, a]``: the smallest non-zero value over the bonds at atom a, 0 for an atom
+    in no ring.  The fusion bond of naphthalene is 6, every bond of cubane 4.  ``descriptors``: the columns of DESCRIPTOR_NAMES, see
+    mol_descriptors().  A row that is no molecule (empty, or status != 0) has all zeros.  mdt_mol_rings in include/mdt_hip.h has
+    every rule.
+    What it is NOT: not RDKit's ring info and not an SSSR (nobody lists rings; ``rings`` is the cycle rank), no envelope rings,
+    aromaticity is as written, not perceived.  L <= 64; the refusals are mol_key()'s, with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens -> mdt::mol_rings."""
+    return tuple(t.long() for t in _rings_of(tokens, vocabulary, device))
+
+
+def mol_descriptors(tokens, vocabulary: "SmilesVocabulary", device):
+    """Sixteen integer descriptors per row -> (descriptors int64 (R, 16), verdict int64 (R,), status int64 (R,), position int64
+    (R,)) for raw (R, L) ids; the columns are DESCRIPTOR_NAMES: heavy atoms (symbol not H), hetero atoms (heavy and not C, ``*``
+    counts), donors (N or O with a hydrogen), acceptors (N or O: Lipinski's N + O count), rotatable bonds (single, not in a ring,
+    both ends with at least two heavy neighbours and no triple bond; an aromatic-order bond is never rotatable, which misses the
+    axis of a biphenyl written without ``-``), rings (edges - atoms + components), ring atoms, ring bonds, smallest ring, largest
+    ring (the largest of the bonds' smallest cycles: naphthalene 6), aromatic atoms (as written), aromatic atoms outside any ring
+    (the ``cc`` that mol_hydrogens() accepts as ethene), sp3 carbons (C, not aromatic, single bonds only), carbons, components, and
+    the weight in milli-dalton (the integer masses of mdt_mol_rings; atoms of other symbols weigh 0).  ``verdict`` is
+    mol_hydrogens()'s.  No logP; not RDKit's descriptors.  The result does not depend on how a molecule is spelled.  L <= 64; the
+    refusals are mol_key()'s.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens -> mdt::mol_rings."""
+    _, _, desc, verdict, status, position = _rings_of(tokens, vocabulary, device)
+    return desc.long(), verdict.long(), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:
@@ -1940,14 +2061,14 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
     ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
-    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize``, with which the tokens go to screen_tokens_diverse instead;
+    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize`` / ``limits``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
                                          "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
-                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize"}
+                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize", "limits"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -1981,6 +2102,10 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     _kekulize_arg(kekulize, vocabulary, model.max_length)
     if kekulize:                                                 # (False: the calls made without the keyword)
         diverse, filters["kekulize"] = True, True
+    limits = screen_tokens_kwargs.pop("limits", None)
+    _limits_arg(limits, vocabulary, model.max_length)
+    if limits is not None:                                       # (None: the calls made without the keyword)
+        diverse, filters["limits"] = True, limits
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

@@ -948,6 +948,54 @@ def _(natoms, atoms, nbonds, bonds, max_steps):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# ring perception and descriptors (csrc/k_molring.hip): rows of at most 64 positions
+@custom_op("mdt::mol_rings", mutates_args=())
+def mol_rings(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, hydrogens: Tensor, lo: Optional[Tensor],
+              hi: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (bond_ring uint8 (R, L), atom_ring uint8 (R, L), descriptors int32 (R, 16), flags uint8 (R,)) of mdt_mol_rings
+    (include/mdt_hip.h) for the graph arrays of mdt::mol_graph and the hydrogens of mdt::mol_hydrogens: per bond entry and per atom
+    the size of the smallest cycle through it (0: none), per row the sixteen descriptors (enum mdt_molr_slot), and 128 where
+    ``lo`` / ``hi`` (int32 (16,), both or neither) are given and a descriptor of a molecule row lies outside them.  All zero where
+    natoms is 0 (no molecule).  Not RDKit's ring info, not an SSSR."""
+    dev = _hip(natoms, atoms, nbonds, bonds, hydrogens, lo, hi)
+    lib = rt.load_library()
+    op = "mdt::mol_rings"
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the rings take 1 to {rt.MOL_MAX_LENGTH}")
+    if hydrogens.dtype != torch.uint8 or tuple(hydrogens.shape) != (R, L):
+        raise RuntimeError(f"{op}: hydrogens must be uint8 ({R}, {L}) (as mdt::mol_hydrogens returns them)")
+    if (lo is None) != (hi is None):
+        raise RuntimeError(f"{op}: lo and hi are given together or not at all")
+    for name, t in (("lo", lo), ("hi", hi)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (rt.MOLR_DESC,)):
+            raise RuntimeError(f"{op}: {name} must be int32 ({rt.MOLR_DESC},)")
+    natoms, atoms, nbonds, bonds, hydrogens = (t.contiguous() for t in (natoms, atoms, nbonds, bonds, hydrogens))
+    lo, hi = (None, None) if lo is None else (lo.contiguous(), hi.contiguous())
+    bond_ring = torch.zeros(R, L, dtype=torch.uint8, device=dev)
+    atom_ring = torch.zeros(R, L, dtype=torch.uint8, device=dev)
+    desc = torch.zeros(R, rt.MOLR_DESC, dtype=torch.int32, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_rings(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), rt.ptr(hydrogens), L, R,
+                                       rt.ptr(lo), rt.ptr(hi), rt.ptr(bond_ring), rt.ptr(atom_ring), rt.ptr(desc), rt.ptr(flags),
+                                       rt.current_stream()))
+    return bond_ring, atom_ring, desc, flags
+
+
+@mol_rings.register_fake
+def _(natoms, atoms, nbonds, bonds, hydrogens, lo, hi):
+    R, L = atoms.shape
+    return (atoms.new_empty(R, L, dtype=torch.uint8), atoms.new_empty(R, L, dtype=torch.uint8),
+            atoms.new_empty(R, rt.MOLR_DESC, dtype=torch.int32), atoms.new_empty(R, dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between compacted id rows (csrc/k_edit.hip): at most 64 positions, ids in [0, 64)
 def _edit_rows(op, packed, length, what):
     if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:
