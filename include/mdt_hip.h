@@ -759,7 +759,8 @@ int mdt_smiles_check(const int32_t *packed, const int32_t *length, int32_t L, in
  * canonical form (none was found among 2,100 random graphs of up to 20 atoms and the 684 graphs of up to 7 nodes and degree 4; the
  * rooting is what separates cubane from cuneane, decalin from bicyclopentyl, two cyclopropanes from cyclohexane).  It is not
  * RDKit's canonical SMILES: no hydrogen or bracket normalisation ([CH4] and C differ), no aromaticity perception (C1=CC=CC=C1 and
- * c1ccccc1 differ), and stereo is ignored (F/C=C/F equals F/C=C\F).
+ * c1ccccc1 differ), and stereo is ignored (F/C=C/F equals F/C=C\F).  (mdt_mol_normalize writes graph arrays on which the first two
+ * pairs have one key.)
  * mdt_mol_key takes the graph arrays (device pointers), so the graph is computed once.  R == 0 launches nothing. */
 int mdt_mol_graph(const int32_t *packed, const int32_t *length, int32_t L, int32_t R, const uint8_t *classes,
                   const uint8_t *max_valence, const uint32_t *elements, int32_t *natoms, uint32_t *atoms, int32_t *nbonds,
@@ -797,7 +798,8 @@ int mdt_key_flags(const uint64_t *key, int32_t N, int32_t G, const uint64_t *kno
  * [1, MDT_FP_SIM_DEN]: "at least as similar as the threshold" means union > 0 && inter * 65536 >= sim_num * union (32 bits suffice).
  * What this is NOT.  It is not RDKit's Morgan or ECFP fingerprint, and bits are not comparable with either.  The round-0 invariant
  * holds no implicit hydrogens (only what the descriptor holds).  Duplicate substructures are not removed (every atom sets a bit in
- * every round).  There is no aromaticity perception (C1=CC=CC=C1 and c1ccccc1 differ) and no stereo.  Folding to 1024 bits can make
+ * every round).  There is no aromaticity perception (C1=CC=CC=C1 and c1ccccc1 differ) and no stereo.  (On the arrays of
+ * mdt_mol_normalize the two are one.)  Folding to 1024 bits can make
  * unequal environments share a bit, so unequal molecules can have similarity 1.  Equal graphs always give equal fingerprints: every
  * combination over the bonds is a sum mod 2^64 and the bit set does not depend on atom numbering.
  * fp uint64 (R,16), count int32 (R).  R == 0 launches nothing. */
@@ -983,8 +985,9 @@ int mdt_mol_hydrogens(const int32_t *natoms, const uint32_t *atoms, const int32_
  * What this is and is NOT.  Not RDKit's ring info and not an SSSR: a bond knows the smallest cycle through it, nobody lists rings,
  * and MDT_MOLR_RINGS is the cycle rank (cubane: 5, though it has six faces).  No envelope rings: the 10-ring
  * around naphthalene is nobody's smallest cycle.  No logP, so Lipinski's fourth rule is not here.  Aromaticity is as written (bit
- * 10), not perceived: C1=CC=CC=C1 has no aromatic atom.  Donors and weight rest on hydrogens as handed in.  Nothing here depends
- * on how the row is spelled but the order of the per-entry and per-atom outputs, which follow the graph row's numbering.
+ * 10), not perceived: C1=CC=CC=C1 has no aromatic atom.  (mdt_mol_normalize perceives it, and takes bond_ring from here.)  Donors
+ * and weight rest on hydrogens as handed in.  Nothing here depends on how the row is spelled but the order of the per-entry and
+ * per-atom outputs, which follow the graph row's numbering.
  * Every loop of the kernel is bounded by nbonds, natoms or both (at most nbonds searches of at most natoms levels), so there is no
  * step cap and no undecided answer.  R == 0 launches nothing.
  * Cost (131,072 mutated rows of L = 32, half of them molecules, 21 % with a ring; one MI355X, 2026-10-20): 0.0952
@@ -1000,6 +1003,61 @@ enum mdt_molr_slot {
 int mdt_mol_rings(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, const uint8_t *hydrogens,
                   int32_t L, int32_t R, const int32_t *lo, const int32_t *hi, uint8_t *bond_ring, uint8_t *atom_ring, int32_t *desc,
                   uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* The normal form of a graph row (csrc/k_molnorm.hip, csrc/mdt_molnorm.h); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* One set of graph arrays for the Kekule, the aromatic and the bracket spelling of a molecule.  mdt_mol_key, mdt_mol_fp and
+ * mdt_sub_match read the graph as written, so C1=CC=CC=C1 and c1ccccc1, [CH4] and C, and the two Kekule structures of one ring are
+ * different molecules to them.  This writes a graph in the same format -- atom and bond indices preserved, so natoms and nbonds are
+ * reused -- in which they are one, and the three consumers take it unchanged.
+ *
+ * Inputs (device pointers), R rows of width 1 <= L <= 64: natoms, atoms, nbonds, bonds of mdt_mol_graph; hydrogens, partner uint8
+ * (R,L) and verdict uint8 (R) of mdt_mol_hydrogens; bond_ring uint8 (R,L) of mdt_mol_rings, all for the same rows.
+ * Outputs, every word defined: out_atoms uint32 (R,L), out_bonds uint32 (R,L), flags uint8 (R).
+ * Rows that are not normalised.  A row that is no molecule -- natoms == 0, counts outside [0, L], a bond naming an atom >= natoms
+ * (the rule of mdt_mol_key) -- has all output words 0 and flags 0.  A row with verdict != 0 has no Kekule structure to read:
+ * atoms[0:natoms] and bonds[0:nbonds] are copied as written, zeros beyond, flags 0.
+ * A normalised row, step by step.
+ *  The Kekule view.  An entry (a, b, o) has the order k = o when o != 5.  When o == 5, k = 2 if a != b and partner[a] == 1 + b and
+ *   partner[b] == 1 + a, otherwise k = 1.
+ *  Per atom x.  g' = group - charge with the groups of mdt_mol_hydrogens' aromatic bracket atoms: B 13, C 14, N and P 15, O and S 16,
+ *   in either case; any other symbol is ineligible, '*' and every two-letter symbol included.  dbl = the entries at x with a != b
+ *   that have k == 2; sigma = the entries at x with a != b, plus hydrogens[x].  The pi electrons p(x) the atom gives to a ring:
+ *    ineligible, if any entry at x (an entry (x, x) included) has k 3 or 4, or if dbl >= 2;
+ *    dbl == 1 and that entry has bond_ring != 0: p = 1;
+ *    dbl == 1 and that entry is no ring bond: p = 0 if x is a neutral C and the other end's symbol is N, O or S (the C of an
+ *     exocyclic C=O), otherwise ineligible;
+ *    dbl == 0: p = 2 if g' == 16 and sigma == 2 or g' == 15 and sigma == 3 (the O of furan, the N of pyrrole, the C of [CH-]); p = 0
+ *     if g' == 13 and sigma == 3 (B, the C of [CH+]); otherwise ineligible.
+ *  The rings tried.  For every entry e = (a, b) with a != b, bond_ring[e] != 0 and both ends eligible: the breadth-first search of
+ *   mdt_mol_rings from a to b in the ring graph without the edge {a, b}, every atom keeping the level at which it was reached;
+ *   then two walks back from b to a, at every level to the LOWEST-numbered neighbour of that level, and again to the HIGHEST.
+ *   Each walk is a smallest cycle through e, hence chordless, kept as a 64-bit atom set; the two are equal when e lies in one
+ *   smallest cycle.  Trying both makes the set of rings tried independent of the numbering whenever a bond lies in at most two
+ *   smallest cycles, which every fusion bond of a planar ring system does.
+ *  Hueckel.  A ring is aromatic when every atom in it is eligible and the sum of p over it is 2 mod 4.  Any ring size counts.
+ *  The normal form.  An atom in some aromatic ring gets bit 10 set, every other atom gets it cleared.  An entry with both ends in
+ *   ONE aromatic ring gets order 5 (so does an entry (x, x) at an atom of it); every other entry gets its Kekule order k.  Every
+ *   atom word keeps symbol, charge and isotope as written, has the bracket bit 11 set and min(hydrogens[x], 15) in its H field.
+ *   out_bonds[e] = a | b << 8 | order << 16.  Words beyond natoms / nbonds are 0.
+ *  flags: MDT_MOLN_NORMALIZED (1) the row is normalised; MDT_MOLN_AROMATIC (2) at least one ring is aromatic; MDT_MOLN_CHANGED (4)
+ *   some aromatic bit or bond order differs from what was written.
+ * So [CH4] and C, c1ccccc1 and C1=CC=CC=C1, CC1=C(O)C=CC=C1 and CC=1C(O)=CC=CC=1 get one mdt_mol_key; the Kekule view of an aromatic
+ * row normalises to the same words, bit for bit; normalising a normal form again (hydrogens and rings computed afresh) is the
+ * identity.  Through the H field a pattern [CH4] of mdt_sub_match accepts the C of a normalised target, and [nH] the N of C1=CNC=C1.
+ * What this is and is NOT.  Not RDKit's aromaticity model.  Rings are judged one at a time, so there are no envelope rings: azulene
+ * (c1ccc2cccc2cc1: a 7-ring and a 5-ring, 10 electrons only around both) is NOT aromatic here, and RDKit says it is.  A bond in
+ * three or more equally small cycles (cubane-like) may try numbering-dependent rings.  A lower-case atom outside every perceived
+ * ring keeps the Kekule structure that mdt_mol_hydrogens found (cc comes out as C=C; c1ccc1 as one of its two structures).  No
+ * tautomers, no charge normalisation ([O-][n+]1ccccc1 stays charged), no stereo.  bond_ring is taken at its word: an entry it calls
+ * a ring bond that the search cannot close is skipped.
+ * Every loop of the kernel is bounded by nbonds or natoms (at most nbonds searches of at most natoms levels, two walks of fewer
+ * levels each), so there is no step cap and no undecided answer.  R == 0 launches nothing.  The cost is in DESIGN.md section 6. */
+enum mdt_moln_flag { MDT_MOLN_NORMALIZED = 1, MDT_MOLN_AROMATIC = 2, MDT_MOLN_CHANGED = 4 };
+int mdt_mol_normalize(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds,
+                      const uint8_t *hydrogens, const uint8_t *partner, const uint8_t *verdict, const uint8_t *bond_ring, int32_t L,
+                      int32_t R, uint32_t *out_atoms, uint32_t *out_bonds, uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

@@ -48,6 +48,7 @@ SOURCES = [
     ("k_molsub.hip", []),
     ("k_molh.hip", []),
     ("k_molring.hip", []),
+    ("k_molnorm.hip", []),
     ("mdt_api.cpp", ["-x", "hip"]),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

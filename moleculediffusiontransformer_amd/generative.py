@@ -959,12 +959,15 @@ class KnownSet:
                                 torch.from_numpy(self.lengths).to(device))
         return self._on[device]
 
-    def mol_keys(self, vocabulary: "SmilesVocabulary", device) -> Tensor:
+    def mol_keys(self, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False) -> Tensor:
         """The graph keys of the known molecules (mol_key()): int64 (M',) on ``device`` holding the uint64 bits of the sorted unique
         NON-ZERO keys of the known rows -- rows that are no molecule under ``vocabulary`` (key 0) drop out, respellings of one
         molecule count once.  Computed once by mdt::mol_graph -> mdt::mol_key and cached per (vocabulary, device).  Sorted ascending
         AS UNSIGNED, which is what mdt::key_flags' binary search needs: on int64 storage that is a signed sort of (key ^ 2^63) --
-        flipping the top bit maps unsigned order onto signed order -- flipped back afterwards.  ``width`` > 64 raises ValueError."""
+        flipping the top bit maps unsigned order onto signed order -- flipped back afterwards.  ``width`` > 64 raises ValueError.
+        ``normalize=True``: the keys of the normal forms (mol_normalize(): mdt::mol_hydrogens -> mdt::mol_rings ->
+        mdt::mol_normalize between the two launches), cached apart from the keys as written."""
+        _normalize_arg(normalize)
         if not isinstance(vocabulary, SmilesVocabulary):
             raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
         if self.width > MAX_MOL_LENGTH:
@@ -973,21 +976,23 @@ class KnownSet:
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        at = (id(vocabulary), device)
+        at = (id(vocabulary), device, normalize)
         if at not in self._mol_keys:
             _, packed, lengths = self.on(device)
-            natoms, atoms, nbonds, bonds, _, _ = torch.ops.mdt.mol_graph(packed, lengths, *vocabulary.on(device))
-            key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+            graph, _, _ = _graph_rows(packed, lengths, vocabulary, device, normalize)
+            key = torch.ops.mdt.mol_key(*graph)
             top = -2 ** 63                                                     # the bit pattern 1 << 63
             key = torch.unique(key[key != 0] ^ top) ^ top                      # unique() sorts ascending (signed)
             self._mol_keys[at] = (vocabulary, key)                             # (the vocabulary is held: its id stays its own)
         return self._mol_keys[at][1]
 
-    def fingerprints(self, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+    def fingerprints(self, vocabulary: "SmilesVocabulary", device, radius: int = 2, *, normalize: bool = False):
         """The fingerprints of the known molecules (mol_fingerprint()): (fp int64 (M, 16): the uint64 bits, count int32 (M,)) on
         ``device`` for ALL rows of ``packed``, in that order, so an index into them is an index into ``packed``.  Rows that are no
         molecule under ``vocabulary`` have an all-zero fingerprint (similarity 0 to everything).  Computed once by mdt::mol_graph ->
-        mdt::mol_fp and cached per (vocabulary, device, radius).  ``width`` > 64 raises ValueError."""
+        mdt::mol_fp and cached per (vocabulary, device, radius).  ``width`` > 64 raises ValueError.  ``normalize=True``: the
+        fingerprints of the normal forms (mol_normalize()), cached apart from those of the rows as written."""
+        _normalize_arg(normalize)
         if not isinstance(vocabulary, SmilesVocabulary):
             raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
         if self.width > MAX_MOL_LENGTH:
@@ -997,11 +1002,11 @@ class KnownSet:
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        at = (id(vocabulary), device, radius)
+        at = (id(vocabulary), device, radius, normalize)
         if at not in self._fingerprints:
             _, packed, lengths = self.on(device)
-            natoms, atoms, nbonds, bonds, _, _ = torch.ops.mdt.mol_graph(packed, lengths, *vocabulary.on(device))
-            self._fingerprints[at] = (vocabulary, torch.ops.mdt.mol_fp(natoms, atoms, nbonds, bonds, radius))
+            graph, _, _ = _graph_rows(packed, lengths, vocabulary, device, normalize)
+            self._fingerprints[at] = (vocabulary, torch.ops.mdt.mol_fp(*graph, radius))
         return self._fingerprints[at][1]
 
     def id_range(self):
@@ -1140,13 +1145,15 @@ def _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, v
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
             min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
-            fingerprint_radius=2, require=None, forbid=None, kekulize=False, limits=None) -> Screened:
+            fingerprint_radius=2, require=None, forbid=None, kekulize=False, limits=None, normalize=False) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
     with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`;
     with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in; with ``kekulize`` one mdt::mol_hydrogens on the
     same graph, right after mdt::mol_graph, ORs bit 64 in where its verdict is not 0; with ``limits`` one mdt::mol_rings after that
-    mdt::mol_hydrogens (made once when both are asked for) ORs bit 128 in where a descriptor lies outside its bounds."""
+    mdt::mol_hydrogens (made once when both are asked for) ORs bit 128 in where a descriptor lies outside its bounds; with
+    ``normalize`` one mdt::mol_normalize follows those two launches (made for it where nobody else asked) and mdt::mol_key,
+    mdt::sub_match and mdt::mol_fp read its graph, the known set's keys and fingerprints being the normalised ones."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     width = torch.as_tensor(tokens).shape[1]
@@ -1156,6 +1163,8 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     fragments = _substructure_args(require, forbid, vocabulary, width)
     _kekulize_arg(kekulize, vocabulary, width)
     _limits_arg(limits, vocabulary, width)
+    _screen_normalize_arg(normalize, vocabulary, width, identity == "graph" or sim_num is not None or known_sim_num is not None or
+                          fragments is not None)
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1172,18 +1181,23 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     if vocabulary is not None:                                   # is it a molecule at all?  bits 32 / 64, never kept
         reject, _ = torch.ops.mdt.smiles_check(packed, length, *vocabulary.on(device))
     graph = None
-    if kekulize or limits is not None:                           # the hydrogens: one launch for the Kekule check and the descriptors
-        graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
-        hydrogens, _, verdict, _, _ = torch.ops.mdt.mol_hydrogens(*graph, MOLH_MAX_STEPS)
+    if kekulize or limits is not None or normalize:              # the hydrogens: one launch for the Kekule check, the descriptors
+        graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]      # and the normal form
+        hydrogens, partner, verdict, _, _ = torch.ops.mdt.mol_hydrogens(*graph, MOLH_MAX_STEPS)
     if kekulize:                                                 # can its aromatic atoms be satisfied?  bit 64, never kept
         reject = reject | ((verdict != 0).to(torch.uint8) * rt.SCREEN_OVERVALENT)
+    if limits is not None or normalize:                          # the rings: one launch for the bounds and the normal form
+        bounds = limits.on(device) if limits is not None else (None, None)
+        bond_ring, _, _, outside = torch.ops.mdt.mol_rings(*graph, hydrogens, *bounds)
     if limits is not None:                                       # is it inside the descriptor bounds?  bit 128, never kept
-        reject = reject | torch.ops.mdt.mol_rings(*graph, hydrogens, *limits.on(device))[3]
+        reject = reject | outside                                # (the graph as written)
+    if normalize:                                                # from here on the graph is its normal form
+        graph = _normal_form(*graph, hydrogens, partner, verdict, bond_ring)[0]
     if identity == "graph":                                      # which molecule is it?  bits 4 / 8 by the graph key
         if graph is None:
             graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
         graph_key = torch.ops.mdt.mol_key(*graph)
-        known_graph = known.mol_keys(vocabulary, device) if known is not None and len(known) else None
+        known_graph = known.mol_keys(vocabulary, device, normalize=normalize) if known is not None and len(known) else None
         reject = reject | torch.ops.mdt.key_flags(graph_key, N, known_graph)
     if fragments is not None:                                    # does it contain the fragment?  bit 128, never kept
         if graph is None:
@@ -1195,7 +1209,7 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
             graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
         fp, fp_count = torch.ops.mdt.mol_fp(*graph, fingerprint_radius)
     if known_sim_num is not None:                                # bit 8 where the nearest known molecule is at least that similar
-        known_fp, _ = known.fingerprints(vocabulary, device, fingerprint_radius)
+        known_fp, _ = known.fingerprints(vocabulary, device, fingerprint_radius, normalize=normalize)
         _, inter, union = torch.ops.mdt.fp_nearest(fp, known_fp)
         near = (union > 0) & (inter.long() * FP_SIM_DEN >= known_sim_num * union.long())     # the integer rule of mdt_hip.h
         reject = reject | (near.to(torch.uint8) * rt.SCREEN_KNOWN)
@@ -1251,7 +1265,7 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
                           max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2, require=None, forbid=None,
-                          kekulize: bool = False, limits=None, **screen_tokens_kwargs) -> Screened:
+                          kekulize: bool = False, limits=None, normalize: bool = False, **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
     ``vocabulary=``, with "is it a molecule at all?" asked of every candidate.
@@ -1327,11 +1341,25 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     its bounds.  No status bit is free, so under ``limits=`` bit 128 also means "a descriptor lies outside its bounds".  Such a
     candidate is never kept and pushes nothing out.  ``DescriptorLimits.lipinski()`` is weight <= 500, donors <= 5, acceptors <=
     10.  With None the call makes exactly the launches it makes without the keyword, in the same order.
+
+    ``normalize``: True asks "which molecule is it?", "how similar?" and "does it contain the fragment?" of the NORMAL FORM of
+    every row (mol_normalize(): hydrogens folded into the atoms, aromatic rings perceived by Hueckel's count on the Kekule
+    structure), so that under ``identity="graph"`` OC1=CC=CC=C1 after c1ccccc1O gets bit 4 and a Kekule spelling of a known
+    aromatic molecule bit 8, the similarity bounds compare fingerprints of normal forms, and ``forbid=["c1ccccc1"]`` rejects
+    C1=CC=CC=C1 (aromatic fragments must then be written in lower case).  It needs a ``vocabulary``, rows of at most 64 positions
+    and at least one consumer -- ``identity="graph"``, a similarity bound, or ``require`` / ``forbid`` -- refused with ValueError
+    before anything is launched.  The launches: the one mdt::mol_graph, the one mdt::mol_hydrogens and the one mdt::mol_rings
+    that ``kekulize`` / ``limits`` also use (never a second one), then one mdt::mol_normalize, after which mdt::mol_key /
+    mdt::key_flags / mdt::sub_match / mdt::mol_fp read the normal form; the known set's keys and fingerprints are the normalised
+    ones (KnownSet.mol_keys(normalize=True) / fingerprints(normalize=True), cached).  ``limits`` still reads the graph as
+    written.  Its limits are mol_normalize()'s: not RDKit's aromaticity model, no envelope rings (azulene is not aromatic), no
+    tautomers; a row whose Kekule verdict is not 0 is read as written.  With False (the default) the call makes exactly the
+    launches it makes without the keyword, in the same order.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
                    vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
                    max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, require=require, forbid=forbid,
-                   kekulize=kekulize, limits=limits, **screen_tokens_kwargs)
+                   kekulize=kekulize, limits=limits, normalize=normalize, **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1553,7 +1581,32 @@ def mol_graph(tokens, vocabulary: "SmilesVocabulary", device):
     return natoms.long(), atoms.long() & 0xFFFFFFFF, nbonds.long(), bonds.long(), status.long(), position.long()
 
 
-def mol_key(tokens, vocabulary: "SmilesVocabulary", device):
+def _normalize_arg(normalize) -> None:
+    if not isinstance(normalize, bool):
+        raise ValueError(f"normalize must be True or False, got {normalize!r}")
+
+
+def _normal_form(natoms, atoms, nbonds, bonds, hydrogens=None, partner=None, verdict=None, bond_ring=None):
+    """The normal form of graph arrays -> ((natoms, atoms', nbonds, bonds'), flags, verdict): mdt::mol_hydrogens -> mdt::mol_rings ->
+    mdt::mol_normalize, the first two only where the caller has not made them already."""
+    if hydrogens is None:
+        hydrogens, partner, verdict, _, _ = torch.ops.mdt.mol_hydrogens(natoms, atoms, nbonds, bonds, MOLH_MAX_STEPS)
+    if bond_ring is None:
+        bond_ring = torch.ops.mdt.mol_rings(natoms, atoms, nbonds, bonds, hydrogens, None, None)[0]
+    out_atoms, out_bonds, flags = torch.ops.mdt.mol_normalize(natoms, atoms, nbonds, bonds, hydrogens, partner, verdict, bond_ring)
+    return (natoms, out_atoms, nbonds, out_bonds), flags, verdict
+
+
+def _graph_rows(packed, n, vocabulary, device, normalize=False):
+    """mdt::mol_graph on compacted rows -> ((natoms, atoms, nbonds, bonds), status, position); with ``normalize`` the graph is its
+    normal form (_normal_form), without it nothing more is launched."""
+    *graph, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    if normalize:
+        graph = _normal_form(*graph)[0]
+    return tuple(graph), status, position
+
+
+def mol_key(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False):
     """Which molecule is each row?  -> (key int64 (R,): the uint64 bits, status int64 (R,), position int64 (R,)) for raw (R, L) ids
     of any integer dtype, zeros anywhere.  ``key`` is a 64-bit key of the molecular graph behind the row (mol_graph()) that does not
     depend on how the row spells it: start atom, branch order, ring numbers (``%nn`` included), which end of a ring closure carries
@@ -1567,25 +1620,30 @@ def mol_key(tokens, vocabulary: "SmilesVocabulary", device):
     cuneane); and it is not RDKit's canonical SMILES, which the reference's callers would get (Chem.MolFromSmiles,
     generative.py:954-994).  These count as different molecules: [CH4] and C (no hydrogen or bracket normalisation);
     C1=CC=CC=C1 and c1ccccc1 (no aromaticity perception).  Stereo is ignored: F/C=C/F equals F/C=C\\F.
+    ``normalize=True`` keys the normal form of mol_normalize() instead: there [CH4] and C, C1=CC=CC=C1 and c1ccccc1, and the two
+    Kekule structures of one ring have one key (its limits are written at mol_normalize(): not RDKit's aromaticity model, no
+    envelope rings, no tautomers); a row whose mol_hydrogens() verdict is not 0 is keyed as written.
     L <= 64; the refusals are smiles_check()'s and L > 64, with ValueError before anything is launched.
-    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_key."""
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_key; with ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings ->
+    mdt::mol_normalize go between the last two, with False exactly the launches named."""
+    _normalize_arg(normalize)
     packed, n = _mol_rows(tokens, vocabulary, device)
-    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
-    key = torch.ops.mdt.mol_key(natoms, atoms, nbonds, bonds)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    key = torch.ops.mdt.mol_key(*graph)
     return key, status.long(), position.long()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # how similar are two molecules?  Tanimoto similarity of graph fingerprints (csrc/k_molfp.hip): rows of at most 64 positions
 # ----------------------------------------------------------------------------------------------------------------------
-def _fp_of(tokens, vocabulary, device, radius):
+def _fp_of(tokens, vocabulary, device, radius, normalize=False):
     packed, n = _mol_rows(tokens, vocabulary, device)
-    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
-    fp, count = torch.ops.mdt.mol_fp(natoms, atoms, nbonds, bonds, radius)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    fp, count = torch.ops.mdt.mol_fp(*graph, radius)
     return fp, count, status, position
 
 
-def mol_fingerprint(tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+def mol_fingerprint(tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2, *, normalize: bool = False):
     """A circular fingerprint of the molecule behind each row -> (fp int64 (R, 16): the uint64 bits of 1024 bits, count int64 (R,):
     the set bits, status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer dtype, zeros anywhere.  ``status`` /
     ``position`` are smiles_check()'s.  A row that is no molecule (empty, or status != 0) has an all-zero fingerprint and count 0.
@@ -1596,33 +1654,39 @@ def mol_fingerprint(tokens, vocabulary: "SmilesVocabulary", device, radius: int 
     fingerprints, whatever the spelling: OCC and CCO have one fingerprint.  What it is NOT: it is not RDKit's Morgan or ECFP
     fingerprint, and its bits compare with neither; the round-0 invariant holds no implicit hydrogens; duplicate substructures are not
     removed; there is no aromaticity perception (C1=CC=CC=C1 and c1ccccc1 differ) and no stereo; and folding to 1024 bits can make
-    unequal environments share a bit, so unequal molecules can reach similarity 1.
+    unequal environments share a bit, so unequal molecules can reach similarity 1.  ``normalize=True`` fingerprints the normal form
+    of mol_normalize() instead, in which hydrogens are folded into the atoms and aromatic rings are perceived (within its limits).
     L <= 64; the refusals are mol_key()'s and a radius outside [0, 3], with ValueError before anything is launched.
-    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp."""
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp; with ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings ->
+    mdt::mol_normalize go between the last two."""
     radius = _radius_arg(radius)
-    fp, count, status, position = _fp_of(tokens, vocabulary, device, radius)
+    _normalize_arg(normalize)
+    fp, count, status, position = _fp_of(tokens, vocabulary, device, radius, normalize)
     return fp, count.long(), status.long(), position.long()
 
 
-def tanimoto(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+def tanimoto(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2, *, normalize: bool = False):
     """How similar are the molecules of ``a_tokens`` and ``b_tokens``, row by row?  -> (similarity float32 (R,), inter int64 (R,),
     union int64 (R,)): the Tanimoto similarity of their mol_fingerprint()s, ``inter = popcount(A & B)``, ``union = |A| + |B| -
     inter``, ``similarity = inter / max(union, 1)`` computed in torch from the exact counts (compare the counts, not the floats,
     where exactness matters).  1 for two spellings of one molecule; 0 when either row is no molecule.  It is not RDKit's Morgan or
     ECFP similarity: no implicit hydrogens, no aromaticity perception, no stereo, duplicate substructures are not removed, and
     folding can make unequal molecules share bits (see mol_fingerprint()).  Both are raw (R, L) ids of the same shape, L <= 64.
+    ``normalize=True`` compares the normal forms of mol_normalize(): c1ccccc1 and C1=CC=CC=C1 then have similarity 1.
     Sequence: per side mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp, then mdt::fp_tanimoto."""
     radius = _radius_arg(radius)
+    _normalize_arg(normalize)
     a, b = _integer_ids(a_tokens, "a_tokens"), _integer_ids(b_tokens, "b_tokens")
     if tuple(a.shape) != tuple(b.shape):
         raise ValueError(f"a_tokens {tuple(a.shape)} and b_tokens {tuple(b.shape)} must have the same shape")
-    fa, fb = _fp_of(a, vocabulary, device, radius)[0], _fp_of(b, vocabulary, device, radius)[0]
+    fa, fb = _fp_of(a, vocabulary, device, radius, normalize)[0], _fp_of(b, vocabulary, device, radius, normalize)[0]
     inter, union = torch.ops.mdt.fp_tanimoto(fa, fb)
     inter, union = inter.long(), union.long()
     return inter.float() / union.clamp(min=1).float(), inter, union
 
 
-def nearest_known_tanimoto(tokens, known_tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2):
+def nearest_known_tanimoto(tokens, known_tokens, vocabulary: "SmilesVocabulary", device, radius: int = 2, *,
+                           normalize: bool = False):
     """Which known molecule is each molecule most similar to?  -> (similarity float32 (R,), index int64 (R,), inter int64 (R,),
     union int64 (R,)): the largest Tanimoto similarity (mol_fingerprint(), tanimoto()) of row r of ``tokens`` to any molecule of
     ``known_tokens`` -- a KnownSet, or raw ids, wrapped as screen_tokens does -- the LOWEST row of ``KnownSet.packed`` that attains
@@ -1631,8 +1695,9 @@ def nearest_known_tanimoto(tokens, known_tokens, vocabulary: "SmilesVocabulary",
     implicit hydrogens, no aromaticity perception, no stereo; duplicate substructures are not removed; folding can make unequal
     molecules share bits).  L <= 64 in both; an empty known set has no nearest: refused with ValueError before anything is
     launched.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_fp -> mdt::fp_nearest (the known set's fingerprints:
-    KnownSet.fingerprints(), computed once)."""
+    KnownSet.fingerprints(), computed once).  ``normalize=True`` compares normal forms (mol_normalize()) on both sides."""
     radius = _radius_arg(radius)
+    _normalize_arg(normalize)
     tok = _integer_ids(tokens, "tokens")
     length = tok.shape[1]
     if not isinstance(vocabulary, SmilesVocabulary):
@@ -1647,8 +1712,8 @@ def nearest_known_tanimoto(tokens, known_tokens, vocabulary: "SmilesVocabulary",
         raise ValueError(f"known_tokens was built for rows of {known.width} positions, tokens has {length}")
     if len(known) == 0:
         raise ValueError("known_tokens is empty: there is no nearest known molecule")
-    fp = _fp_of(tok, vocabulary, device, radius)[0]
-    known_fp, _ = known.fingerprints(vocabulary, device, radius)
+    fp = _fp_of(tok, vocabulary, device, radius, normalize)[0]
+    known_fp, _ = known.fingerprints(vocabulary, device, radius, normalize=normalize)
     index, inter, union = torch.ops.mdt.fp_nearest(fp, known_fp)
     inter, union = inter.long(), union.long()
     return inter.float() / union.clamp(min=1).float(), index.long(), inter, union
@@ -1774,11 +1839,30 @@ def has_substructure(tokens, patterns, vocabulary: "SmilesVocabulary", device):
     of small patterns and random molecules of up to 20 atoms; ``C.C.C.C.C.C.CN`` against 62 carbons and a lone N is.
     What it is NOT: not SMARTS and not RDKit's HasSubstructMatch.  There are no implicit hydrogens, so [CH4] does not accept C; no
     aromaticity perception, so c1ccccc1 is not found in C1=CC=CC=C1; no stereo, no recursive or logical atom expressions, and no
-    mapping is returned.  The fingerprint of mol_fingerprint() is no pre-filter for this: an atom's degree enters its first
+    mapping is returned.  (has_substructure_normalized() matches against the normal form of the rows, which lifts the first two.)
+    The fingerprint of mol_fingerprint() is no pre-filter for this: an atom's degree enters its first
     round, so a fragment's bits are not a subset of its host's.
     L <= 64; non-integer ids, L < 1, L > 64, a vocabulary that is no SmilesVocabulary and patterns that SubstructureSet refuses
     raise ValueError before anything is launched.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::sub_match (the
     patterns' graphs: SubstructureSet.on(), computed once)."""
+    return _has_substructure(tokens, patterns, vocabulary, device, False)
+
+
+def has_substructure_normalized(tokens, patterns, vocabulary: "SmilesVocabulary", device):
+    """has_substructure() against the NORMAL FORM of the rows (mol_normalize()) -> the same four results.  The targets are
+    normalised, the patterns are matched as written.  Every atom of a normalised target is a bracket atom with its hydrogens in
+    its H field, so the bracket pattern [CH4] now accepts C, and [nH] accepts the N of C1=CNC=C1; aromaticity is perceived, so
+    c1ccccc1 is found in C1=CC=CC=C1 and C1=CC=CC=C1 no longer is: AROMATIC FRAGMENTS MUST BE WRITTEN IN LOWER CASE, because the
+    pattern's own case and bond orders are compared with the perceived ones.  A pattern atom without brackets accepts any hydrogen
+    count, charge and isotope, as before; a bracket pattern atom wants the target's full hydrogen count ([CH3] does not accept the C
+    of methane).  A row whose mol_hydrogens() verdict is not 0 is matched as written.  The limits are mol_normalize()'s (not RDKit's
+    aromaticity model, no envelope rings) and has_substructure()'s (not SMARTS, a step cap, no stereo, no mapping).  The refusals
+    are has_substructure()'s.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens -> mdt::mol_rings ->
+    mdt::mol_normalize -> mdt::sub_match."""
+    return _has_substructure(tokens, patterns, vocabulary, device, True)
+
+
+def _has_substructure(tokens, patterns, vocabulary, device, normalize):
     tok = _integer_ids(tokens, "tokens")
     if not isinstance(vocabulary, SmilesVocabulary):
         raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
@@ -1789,8 +1873,8 @@ def has_substructure(tokens, patterns, vocabulary: "SmilesVocabulary", device):
                          "(wider rows are out of scope)")
     fragments = _substructure_set(patterns, vocabulary, "patterns")
     packed, n = _mol_rows(tok, vocabulary, device)
-    natoms, atoms, nbonds, bonds, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
-    match, undecided, _ = torch.ops.mdt.sub_match(natoms, atoms, nbonds, bonds, *fragments.on(device), 0, 0)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    match, undecided, _ = torch.ops.mdt.sub_match(*graph, *fragments.on(device), 0, 0)
     bit = torch.arange(len(fragments), device=match.device)
     spread = lambda word: ((word.long().unsqueeze(1) >> bit) & 1).bool()  # noqa: E731
     return spread(match), spread(undecided), status.long(), position.long()
@@ -1970,6 +2054,21 @@ def _limits_arg(limits, vocabulary, length: int) -> None:
                          "(wider rows are out of scope)")
 
 
+def _screen_normalize_arg(normalize, vocabulary, length: int, consumed: bool) -> None:
+    """The refusals of the screening calls' ``normalize=``, before anything is launched."""
+    _normalize_arg(normalize)
+    if not normalize:
+        return
+    if vocabulary is None:
+        raise ValueError("normalize=True reads the rows as strings: give a vocabulary")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the normal form takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    if not consumed:
+        raise ValueError('normalize=True changes what identity="graph", max_similarity / max_known_similarity and require / forbid '
+                         "read: ask for one of them")
+
+
 def _rings_of(tokens, vocabulary, device):
     packed, n = _mol_rows(tokens, vocabulary, device)
     *graph, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
@@ -2008,6 +2107,39 @@ def mol_descriptors(tokens, vocabulary: "SmilesVocabulary", device):
     refusals are mol_key()'s.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens -> mdt::mol_rings."""
     _, _, desc, verdict, status, position = _rings_of(tokens, vocabulary, device)
     return desc.long(), verdict.long(), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# one graph for the Kekule, the aromatic and the bracket spelling of a molecule: the normal form (csrc/k_molnorm.hip): rows of at
+# most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+def mol_normalize(tokens, vocabulary: "SmilesVocabulary", device):
+    """The normal form of the molecular graph behind each row -> (natoms int64 (R,), atoms int64 (R, L), nbonds int64 (R,), bonds
+    int64 (R, L), flags int64 (R,), verdict int64 (R,), status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer
+    dtype, zeros anywhere.  ``natoms`` / ``nbonds`` / ``status`` / ``position`` and the indices of atoms and bonds are mol_graph()'s,
+    ``verdict`` is mol_hydrogens()'s; ``atoms`` and ``bonds`` have mol_graph()'s format and are what mol_key(normalize=True),
+    mol_fingerprint(normalize=True) and has_substructure_normalized() read.
+
+    In the normal form every atom is a bracket atom that carries its hydrogens in its H field (at most 15), so [CH4] and C are one
+    molecule; aromaticity is perceived, not read: the Kekule structure of mol_hydrogens() replaces the aromatic bonds, every atom
+    gives 0, 1 or 2 pi electrons or is ineligible, and a smallest ring whose atoms are all eligible and give 2 mod 4 electrons
+    (Hueckel) is aromatic -- its atoms get the aromatic bit, its bonds order 5, everything else its Kekule order -- so c1ccccc1 and
+    C1=CC=CC=C1, and the two Kekule structures of any ring, are one molecule.  mdt_mol_normalize in include/mdt_hip.h has every
+    rule.  ``flags``: 1 the row is normalised, 2 it has an aromatic ring, 4 an aromatic bit or bond order differs from what was
+    written.  A row whose ``verdict`` is not 0 has no Kekule structure to read and comes back as written with flags 0; a row that is
+    no molecule (empty, or status != 0) is all zero.  The normal form does not depend on the spelling but for the numbering of atoms
+    and bonds; normalising it again changes nothing.
+    What it is NOT: not RDKit's aromaticity model.  Rings are judged one at a time, so there are no envelope rings: azulene is NOT
+    aromatic here, and RDKit says it is.  A bond in three or more equally small cycles (cubane-like) may try numbering-dependent
+    rings.  A lower-case atom outside every perceived ring keeps the Kekule structure that mol_hydrogens() found (cc becomes C=C).
+    No tautomers, no charge normalisation, no stereo.
+    L <= 64; the refusals are mol_key()'s, with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize."""
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    *graph, status, position = torch.ops.mdt.mol_graph(packed, n, *vocabulary.on(torch.device(device)))
+    (natoms, atoms, nbonds, bonds), flags, verdict = _normal_form(*graph)
+    return (natoms.long(), atoms.long() & 0xFFFFFFFF, nbonds.long(), bonds.long(), flags.long(), verdict.long(), status.long(),
+            position.long())
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -2061,14 +2193,14 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
     ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
-    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize`` / ``limits``, with which the tokens go to screen_tokens_diverse instead;
+    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize`` / ``limits`` / ``normalize``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
                                          "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
-                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize", "limits"}
+                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize", "limits", "normalize"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -2106,6 +2238,11 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     _limits_arg(limits, vocabulary, model.max_length)
     if limits is not None:                                       # (None: the calls made without the keyword)
         diverse, filters["limits"] = True, limits
+    normalize = screen_tokens_kwargs.pop("normalize", False)
+    _screen_normalize_arg(normalize, vocabulary, model.max_length, identity == "graph" or bool(fragments) or any(
+        similar.get(k) is not None for k in ("max_similarity", "max_known_similarity")))
+    if normalize:                                                # (False: the calls made without the keyword)
+        diverse, filters["normalize"] = True, True
     N, G = candidates, conditioning.shape[0]
     scale = guidance_rows(cond_scale, N, "cond_scale")
     if isinstance(scale, Tensor):

@@ -996,6 +996,52 @@ def _(natoms, atoms, nbonds, bonds, hydrogens, lo, hi):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# the normal form of a graph row (csrc/k_molnorm.hip): rows of at most 64 positions
+@custom_op("mdt::mol_normalize", mutates_args=())
+def mol_normalize(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, hydrogens: Tensor, partner: Tensor, verdict: Tensor,
+                  bond_ring: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (atoms int32 (R, L), bonds int32 (R, L), flags uint8 (R,)) of mdt_mol_normalize (include/mdt_hip.h) for the graph arrays
+    of mdt::mol_graph, the hydrogens, partner and verdict of mdt::mol_hydrogens and the bond_ring of mdt::mol_rings: graph arrays in
+    the same format, indices preserved (natoms and nbonds are reused), in which the Kekule, the aromatic and the bracket spelling of
+    a molecule are one; flags 1 normalised, 2 an aromatic ring, 4 something differs from what was written.  A row of verdict != 0
+    comes back as written, a row that is no molecule all zero, both with flags 0.  Not RDKit's aromaticity model."""
+    dev = _hip(natoms, atoms, nbonds, bonds, hydrogens, partner, verdict, bond_ring)
+    lib = rt.load_library()
+    op = "mdt::mol_normalize"
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the normal form takes 1 to {rt.MOL_MAX_LENGTH}")
+    for name, t in (("hydrogens", hydrogens), ("partner", partner)):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (R, L):
+            raise RuntimeError(f"{op}: {name} must be uint8 ({R}, {L}) (as mdt::mol_hydrogens returns it)")
+    if verdict.dtype != torch.uint8 or tuple(verdict.shape) != (R,):
+        raise RuntimeError(f"{op}: verdict must be uint8 ({R},) (as mdt::mol_hydrogens returns it)")
+    if bond_ring.dtype != torch.uint8 or tuple(bond_ring.shape) != (R, L):
+        raise RuntimeError(f"{op}: bond_ring must be uint8 ({R}, {L}) (as mdt::mol_rings returns it)")
+    natoms, atoms, nbonds, bonds, hydrogens, partner, verdict, bond_ring = (
+        t.contiguous() for t in (natoms, atoms, nbonds, bonds, hydrogens, partner, verdict, bond_ring))
+    out_atoms = torch.zeros(R, L, dtype=torch.int32, device=dev)
+    out_bonds = torch.zeros(R, L, dtype=torch.int32, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_normalize(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), rt.ptr(hydrogens),
+                                           rt.ptr(partner), rt.ptr(verdict), rt.ptr(bond_ring), L, R, rt.ptr(out_atoms),
+                                           rt.ptr(out_bonds), rt.ptr(flags), rt.current_stream()))
+    return out_atoms, out_bonds, flags
+
+
+@mol_normalize.register_fake
+def _(natoms, atoms, nbonds, bonds, hydrogens, partner, verdict, bond_ring):
+    R, L = atoms.shape
+    return (atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between compacted id rows (csrc/k_edit.hip): at most 64 positions, ids in [0, 64)
 def _edit_rows(op, packed, length, what):
     if packed.dim() != 2 or packed.dtype != torch.int32 or length.dtype != torch.int32 or length.numel() != packed.shape[0]:

@@ -57,6 +57,7 @@ SUB_MAX_PATTERNS, SUB_MAX_WIDTH, SUB_MAX_STEPS = 32, 32, 4096    # mdt_sub_match
 MOLH_MAX_STEPS, MOLH_FORMULA = 4096, 13     # mdt_mol_hydrogens: tries of a row's matching search, words of a formula row
 MOLH_OK, MOLH_AROMATIC_OVERVALENT, MOLH_NO_KEKULE, MOLH_UNDECIDED = 0, 1, 2, 3    # enum mdt_molh_verdict
 MOLR_DESC = 16                               # mdt_mol_rings: words of a descriptor row (enum mdt_molr_slot)
+MOLN_NORMALIZED, MOLN_AROMATIC, MOLN_CHANGED = 1, 2, 4    # enum mdt_moln_flag: the flags of mdt_mol_normalize
 FP_KNOWN_CHUNK = 512             # MDT_FP_KNOWN_CHUNK: known rows of one workgroup of mdt_fp_nearest
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
@@ -136,6 +137,7 @@ SYMBOLS = {
     "mdt_sub_match": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _U32, _U32, _P, _P, _P, _P]),
     "mdt_mol_hydrogens": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_rings": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mdt_mol_normalize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mdt_edit_distance_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "mdt_edit_nearest": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "mdt_timer_create": (_P, [_I]),
