@@ -46,6 +46,9 @@ int mdt_set_tuning(const char *key, int32_t value);
  * mdt_set_tuning("pair_capacity", v > 0) replaces it (tests: force chunking on a small batch; 0 = back to the device's); the
  * override is a TEST HOOK: it is refused unless the process has MDT_TEST_HOOKS=1 in its environment. */
 int32_t mdt_pair_capacity(void);
+/* Which cross-attention core a MDT_OP_TF256 launch with T tokens per sample and Tk context rows runs (the launch's own
+ * selection function, for tests): 1 = per-sample 4 x 4 MFMA blocks (T = 4), 0 = 16 x 16 tiles over the wave's 16 rows. */
+int32_t mdt_tf256_block_core(int32_t T, int32_t Tk, int32_t cross);
 /* Test hook: enqueue a kernel of n_workgroups workgroups that only HOLD compute units -- each allocates lds_bytes of LDS (<= 160
  * KiB: nothing else fits next to it) and spins for `ticks` of the 100 MHz real-time counter.  Used to break the co-residency
  * of pair-split launches on purpose (another stream holding most of the device) and check that the failure is reported.

@@ -24,6 +24,11 @@
 //
 // Ring protocol, sub-tile formats and the attention core are those of k_tblock32.hip / k_tblock_lw.hip.
 //
+// Cross-attention of 4-token samples (BLK) runs per-sample 4 x 4 blocks instead of 16 x 16 tiles over the wave's four samples:
+//   v_mfma_f32_4x4x1_16b_f32 | 16 blocks, block = lane >> 2; A: row lane & 3, B: column lane & 3, D: register r = row r, column
+//                            | lane & 3; 8.5 cycles per SIMD back to back, 12.3 on one dependent accumulator; exact fp32 (an fmaf
+//                            | chain, bitwise) -- tools/ubench/mfma4x4_probe.hip.  v_mfma_f32_16x16x4_f32: 32 / 40.
+//
 // NSPLIT = 2 (the form for batches that do not fill the chip with 32-row workgroups, e.g. 128 row blocks at B = 1024): the
 // heads / hidden chunks / to_in output chunks of a row block are split over a PAIR of workgroups, each with its own tile
 // descriptor table (tiles + hh * NT) over the shared weight stream.  Both keep the whole residual row; at the end of every
@@ -122,8 +127,17 @@ constexpr int VEC_BYTES = VEC_FLOATS * 4;
 #if MDT_RING_HALF != 0 && !defined(MDT_TUNING)
 #error "MDT_RING_HALF=1 is the A/B schedule of tuning builds: add -DMDT_TUNING"
 #endif
+// Ablation of the attention cores (tuning builds, WRONG results, timing only): bit 0 compiles out the cross-attention core (S, the
+// partial exchange's payload, softmax, P V; the K / V reads, their waits and the three barriers stay), bit 1 the self-attention
+// core -- what the arithmetic between the barriers costs, i.e. the most a cheaper core can return
+#ifndef MDT_ABL_ATTN256
+#define MDT_ABL_ATTN256 0
+#endif
+#if MDT_ABL_ATTN256 != 0 && !defined(MDT_TUNING)
+#error "MDT_ABL_ATTN256 gives wrong results: timing builds only, add -DMDT_TUNING"
+#endif
 #ifndef MDT_XH_ADDR
-#define MDT_XH_ADDR 1        // 1: whole address in the VECTOR offset (scalar offset 0), as tools/ubench/pair_handoff.hip does
+#define MDT_XH_ADDR 1       // 1: whole address in the VECTOR offset (scalar offset 0), as tools/ubench/pair_handoff.hip does
 #endif
 constexpr int AUX_ST = MDT_XH_MODE == 1 ? 17 : (MDT_XH_MODE == 3 ? 18 : (MDT_XH_MODE == 4 ? 19 : 16));   // 18 = sc1 nt, 19 = sc0 sc1 nt
 constexpr int AUX_LD = MDT_XH_MODE == 0 ? 16 : (MDT_XH_MODE == 3 ? 18 : (MDT_XH_MODE == 4 ? 19 : 17));
@@ -143,7 +157,9 @@ constexpr int STAMP_LDS = 0;
 //      sub-tile is fragments (feature tile ft, k-step st, half lo) at ft * 8192 + st * 2048 + lo * 1024, a [128][64] output
 //      sub-tile (row tile ct, k-step sp, half lo) at ct * 4096 + sp * 2048 + lo * 1024; lane (i, g) float r of a fragment =
 //      W[16 rt + i][k-slot 32 st + 8 g + 4 lo + r].  The loader waves copy such a sub-tile linearly.
-template <int NPW, int NSPLIT, bool F32>
+// BLK: the cross-attention core of 4-token samples as per-sample 4 x 4 blocks (v_mfma_f32_4x4x1_16b_f32), see the core itself;
+//      T = 4 only (tf256_block_core), every other T runs the 16 x 16 tile core.  One core per code object.
+template <int NPW, int NSPLIT, bool F32, bool BLK>
 __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   unsigned char* red_b = smem + NS * SLOT;
@@ -168,6 +184,11 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
   if (wave >= 4) {
     // ================= loader waves (k_tblock32.hip, descriptor-driven as k_tf128.hip) =================
     const int iw = wave - 4;
+    // (BLK: the loader reads its lane id from the hardware, as lane_now() below does for the compute waves.  hipcc lays this block
+    //  out BEHIND the compute waves' path, so threadIdx.x would stay live across the whole block loop for its sake -- the one
+    //  register the block-core instantiations do not have: 8 bytes of scratch per lane.  The tile-core code objects are unchanged.)
+    const int lane = BLK ? [] { int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(l)); return l; }()
+                         : (tid & 63);
     __builtin_amdgcn_s_setprio(MDT_LOADER_PRIO);
     const cu32p tiles = (cu32p)(a.tiles + (NSPLIT == 2 ? hh * NT : 0));   // kind (3 bits) | aux << 3
     const int lpP = lane >> 5;
@@ -195,7 +216,12 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         const int R = 4 * (iw + 4 * q) + (lane >> 4);
         const int Rc = min(R, kv_rows - 1);
         const int sm = min(Rc / a.Tk, a.nsamples - 1 - sample0), key = Rc % a.Tk;
-        voffKV[q] = (unsigned)(((sm * bstr + key) * a.ldkv + 4 * ((lane & 15) ^ (R & 15))) * 4);
+        // chunk swizzle of the row: R & 15 for the tile core; for the block core 2 s ^ Y(key & 3), s = sample of the wave,
+        // Y = 0, 1, 8, 9: independent of the key group (the readers' key offsets are immediates) and conflict-free for every Tk in
+        // both reads -- the K float4 of a ds_read_b128 lane group (four (s, g) quads x key & 3: a coset of {0, 3, 5, 6} ^ Y) and
+        // the V floats of a ds_read_b32 half wave (32 banks: bit 0 of g, 2 s)
+        const int swz = BLK ? (2 * ((Rc / a.Tk) & 3)) ^ ((key & 1) | ((key & 2) << 2)) : (R & 15);
+        voffKV[q] = (unsigned)(((sm * bstr + key) * a.ldkv + 4 * ((lane & 15) ^ swz)) * 4);
       }
     }
     // The loader's lambdas are inlined BEFORE anything else is done to them (always_inline): optimised on their own, with the
@@ -697,13 +723,26 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         if (jj >= k_lo && jj < k_hi) okbits |= 1u << (4 * kt + r);
       }
   };
+  // Block core (BLK): lane = 16 g + 4 s + j is query j of the wave's sample s; block s + 4 g of the 4 x 4 MFMA is (sample s, lane
+  // group g).  The sample's keys are rows R0 .. R0 + Tk - 1 of the tile, R0 = (4 rt + s) Tk; chunk c of a row sits at position
+  // c ^ 2 s ^ Y(key & 3), Y = 0, 1, 8, 9 (the loader's voffKV).  kb: the float4 of K row R0 + j (key 4 kg + j at + 1024 kg), features
+  // 32 fh + 4 g .. + 3 (the second 16-feature half: ^ 64).  vb: the float V[key 0][32 fh + 4 g + j] (key k: + 256 k, ^ 16 Y(k & 3);
+  // second half ^ 64).
+  auto cross_consts_blk = [&](int l, unsigned& kb, unsigned& vb) {
+    const int j_ = l & 3, s_ = (l >> 2) & 3, g_ = l >> 4;
+    const int R0 = (4 * rt + s_) * a.Tk;
+    const int pos = (8 * fh + g_) ^ (2 * s_);
+    kb = (unsigned)((R0 + j_) * 256 + ((pos ^ ((j_ & 1) | ((j_ & 2) << 2))) << 4));
+    vb = (unsigned)(R0 * 256 + (pos << 4) + 4 * j_);
+  };
   // The variables themselves live here; the split-bf16 instantiations ASSIGN them at every head (from the opaque lane id, so
   // that they are dead in between), the exact-fp32 ones once, now.  (No copies into per-head arrays: a register array that is
   // copied element-wise through a reference ends up in scratch memory -- 148 bytes per lane when this was tried.)
   unsigned kbits = 0, kb0 = 0, vb0[4] = {0, 0, 0, 0}, okbits = 0;
   if constexpr (F32) {
     kbits = self_mask(lane);
-    if constexpr (NPW > 0) cross_consts(lane, kb0, vb0, okbits);
+    if constexpr (NPW > 0 && BLK) cross_consts_blk(lane, kb0, vb0[0]);
+    else if constexpr (NPW > 0) cross_consts(lane, kb0, vb0, okbits);
   }
   const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
   const float t1 = a.T > 1 ? 1.f : 0.f, t2 = a.T > 2 ? 1.f : 0.f, t4 = a.T > 4 ? 1.f : 0.f, t8 = a.T > 8 ? 1.f : 0.f;
@@ -1000,6 +1039,17 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
           qT[0] += bq[0];
           qT[1] += bq[1];
         }
+#if MDT_ABL_ATTN256 & 2   // timing only: no S, no softmax, no P V; the exchange, its wait and the barrier stay
+        const f32x4 mine = qT[0] + kTt[1];
+        f32x4* redl = red + lane_now();
+        redl[wave * 64] = mine;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        MDT_BARRIER();                         // B(first output sub-tile) + partial exchange
+        const f32x4 other = redl[(wave ^ 1) * 64];
+        prefetch2(kO, slot_of(tau), 1);
+        oT[0] = (qT[1] + kTt[0]) + (vT[0] + other);
+        oT[1] = vT[1] + mine;
+#else
         f32x4 sp0 = zero4, sp1 = zero4;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1042,6 +1092,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
           oT[0] = MDT_MFMA_F32(vT[0][r], p, oT[0], 0, 0, 0);
           oT[1] = MDT_MFMA_F32(vT[1][r], p, oT[1], 0, 0, 0);
         }
+#endif
         bf16x8 oh[1], ol[1];
         {
           float v[8];
@@ -1072,7 +1123,107 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         phase(kT, IC0{}, kT, true, qT, xh, xl);
         phase(kT, IC1{}, kT, false, qT, xh + 4, xl + 4);
         MDT_BARRIER();                         // B(K tile)
+        MDT_HSTAMP();
         const unsigned char* sk = slot_of(tau);
+        if constexpr (BLK) {
+          // T = 4: a query attends to the Tk <= 12 keys of its own sample, so the 16 x 16 tiles above spend 3/4 of their MFMA
+          // cycles (32 per instruction) on entries the mask removes.  v_mfma_f32_4x4x1_16b_f32 is 16 independent 4 x 4 x 1 products
+          // (A: lane l = row l & 3 of block l >> 2, B: column l & 3, D: register r = row r, column l & 3; tools/ubench/
+          // mfma4x4_probe.hip) at a quarter of the cycles; block s + 4 g = (sample s, lane group g) takes the operands as the
+          // projections leave them: B = qT (query j, the lane group's 8 features), A = 4 keys x those features, one float4 per
+          // (key group, feature half).  The lane groups' partial scores are reduce-scattered with the permlane swaps (12 -> 3 per
+          // lane: lane group g ends with keys 4 n + 2 (g & 1) + (g >> 1)), the wave pair's halves are added through `red` in the
+          // fixed order, softmax runs on 3 scores per lane with the lane-group max / sum of the tile core, the probabilities are
+          // all-gathered (3 -> 12) and P V leaves oT in the tile core's layout: A = V[key k][feature 16 dt + 4 g + j], B = p[k].
+          constexpr int NKG = (NPW + 1) / 2;             // key groups of 4 (Tk <= 2 NPW)
+          if constexpr (!F32) cross_consts_blk(lane_now(), kb0, vb0[0]);             // per head, from the opaque lane id (see lane_now())
+          {
+            f32x4 bq[2];
+            lds_read_f4_off<0>(bq[0], bl + 256 * h); lds_read_f4_off<64>(bq[1], bl + 256 * h);
+            frag_wait<0>();
+            qT[0] += bq[0];
+            qT[1] += bq[1];
+          }
+          float4 kf[NKG][2];
+#pragma unroll
+          for (int kg = 0; kg < NKG; ++kg) {
+            kf[kg][0] = *reinterpret_cast<const float4*>(sk + kb0 + 1024 * kg);
+            kf[kg][1] = *reinterpret_cast<const float4*>(sk + (kb0 ^ 64u) + 1024 * kg);
+          }
+          f32x4 sp[NKG];
+#pragma unroll
+          for (int kg = 0; kg < NKG; ++kg) sp[kg] = zero4;
+#pragma unroll
+          for (int ft = 0; ft < 2; ++ft) {
+#pragma unroll
+            for (int kg = 0; kg < NKG; ++kg) sp[kg] = MDT_MFMA_F32_BLK(kf[kg][ft].x, qT[ft][0], sp[kg], 0, 0, 0);
+#pragma unroll
+            for (int kg = 0; kg < NKG; ++kg) sp[kg] = MDT_MFMA_F32_BLK(kf[kg][ft].y, qT[ft][1], sp[kg], 0, 0, 0);
+#pragma unroll
+            for (int kg = 0; kg < NKG; ++kg) sp[kg] = MDT_MFMA_F32_BLK(kf[kg][ft].z, qT[ft][2], sp[kg], 0, 0, 0);
+#pragma unroll
+            for (int kg = 0; kg < NKG; ++kg) sp[kg] = MDT_MFMA_F32_BLK(kf[kg][ft].w, qT[ft][3], sp[kg], 0, 0, 0);
+          }
+          // sp[kg][r] = S[key 4 kg + r][this lane's query] over the lane group's 8 features: sum over the four lane groups
+          // (the swaps are asm statements, which hipcc's hazard recogniser does not look into: the wait states between an MFMA
+          //  and a read of its result -- 5 for this 2-pass form -- are put here by hand, behind the last MFMA)
+          __builtin_amdgcn_sched_barrier(0);
+          asm volatile("s_nop 4" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          f32x4 mine = zero4;
+#pragma unroll
+          for (int kg = 0; kg < NKG; ++kg) mine[kg] = rs16_add(rs32_add(sp[kg][0], sp[kg][1]), rs32_add(sp[kg][2], sp[kg][3]));
+          f32x4* redl = red + lane_now();
+          redl[wave * 64] = mine;
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          ++tau;
+          MDT_BARRIER();                         // B(V tile) + partial exchange
+          MDT_HSTAMP();
+          const unsigned char* sv = slot_of(tau);
+          const f32x4 other = redl[(wave ^ 1) * 64];
+          const f32x4 s01 = fh ? (other + mine) : (mine + other);
+          const int lq = lane_now();
+          const int kq = 2 * ((lq >> 4) & 1) + (lq >> 5);        // this lane group's key of every key group
+          float e[NKG];
+          float mx = -INFINITY;
+#pragma unroll
+          for (int n = 0; n < NKG; ++n) {
+            e[n] = 4 * n + kq < a.Tk ? s01[n] * scale2 : -INFINITY;
+            mx = fmaxf(mx, e[n]);
+          }
+          mx = xg16_max(mx);
+          mx = xg32_max(mx);
+          float sum = 0.f;
+#pragma unroll
+          for (int n = 0; n < NKG; ++n) {
+            e[n] = __builtin_amdgcn_exp2f(e[n] - mx);
+            sum += e[n];
+          }
+          sum = xg16_add(sum);
+          sum = xg32_add(sum);
+          const float inv = __builtin_amdgcn_rcpf(sum);
+          float p[4 * NKG];
+#pragma unroll
+          for (int n = 0; n < NKG; ++n) {
+            float even, odd;
+            ag16(e[n] * inv, even, odd);                         // keys 4 n + (g >> 1) and 4 n + 2 + (g >> 1) of the lane's half
+            ag32(even, p[4 * n], p[4 * n + 1]);
+            ag32(odd, p[4 * n + 2], p[4 * n + 3]);
+          }
+          float vf[4 * NKG][2];
+#pragma unroll
+          for (int k = 0; k < 4 * NKG; ++k) {
+            const unsigned yk = 16u * ((k & 1) | ((k & 2) << 2));           // Y(k & 3) << 4
+            vf[k][0] = *reinterpret_cast<const float*>(sv + (vb0[0] ^ yk) + 256 * k);
+            vf[k][1] = *reinterpret_cast<const float*>(sv + (vb0[0] ^ yk ^ 64u) + 256 * k);
+          }
+          oT[0] = zero4; oT[1] = zero4;
+#pragma unroll
+          for (int k = 0; k < 4 * NKG; ++k) {                    // (keys >= Tk: p = 0 exactly, V rows finite -- see above)
+            oT[0] = MDT_MFMA_F32_BLK(vf[k][0], p[k], oT[0], 0, 0, 0);
+            oT[1] = MDT_MFMA_F32_BLK(vf[k][1], p[k], oT[1], 0, 0, 0);
+          }
+        } else {
         if constexpr (!F32) cross_consts(lane_now(), kb0, vb0, okbits);      // per head, from the opaque lane id (see lane_now())
         {
           f32x4 bq[2];
@@ -1088,6 +1239,31 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
           k0[kt] = *reinterpret_cast<const float4*>(sk + kb0 + 4096 * kt);
           k1[kt] = *reinterpret_cast<const float4*>(sk + (kb0 ^ 64u) + 4096 * kt);
         }
+#if MDT_ABL_ATTN256 & 1   // timing only: no S, no softmax, no P V; the K / V reads, the exchange, the waits and the barriers stay
+        f32x4* redl = red + lane_now();
+#pragma unroll
+        for (int kt = 0; kt < KTM; ++kt) {
+          st[kt] = f32x4{k0[kt].x, k0[kt].y, k1[kt].z, k1[kt].w};
+          asm volatile("" ::"v"(k0[kt].z), "v"(k0[kt].w), "v"(k1[kt].x), "v"(k1[kt].y));
+          redl[(kt * 4 + wave) * 64] = st[kt];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        ++tau;
+        MDT_BARRIER();                         // B(V tile) + partial exchange
+        const unsigned char* sv = slot_of(tau);
+        oT[0] = qT[0]; oT[1] = qT[1];
+#pragma unroll
+        for (int kt = 0; kt < KTM; ++kt) {
+          const f32x4 other = redl[(kt * 4 + (wave ^ 1)) * 64];
+          asm volatile("" ::"v"(other));
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float va = *reinterpret_cast<const float*>(sv + vb0[r] + 4096 * kt);
+            const float vb = *reinterpret_cast<const float*>(sv + (vb0[r] ^ 64u) + 4096 * kt);
+            asm volatile("" ::"v"(va), "v"(vb));
+          }
+        }
+#else
         f32x4 sp0[KTM], sp1[KTM];
 #pragma unroll
         for (int kt = 0; kt < KTM; ++kt) { sp0[kt] = zero4; sp1[kt] = zero4; }
@@ -1108,6 +1284,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         ++tau;
         MDT_BARRIER();                         // B(V tile) + partial exchange
+        MDT_HSTAMP();
         const unsigned char* sv = slot_of(tau);
         float mx = -INFINITY;
 #pragma unroll
@@ -1152,9 +1329,12 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
             oT[0] = MDT_MFMA_F32(v0[kt][r], p, oT[0], 0, 0, 0);
             oT[1] = MDT_MFMA_F32(v1[kt][r], p, oT[1], 0, 0, 0);
           }
+#endif
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // V reads complete before the slot can be refilled
         ++tau;
         MDT_BARRIER();                         // B(first output sub-tile)
+        MDT_HSTAMP();
         prefetch2(kO, slot_of(tau), 1);
         bf16x8 oh[1], ol[1];
         {
@@ -1165,6 +1345,7 @@ __global__ __launch_bounds__(512) void k_tf256(TFArgs a) {
         }
         phase(kO, IC1{}, kO, true, accT, oh, ol);
         phase(kO, IC2{}, kT, more, accT + 8, oh, ol);
+        MDT_HSTAMP();
       }
       exchange();
       next_subblock();
@@ -1295,17 +1476,17 @@ extern int g_pair_capacity_override;
 int g_pair_capacity_override = 0;     // tests (mdt_set_tuning("pair_capacity", v)): pretend the device runs only v workgroups at once
 #endif
 
-template <int NPW, int NSPLIT, bool F32>
+template <int NPW, int NSPLIT, bool F32, bool BLK>
 static hipError_t launch_tf2(const TFArgs& a, hipStream_t s) {
   const size_t smem = (size_t)NS * SLOT + RED_BYTES + 2 * VEC_BYTES + 1024 + STAMP_LDS;   // ring, S^T exchange, vectors, prefetch sink
   static DevOnce attr_once;                          // per device (mdt_kernels.h)
   if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tf256<NPW, NSPLIT, F32>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tf256<NPW, NSPLIT, F32, BLK>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(160 * 1024));
   }
   const int nrb = (a.M + 31) / 32;
   if constexpr (NSPLIT == 1) {
-    hipLaunchKernelGGL((k_tf256<NPW, NSPLIT, F32>), dim3((unsigned)nrb), dim3(512), smem, s, a);
+    hipLaunchKernelGGL((k_tf256<NPW, NSPLIT, F32, BLK>), dim3((unsigned)nrb), dim3(512), smem, s, a);
     return hipGetLastError();
   } else {
     // The two workgroups of a pair spin on each other's flag, so BOTH must be resident at the same time: a launch may not hold
@@ -1322,7 +1503,7 @@ static hipError_t launch_tf2(const TFArgs& a, hipStream_t s) {
     if (cap_of[dev] == 0) {
       int cus = 0, per_cu = 0;
       if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return hipErrorInvalidDevice;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_tf256<NPW, NSPLIT, F32>), 512, smem) != hipSuccess)
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_tf256<NPW, NSPLIT, F32, BLK>), 512, smem) != hipSuccess)
         return hipErrorInvalidValue;
       cap_of[dev] = cus * per_cu > 0 ? cus * per_cu : -1;
     }
@@ -1334,7 +1515,7 @@ static hipError_t launch_tf2(const TFArgs& a, hipStream_t s) {
       TFArgs b = a;
       b.rb_base = g0 * S;
       const int ng = ngroups - g0 < groups_fit ? ngroups - g0 : groups_fit;
-      hipLaunchKernelGGL((k_tf256<NPW, NSPLIT, F32>), dim3(2u * (unsigned)S * (unsigned)ng), dim3(512), smem, s, b);
+      hipLaunchKernelGGL((k_tf256<NPW, NSPLIT, F32, BLK>), dim3(2u * (unsigned)S * (unsigned)ng), dim3(512), smem, s, b);
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
@@ -1346,14 +1527,26 @@ template <int NSPLIT>
 static hipError_t launch_tf256_n(const TFArgs& a, hipStream_t s) {
   constexpr bool kF32 = MDT_TF_F32 != 0;
   const bool cross = a.kv != nullptr;
-  if (!cross) return launch_tf2<0, NSPLIT, kF32>(a, s);
-  switch (((32 / a.T) * a.Tk + 15) / 16) {
-    case 1: return launch_tf2<1, NSPLIT, kF32>(a, s);
-    case 2: return launch_tf2<2, NSPLIT, kF32>(a, s);
-    case 3: return launch_tf2<3, NSPLIT, kF32>(a, s);
-    case 4: return launch_tf2<4, NSPLIT, kF32>(a, s);
-    case 5: return launch_tf2<5, NSPLIT, kF32>(a, s);
-    case 6: return launch_tf2<6, NSPLIT, kF32>(a, s);
+  if (!cross) return launch_tf2<0, NSPLIT, kF32, false>(a, s);
+  const int npw = ((32 / a.T) * a.Tk + 15) / 16;
+  if (tf256_block_core(a.T, a.Tk, cross)) {            // T = 4: 8 samples per workgroup, NPW = ceil(Tk / 2)
+    switch (npw) {
+      case 1: return launch_tf2<1, NSPLIT, kF32, true>(a, s);
+      case 2: return launch_tf2<2, NSPLIT, kF32, true>(a, s);
+      case 3: return launch_tf2<3, NSPLIT, kF32, true>(a, s);
+      case 4: return launch_tf2<4, NSPLIT, kF32, true>(a, s);
+      case 5: return launch_tf2<5, NSPLIT, kF32, true>(a, s);
+      case 6: return launch_tf2<6, NSPLIT, kF32, true>(a, s);
+      default: return hipErrorInvalidValue;
+    }
+  }
+  switch (npw) {
+    case 1: return launch_tf2<1, NSPLIT, kF32, false>(a, s);
+    case 2: return launch_tf2<2, NSPLIT, kF32, false>(a, s);
+    case 3: return launch_tf2<3, NSPLIT, kF32, false>(a, s);
+    case 4: return launch_tf2<4, NSPLIT, kF32, false>(a, s);
+    case 5: return launch_tf2<5, NSPLIT, kF32, false>(a, s);
+    case 6: return launch_tf2<6, NSPLIT, kF32, false>(a, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1368,10 +1561,14 @@ int tf256_pair_capacity() {
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   const size_t smem = (size_t)NS * SLOT + RED_BYTES + 2 * VEC_BYTES + 1024 + STAMP_LDS;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tf256<6, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_tf256<6, 2, false>), 512, smem) != hipSuccess) return 0;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tf256<6, 2, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_tf256<6, 2, false, false>), 512, smem) != hipSuccess) return 0;
   return cus * per_cu;
 }
+
+// the cross-attention core of a launch: true = per-sample 4 x 4 blocks (4-token samples; Tk <= 12 follows from tf256_supported),
+// false = 16 x 16 tiles over the wave's 16 rows.  Self-attention runs the tile core at every T.
+bool tf256_block_core(int T, int Tk, bool cross) { return cross && T == 4 && Tk >= 1 && Tk <= 12; }
 
 bool tf256_supported(int T, int Tk, int nheads, int nff, bool cross) {
   if (T <= 0 || 16 % T || nheads != 8 || nff != 8) return false;        // vectors: [bq 512 | bo 256] / [b1 512 | b2 256]

@@ -72,6 +72,7 @@ int mdt_set_tuning(const char* key, int32_t value) {
 }
 const char* mdt_last_error(void) { return g_err.c_str(); }
 int32_t mdt_pair_capacity(void) { return mdt::tf256_pair_capacity(); }
+int32_t mdt_tf256_block_core(int32_t T, int32_t Tk, int32_t cross) { return mdt::tf256_block_core(T, Tk, cross != 0) ? 1 : 0; }
 int mdt_test_occupy(int32_t n_workgroups, int32_t lds_bytes, uint64_t ticks, void* stream) {
   if (!test_hooks_enabled()) return fail("mdt_test_occupy: a test hook, needs MDT_TEST_HOOKS=1 in the environment");
   if (n_workgroups <= 0 || n_workgroups > 4096 || lds_bytes < 0 || lds_bytes > 160 * 1024) return fail("mdt_test_occupy: bad arguments");

@@ -11,6 +11,7 @@
 
 #define MDT_MFMA_BF16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define MDT_MFMA_F32 __builtin_amdgcn_mfma_f32_16x16x4f32
+#define MDT_MFMA_F32_BLK __builtin_amdgcn_mfma_f32_4x4x1f32   // 16 independent 4 x 4 x 1 blocks (block = lane >> 2), same exact fp32 products
 
 // ring slot of tile t (run-time t; NS = the including file's slot count, a power of two): a mask, not the signed modulo
 // (7 scalar instructions per use)
@@ -51,6 +52,26 @@ MDT_XG(xg32_add, "v_permlane32_swap_b32", a + b)
 MDT_XG(xg16_max, "v_permlane16_swap_b32", fmaxf(a, b))
 MDT_XG(xg32_max, "v_permlane32_swap_b32", fmaxf(a, b))
 #undef MDT_XG
+
+// The same swaps fed TWO values: a reduce-scatter step (each half of the lane pair keeps the sum of one value) and an all-gather
+// step (both lanes of the pair get both values, in the pair's order).  v_permlane32_swap_b32 a, b exchanges lanes 32-63 of a with
+// lanes 0-31 of b; v_permlane16_swap_b32 the odd 16-lane rows of a with the even rows of b.
+__device__ __forceinline__ float rs32_add(float x, float y) {   // lanes 0-31: x + (x of lane + 32); lanes 32-63: (y of lane - 32) + y
+  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+  return x + y;
+}
+__device__ __forceinline__ float rs16_add(float x, float y) {   // even rows: x + (x of lane + 16); odd rows: (y of lane - 16) + y
+  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+  return x + y;
+}
+__device__ __forceinline__ void ag32(float v, float& lo, float& hi) {       // lo / hi: v of the pair's lane in lanes 0-31 / 32-63
+  lo = v; hi = v;
+  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
+}
+__device__ __forceinline__ void ag16(float v, float& even, float& odd) {    // even / odd: v of the pair's lane in the even / odd row
+  even = v; odd = v;
+  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(even), "+v"(odd));
+}
 
 __device__ __forceinline__ float gelu(float x) {   // exact-erf GELU, branch-free erf (A&S 7.1.26, |error| < 1.5e-7)
   const float z = fabsf(x) * 0.70710678118654752440f;

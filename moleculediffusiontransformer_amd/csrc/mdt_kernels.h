@@ -345,6 +345,7 @@ hipError_t launch_tf128_f32(const TFArgs& a, hipStream_t s);    // the exact-fp3
 // sub-block's vectors) | aux << 3; every sub-block is followed by two scratch tiles; vectors are 768 floats per sub-block
 // ([bq 512 | bo 256], [b1 512 | b2 256], to_in: [bias 256]); npost = 8 sub-tiles.
 bool tf256_supported(int T, int Tk, int nheads, int nff, bool cross);
+bool tf256_block_core(int T, int Tk, bool cross);   // cross-attention core of the launch: per-sample 4 x 4 MFMA blocks (T = 4) or 16 x 16 tiles
 hipError_t launch_tf256(const TFArgs& a, hipStream_t s);
 hipError_t launch_tf256_f32(const TFArgs& a, hipStream_t s);
 // MDT_OP_RES256 (k_res256.hip): a chain of ResnetBlock1d blocks of a 256-channel level in one launch; TFArgs fields as the ResNet

@@ -86,6 +86,7 @@ SYMBOLS = {
     "mdt_last_error": (C.c_char_p, []),
     "mdt_set_tuning": (_I, [C.c_char_p, _I]),
     "mdt_pair_capacity": (_I, []),
+    "mdt_tf256_block_core": (_I, [_I, _I, _I]),
     "mdt_test_occupy": (_I, [_I, _I, _U64, _P]),
     "mdt_program_create": (_P, [C.POINTER(MdtOp), _I]),
     "mdt_program_destroy": (None, [_P]),
