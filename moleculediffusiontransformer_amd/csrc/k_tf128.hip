@@ -65,6 +65,56 @@ constexpr int NST = C / 32;     // k-steps of a projection
 constexpr int NCT = C / 16;     // 16-row tiles of the output projection
 constexpr int NU = 8;           // units (4 fragment reads + 6 MFMAs) per tile, all three kinds
 
+// The attention core of one head on split-bf16 products (F32 = false): a wave's 16-row tile against its 16 key rows, 64 features.
+// q, k, v come out of split-bf16 projections (or, cross-attention, from the hoisted K / V rows) and the mode's rule holds for the
+// core as for every other product: a b = a_hi b_hi + a_hi b_lo + a_lo b_hi, accumulated in fp32.  No lane movement: qT / kTt hold
+// features 16 ft + 4 g + r of row i in BOTH operands, so registers ft = 2 sp, 2 sp + 1 are the 8 k-slots of 16x16x32 step sp (any
+// feature-to-slot map is valid that both operands share); vT[dt][0..3] and the lane's four probabilities (keys 4 g + r) are the 4
+// k-slots of the 16-key MFMA.  Against the exact form (32 x v_mfma_f32_16x16x4_f32, 32 cycles each): 6 + 12 MFMAs of 16 cycles.
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 mfma_k16(const bf16x4& a, const bf16x4& b, const f32x4& c) {
+  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+}
+// S^T[key 4 g + r][query i] = sum over 64 features of k q
+__device__ __forceinline__ f32x4 scores_split(const f32x4* kf, const f32x4* qf) {
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int sp = 0; sp < 2; ++sp) {
+    float kv[8], qv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      kv[e] = kf[2 * sp + (e >> 2)][e & 3];
+      qv[e] = qf[2 * sp + (e >> 2)][e & 3];
+    }
+    bf16x8 kh, kl, qh, ql;
+    split8<false>(kv, kh, kl);
+    split8<false>(qv, qh, ql);
+    s = MDT_MFMA_BF16(kl, qh, s, 0, 0, 0);
+    s = MDT_MFMA_BF16(kh, ql, s, 0, 0, 0);
+    s = MDT_MFMA_BF16(kh, qh, s, 0, 0, 0);
+  }
+  return s;
+}
+__device__ __forceinline__ void split_v(const f32x4* vT, bf16x4* vh, bf16x4* vl) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const float v[4] = {vT[dt][0], vT[dt][1], vT[dt][2], vT[dt][3]};
+    split4(v, vh[dt], vl[dt]);
+  }
+}
+// O^T[feature 16 dt + 4 g + r][query i] = sum over the 16 keys of v p
+__device__ __forceinline__ void pv_split(const bf16x4* vh, const bf16x4* vl, const float p[4], f32x4* oT) {
+  bf16x4 ph, pl;
+  split4(p, ph, pl);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oT[dt] = mfma_k16(vl[dt], ph, zero);   // product-major: no MFMA waits for the one before it
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oT[dt] = mfma_k16(vh[dt], pl, oT[dt]);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oT[dt] = mfma_k16(vh[dt], ph, oT[dt]);
+}
+
 }  // namespace
 
 // NPW: LDS-DMA pieces per loader wave per K / V tile = ceil(context rows of the workgroup / 16); 0 = no cross segment
@@ -691,18 +741,24 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
         for (int dt = 0; dt < 4; ++dt) oT[dt] = qT[dt] + kTt[dt] + vT[dt];
 #else
         f32x4 s0 = zero4, s1 = zero4;
+        bf16x4 vh[4], vl[4];
+        if constexpr (F32) {
 #pragma unroll
-        for (int ft = 0; ft < 4; ++ft) {
-          s0 = MDT_MFMA_F32(kTt[ft][0], qT[ft][0], s0, 0, 0, 0);
-          s1 = MDT_MFMA_F32(kTt[ft][1], qT[ft][1], s1, 0, 0, 0);
-          s0 = MDT_MFMA_F32(kTt[ft][2], qT[ft][2], s0, 0, 0, 0);
-          s1 = MDT_MFMA_F32(kTt[ft][3], qT[ft][3], s1, 0, 0, 0);
+          for (int ft = 0; ft < 4; ++ft) {
+            s0 = MDT_MFMA_F32(kTt[ft][0], qT[ft][0], s0, 0, 0, 0);
+            s1 = MDT_MFMA_F32(kTt[ft][1], qT[ft][1], s1, 0, 0, 0);
+            s0 = MDT_MFMA_F32(kTt[ft][2], qT[ft][2], s0, 0, 0, 0);
+            s1 = MDT_MFMA_F32(kTt[ft][3], qT[ft][3], s1, 0, 0, 0);
+          }
+        } else {
+          s0 = scores_split(kTt, qT);
+          split_v(vT, vh, vl);                         // beside the S MFMAs
         }
         f32x4 st;
         float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                  // key token 4 g + r (within the wave's 16 rows)
-          const float sv = (s0[r] + s1[r]) * scale2 + kmask[r];
+          const float sv = (F32 ? s0[r] + s1[r] : s0[r]) * scale2 + kmask[r];
           st[r] = sv;
           mx = fmaxf(mx, sv);
         }
@@ -718,13 +774,18 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
         sum = xg16_add(sum);
         sum = xg32_add(sum);
         const float inv = __builtin_amdgcn_rcpf(sum);
+        if constexpr (F32) {
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) oT[dt] = zero4;
+          for (int dt = 0; dt < 4; ++dt) oT[dt] = zero4;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = st[r] * inv;
+          for (int r = 0; r < 4; ++r) {
+            const float p = st[r] * inv;
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) oT[dt] = MDT_MFMA_F32(vT[dt][r], p, oT[dt], 0, 0, 0);
+            for (int dt = 0; dt < 4; ++dt) oT[dt] = MDT_MFMA_F32(vT[dt][r], p, oT[dt], 0, 0, 0);
+          }
+        } else {
+          const float p[4] = {st[0] * inv, st[1] * inv, st[2] * inv, st[3] * inv};
+          pv_split(vh, vl, p, oT);
         }
 #endif
         bf16x8 oh[2], ol[2];
@@ -765,13 +826,22 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
           for (int ft = 0; ft < 4; ++ft) qT[ft] += bq[ft];
         }
         f32x4 s0 = zero4, s1 = zero4;
+#ifndef MDT_ABL_ATTNX
+        if constexpr (F32) {
 #pragma unroll
-        for (int ft = 0; ft < 4; ++ft) {
-          s0 = MDT_MFMA_F32(kk[ft].x, qT[ft][0], s0, 0, 0, 0);
-          s1 = MDT_MFMA_F32(kk[ft].y, qT[ft][1], s1, 0, 0, 0);
-          s0 = MDT_MFMA_F32(kk[ft].z, qT[ft][2], s0, 0, 0, 0);
-          s1 = MDT_MFMA_F32(kk[ft].w, qT[ft][3], s1, 0, 0, 0);
+          for (int ft = 0; ft < 4; ++ft) {
+            s0 = MDT_MFMA_F32(kk[ft].x, qT[ft][0], s0, 0, 0, 0);
+            s1 = MDT_MFMA_F32(kk[ft].y, qT[ft][1], s1, 0, 0, 0);
+            s0 = MDT_MFMA_F32(kk[ft].z, qT[ft][2], s0, 0, 0, 0);
+            s1 = MDT_MFMA_F32(kk[ft].w, qT[ft][3], s1, 0, 0, 0);
+          }
+        } else {
+          f32x4 kf[4];
+#pragma unroll
+          for (int ft = 0; ft < 4; ++ft) kf[ft] = f32x4{kk[ft].x, kk[ft].y, kk[ft].z, kk[ft].w};
+          s0 = scores_split(kf, qT);
         }
+#endif
         ++tau;
         __builtin_amdgcn_s_barrier();                  // B(V tile)
         const unsigned char* sv = slot_of(tau);
@@ -781,11 +851,18 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             vT[dt][r] = *reinterpret_cast<const float*>(sv + aV[r] + (((4 * dt + (i >> 2)) ^ xV[r]) << 4));
+#ifdef MDT_ABL_ATTNX   // timing experiment only (wrong results): the attention core of cross-attention (S, softmax, P V) skipped;
+                       // the K / V reads, their waits and the three barriers stay
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) oT[dt] = qT[dt] + f32x4{kk[dt].x, kk[dt].y, kk[dt].z, kk[dt].w} + vT[dt] + s0 + s1;
+#else
+        bf16x4 vh[4], vl[4];
+        if constexpr (!F32) split_v(vT, vh, vl);
         f32x4 st;
         float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float sv2 = kok[r] ? (s0[r] + s1[r]) * scale2 : -INFINITY;
+          const float sv2 = kok[r] ? (F32 ? s0[r] + s1[r] : s0[r]) * scale2 : -INFINITY;
           st[r] = sv2;
           mx = fmaxf(mx, sv2);
         }
@@ -801,14 +878,20 @@ __global__ __launch_bounds__(512) void k_tf128(TFArgs a) {
         sum = xg16_add(sum);
         sum = xg32_add(sum);
         const float inv = __builtin_amdgcn_rcpf(sum);
+        if constexpr (F32) {
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) oT[dt] = zero4;
+          for (int dt = 0; dt < 4; ++dt) oT[dt] = zero4;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = st[r] * inv;
+          for (int r = 0; r < 4; ++r) {
+            const float p = st[r] * inv;
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) oT[dt] = MDT_MFMA_F32(vT[dt][r], p, oT[dt], 0, 0, 0);
+            for (int dt = 0; dt < 4; ++dt) oT[dt] = MDT_MFMA_F32(vT[dt][r], p, oT[dt], 0, 0, 0);
+          }
+        } else {
+          const float p[4] = {st[0] * inv, st[1] * inv, st[2] * inv, st[3] * inv};
+          pv_split(vh, vl, p, oT);
         }
+#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the V reads are complete before the slot can be refilled
         ++tau;
         __builtin_amdgcn_s_barrier();                  // B(output tile)

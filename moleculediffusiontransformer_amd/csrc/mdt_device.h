@@ -85,6 +85,19 @@ __device__ __forceinline__ float gelu(float x) {   // exact-erf GELU, branch-fre
 // v_rcp / __expf form)
 __device__ __forceinline__ float silu_exact(float x) { return x / (1.0f + expf(-x)); }
 
+// Two values -> their packed bf16 hi halves and packed bf16 lo halves (v = hi + lo to 2^-17), both rounded to nearest: one
+// v_cvt_pk_bf16_f32 for the pair's hi, a shift and a mask to widen them back, two subtractions, one v_cvt_pk_bf16_f32 for the lo --
+// 6 VALU instructions per pair (5 where the compiler packs the subtractions).  Written pairwise on purpose: from the per-element
+// form `h = (__bf16)v; lo = (__bf16)(v - (float)h)` hipcc 7.2 converts about a third of the values twice (once alone for the
+// subtraction, once packed for the operand), 8 instructions per pair.  Same roundings, same bits.
+__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
+  const float la = a - __uint_as_float(hi << 16), lb = b - __uint_as_float(hi & 0xffff0000u);
+  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{la, lb}, bf16x2));
+}
+
 // 8 values of one k-step -> the two 128-bit operand registers of the step.  Split-bf16 products (F32 = false): bf16 hi plane /
 // lo plane (v = hi + lo to 2^-17).  Exact fp32 products (F32 = true): the values themselves, slots e = 0..3 in `hi`, 4..7 in
 // `lo` (bit casts: the operand arrays keep one type for both instantiations; an fp32 k-step is eight 16x16x4 MFMAs, slot
@@ -95,23 +108,33 @@ __device__ __forceinline__ void split8(const float v[8], bf16x8& hi, bf16x8& lo)
     hi = __builtin_bit_cast(bf16x8, f32x4{v[0], v[1], v[2], v[3]});
     lo = __builtin_bit_cast(bf16x8, f32x4{v[4], v[5], v[6], v[7]});
   } else {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 h, l;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 h = (__bf16)v[e];
-      hi[e] = h;
-      lo[e] = (__bf16)(v[e] - (float)h);
+    for (int p = 0; p < 4; ++p) {
+      unsigned hh, ll;
+      split2(v[2 * p], v[2 * p + 1], hh, ll);
+      h[p] = hh;
+      l[p] = ll;
     }
+    hi = __builtin_bit_cast(bf16x8, h);
+    lo = __builtin_bit_cast(bf16x8, l);
   }
 }
 
-// 4 values -> their bf16 hi / lo planes (8-byte LDS writes of an activation row)
+// 4 values -> their bf16 hi / lo planes (8-byte LDS writes of an activation row; the 4 k-slots of a 16-key MFMA operand)
 __device__ __forceinline__ void split4(const float v[4], bf16x4& hi, bf16x4& lo) {
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  u32x2 h, l;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const __bf16 h = (__bf16)v[e];
-    hi[e] = h;
-    lo[e] = (__bf16)(v[e] - (float)h);
+  for (int p = 0; p < 2; ++p) {
+    unsigned hh, ll;
+    split2(v[2 * p], v[2 * p + 1], hh, ll);
+    h[p] = hh;
+    l[p] = ll;
   }
+  hi = __builtin_bit_cast(bf16x4, h);
+  lo = __builtin_bit_cast(bf16x4, l);
 }
 
 __device__ __forceinline__ unsigned lds_addr(const unsigned char* p) {

@@ -9,7 +9,7 @@
 // identifies itself: mdt_abi_version() carries MDT_ABI_TUNING_BIT, which runtime.load_library() refuses unless the caller
 // (a tool under tools/) sets MDT_ALLOW_TUNING=1 -- a timing-only library cannot be loaded for real sampling by accident.
 #if (defined(MDT_ABL_BAR) || defined(MDT_ABL_VMWAIT) || defined(MDT_ABL_LGKM) || defined(MDT_ABL_LDSBC) || defined(MDT_ABL_GELU) ||     \
-     defined(MDT_ABL_ATTN) || defined(MDT_RING_NODRAIN) || defined(MDT_STAGGER) || defined(MDT_XH_D2) ||                               \
+     defined(MDT_ABL_ATTN) || defined(MDT_ABL_ATTNX) || defined(MDT_RING_NODRAIN) || defined(MDT_STAGGER) || defined(MDT_XH_D2) ||                               \
      (defined(MDT_XH_ADDR) && MDT_XH_ADDR == 0) || (defined(MDT_XH_MODE) && MDT_XH_MODE != 0)) &&                                       \
     !defined(MDT_TUNING)
 #error "MDT_ABL_* / MDT_RING_NODRAIN / MDT_STAGGER / MDT_XH_D2 / MDT_XH_ADDR=0 / MDT_XH_MODE!=0 give wrong results: timing builds only, add -DMDT_TUNING"
