@@ -1063,6 +1063,73 @@ int mdt_mol_normalize(const int32_t *natoms, const uint32_t *atoms, const int32_
                       int32_t R, uint32_t *out_atoms, uint32_t *out_bonds, uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* The scaffold of a graph row (csrc/k_molscaf.hip, csrc/mdt_molscaf.h, csrc/k_screen.hip); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* Which ring framework is the molecule built on?  The layers above say which molecule a row is, how similar two are and what rings
+ * one has; none says that two molecules are the same ring system with different side chains.  This is a precisely defined answer
+ * in the spirit of Bemis and Murcko's frameworks (rings plus the linkers between them): a second set of graph arrays, in the format
+ * of mdt_mol_graph, that holds the scaffold alone and that mdt_mol_key takes unchanged.
+ *
+ * Inputs (device pointers), R rows of width 1 <= L <= 64: natoms, atoms, nbonds, bonds of mdt_mol_graph or of mdt_mol_normalize.
+ * mode: bit 0 MDT_MOLS_EXOCYCLIC (1), bit 1 MDT_MOLS_GENERIC (2); any other bit is refused before any launch.
+ * Outputs, every word defined: out_natoms int32 (R), out_atoms uint32 (R,L), out_nbonds int32 (R), out_bonds uint32 (R,L),
+ * atom_map uint8 (R,L), flags uint8 (R).
+ * No molecule.  A row that is no molecule -- natoms == 0, a count outside [0, L], a bond naming an atom >= natoms (the rule of
+ * mdt_mol_key) -- has every output word 0 and flag 0.
+ * The ring graph is mdt_mol_rings': the distinct unordered pairs {a, b}, a != b, named by at least one entry, whatever the order;
+ * entries listed twice collapse to one edge, an entry (a, a) is never an edge.
+ * The core S.  Start from all atoms; in rounds, remove at once every atom with at most one neighbour among the atoms still present,
+ *  until a round removes none.  What is left is the 2-core of the ring graph; it does not depend on the numbering.  It is the atoms
+ *  on a cycle or on a path between two cycles: the rings plus the linkers, over all components.  At most ceil(n / 2) rounds remove
+ *  an atom when S comes out empty (every tree loses two leaves a round), and fewer than n in any case (a tail on a ring loses one
+ *  atom a round).
+ * The exocyclic atoms X exist only with MDT_MOLS_EXOCYCLIC: the atoms x not in S with at least one entry (a, b, o), a != b, o == 2,
+ *  whose other end is in S.  Such an x has exactly one neighbour in S and none in X, or it would be in the core.  One pass, no
+ *  recursion: the =O of a ring C(=O) is kept, what hangs on it is not.  Kept = S with X; without the bit Kept = S.  If S is empty
+ *  nothing is kept.
+ * Kept entries: every entry with a != b and both ends kept, in its original relative order and orientation.  Entries (a, a) are
+ *  dropped.
+ * Renumbering: the new index x' of a kept atom x is the number of kept atoms below x.  out_bonds[e'] = a' | b' << 8 | o << 16.
+ *  out_natoms / out_nbonds are the kept counts; words beyond them are 0.
+ * Atom words.  Without MDT_MOLS_GENERIC an atom's word stays as written, with one exception: a bracket atom (bit 11) has its H
+ *  field (bits 17..20) set to min(15, H + the sum of w(o)) over the entries at x with a != b whose other end is not kept, w(o) = o
+ *  for 1 <= o <= 4 and 1 otherwise; an entry listed twice counts twice.  An unbracketed atom is unchanged, because its hydrogens
+ *  are implicit.  The H rule is what lets scaffolds be compared on the normal form: the [c] of a normalised toluene becomes [cH], as
+ *  in a normalised benzene.  With MDT_MOLS_GENERIC every kept atom's word is the word mdt_mol_graph writes for an unbracketed C,
+ *  and every kept entry has order 1.
+ * atom_map[x]: 1 + x' for a kept atom, 0 otherwise and beyond natoms.
+ * flags: MDT_MOLS_MOLECULE (1) the row is a molecule; MDT_MOLS_SCAFFOLD (2) out_natoms > 0; MDT_MOLS_WHOLE (4) out_natoms ==
+ *  natoms, nothing was pruned.
+ * What this is and is NOT.  Not RDKit's MurckoScaffold.  Aromaticity and hydrogens are as handed in: nothing is perceived here, so
+ * scaffolds of the rows as written compare spellings (c1ccccc1 and C1=CC=CC=C1 differ), scaffolds of normal forms compare
+ * molecules.  With MDT_MOLS_EXOCYCLIC clear a ring C(=O) loses its O and gains two H when bracketed; on a normal form that can leave
+ * an aromatic atom with an odd H count.  Stereo is ignored.  An acyclic molecule has NO scaffold: all zero, mdt_mol_key 0.
+ * Applying it again with the same mode is the identity, bit for bit, in modes 0, 1 and 2; in mode 3 it is not: GENERIC rewrites the
+ * exocyclic order, so a second pass drops X.  "Scaffold of the normal form" equals "normal form of the scaffold's own spelling" on
+ * the hand table of the tests; it is not promised in general.
+ * Every loop of the kernel is bounded by nbonds or natoms (two passes over the entries, at most natoms rounds of one ballot each),
+ * so there is no step cap and no undecided answer.  R == 0 launches nothing and reads nothing.
+ * Cost (131,072 mutated rows of L = 32, half of them molecules, 21 % with a scaffold; one MI355X, 2026-10-21, the
+ * tree of the commit that adds k_molscaf.hip): 0.0620 ms a call beside 0.0956 ms for mdt_mol_rings on the same rows; the estimate
+ * written before the first run (instruction issue, 2.2 peel rounds a molecule row) said 0.0307 ms: ratio 2.02. */
+enum mdt_mols_mode { MDT_MOLS_EXOCYCLIC = 1, MDT_MOLS_GENERIC = 2 };
+enum mdt_mols_flag { MDT_MOLS_MOLECULE = 1, MDT_MOLS_SCAFFOLD = 2, MDT_MOLS_WHOLE = 4 };
+int mdt_mol_scaffold(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L,
+                     int32_t R, int32_t mode, int32_t *out_natoms, uint32_t *out_atoms, int32_t *out_nbonds, uint32_t *out_bonds,
+                     uint8_t *atom_map, uint8_t *flags, void *stream);
+/* mdt_screen_select_similar with classes as a third way to be CLOSE: class_key uint64 (N*G), e.g. mdt_mol_key of the scaffold
+ * arrays above, and max_per_class >= 1.  In step 2 a candidate with class_key != 0 is also passed over, and gets bit 16, when at
+ * least max_per_class candidates kept before it carry the same class_key.  Class 0 ("no scaffold") is never counted: any number of
+ * such candidates may be kept.  fp and fp_count may both be NULL (no similarity test, sim_num ignored), as may be asked of
+ * mdt_screen_select_similar.  class_key == NULL: mdt_screen_select_similar itself, the same launch, max_per_class ignored. */
+int mdt_screen_select_classes(const float *score, const uint64_t *key, const int32_t *packed, const int32_t *length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t *known_key, const int32_t *known_packed, const int32_t *known_len,
+                              int32_t M, int32_t K, const int32_t *known_dist, int32_t min_novelty, int32_t min_distance,
+                              const uint8_t *reject, const uint64_t *fp, const int32_t *fp_count, int32_t sim_num,
+                              const uint64_t *class_key, int32_t max_per_class, uint8_t *status, int32_t *index, int32_t *count,
+                              void *stream);
+
+/* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */
 /* ------------------------------------------------------------------ */
 typedef struct mdt_timer mdt_timer;

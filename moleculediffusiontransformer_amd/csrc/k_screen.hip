@@ -200,14 +200,18 @@ __global__ __launch_bounds__(256) void k_screen_select(const float* __restrict__
 // kFp (mdt_screen_select_similar): "closer" also when the candidate's fingerprint (fp (N*G,16), its popcount fp_count) is at least
 // sim_num / 65536 Tanimoto-similar to a kept one's; the threads share out the kept rows in the same way, 16 words per pair.
 // Without kFp the fingerprint arguments are not looked at and the code is the one that ran before the switch existed.
-template <bool kFp>
+// kClass (mdt_screen_select_classes): "closer" also when the candidate's class_key is not 0 and at least max_per_class of the kept
+// rows carry the same one; the threads share out the kept rows, and the count is block-wide: a wave reduction and one LDS word.
+// Without kClass the class arguments are not looked at and the code is the one that ran before this switch existed.
+template <bool kFp, bool kClass>
 __global__ __launch_bounds__(256) void k_screen_select_diverse(
     const float* __restrict__ score, const uint64_t* __restrict__ key, const int32_t* __restrict__ packed,
     const int32_t* __restrict__ length, int L, int N, int G, const uint64_t* __restrict__ known_key,
     const int32_t* __restrict__ known_packed, const int32_t* __restrict__ known_len, int M, int K,
     const int32_t* __restrict__ known_dist, int min_novelty, int min_distance, const uint8_t* __restrict__ reject,
-    const uint64_t* __restrict__ fp, const int32_t* __restrict__ fp_count, uint32_t sim_num, uint8_t* __restrict__ status,
-    int32_t* __restrict__ index, int32_t* __restrict__ count) {
+    const uint64_t* __restrict__ fp, const int32_t* __restrict__ fp_count, uint32_t sim_num,
+    const uint64_t* __restrict__ class_key, int max_per_class, uint8_t* __restrict__ status, int32_t* __restrict__ index,
+    int32_t* __restrict__ count) {
   __shared__ uint64_t s_key[kScreenMaxN];
   __shared__ float s_score[kScreenMaxN];
   __shared__ int32_t s_len[kScreenMaxN];
@@ -216,8 +220,11 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
   __shared__ int32_t s_kept[kScreenMaxN];
   __shared__ unsigned long long s_peq[64];
   __shared__ int s_eligible;
+  __shared__ int s_same;
   const int g = blockIdx.x;
   const int tid = threadIdx.x;
+  if constexpr (kClass)
+    if (tid == 0) s_same = 0;                                    // (the prologue's barriers lie between this and its first use)
   const int eligible = select_prologue(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, known_dist,
                                        min_novelty, reject, status, s_key, s_score, s_len, s_status, &s_eligible);
   for (int c = tid; c < N; c += 256) {
@@ -235,6 +242,18 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
     const int c = s_order[e];
     const int m = s_len[c];                                      // >= 1: an empty row is not eligible
     int closer = 0;
+    if constexpr (kClass) {
+      __syncthreads();                                           // (s_kept and s_same as thread 0 left them in the step before)
+      const uint64_t mine = class_key[(int64_t)c * G + g];       // (the same in every thread; class 0 is never counted)
+      if (mine != 0) {
+        int same = 0;
+        for (int t = tid; t < kept; t += 256) same += class_key[(int64_t)s_kept[t] * G + g] == mine;
+        for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off, 64);
+        if ((tid & 63) == 0 && same) atomicAdd(&s_same, same);
+        __syncthreads();
+        closer = s_same >= max_per_class;
+      }
+    }
     if constexpr (kFp) {
       __syncthreads();                                           // (s_kept as thread 0 left it in the step before)
       const uint64_t* mine = fp + ((int64_t)c * G + g) * 16;
@@ -272,6 +291,8 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
       }
     }
     closer = __syncthreads_or(closer);                           // (also: s_peq and s_kept are free to be written again)
+    if constexpr (kClass)
+      if (tid == 0) s_same = 0;
     if (closer) {
       if (tid == 0) status[(int64_t)c * G + g] = MDT_SCREEN_CLOSE;
     } else if (kept < K) {
@@ -293,7 +314,8 @@ __global__ __launch_bounds__(256) void k_screen_select_diverse(
 // ------------------------------------------------------------------------------------------------
 namespace {
 // Every selection's checks and its launch.  name: what the messages start with; L_max: 1024 takes k_screen_select, 64 the diverse
-// kernel (rows of one 64-bit word), which looks at the fingerprints iff with_fp.  Two things here are as callers have come to know
+// kernel (rows of one 64-bit word), which looks at the fingerprints iff with_fp and at the classes iff class_key is given (the
+// entry point that takes them forwards a NULL class_key elsewhere, so here NULL means "not asked").  Two things here are as callers have come to know
 // them, and the host tests pin both: the entry points with `reject` report under the name of the one without (they were added as
 // its extension and share its messages), and with fingerprints the ranges are checked BEFORE an empty batch (G <= 0) returns 0,
 // without them after.
@@ -301,7 +323,8 @@ int select_launch(const char* name, int L_max, bool with_fp, const float* score,
                   const int32_t* length, int32_t L, int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed,
                   const int32_t* known_len, int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty,
                   int32_t min_distance, const uint8_t* reject, const uint64_t* fp, const int32_t* fp_count, int32_t sim_num,
-                  uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+                  const uint64_t* class_key, int32_t max_per_class, uint8_t* status, int32_t* index, int32_t* count, void* stream) {
+  if (class_key && max_per_class < 1) return mdt_bad(name, ": need max_per_class >= 1");
   if (!with_fp && G <= 0) return 0;
   if (N < 1 || N > mdt::kScreenMaxN) return mdt_bad(name, ": need 1 <= N <= 1024 candidates per group");
   if (K < 1 || K > N) return mdt_bad(name, ": need 1 <= K <= N");
@@ -320,14 +343,22 @@ int select_launch(const char* name, int L_max, bool with_fp, const float* score,
   if (L_max == 1024)
     hipLaunchKernelGGL(mdt::k_screen_select, grid, block, 0, (hipStream_t)stream, score, key, packed, length, L, N, G, known_key,
                        known_packed, known_len, M, K, reject, status, index, count);
+  else if (class_key && with_fp)
+    hipLaunchKernelGGL((mdt::k_screen_select_diverse<true, true>), grid, block, 0, (hipStream_t)stream, score, key, packed, length, L,
+                       N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count,
+                       (uint32_t)sim_num, class_key, max_per_class, status, index, count);
+  else if (class_key)
+    hipLaunchKernelGGL((mdt::k_screen_select_diverse<false, true>), grid, block, 0, (hipStream_t)stream, score, key, packed, length, L,
+                       N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject,
+                       (const uint64_t*)nullptr, (const int32_t*)nullptr, 0u, class_key, max_per_class, status, index, count);
   else if (with_fp)
-    hipLaunchKernelGGL(mdt::k_screen_select_diverse<true>, grid, block, 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
-                       known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count,
-                       (uint32_t)sim_num, status, index, count);
+    hipLaunchKernelGGL((mdt::k_screen_select_diverse<true, false>), grid, block, 0, (hipStream_t)stream, score, key, packed, length, L,
+                       N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count,
+                       (uint32_t)sim_num, (const uint64_t*)nullptr, 0, status, index, count);
   else
-    hipLaunchKernelGGL(mdt::k_screen_select_diverse<false>, grid, block, 0, (hipStream_t)stream, score, key, packed, length, L, N, G,
-                       known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject,
-                       (const uint64_t*)nullptr, (const int32_t*)nullptr, 0u, status, index, count);
+    hipLaunchKernelGGL((mdt::k_screen_select_diverse<false, false>), grid, block, 0, (hipStream_t)stream, score, key, packed, length,
+                       L, N, G, known_key, known_packed, known_len, M, K, known_dist, min_novelty, min_distance, reject,
+                       (const uint64_t*)nullptr, (const int32_t*)nullptr, 0u, (const uint64_t*)nullptr, 0, status, index, count);
   return mdt_finish(name);
 }
 }  // namespace
@@ -365,7 +396,7 @@ int mdt_screen_select_reject(const float* score, const uint64_t* key, const int3
                              int32_t M, int32_t K, const uint8_t* reject, uint8_t* status, int32_t* index, int32_t* count,
                              void* stream) {
   return select_launch("mdt_screen_select", 1024, false, score, key, packed, length, L, N, G, known_key, known_packed, known_len, M,
-                       K, nullptr, 0, 0, reject, nullptr, nullptr, 0, status, index, count, stream);
+                       K, nullptr, 0, 0, reject, nullptr, nullptr, 0, nullptr, 0, status, index, count, stream);
 }
 
 int mdt_screen_select(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L, int32_t N,
@@ -381,8 +412,8 @@ int mdt_screen_select_diverse_reject(const float* score, const uint64_t* key, co
                                      int32_t min_distance, const uint8_t* reject, uint8_t* status, int32_t* index, int32_t* count,
                                      void* stream) {
   return select_launch("mdt_screen_select_diverse", 64, false, score, key, packed, length, L, N, G, known_key, known_packed,
-                       known_len, M, K, known_dist, min_novelty, min_distance, reject, nullptr, nullptr, 0, status, index, count,
-                       stream);
+                       known_len, M, K, known_dist, min_novelty, min_distance, reject, nullptr, nullptr, 0, nullptr, 0, status, index,
+                       count, stream);
 }
 
 int mdt_screen_select_similar(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
@@ -394,7 +425,22 @@ int mdt_screen_select_similar(const float* score, const uint64_t* key, const int
     return mdt_screen_select_diverse_reject(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, K,
                                             known_dist, min_novelty, min_distance, reject, status, index, count, stream);
   return select_launch("mdt_screen_select_similar", 64, true, score, key, packed, length, L, N, G, known_key, known_packed, known_len,
-                       M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count, sim_num, status, index, count, stream);
+                       M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count, sim_num, nullptr, 0, status, index, count,
+                       stream);
+}
+
+int mdt_screen_select_classes(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,
+                              int32_t N, int32_t G, const uint64_t* known_key, const int32_t* known_packed, const int32_t* known_len,
+                              int32_t M, int32_t K, const int32_t* known_dist, int32_t min_novelty, int32_t min_distance,
+                              const uint8_t* reject, const uint64_t* fp, const int32_t* fp_count, int32_t sim_num,
+                              const uint64_t* class_key, int32_t max_per_class, uint8_t* status, int32_t* index, int32_t* count,
+                              void* stream) {
+  if (!class_key)                                               // no classes: the selection as it was, the same launch
+    return mdt_screen_select_similar(score, key, packed, length, L, N, G, known_key, known_packed, known_len, M, K, known_dist,
+                                     min_novelty, min_distance, reject, fp, fp_count, sim_num, status, index, count, stream);
+  return select_launch("mdt_screen_select_classes", 64, fp || fp_count, score, key, packed, length, L, N, G, known_key, known_packed,
+                       known_len, M, K, known_dist, min_novelty, min_distance, reject, fp, fp_count, sim_num, class_key,
+                       max_per_class, status, index, count, stream);
 }
 
 int mdt_screen_select_diverse(const float* score, const uint64_t* key, const int32_t* packed, const int32_t* length, int32_t L,

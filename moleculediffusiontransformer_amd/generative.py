@@ -943,6 +943,7 @@ class KnownSet:
         self._on = {}
         self._mol_keys = {}
         self._fingerprints = {}
+        self._scaffold_keys = {}
         self._id_range = None
 
     def __len__(self) -> int:
@@ -1008,6 +1009,33 @@ class KnownSet:
             graph, _, _ = _graph_rows(packed, lengths, vocabulary, device, normalize)
             self._fingerprints[at] = (vocabulary, torch.ops.mdt.mol_fp(*graph, radius))
         return self._fingerprints[at][1]
+
+    def scaffold_keys(self, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True,
+                      generic: bool = False) -> Tensor:
+        """The scaffold keys of the known molecules (scaffold_key()): int64 (M',) on ``device`` holding the uint64 bits of the sorted
+        unique NON-ZERO keys -- rows that are no molecule and acyclic molecules (no scaffold: key 0) drop out, all decorations of one
+        ring framework count once.  Sorted ascending AS UNSIGNED, as mol_keys() and for the same reader (mdt::key_flags).  Computed
+        once by mdt::mol_graph -> mdt::mol_scaffold -> mdt::mol_key (``normalize=True``: the three launches of the normal form
+        after the first) and cached per (vocabulary, device, normalize, exocyclic, generic).  ``width`` > 64 raises ValueError."""
+        _normalize_arg(normalize)
+        mode = _scaffold_mode(exocyclic, generic)
+        if not isinstance(vocabulary, SmilesVocabulary):
+            raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+        if self.width > MAX_MOL_LENGTH:
+            raise ValueError(f"known_tokens has rows of {self.width} positions; the scaffold takes at most {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        at = (id(vocabulary), device, normalize, exocyclic, generic)
+        if at not in self._scaffold_keys:
+            _, packed, lengths = self.on(device)
+            graph, _, _ = _graph_rows(packed, lengths, vocabulary, device, normalize)
+            key = torch.ops.mdt.mol_key(*torch.ops.mdt.mol_scaffold(*graph, mode)[:4])
+            top = -2 ** 63                                                     # the bit pattern 1 << 63
+            key = torch.unique(key[key != 0] ^ top) ^ top                      # unique() sorts ascending (signed)
+            self._scaffold_keys[at] = (vocabulary, key)                        # (the vocabulary is held: its id stays its own)
+        return self._scaffold_keys[at][1]
 
     def id_range(self):
         """(lowest, highest) id of the set, looked up once on the host arrays; (0, 0) for an empty set."""
@@ -1145,7 +1173,8 @@ def _similarity_args(max_similarity, max_known_similarity, fingerprint_radius, v
 def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, known_tokens=None, weights=None,
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
             min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
-            fingerprint_radius=2, require=None, forbid=None, kekulize=False, limits=None, normalize=False) -> Screened:
+            fingerprint_radius=2, require=None, forbid=None, kekulize=False, limits=None, max_per_scaffold=None,
+            novel_scaffold=False, scaffold_exocyclic=True, scaffold_generic=False, normalize=False) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
     with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`;
@@ -1153,7 +1182,9 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     same graph, right after mdt::mol_graph, ORs bit 64 in where its verdict is not 0; with ``limits`` one mdt::mol_rings after that
     mdt::mol_hydrogens (made once when both are asked for) ORs bit 128 in where a descriptor lies outside its bounds; with
     ``normalize`` one mdt::mol_normalize follows those two launches (made for it where nobody else asked) and mdt::mol_key,
-    mdt::sub_match and mdt::mol_fp read its graph, the known set's keys and fingerprints being the normalised ones."""
+    mdt::sub_match and mdt::mol_fp read its graph, the known set's keys and fingerprints being the normalised ones; with
+    ``max_per_scaffold`` / ``novel_scaffold`` one mdt::mol_scaffold -> mdt::mol_key on that graph gives every row its scaffold key,
+    which the selection (mdt::screen_select_classes) takes as `class_key` and mdt::key_flags looks up in the known set's."""
     weights, known = _screen_args(conditioning, candidates, keep, known_tokens, weights, tokens=tokens)
     diverse = _diverse_args(min_distance, min_novelty, known, tokens=tokens)
     width = torch.as_tensor(tokens).shape[1]
@@ -1163,8 +1194,9 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     fragments = _substructure_args(require, forbid, vocabulary, width)
     _kekulize_arg(kekulize, vocabulary, width)
     _limits_arg(limits, vocabulary, width)
+    scaffold_mode = _scaffold_args(max_per_scaffold, novel_scaffold, scaffold_exocyclic, scaffold_generic, vocabulary, known, width)
     _screen_normalize_arg(normalize, vocabulary, width, identity == "graph" or sim_num is not None or known_sim_num is not None or
-                          fragments is not None)
+                          fragments is not None or scaffold_mode is not None)
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1213,7 +1245,18 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
         _, inter, union = torch.ops.mdt.fp_nearest(fp, known_fp)
         near = (union > 0) & (inter.long() * FP_SIM_DEN >= known_sim_num * union.long())     # the integer rule of mdt_hip.h
         reject = reject | (near.to(torch.uint8) * rt.SCREEN_KNOWN)
-    distances = diverse or sim_num is not None                   # the selections that take known_dist and the two minima
+    class_key = None
+    if scaffold_mode is not None:                                # which ring framework is it built on?  the key of its scaffold
+        if graph is None:
+            graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
+        ring_key = torch.ops.mdt.mol_key(*torch.ops.mdt.mol_scaffold(*graph, scaffold_mode)[:4])
+        if novel_scaffold:                                       # bit 8 where the known set holds that scaffold (key 0: never)
+            known_rings = known.scaffold_keys(vocabulary, device, normalize=normalize, exocyclic=scaffold_exocyclic,
+                                              generic=scaffold_generic)
+            reject = reject | (torch.ops.mdt.key_flags(ring_key, N, known_rings) & rt.SCREEN_KNOWN)
+        if max_per_scaffold is not None:                         # at most that many kept per scaffold: the selection's classes
+            class_key = ring_key
+    distances = diverse or sim_num is not None or class_key is not None     # the selections that take known_dist and the two minima
     known_dist = None
     if distances and min_novelty > 1:                            # novelty as a distance: the nearest known row of every candidate
         known_dist, _ = torch.ops.mdt.edit_nearest(packed, length, kp, kl)
@@ -1221,7 +1264,12 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     args = (score, key, packed, length, N, K, kk, kp, kl)
     if distances:
         args += (known_dist, min_novelty, min_distance)
-    if sim_num is not None:
+    if class_key is not None:
+        if sim_num is None:                                      # (fingerprints made for the known set alone are not the selection's)
+            fp = fp_count = None
+        status, index, count = torch.ops.mdt.screen_select_classes(*args, reject, fp, fp_count, sim_num or 0, class_key,
+                                                                   max_per_scaffold)
+    elif sim_num is not None:
         status, index, count = torch.ops.mdt.screen_select_similar(*args, reject, fp, fp_count, sim_num)
     elif reject is not None:
         select = torch.ops.mdt.screen_select_diverse_reject if diverse else torch.ops.mdt.screen_select_reject
@@ -1265,7 +1313,9 @@ def screen_tokens(model_forward: "QMDiffusionForward", tokens: Tensor, condition
 def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, conditioning: Tensor, device, candidates: int,
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
                           max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2, require=None, forbid=None,
-                          kekulize: bool = False, limits=None, normalize: bool = False, **screen_tokens_kwargs) -> Screened:
+                          kekulize: bool = False, limits=None, max_per_scaffold: Optional[int] = None, novel_scaffold: bool = False,
+                          scaffold_exocyclic: bool = True, scaffold_generic: bool = False, normalize: bool = False,
+                          **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
     ``vocabulary=``, with "is it a molecule at all?" asked of every candidate.
@@ -1355,11 +1405,28 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     written.  Its limits are mol_normalize()'s: not RDKit's aromaticity model, no envelope rings (azulene is not aromatic), no
     tautomers; a row whose Kekule verdict is not 0 is read as written.  With False (the default) the call makes exactly the
     launches it makes without the keyword, in the same order.
+
+    ``max_per_scaffold`` / ``novel_scaffold``: "distinct" and "novel" asked of the RING FRAMEWORK a molecule is built on, the
+    scaffold of mol_scaffold() (see there for the definition and its limits: the 2-core of the ring graph plus, with
+    ``scaffold_exocyclic`` (default True), the atoms double-bonded to it; ``scaffold_generic`` (default False) compares frameworks
+    with every atom a C and every bond single; not RDKit's MurckoScaffold, aromaticity and hydrogens as handed in, an acyclic
+    molecule has NO scaffold).  Both need a ``vocabulary`` and rows of at most 64 positions, and both count as consumers of
+    ``normalize``: with ``normalize=True`` the scaffold is read from the normal form, so a Kekule and an aromatic spelling share
+    one.  One mdt::mol_scaffold -> mdt::mol_key runs over the N * G rows on the graph the call already has (mdt::mol_graph is never
+    launched twice).  ``max_per_scaffold=m`` (an int >= 1, None: off): of the candidates of a target that share a scaffold key at most
+    m are kept; one that finds m kept before it is passed over and gets status bit 16, as under ``min_distance``, with which and
+    with ``max_similarity`` it combines (any test passes a candidate over); the selection goes to mdt::screen_select_classes.
+    Candidates without a scaffold (key 0) are never counted.  ``novel_scaffold=True``: needs a non-empty known set; bit 8 is OR-ed
+    into `reject` where the scaffold key is found in KnownSet.scaffold_keys() (computed once), so a new decoration of a known ring
+    system counts as known.  Refusals come with ValueError before anything is launched.  With both at their defaults the call
+    makes exactly the launches it makes without the keywords, in the same order.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
                    vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
                    max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, require=require, forbid=forbid,
-                   kekulize=kekulize, limits=limits, normalize=normalize, **screen_tokens_kwargs)
+                   kekulize=kekulize, limits=limits, max_per_scaffold=max_per_scaffold, novel_scaffold=novel_scaffold,
+                   scaffold_exocyclic=scaffold_exocyclic, scaffold_generic=scaffold_generic, normalize=normalize,
+                   **screen_tokens_kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -2143,6 +2210,91 @@ def mol_normalize(tokens, vocabulary: "SmilesVocabulary", device):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# which ring framework is a molecule built on?  the scaffold of a graph row (csrc/k_molscaf.hip): rows of at most 64 positions
+# ----------------------------------------------------------------------------------------------------------------------
+def _scaffold_mode(exocyclic, generic) -> int:
+    """The refusals of ``exocyclic=`` / ``generic=`` -> the mode of mdt::mol_scaffold."""
+    for name, v in (("exocyclic", exocyclic), ("generic", generic)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{name} must be True or False, got {v!r}")
+    return (rt.MOLS_EXOCYCLIC if exocyclic else 0) | (rt.MOLS_GENERIC if generic else 0)
+
+
+def _scaffold_args(max_per_scaffold, novel_scaffold, exocyclic, generic, vocabulary, known, length: int):
+    """The refusals of the screening calls' scaffold keywords, before anything is launched.  -> the mode of mdt::mol_scaffold, or
+    None when neither ``max_per_scaffold`` nor ``novel_scaffold`` asks for a scaffold."""
+    if max_per_scaffold is not None and (isinstance(max_per_scaffold, bool) or not isinstance(max_per_scaffold, int) or
+                                         max_per_scaffold < 1):
+        raise ValueError(f"max_per_scaffold must be an int >= 1 or None, got {max_per_scaffold!r}")
+    if not isinstance(novel_scaffold, bool):
+        raise ValueError(f"novel_scaffold must be True or False, got {novel_scaffold!r}")
+    try:
+        mode = _scaffold_mode(exocyclic, generic)
+    except ValueError as e:
+        raise ValueError("scaffold_" + str(e)) from None
+    if max_per_scaffold is None and not novel_scaffold:
+        return None
+    if vocabulary is None:
+        raise ValueError("max_per_scaffold / novel_scaffold read the rows as strings: give a vocabulary")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the scaffold takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    if novel_scaffold and (known is None or len(known) == 0):
+        raise ValueError("novel_scaffold=True asks whether the known set holds the scaffold: give a non-empty known_tokens")
+    return mode
+
+
+def _scaffold_of(tokens, vocabulary, device, normalize, exocyclic, generic):
+    _normalize_arg(normalize)
+    mode = _scaffold_mode(exocyclic, generic)
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    return torch.ops.mdt.mol_scaffold(*graph, mode), status, position
+
+
+def mol_scaffold(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True,
+                 generic: bool = False):
+    """Which ring framework is each molecule built on?  -> (natoms int64 (R,), atoms int64 (R, L), nbonds int64 (R,), bonds int64
+    (R, L), atom_map int64 (R, L), flags int64 (R,), status int64 (R,), position int64 (R,)) for raw (R, L) ids of any integer dtype,
+    zeros anywhere.  ``status`` / ``position`` are smiles_check()'s.  The first four are graph arrays in mol_graph()'s format that
+    hold the SCAFFOLD alone, renumbered: ``atom_map[r, a]`` is 1 + the scaffold index of atom a of mol_graph(), 0 for an atom that
+    was pruned.  ``flags``: 1 the row is a molecule, 2 it has a scaffold, 4 the scaffold is the whole molecule.
+
+    The scaffold is the 2-core of the ring graph: in rounds every atom with at most one neighbour left is removed, until none is;
+    what stays is the atoms on a cycle or on a path between two cycles -- Bemis and Murcko's rings plus linkers, over all dotted
+    components.  ``exocyclic=True`` (the default) also keeps an atom double-bonded to a kept one (the O of a ring C=O), and nothing
+    that hangs on it.  A kept BRACKET atom adds what it lost to its H count (an entry of order o weighs o; at most 15), so on the
+    normal form the [c] of toluene becomes the [cH] of benzene; an unbracketed atom stays as written, its hydrogens being implicit.
+    ``generic=True`` makes every kept atom a plain C and every kept bond single: frameworks compared as bare graphs.
+    ``normalize=True`` reads the normal form of mol_normalize() instead of the row as written, so that Cc1ccccc1 and CC1=CC=CC=C1
+    have one scaffold.  mdt_mol_scaffold in include/mdt_hip.h has every rule.
+    What it is NOT: not RDKit's MurckoScaffold.  Aromaticity and hydrogens are as handed in.  With ``exocyclic=False`` a ring C(=O)
+    loses its O and gains two H when bracketed; on a normal form that can leave an aromatic atom with an odd H count.  Stereo is
+    ignored.  An acyclic molecule has NO scaffold: all zero, scaffold_key() 0.  Applying it again with the same keywords is the
+    identity, except with exocyclic and generic both on: GENERIC rewrites the exocyclic order, so a second pass drops those atoms.
+    "Scaffold of the normal form" equals "normal form of the scaffold's own spelling" on the table of the tests; it is not promised
+    in general.  There is no SMILES writer: the scaffold comes back as graph arrays and as a key.
+    L <= 64; the refusals are mol_key()'s, with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_scaffold; with ``normalize=True`` mdt::mol_hydrogens ->
+    mdt::mol_rings -> mdt::mol_normalize go between the last two."""
+    (natoms, atoms, nbonds, bonds, atom_map, flags), status, position = _scaffold_of(tokens, vocabulary, device, normalize, exocyclic,
+                                                                                      generic)
+    return (natoms.long(), atoms.long() & 0xFFFFFFFF, nbonds.long(), bonds.long(), atom_map.long(), flags.long(), status.long(),
+            position.long())
+
+
+def scaffold_key(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True,
+                 generic: bool = False):
+    """mol_key() of the scaffold of each row (mol_scaffold(), whose keywords this takes; see there for what a scaffold is and is
+    not -- not RDKit's MurckoScaffold) -> (key int64 (R,): the uint64 bits, flags int64 (R,), status int64 (R,), position int64
+    (R,)).  Two molecules on one ring framework have one key whatever their side chains; KEY 0 MEANS "NO SCAFFOLD": no molecule, or
+    an acyclic one.  ``flags`` are mol_scaffold()'s.  The key is mol_key()'s refinement hash, with its limits.
+    Sequence: mol_scaffold()'s, then mdt::mol_key."""
+    out, status, position = _scaffold_of(tokens, vocabulary, device, normalize, exocyclic, generic)
+    return torch.ops.mdt.mol_key(*out[:4]), out[5].long(), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:
@@ -2193,14 +2345,16 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     """Best-of-N per target as one call: ``model.sample_tokens(conditioning.repeat(N, 1), ...)`` -- N = ``candidates`` tries for each
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
     ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
-    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize`` / ``limits`` / ``normalize``, with which the tokens go to screen_tokens_diverse instead;
+    ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize`` / ``limits`` / ``normalize`` / ``max_per_scaffold`` /
+    ``novel_scaffold`` / ``scaffold_exocyclic`` / ``scaffold_generic``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
     pinned ``kernel_choice``)."""
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
                                          "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
-                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize", "limits", "normalize"}
+                                         "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize", "limits", "normalize",
+                                         "max_per_scaffold", "novel_scaffold", "scaffold_exocyclic", "scaffold_generic"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -2238,8 +2392,16 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     _limits_arg(limits, vocabulary, model.max_length)
     if limits is not None:                                       # (None: the calls made without the keyword)
         diverse, filters["limits"] = True, limits
+    scaffold = {k: screen_tokens_kwargs.pop(k) for k in ("max_per_scaffold", "novel_scaffold", "scaffold_exocyclic", "scaffold_generic")
+                if k in screen_tokens_kwargs}
+    scaffold_on = _scaffold_args(scaffold.get("max_per_scaffold"), scaffold.get("novel_scaffold", False),
+                                 scaffold.get("scaffold_exocyclic", True), scaffold.get("scaffold_generic", False), vocabulary, known,
+                                 model.max_length) is not None
+    if scaffold_on:                                              # (None and False: the calls made without the keywords)
+        diverse = True
+        filters.update(scaffold)
     normalize = screen_tokens_kwargs.pop("normalize", False)
-    _screen_normalize_arg(normalize, vocabulary, model.max_length, identity == "graph" or bool(fragments) or any(
+    _screen_normalize_arg(normalize, vocabulary, model.max_length, identity == "graph" or bool(fragments) or scaffold_on or any(
         similar.get(k) is not None for k in ("max_similarity", "max_known_similarity")))
     if normalize:                                                # (False: the calls made without the keyword)
         diverse, filters["normalize"] = True, True

@@ -489,14 +489,16 @@ def _(props, target, weights, candidates):
 
 
 def _screen_select(op, score, key, packed, length, candidates, keep, known_key, known_packed, known_len, *, diverse=None,
-                   reject=None, similar=None):
-    """The one body of the five selection ops: the argument checks, the three outputs, the call.  diverse: (known_dist, min_novelty,
+                   reject=None, similar=None, classes=None):
+    """The one body of the six selection ops: the argument checks, the three outputs, the call.  diverse: (known_dist, min_novelty,
     min_distance) of the ops that take them -- their rows have at most the 64 positions of the edit distance; reject: the byte per
-    row, or None; similar: (fp, fp_count, sim_num) of mdt::screen_select_similar.  The C symbol is the op's own, except that a
+    row, or None; similar: (fp, fp_count, sim_num) of mdt::screen_select_similar; classes: (class_key, max_per_class) of
+    mdt::screen_select_classes.  The C symbol is the op's own, except that a
     ..._reject op whose reject is None calls the symbol without it: that op's launch, bit for bit."""
     known_dist, min_novelty, min_distance = diverse if diverse is not None else (None, 0, 0)
     fp, fp_count, sim_num = similar if similar is not None else (None, None, 0)
-    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject, fp, fp_count)
+    class_key, max_per_class = classes if classes is not None else (None, 0)
+    dev = _hip(score, key, packed, length, known_key, known_packed, known_len, known_dist, reject, fp, fp_count, class_key)
     lib = rt.load_library()
     rows, L = packed.shape
     N = candidates
@@ -534,6 +536,12 @@ def _screen_select(op, score, key, packed, length, candidates, keep, known_key, 
         fp_count = fp_count.contiguous()
         if not 1 <= sim_num <= rt.FP_SIM_DEN:
             raise RuntimeError(f"{op}: sim_num = {sim_num} must lie in [1, {rt.FP_SIM_DEN}]")
+    if class_key is not None:
+        if class_key.dtype != torch.int64 or class_key.numel() != rows:
+            raise RuntimeError(f"{op}: class_key must hold one int64 (the uint64 bits, as mdt::mol_key returns them) per row of packed")
+        if max_per_class < 1:
+            raise RuntimeError(f"{op}: max_per_class = {max_per_class} must be at least 1")
+        class_key = class_key.contiguous()
     if reject is not None:
         if reject.dtype != torch.uint8 or reject.numel() != rows:
             raise RuntimeError(f"{op}: reject must hold one uint8 per row of packed")
@@ -549,6 +557,8 @@ def _screen_select(op, score, key, packed, length, candidates, keep, known_key, 
             args += [rt.ptr(known_dist), int(min_novelty), int(min_distance)]
         if similar is not None:
             args += [rt.ptr(reject), rt.ptr(fp), rt.ptr(fp_count), int(sim_num)]
+            if classes is not None:
+                args += [rt.ptr(class_key), int(max_per_class)]
         elif reject is not None:
             args += [rt.ptr(reject)]
         else:
@@ -618,7 +628,24 @@ def screen_select_similar(score: Tensor, key: Tensor, packed: Tensor, length: Te
                           known_len, diverse=(known_dist, min_novelty, min_distance), reject=reject, similar=(fp, fp_count, sim_num))
 
 
-for _op in (screen_select, screen_select_diverse, screen_select_reject, screen_select_diverse_reject, screen_select_similar):
+@custom_op("mdt::screen_select_classes", mutates_args=())
+def screen_select_classes(score: Tensor, key: Tensor, packed: Tensor, length: Tensor, candidates: int, keep: int,
+                          known_key: Optional[Tensor], known_packed: Optional[Tensor], known_len: Optional[Tensor],
+                          known_dist: Optional[Tensor], min_novelty: int, min_distance: int, reject: Optional[Tensor],
+                          fp: Optional[Tensor], fp_count: Optional[Tensor], sim_num: int, class_key: Optional[Tensor],
+                          max_per_class: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """mdt::screen_select_similar with classes as a third way to be passed over (mdt_screen_select_classes, include/mdt_hip.h): a
+    candidate whose ``class_key`` (int64 (N * G): the uint64 bits, e.g. mdt::mol_key of the arrays of mdt::mol_scaffold) is not 0
+    gets bit 16 when at least ``max_per_class`` candidates kept before it carry the same one; class 0 is never counted.  fp and
+    fp_count may be None (no similarity test).  class_key None: mdt::screen_select_similar's launch on the same inputs, bit for
+    bit."""
+    return _screen_select("mdt::screen_select_classes", score, key, packed, length, candidates, keep, known_key, known_packed,
+                          known_len, diverse=(known_dist, min_novelty, min_distance), reject=reject, similar=(fp, fp_count, sim_num),
+                          classes=(class_key, max_per_class))
+
+
+for _op in (screen_select, screen_select_diverse, screen_select_reject, screen_select_diverse_reject, screen_select_similar,
+            screen_select_classes):
     _op.register_fake(_screen_select_fake)
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1039,6 +1066,51 @@ def mol_normalize(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, 
 def _(natoms, atoms, nbonds, bonds, hydrogens, partner, verdict, bond_ring):
     R, L = atoms.shape
     return (atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the scaffold of a graph row (csrc/k_molscaf.hip): rows of at most 64 positions
+@custom_op("mdt::mol_scaffold", mutates_args=())
+def mol_scaffold(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor,
+                 mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (natoms int32 (R,), atoms int32 (R, L), nbonds int32 (R,), bonds int32 (R, L), atom_map uint8 (R, L), flags uint8 (R,)) of
+    mdt_mol_scaffold (include/mdt_hip.h) for the graph arrays of mdt::mol_graph or of mdt::mol_normalize: the 2-core of the ring
+    graph -- rings plus linkers -- with mode bit 0 (runtime.MOLS_EXOCYCLIC) plus the atoms double-bonded to it, renumbered, as graph
+    arrays that mdt::mol_key takes; mode bit 1 (runtime.MOLS_GENERIC) makes every atom a plain C and every bond single.  atom_map:
+    1 + the new index of a kept atom, else 0; flags 1 a molecule, 2 it has a scaffold, 4 nothing was pruned.  An acyclic molecule
+    has no scaffold: all zero.  Not RDKit's MurckoScaffold."""
+    dev = _hip(natoms, atoms, nbonds, bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_scaffold"
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the scaffold takes 1 to {rt.MOL_MAX_LENGTH}")
+    if not 0 <= mode <= (rt.MOLS_EXOCYCLIC | rt.MOLS_GENERIC):
+        raise RuntimeError(f"{op}: mode = {mode} must be 0 or a sum of MOLS_EXOCYCLIC (1) and MOLS_GENERIC (2)")
+    natoms, atoms, nbonds, bonds = (t.contiguous() for t in (natoms, atoms, nbonds, bonds))
+    out_natoms = torch.zeros(R, dtype=torch.int32, device=dev)
+    out_atoms = torch.zeros(R, L, dtype=torch.int32, device=dev)
+    out_nbonds = torch.zeros(R, dtype=torch.int32, device=dev)
+    out_bonds = torch.zeros(R, L, dtype=torch.int32, device=dev)
+    atom_map = torch.zeros(R, L, dtype=torch.uint8, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_scaffold(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, int(mode),
+                                          rt.ptr(out_natoms), rt.ptr(out_atoms), rt.ptr(out_nbonds), rt.ptr(out_bonds),
+                                          rt.ptr(atom_map), rt.ptr(flags), rt.current_stream()))
+    return out_natoms, out_atoms, out_nbonds, out_bonds, atom_map, flags
+
+
+@mol_scaffold.register_fake
+def _(natoms, atoms, nbonds, bonds, mode):
+    R, L = atoms.shape
+    return (atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, dtype=torch.int32),
+            atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, L, dtype=torch.uint8), atoms.new_empty(R, dtype=torch.uint8))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -58,6 +58,8 @@ MOLH_MAX_STEPS, MOLH_FORMULA = 4096, 13     # mdt_mol_hydrogens: tries of a row'
 MOLH_OK, MOLH_AROMATIC_OVERVALENT, MOLH_NO_KEKULE, MOLH_UNDECIDED = 0, 1, 2, 3    # enum mdt_molh_verdict
 MOLR_DESC = 16                               # mdt_mol_rings: words of a descriptor row (enum mdt_molr_slot)
 MOLN_NORMALIZED, MOLN_AROMATIC, MOLN_CHANGED = 1, 2, 4    # enum mdt_moln_flag: the flags of mdt_mol_normalize
+MOLS_EXOCYCLIC, MOLS_GENERIC = 1, 2          # enum mdt_mols_mode: the mode bits of mdt_mol_scaffold
+MOLS_MOLECULE, MOLS_SCAFFOLD, MOLS_WHOLE = 1, 2, 4        # enum mdt_mols_flag: its flags
 FP_KNOWN_CHUNK = 512             # MDT_FP_KNOWN_CHUNK: known rows of one workgroup of mdt_fp_nearest
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
@@ -139,6 +141,9 @@ SYMBOLS = {
     "mdt_mol_hydrogens": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_rings": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_normalize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mdt_mol_scaffold": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mdt_screen_select_classes": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P,
+                                       _P]),
     "mdt_edit_distance_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "mdt_edit_nearest": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "mdt_timer_create": (_P, [_I]),
