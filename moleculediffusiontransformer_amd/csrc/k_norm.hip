@@ -47,7 +47,9 @@ __global__ __launch_bounds__(NT) void k_gn_stats(GnStatsArgs g) {
   const float var = block_sum<NT>(ss, red) / (float)n;
   if (threadIdx.x == 0) {
     g.stats[(int64_t)blockIdx.x * 2] = mean;
-    g.stats[(int64_t)blockIdx.x * 2 + 1] = 1.0f / sqrtf(var + g.eps);
+    // one thread per (sample, group): in fp64, rounded once.  sqrtf and the division, each correctly rounded, leave an all-zero
+    // unit at eps 1e-6 1.02 fp32 ulp from 1 / sqrt(eps) (999.99994 for 1000.00002; worst case of the pair 1.5 ulp)
+    g.stats[(int64_t)blockIdx.x * 2 + 1] = (float)(1.0 / sqrt((double)var + (double)g.eps));
   }
 }
 

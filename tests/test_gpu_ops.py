@@ -4,7 +4,9 @@ import math
 import pytest
 import torch
 
+import op_cases as cases
 from gpu_util import DEV, ref, rnd, run_both
+from op_cases import gemm_op, gn_stats_op
 from moleculediffusiontransformer_amd import runtime as rt
 
 pytestmark = pytest.mark.gpu
@@ -24,25 +26,6 @@ def prod(request, monkeypatch):
         orig(self, cfg, length, cond_len, sd, max_time_rows, request.param if gemm_mode == "bf16x3" else gemm_mode, fuse_blocks, tf256)
     monkeypatch.setattr(compiler.UNetCompiler, "__init__", init)
     return request.param
-
-
-def gemm_op(**kw):
-    op = rt.MdtOp()
-    op.kind = rt.OP_GEMM
-    for k in ("a", "w", "bias", "out", "res", "p0", "p1", "p2", "p3"):
-        if k in kw:
-            setattr(op, k, kw.pop(k))
-    i = op.i
-    i[rt.G_T_STRIDE], i[rt.G_O_STRIDE] = 1, 1
-    names = dict(r_out=rt.G_R_OUT, r_in=rt.G_R_IN, lda=rt.G_LDA, cin=rt.G_CIN, taps=rt.G_TAPS, t_stride=rt.G_T_STRIDE,
-                 t_dj=rt.G_T_DJ, t_off=rt.G_T_OFF, n=rt.G_N, ldc=rt.G_LDC, o_rows=rt.G_O_ROWS,
-                 o_stride=rt.G_O_STRIDE, o_off=rt.G_O_OFF, ldr=rt.G_LDR, pro=rt.G_PRO, groups=rt.G_GROUPS,
-                 gsize=rt.G_GSIZE, pro_silu=rt.G_PRO_SILU, act=rt.G_ACT, m_mode=rt.G_M_MODE, a_col=rt.G_A_COL,
-                 o_col=rt.G_O_COL)
-    op.f[0] = kw.pop("eps", 0.0)
-    for k, v in kw.items():
-        i[names[k]] = v
-    return op
 
 
 @pytest.mark.parametrize("B,R,cin,N,taps", [(3, 16, 128, 512, 1), (5, 64, 16, 64, 3), (2, 4, 512, 256, 3),
@@ -71,27 +54,9 @@ def test_row_stationary_projection_on_ring_tiles(B, R, cin, N, ln, res, prod):
     """k_proj (MDT_G_WFMT = 16): LayerNorm prologue (without affine -- what the compiler emits, gain / bias folded into W / bias -- and
     with gain / bias vectors), bias, residual IN PLACE on the output, row counts that are no multiple of the workgroup's rows, one to
     several workgroups per row block; against the interpreter (split-bf16 weights) and the exact fp32 product."""
-    from moleculediffusiontransformer_amd.compiler import UNetCompiler
-    w = rnd(N, cin, seed=1, scale=cin ** -0.5)
+    c = cases.ring_projection(B, R, cin, N, ln, res, prod)
+    op, weights, act, w, x, out0, nb = c.ops[0], c.weights, c.act, c.w, c.x, c.out0, c.nb
     f32 = prod == "f32"                  # MDT_G_WFMT = 17: fp32 fragment tiles, exact fp32 MFMA products
-    tile = UNetCompiler._tile_f32 if f32 else UNetCompiler._tile
-    tiles = [tile(w[64 * c: 64 * c + 64, 128 * h: 128 * h + 128]) for c in range(N // 64) for h in range(cin // 128)]
-    wt = torch.cat(tiles)
-    weights = torch.cat([wt, rnd(N, seed=2), 1 + 0.1 * rnd(cin, seed=5), 0.1 * rnd(cin, seed=6)])
-    nb = wt.numel()
-    x = rnd(B * R * cin, seed=3) * 1.3 + 0.2
-    out0 = rnd(B * R * N, seed=4)
-    act = torch.cat([x, out0])
-    op = gemm_op(a=ref(A, 0), w=ref(W, 0), bias=ref(W, nb), out=ref(A, R * cin), r_out=R, r_in=R, lda=cin, cin=cin, taps=1, n=N,
-                 ldc=N, o_rows=R, eps=1e-5)
-    if ln:
-        op.i[rt.G_PRO] = rt.PRO_LAYERNORM
-        if ln == "affine":
-            op.p0, op.p1 = ref(W, nb + N), ref(W, nb + N + cin)
-    if res:
-        op.res = ref(A, R * cin)
-        op.i[rt.G_LDR] = N
-    op.i[rt.G_WFMT] = 17 if f32 else 16
     (ga, _, _), (ca, _, _) = run_both([op], weights, act, torch.zeros(4), {}, B)
     assert torch.equal(ga[: B * R * cin], x)
     assert (ga - ca).abs().max() < (1e-5 if f32 else 5e-5)      # (summation order; the split planes carry ~2^-17 relative rounding)
@@ -270,10 +235,8 @@ def test_gemm_strided_conv_and_transposed_phases():
 
 @pytest.mark.parametrize("B,R,C,N", [(4, 16, 128, 512), (3, 12, 128, 1024), (2, 4, 256, 512), (130, 1, 64, 64)])
 def test_gemm_layernorm_prologue(B, R, C, N):
-    weights = torch.cat([rnd(N, C, seed=1, scale=C ** -0.5).view(-1), 1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3)])
-    act = torch.cat([rnd(B * R * C, seed=4) * 2 + 0.5, torch.zeros(B * R * N)])
-    ops = [gemm_op(a=ref(A, 0), w=ref(W, 0), out=ref(A, R * C), p0=ref(W, N * C), p1=ref(W, N * C + C), r_out=R,
-                   r_in=R, lda=C, cin=C, taps=1, n=N, ldc=N, o_rows=R, pro=rt.PRO_LAYERNORM, eps=1e-5)]
+    c = cases.layernorm_gemm(B, R, C, N)
+    ops, weights, act = c.ops, c.weights, c.act
     (ga, _, _), (ca, _, _) = run_both(ops, weights, act, torch.zeros(4), {}, B)
     assert (ga - ca).abs().max() < 3e-5
     x = act[: B * R * C].view(B * R, C)
@@ -288,23 +251,8 @@ def test_gemm_layernorm_prologue(B, R, C, N):
                                                       (3, 16, 128, 32, 128, False, False, 1e-6),
                                                       (2, 32, 32, 32, 32, False, False, 1e-6)])
 def test_gn_stats_and_groupnorm_prologue(B, R, C, G, N, film, silu, eps):
-    gs = C // G
-    taps = 3 if silu else 1
-    K = taps * C
-    weights = torch.cat([rnd(N, K, seed=1, scale=K ** -0.5).view(-1), 1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3)])
-    shr = 0.3 * rnd(2 * C, seed=9)
-    xoff, stoff, ooff = 0, R * C, R * C + 64
-    act = torch.zeros(B * (R * C + 64 + R * N))
-    act[: B * R * C] = rnd(B * R * C, seed=4) * 1.5 + 0.3
-    st = rt.MdtOp()
-    st.kind = rt.OP_GN_STATS
-    st.a, st.out = ref(A, xoff), ref(A, stoff)
-    st.i[rt.N_ROWS], st.i[rt.N_LD], st.i[rt.N_GROUPS], st.i[rt.N_GSIZE] = R, C, G, gs
-    st.f[0] = eps
-    ops = [st, gemm_op(a=ref(A, xoff), w=ref(W, 0), out=ref(A, ooff), p0=ref(W, N * K), p1=ref(W, N * K + C),
-                       p2=ref(A, stoff), p3=ref(S, 0) if film else ref(rt.SP_NONE), r_out=R, r_in=R, lda=C, cin=C,
-                       taps=taps, t_dj=1 if taps > 1 else 0, t_off=-(taps // 2), n=N, ldc=N, o_rows=R,
-                       pro=rt.PRO_GROUPNORM, groups=G, gsize=gs, pro_silu=int(silu))]
+    c = cases.groupnorm_gemm(B, R, C, G, N, film, silu, eps)
+    ops, weights, act, shr, taps, K, ooff = c.ops, c.weights, c.act, c.shr, c.taps, c.K, c.ooff
     # NB: stats are per-sample 2G floats at ACT offset stoff (scaled by B at run time) -> needs 2G <= 64
     (ga, _, _), (ca, _, _) = run_both(ops, weights, act, shr, {}, B)
     assert (ga - ca).abs().max() < 5e-5
@@ -548,12 +496,6 @@ def test_counter_based_noise_is_normal_and_sharding_independent():
     assert abs((f[:, :, 1:] * f[:, :, :-1]).mean()) < 0.01
 
 
-def _split_planes(w):
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16)
-    return hi.contiguous().view(-1).view(torch.float32), lo.contiguous().view(-1).view(torch.float32)
-
-
 @pytest.mark.parametrize("B,R,cin,N,taps,pro", [
     (64, 16, 128, 512, 1, rt.PRO_LAYERNORM),      # 128x128 tiles
     (1024, 16, 128, 128, 3, rt.PRO_GROUPNORM),    # 128x64 tiles, conv taps, GN+FiLM+SiLU
@@ -567,32 +509,8 @@ def _split_planes(w):
 ])
 def test_gemm_split_bf16(B, R, cin, N, taps, pro):
     """k_gemm3 (bf16x3) against the interpreter (fp32 activations x reconstructed hi+lo weights)."""
-    K = taps * cin
-    w = rnd(N, K, seed=1, scale=K ** -0.5)
-    hi, lo = _split_planes(w)
-    G = 8
-    gs = cin // G
-    weights = torch.cat([hi, lo, rnd(N, seed=2), 1 + 0.1 * rnd(cin, seed=3), 0.1 * rnd(cin, seed=4)])
-    o_hi, o_lo, o_b, o_g, o_nb = 0, hi.numel(), 2 * hi.numel(), 2 * hi.numel() + N, 2 * hi.numel() + N + cin
-    xoff, stoff, ooff, roff = 0, R * cin, R * cin + 64, R * cin + 64 + R * N
-    act = torch.zeros(B * (roff + R * N))
-    act[: B * R * cin] = rnd(B * R * cin, seed=5) * 1.3 + 0.2
-    act[B * roff:] = rnd(B * R * N, seed=6)
-    shr = 0.3 * rnd(2 * cin, seed=7)
-    ops = []
-    if pro == rt.PRO_GROUPNORM:
-        st = rt.MdtOp()
-        st.kind = rt.OP_GN_STATS
-        st.a, st.out = ref(A, xoff), ref(A, stoff)
-        st.i[rt.N_ROWS], st.i[rt.N_LD], st.i[rt.N_GROUPS], st.i[rt.N_GSIZE] = R, cin, G, gs
-        st.f[0] = 1e-5
-        ops.append(st)
-    op = gemm_op(a=ref(A, xoff), w=ref(W, o_hi), bias=ref(W, o_b), out=ref(A, ooff), res=ref(A, roff),
-                 p0=ref(W, o_g), p1=ref(W, o_nb), p2=ref(A, stoff), p3=ref(S, 0), r_out=R, r_in=R, lda=cin, cin=cin,
-                 taps=taps, t_dj=1 if taps > 1 else 0, t_off=-(taps // 2), n=N, ldc=N, o_rows=R, ldr=N, pro=pro,
-                 groups=G, gsize=gs, pro_silu=1, act=0, eps=1e-5)
-    op.a2 = ref(W, o_lo)
-    ops.append(op)
+    c = cases.split_gemm(B, R, cin, N, taps, pro)
+    ops, weights, act, shr, ooff, roff = c.ops, c.weights, c.act, c.shr, c.ooff, c.roff
     (ga, _, _), (ca, _, _) = run_both(ops, weights, act, shr, {}, B)
     out_g, out_c = ga[B * ooff: B * roff], ca[B * ooff: B * roff]
     scale = out_c.abs().max().item()
@@ -626,12 +544,7 @@ def test_gemm_plain_bf16(B, R, cin, N, taps, pro):
     shr = 0.3 * rnd(2 * cin, seed=7)
     ops = []
     if pro == rt.PRO_GROUPNORM:
-        st = rt.MdtOp()
-        st.kind = rt.OP_GN_STATS
-        st.a, st.out = ref(A, xoff), ref(A, stoff)
-        st.i[rt.N_ROWS], st.i[rt.N_LD], st.i[rt.N_GROUPS], st.i[rt.N_GSIZE] = R, cin, G, gs
-        st.f[0] = 1e-5
-        ops.append(st)
+        ops.append(gn_stats_op(xoff, stoff, R, cin, G, gs, 1e-5))
     op = gemm_op(a=ref(A, xoff), w=ref(W, 0), bias=ref(W, o_b), out=ref(A, ooff), res=ref(A, roff),
                  p0=ref(W, o_g), p1=ref(W, o_nb), p2=ref(A, stoff), p3=ref(S, 0), r_out=R, r_in=R, lda=cin, cin=cin,
                  taps=taps, t_dj=1 if taps > 1 else 0, t_off=-(taps // 2), n=N, ldc=N, o_rows=R, ldr=N, pro=pro,
@@ -685,12 +598,7 @@ def test_gemm_bf16_streamed(B, R, cin, N, taps, pro, act, tile):
     shr = 0.3 * rnd(2 * cin, seed=7)
     ops = []
     if pro == rt.PRO_GROUPNORM:
-        st = rt.MdtOp()
-        st.kind = rt.OP_GN_STATS
-        st.a, st.out = ref(A, xoff), ref(A, stoff)
-        st.i[rt.N_ROWS], st.i[rt.N_LD], st.i[rt.N_GROUPS], st.i[rt.N_GSIZE] = R, cin, G, gs
-        st.f[0] = 1e-5
-        ops.append(st)
+        ops.append(gn_stats_op(xoff, stoff, R, cin, G, gs, 1e-5))
     pre = rt.MdtOp()
     pre.kind = rt.OP_PREP16
     pre.a, pre.out, pre.p0, pre.p1, pre.p2, pre.p3 = ref(A, xoff), ref(A, a16off), ref(W, o_g), ref(W, o_nb), ref(A, stoff), ref(S, 0)
@@ -989,16 +897,8 @@ def test_fused_transformer_sub_block(mode, C, T, B, variant, products):
                                                     (2, 8, 2048, 8, False, True, 1e-5)])
 def test_gn_act(B, R, C, G, film, silu, eps):
     """k_gn_act (statistics + normalise + FiLM + SiLU in one pass) against torch's GroupNorm."""
-    weights = torch.cat([1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3)])
-    shr = 0.3 * rnd(2 * C, seed=9)
-    act = torch.cat([rnd(B * R * C, seed=4) * 1.5 + 0.3, torch.zeros(B * R * C)])
-    op = rt.MdtOp()
-    op.kind = rt.OP_GN_ACT
-    op.a, op.out, op.p0, op.p1 = ref(A, 0), ref(A, R * C), ref(W, 0), ref(W, C)
-    if film:
-        op.p3 = ref(S, 0)
-    op.i[rt.N_ROWS], op.i[rt.N_LD], op.i[rt.N_GROUPS], op.i[rt.N_GSIZE], op.i[rt.N_SILU] = R, C, G, C // G, int(silu)
-    op.f[0] = eps
+    c = cases.gn_act(B, R, C, G, film, silu, eps)
+    op, weights, act, shr = c.ops[0], c.weights, c.act, c.shr
     (ga, _, _), (ca, _, _) = run_both([op], weights, act, shr, {}, B)
     assert (ga - ca).abs().max() < 2e-5
     x = act[: B * R * C].view(B, R, C).transpose(1, 2)
@@ -1015,20 +915,8 @@ def test_gn_act_on_two_sources_with_raw_copy(B, R, C, G):
     """MDT_OP_GN_ACT, round 6: the input is cat([a, SCALE2 * a2]) read from its two sources (the up path's ResnetBlock1d, plain-bf16
     mode), the normalised + SiLU output is bf16 and a raw bf16 copy of the input goes to p2 -- every kernel form (one workgroup per
     (sample, group) / per sample, 256 / 1024 threads) against the interpreter and torch's GroupNorm on the concatenated tensor."""
-    ld = 2 * C
-    weights = torch.cat([1 + 0.1 * rnd(ld, seed=2), 0.1 * rnd(ld, seed=3)])
-    # per-sample arena (floats): [a (R C) | a2 (R C) | y16 (R ld / 2) | raw16 (R ld / 2)]
-    aoff, boff, yoff = 0, R * C, 2 * R * C
-    roff = yoff + R * ld // 2
-    act = torch.zeros(B * (roff + R * ld // 2))
-    xa, xb = rnd(B * R * C, seed=4) * 1.5 + 0.3, rnd(B * R * C, seed=5) * 0.8 - 0.2
-    act[: B * R * C], act[B * boff: B * yoff] = xa, xb
-    op = rt.MdtOp()
-    op.kind = rt.OP_GN_ACT
-    op.a, op.a2, op.out, op.p0, op.p1, op.p2 = ref(A, aoff), ref(A, boff), ref(A, yoff), ref(W, 0), ref(W, ld), ref(A, roff)
-    i = op.i
-    i[rt.N_ROWS], i[rt.N_LD], i[rt.N_GROUPS], i[rt.N_GSIZE], i[rt.N_SILU], i[rt.N_OUT16], i[rt.N_CA] = R, ld, G, ld // G, 1, 1, C
-    op.f[0], op.f[1] = 1e-5, 0.7071
+    c = cases.gn_act_two_sources(B, R, C, G)
+    op, weights, act, xa, xb, ld, yoff, roff = c.ops[0], c.weights, c.act, c.xa, c.xb, c.ld, c.yoff, c.roff
     (ga, _, _), (ca, _, _) = run_both([op], weights, act, torch.zeros(4), {}, B)
     assert torch.equal(ga[: B * yoff], act[: B * yoff])                                   # the sources are untouched
     yg, yc = ga[B * yoff: B * roff].view(torch.bfloat16).float(), ca[B * yoff: B * roff].view(torch.bfloat16).float()
@@ -1049,18 +937,9 @@ def test_gn_act_on_two_sources_with_raw_copy(B, R, C, G):
 def test_row_stationary_conv_two_sources(C, T, B, taps, gsize, silu, in_scale2, prod):
     """k_rconv on a concatenated input that is never materialised: prologue + taps for source a, then for source b,
     into the same accumulators (second exchange barrier, fragment-set rotation between the sources)."""
-    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
-    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
-    comp = UNetCompiler(inverse_unet_config(16, 64, 128, 12), 64, 12, {})
-    w = rnd(C, 2 * C, taps, seed=1, scale=(2 * C * taps) ** -0.5)
-    gb = torch.cat([1 + 0.1 * rnd(2 * C, seed=2), 0.1 * rnd(2 * C, seed=3), 0.1 * rnd(C, seed=5)])   # gain | beta | conv bias
-    g_off = comp.W.add("gb", gb)
-    xa, out, xb = Ten(A, 0, T, C), Ten(A, T * C, T, C), Ten(A, 2 * T * C, T, C)
-    comp.rconv(xa, w, "w", out, taps=taps, bias_off=g_off + 4 * C,
-               gn=(g_off, g_off + 2 * C, gsize, 1e-5, silu) if gsize else None, x2=xb, in_scale2=in_scale2)
-    op = comp.ops[0]
-    act = torch.cat([rnd(B * T * C, seed=4) * 1.5 + 0.3, rnd(B * T * C, seed=6), rnd(B * T * C, seed=7) * 0.8 - 0.2])
-    (ga, _, _), (ca, _, _) = run_both([op], comp.W.pack(), act, torch.zeros(4), {}, B)
+    c = cases.ring_conv_two_sources(C, T, B, taps, gsize, silu, in_scale2, prod)
+    op, weights, act, w, gb = c.ops[0], c.weights, c.act, c.w, c.gb
+    (ga, _, _), (ca, _, _) = run_both([op], weights, act, torch.zeros(4), {}, B)
     og, oc = ga[B * T * C: 2 * B * T * C], ca[B * T * C: 2 * B * T * C]
     scale = max(1.0, oc.abs().max().item())
     assert torch.isfinite(og).all() and (og - oc).abs().max() < 1e-4 * scale, (og - oc).abs().max().item()
@@ -1086,23 +965,9 @@ def test_row_stationary_conv_two_sources(C, T, B, taps, gsize, silu, in_scale2, 
 def test_row_stationary_conv(C, T, B, taps, gsize, film, silu, res, in_scale, prod):
     """k_rconv (GroupNorm + FiLM + SiLU prologue, DPP-shifted taps, loader-wave weight ring) against the interpreter
     and against torch's group_norm / conv1d."""
-    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
-    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
-    comp = UNetCompiler(inverse_unet_config(16, 64, 128, 12), 64, 12, {})
-    w = rnd(C, C, taps, seed=1, scale=(C * taps) ** -0.5)
-    gb = torch.cat([1 + 0.1 * rnd(C, seed=2), 0.1 * rnd(C, seed=3), 0.1 * rnd(C, seed=5)])   # gain | beta | conv bias
-    g_off = comp.W.add("gb", gb)
-    x, out, other = Ten(A, 0, T, C), Ten(A, T * C, T, C), Ten(A, 2 * T * C, T, C)
-    eps = 1e-6 if taps == 1 else 1e-5
-    comp.rconv(x, w, "w", out, taps=taps, bias_off=None if res == "accumulate" else g_off + 2 * C,
-               res={"other": other, "accumulate": out, None: None}[res],
-               gn=(g_off, g_off + C, gsize, eps, silu) if gsize else None, in_scale=in_scale)
-    op = comp.ops[0]
-    if film:
-        op.p3 = ref(S, 0)
-    shr = 0.3 * rnd(2 * C, seed=9)
-    act = torch.cat([rnd(B * T * C, seed=4) * 1.5 + 0.3, rnd(B * T * C, seed=6), rnd(B * T * C, seed=7)])
-    (ga, _, _), (ca, _, _) = run_both([op], comp.W.pack(), act, shr, {}, B)
+    c = cases.ring_conv(C, T, B, taps, gsize, film, silu, res, in_scale, prod)
+    op, weights, act, shr, w, gb, eps = c.ops[0], c.weights, c.act, c.shr, c.w, c.gb, c.eps
+    (ga, _, _), (ca, _, _) = run_both([op], weights, act, shr, {}, B)
     og, oc = ga[B * T * C: 2 * B * T * C], ca[B * T * C: 2 * B * T * C]
     scale = max(1.0, oc.abs().max().item())
     assert torch.isfinite(og).all() and (og - oc).abs().max() < 1e-4 * scale, (og - oc).abs().max().item()
@@ -1123,43 +988,6 @@ def test_row_stationary_conv(C, T, B, taps, gsize, film, silu, res, in_scale, pr
     assert (og.view(B, T, C) - y).abs().max() < 1e-4 * scale
 
 
-def _resblock_case(cin, cout, film):
-    """One MDT_OP_RESBLOCK op with seeded weights + the closed form of the reference block (modules.py:145-205)."""
-    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
-    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
-    p = "blk."
-    sd = {p + "block1.groupnorm.weight": 1 + 0.1 * rnd(cin, seed=1), p + "block1.groupnorm.bias": 0.1 * rnd(cin, seed=2),
-          p + "block1.project.weight": rnd(cout, cin, 3, seed=3, scale=(3 * cin) ** -0.5),
-          p + "block1.project.bias": 0.1 * rnd(cout, seed=4),
-          p + "block2.groupnorm.weight": 1 + 0.1 * rnd(cout, seed=5), p + "block2.groupnorm.bias": 0.1 * rnd(cout, seed=6),
-          p + "block2.project.weight": rnd(cout, cout, 3, seed=7, scale=(3 * cout) ** -0.5),
-          p + "block2.project.bias": 0.1 * rnd(cout, seed=8),
-          p + "to_out.weight": rnd(cout, cin, 1, seed=9, scale=cin ** -0.5), p + "to_out.bias": 0.1 * rnd(cout, seed=10)}
-    comp = UNetCompiler(inverse_unet_config(16, 64, 128, 12), 64, 12, sd)
-    cin_p, cout_p = (cin + 15) // 16 * 16, (cout + 15) // 16 * 16        # the op works on channel counts padded to 16
-    x = Ten(A, 0, 64, cin_p, cin)
-    assert comp.resblock_ok(64, cin, cout, 1, p)
-    y = comp.resnet(x, p, cin, cout, 1, free_input=False)
-    assert len(comp.ops) == 1 and comp.ops[0].kind == rt.OP_RESBLOCK
-    op = comp.ops[0]
-    op.out = ref(A, 64 * cin_p)
-    op.p3 = ref(S, 0) if film else ref(0, 0)
-    shr = torch.zeros(2 * cout_p)                      # [scale(cout_p) | shift(cout_p)], zero on the padding
-    shr[:cout], shr[cout_p: cout_p + cout] = 0.3 * rnd(cout, seed=11), 0.3 * rnd(cout, seed=12)
-
-    def closed_form(xin):                              # xin [B, 64, cin]
-        F = torch.nn.functional
-        xt = xin.transpose(1, 2)
-        h = F.conv1d(F.silu(F.group_norm(xt, 1, sd[p + "block1.groupnorm.weight"], sd[p + "block1.groupnorm.bias"], 1e-5)),
-                     sd[p + "block1.project.weight"], sd[p + "block1.project.bias"], padding=1)
-        h = F.group_norm(h, 1, sd[p + "block2.groupnorm.weight"], sd[p + "block2.groupnorm.bias"], 1e-5)
-        if film:
-            h = h * (shr[:cout].view(1, cout, 1) + 1) + shr[cout_p: cout_p + cout].view(1, cout, 1)
-        yt = F.conv1d(F.silu(h), sd[p + "block2.project.weight"], sd[p + "block2.project.bias"], padding=1)
-        return (yt + F.conv1d(xt, sd[p + "to_out.weight"], sd[p + "to_out.bias"])).transpose(1, 2)
-    return comp, op, shr, closed_form
-
-
 @pytest.mark.parametrize("cin,cout", [(16, 64), (64, 16), (16, 16), (2, 16), (16, 1), (8, 16), (16, 8), (5, 50)])
 @pytest.mark.parametrize("B,film", [(1, True), (2, False), (7, True), (1030, True)])
 def test_fused_resnet_block(cin, cout, B, film, prod):
@@ -1167,7 +995,7 @@ def test_fused_resnet_block(cin, cout, B, film, prod):
     samples wrap the persistent loop) against the interpreter and against torch's group_norm / conv1d.  Channel counts that
     are not multiples of 16 (QMDiffusionForward: 2 -> 16 and 16 -> 1; AnalogDiffusionFull: 8 -> 16, 16 -> 8) run padded, with
     the GroupNorm statistics over the real channels only and exact zeros on the padding of the output."""
-    comp, op, shr, closed_form = _resblock_case(cin, cout, film)
+    comp, op, shr, closed_form, _ = cases.resblock_case(cin, cout, film, prod)
     cin_p, cout_p = (cin + 15) // 16 * 16, (cout + 15) // 16 * 16
     n_in, n_out = B * 64 * cin_p, B * 64 * cout_p
     xin = torch.zeros(B, 64, cin_p)
@@ -1191,7 +1019,7 @@ def test_fused_resnet_block_with_folded_patch_rearranges(cin, cout, pin, pout, B
     (modules.py:208-257) as the load / store pattern of k_resblock, op by op against the interpreter AND against the closed form
     with the rearrange applied by torch: odd B (half a workgroup idle, the B - 1 clamp of the two-samples-per-workgroup tail),
     1030 samples (the persistent loop wraps), p in {2, 4}, padded channel counts together with patching."""
-    comp, op, shr, closed_form = _resblock_case(cin, cout, True)
+    comp, op, shr, closed_form, _ = cases.resblock_case(cin, cout, True, prod)
     op.i[rt.K_PATCH_IN], op.i[rt.K_PATCH_OUT] = pin, pout
     cin_p, cout_p = (cin + 15) // 16 * 16, (cout + 15) // 16 * 16
     n_in, n_out = B * 64 * cin_p, B * 64 * cout_p
@@ -1251,33 +1079,7 @@ def test_chained_split_sub_block(mode, split, with_pin, T, B, prod):
     assert torch.equal(ga[lo + B * n_x: lo + 2 * B * n_x], ca[lo + B * n_x: lo + 2 * B * n_x])   # p_in untouched
 
 
-def _transformer_sd(p, C, layers, cross, ctx=128, mid=512, seed0=100):
-    """Random Transformer1d parameters with the reference's key names (modules.py:469-524)."""
-    k = [seed0]
-
-    def r(*shape, scale=1.0):
-        k[0] += 1
-        return rnd(*shape, seed=k[0], scale=scale)
-    sd = {p + "to_in.0.weight": 1 + 0.2 * r(C), p + "to_in.0.bias": 0.2 * r(C),
-          p + "to_in.1.weight": r(C, C, 1, scale=C ** -0.5), p + "to_in.1.bias": 0.1 * r(C),
-          p + "to_out.1.weight": r(C, C, 1, scale=C ** -0.5), p + "to_out.1.bias": 0.1 * r(C)}
-    for li in range(layers):
-        for name, cf in (("attention.", C),) + ((("cross_attention.", ctx),) if cross else ()):
-            q = p + f"blocks.{li}." + name
-            sd.update({q + "norm.weight": 1 + 0.2 * r(C), q + "norm.bias": 0.2 * r(C),
-                       q + "norm_context.weight": 1 + 0.2 * r(cf), q + "norm_context.bias": 0.2 * r(cf),
-                       q + "to_q.weight": r(mid, C, scale=C ** -0.5), q + "to_kv.weight": r(2 * mid, cf, scale=cf ** -0.5),
-                       q + "attention.to_out.weight": r(C, mid, scale=mid ** -0.5), q + "attention.to_out.bias": 0.1 * r(C)})
-        q = p + f"blocks.{li}.feed_forward."
-        sd.update({q + "0.weight": r(2 * C, C, scale=C ** -0.5), q + "0.bias": 0.1 * r(2 * C),
-                   q + "2.weight": r(C, 2 * C, scale=(2 * C) ** -0.5), q + "2.bias": 0.1 * r(C)})
-    return sd
-
-
-def _handoff_ext(B, T):
-    """bindings.ext[3] / [4] of a pair-split MDT_OP_TF256: zeroed flag words, hand-off blocks (engine.py sizes them alike)."""
-    nrb = (B * T + 31) // 32
-    return {3: torch.zeros(64 + 64 * nrb), 4: torch.zeros(2 * nrb * 2 * 32 * 256)}
+_transformer_sd, _handoff_ext, _resnet_sd = cases.transformer_sd, cases.handoff_ext, cases.resnet_sd
 
 
 @pytest.mark.parametrize("form", ["whole", "pair8", pytest.param("pair1", marks=pytest.mark.slow)])    # (pair1 at model level: the pair-stride switch test)
@@ -1436,18 +1238,6 @@ def test_pair_handoff_is_placement_independent_and_repeatable(T, B, layers, cros
     assert (gaw[B * T * C: 2 * B * T * C] - outs[0].cpu()).abs().max() < tol
 
 
-def _resnet_sd(p, c, cin, seed0):
-    r = lambda *sh, seed, scale=1.0: rnd(*sh, seed=seed0 + seed, scale=scale)   # noqa: E731
-    sd = {p + "block1.groupnorm.weight": 1 + 0.2 * r(cin, seed=1), p + "block1.groupnorm.bias": 0.2 * r(cin, seed=2),
-          p + "block1.project.weight": r(c, cin, 3, seed=3, scale=(3 * cin) ** -0.5), p + "block1.project.bias": 0.1 * r(c, seed=4),
-          p + "block2.groupnorm.weight": 1 + 0.2 * r(c, seed=5), p + "block2.groupnorm.bias": 0.2 * r(c, seed=6),
-          p + "block2.project.weight": r(c, c, 3, seed=7, scale=(3 * c) ** -0.5), p + "block2.project.bias": 0.1 * r(c, seed=8)}
-    if cin != c:
-        sd[p + "to_out.weight"] = r(c, cin, 1, seed=9, scale=cin ** -0.5)
-        sd[p + "to_out.bias"] = 0.1 * r(c, seed=10)
-    return sd
-
-
 @pytest.mark.parametrize("kind,T,B,n_res,layers,cross", [
     (1, 16, 5, 3, 0, False),      # down path: the blocks alone, outputs stored as skips
     (1, 16, 70, 1, 1, True),      # ... and in front of a transformer with cross-attention
@@ -1462,37 +1252,11 @@ def test_resnet_blocks_inside_the_transformer_launch(kind, T, B, n_res, layers, 
     of the transformer in one launch, against (i) the CPU interpreter of the op and (ii) the reference's module arithmetic
     (modules.py:145-205: GroupNorm -> [FiLM] -> SiLU -> Conv1d(k = 3), twice, + to_out(x) | x; :828-829: cat with the scaled
     skip).  Kind 1 also stores every block's output; kind 2 reads its skips in reverse order."""
-    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
-    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
     import torch.nn.functional as F
-    C, n_ctx, mid, G = 128, 12, 512, 8
-    cfg = inverse_unet_config(16, 64, 128, n_ctx)
-    p = "tf."
-    sd = _transformer_sd(p, C, max(layers, 1), cross)
-    blocks = [f"res{k}." for k in range(n_res)]
-    for k, bp in enumerate(blocks):
-        sd.update(_resnet_sd(bp, C, C if kind == 1 else 2 * C, 100 * (k + 1)))
-    comp = UNetCompiler(cfg, 64, n_ctx, sd)
-    assert all(comp.res128_ok(bp, C, T, G, kind == 2) for bp in blocks) and comp.tf128_ok(C, T, layers, cross, kind, n_res)
-    # per-sample arena: [x | y | skip 0 .. n_res-1 | K/V layers]
-    x, y = Ten(A, 0, T, C), Ten(A, T * C, T, C)
-    skips = [Ten(A, (2 + k) * T * C, T, C) for k in range(n_res)]
-    if kind == 2:
-        skips = skips[::-1]                  # consumed from the highest address downwards
-    comp.transformer_fused128(x, p, C, layers, cross, False, res=(kind, blocks, G, skips, 2 ** -0.5), y=y)
-    op = comp.ops[0]
-    assert op.kind == rt.OP_TF128 and len(comp.ops) == 1
-    film_off = 64
-    op.p3 = ref(S, film_off)
-    kv_floats = n_ctx * 2 * mid
-    if cross:
-        op.a2 = ref(A, (2 + n_res) * T * C)
-    act_x = rnd(B * T * C, seed=13) * 1.5 + 0.3
-    sk_in = rnd(n_res * B * T * C, seed=16) * 1.2 - 0.1 if kind == 2 else torch.zeros(n_res * B * T * C)
-    kv_all = rnd(layers * B * kv_floats, seed=14) if cross else torch.zeros(0)
-    act = torch.cat([act_x, torch.zeros(B * T * C), sk_in, kv_all])
-    shr = torch.cat([torch.zeros(film_off), 0.3 * rnd(n_res * 2 * C, seed=15), torch.zeros(256)])
-    (ga, _, _), (ca, _, _) = run_both([op], comp.W.pack(), act, shr, {}, B)
+    c = cases.resnets_in_tf128(kind, T, B, n_res, layers, cross, prod)
+    op, weights, act, shr, sd, blocks, C, G = c.ops[0], c.weights, c.act, c.shr, c.sd, c.blocks, c.C, c.G
+    act_x, sk_in, film_off = c.act_x, c.sk_in, cases.FILM_OFF
+    (ga, _, _), (ca, _, _) = run_both([op], weights, act, shr, {}, B)
     n = B * T * C
     yg, yc = ga[n: 2 * n].view(B, T, C), ca[n: 2 * n].view(B, T, C)
     assert torch.isfinite(yg).all()
@@ -1544,44 +1308,18 @@ def test_resnet_chain_256(kind, T, B, n_res, form, prod, monkeypatch):
     PAIR-SPLIT chain (NSPLIT = 2: half hh streams output chunks 2 hh, 2 hh + 1 of every convolution, the pair hands its chunks to each
     other inside the launch) with the partners 8 workgroup ids apart or neighbours -- the result must not depend on the placement
     and equals the unsplit chain's BIT FOR BIT (every output channel is the same MFMA sequence)."""
-    from moleculediffusiontransformer_amd.compiler import Ten, UNetCompiler
-    from moleculediffusiontransformer_amd.netspec import inverse_unet_config
     import torch.nn.functional as F
     monkeypatch.setenv("MDT_RES256", "1")
-    C, G = 256, 8
-    cfg = inverse_unet_config(16, 64, 128, 12)
-    blocks = [f"res{k}." for k in range(n_res)]
-    sd = {}
-    for k, bp in enumerate(blocks):
-        sd.update(_resnet_sd(bp, C, C if kind == 1 else 2 * C, 100 * (k + 1)))
-    comp = UNetCompiler(cfg, 64, 12, sd, gemm_mode="f32" if prod == "f32" else "bf16x3")
-    assert all(comp.res256_ok(bp, C, T, G, kind == 2) for bp in blocks)
-    # per-sample arena: [x | y | skip 0 .. n_res-1]
-    x, y = Ten(A, 0, T, C), Ten(A, T * C, T, C)
-    skips = [Ten(A, (2 + k) * T * C, T, C) for k in range(n_res)]
-    if kind == 2:
-        skips = skips[::-1]                  # consumed from the highest address downwards
-    comp.pair_stride = 1 if form == "pair1" else 8
-    comp.resnet_chain256(x, blocks, kind, skips, 2 ** -0.5, y, False, nsplit=1 if form == "whole" else 2)
-    op = comp.ops[0]
-    assert op.kind == rt.OP_RES256 and len(comp.ops) == 1 and op.i[rt.F_NPOST] == (1 if T == 1 else 3)
-    assert op.i[rt.F_NSPLIT] == (0 if form == "whole" else 2)
-    ext = {} if form == "whole" else _handoff_ext(B, T)
-    film_off = 64
-    op.p3 = ref(S, film_off)
-    act_x = rnd(B * T * C, seed=13) * 1.5 + 0.3
-    sk_in = rnd(n_res * B * T * C, seed=16) * 1.2 - 0.1 if kind == 2 else torch.zeros(n_res * B * T * C)
-    act = torch.cat([act_x, torch.zeros(B * T * C), sk_in])
-    shr = torch.cat([torch.zeros(film_off), 0.3 * rnd(n_res * 2 * C, seed=15), torch.zeros(256)])
-    (ga, _, ge), (ca, _, _) = run_both([op], comp.W.pack(), act, shr, ext, B)
+    c = cases.resnet_chain256(kind, T, B, n_res, form, prod)
+    op, weights, act, shr, ext, sd, blocks, C, G = c.ops[0], c.weights, c.act, c.shr, c.ext, c.sd, c.blocks, c.C, c.G
+    act_x, sk_in, film_off = c.act_x, c.sk_in, cases.FILM_OFF
+    (ga, _, ge), (ca, _, _) = run_both([op], weights, act, shr, ext, B)
     n = B * T * C
     if form != "whole":
         assert int(ge[3].view(torch.int32)[0]) == 0                 # no hand-off poll timed out
         # the unsplit chain on the same inputs: bitwise equal
-        comp1 = UNetCompiler(cfg, 64, 12, sd, gemm_mode="f32" if prod == "f32" else "bf16x3")
-        comp1.resnet_chain256(x, blocks, kind, skips, 2 ** -0.5, y, False, nsplit=1)
-        comp1.ops[0].p3 = ref(S, film_off)
-        (gw, _, _), _ = run_both([comp1.ops[0]], comp1.W.pack(), act, shr, {}, B)
+        op1, weights1 = c.unsplit()
+        (gw, _, _), _ = run_both([op1], weights1, act, shr, {}, B)
         assert torch.equal(ga, gw)
     yg, yc = ga[n: 2 * n].view(B, T, C), ca[n: 2 * n].view(B, T, C)
     assert torch.isfinite(yg).all()
@@ -1594,7 +1332,7 @@ def test_resnet_chain_256(kind, T, B, n_res, form, prod, monkeypatch):
     else:
         assert torch.equal(ga[2 * n: (2 + n_res) * n], sk_in)
     # repeated launches return the same bits
-    (gb, _, _), _ = run_both([op], comp.W.pack(), act, shr, ext, B)
+    (gb, _, _), _ = run_both([op], weights, act, shr, ext, B)
     assert torch.equal(ga, gb)
     # ---- the reference's arithmetic ----
     h = act_x.view(B, T, C).transpose(1, 2).double()

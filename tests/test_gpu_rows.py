@@ -294,7 +294,7 @@ def test_gn_act_with_one_film_row_per_sample(R, C, G, silu, eps):
 def test_groupnorm_prologue_with_one_film_row_per_sample(R, C, G, N, real, split):
     """The GroupNorm + FiLM + SiLU prologue of MDT_OP_GEMM (exact fp32: k_gemm; split-bf16: k_gemm3) with a FiLM batch stride:
     the blocks whose channel count is padded (`real` < C channels: gain / bias / weights zero on the padding) take it."""
-    from test_gpu_ops import _split_planes, gemm_op
+    from op_cases import gemm_op, split_planes as _split_planes
     B, taps, eps = 5, 3, 1e-5
     K = taps * C
     gs = real // G
