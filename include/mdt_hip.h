@@ -1130,6 +1130,75 @@ int mdt_screen_select_classes(const float *score, const uint64_t *key, const int
                               void *stream);
 
 /* ------------------------------------------------------------------ */
+/* Graph rows back to token rows (csrc/k_molwrite.hip, csrc/mdt_molwrite.h); additions inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* Everything above reads SMILES; these two entries write it.  mdt_mol_rank gives every atom a visiting priority that does not
+ * depend on how the row was numbered; mdt_mol_write spells graph arrays -- of mdt_mol_graph, mdt_mol_normalize, mdt_mol_scaffold or
+ * any other producer -- as a token row that mdt_mol_graph reads back to the same graph, so that a scaffold or a normal form can be
+ * looked at as a string and fed to the entries that take token ids.
+ *
+ * mdt_mol_rank.  Inputs (device pointers), R rows of width 1 <= L <= 64: the four graph arrays.  Output: priority uint64 (R,L).
+ *  1. The rooted refinement of mdt_mol_key, unchanged: for every root r, lab_r[a] after the n rounds and H_r = the sum over the
+ *     atoms of mix(lab_r[a]).
+ *  2. The components of the ring graph of mdt_mol_rings (pairs a != b named by an entry).
+ *  3. For each component c, r*(c) = the root in c with the smallest (H_r, r).
+ *  4. priority[a] = lab_{r*(comp(a))}[a].
+ *  5. Words beyond natoms, and rows that are no molecule by the rule of mdt_mol_key, are 0.
+ *  One root per component, not one per row: with a single root two cubanes in one row would be labelled as seen from one of
+ *  them, and the row would be spelled differently under renumbering.
+ *
+ * mdt_mol_write.  Inputs: the four graph arrays; priority uint64 (R,L) or NULL (all priorities equal: the atom index alone orders
+ * the visit, "as numbered"); class_id uint8 (128), entry c the token id that stands for class c of mdt_smiles_check's class table,
+ * 0: the vocabulary has no such character; the output width 1 <= W <= 128.  Outputs, every word defined: tokens int32 (R,W), the T
+ * tokens at 0..T-1 and zero after; length int32 (R); token_atom uint8 (R,W); flags uint8 (R).
+ * No molecule.  A row that is no molecule (the rule of mdt_mol_key; natoms == 0 included) has every output 0.
+ * Not writable, MDT_MOLW_NOT_WRITABLE (8), every other output 0: an entry (a, a); a pair named by two entries; an order outside
+ *  1..5; an H field (bits 17..20) above 9; a charge field (bits 12..16) outside 0..18; a letter field (bits 0..4, bits 5..9) above 26.
+ * The key of atom a is (priority[a], a).  Neighbours and start atoms are taken in ascending key.
+ * Pass 1, the spanning forest.  While an atom is unvisited, a depth-first walk starts at the unvisited atom of the smallest key;
+ *  seq[a] counts the atoms in the order they are first reached.  At atom a its neighbours b != parent(a) are gone through in
+ *  ascending key: b unvisited when its turn comes is a child of a (in that order) and is walked at once; b visited with seq[b] <
+ *  seq[a]: the entry is a ring closure that OPENS at b and CLOSES at a; b visited with seq[b] > seq[a]: nothing, that closure was
+ *  recorded from the other side.
+ * Pass 2, the emission: the components in the order their roots were started, separated by '.'.  emit(a) writes, in this order,
+ *  (1) the atom text; (2) for the closures that close at a, in ascending seq of their opening atom, that closure's number; (3) for
+ *  the closures that open at a, in ascending seq of their closing atom, the bond symbol if one is needed, then the lowest free number
+ *  in 1..99 (no row reaches 64); (4) for every child c in order: all but the last as '(' symbol emit(c) ')', the last as symbol
+ *  emit(c).  The numbers closed at a become free only after a's own numbers are written.  A number below 10 is one digit, otherwise
+ *  '%' and two digits.
+ * The bond symbol: none when the order is 1 and not both atoms are aromatic (bit 10), or when it is 5 and both are; otherwise
+ *  - = # $ : for the orders 1 to 5 -- the exact inverse of mdt_mol_graph's rule.  A closure's symbol stands at its opening end only.
+ * The atom text.  The symbol is the first letter (upper case, lower case when bit 10 is set, '*' for 26) and, when the second field
+ *  is not 0, the lower-case letter it names.  With bit 11 clear, a charge field of 9 or 0, H 0, isotope 0 and a symbol among B C N O P
+ *  S F I Cl Br * b c n o p s the text is the symbol alone.  Otherwise it is '[' the isotope in decimal when it is not 0, the symbol,
+ *  'H' for H == 1 or 'H' and the digit for 2..9, the charge as '+' / '-' alone for one unit or with the digit for 2..9 (field - 9;
+ *  a field of 9 or 0 writes nothing), ']'.  Chirality and atom class do not exist in the graph, so none is written.
+ * T is the token count.  The flags, exactly one for a molecule, in this precedence: 8 as above; MDT_MOLW_NO_VOCABULARY (4) class_id
+ *  is 0 for a class the text needs; MDT_MOLW_NO_FIT (2) T > W; MDT_MOLW_WRITTEN (1) none of these.  With 4 and with 2 tokens and
+ *  token_atom are all 0 and length = T.
+ * token_atom is 1 + the atom a token belongs to, and 0 for '.' and beyond T: an atom's text and every ring token after it (symbol,
+ *  '%', digits) belong to that atom; a bond symbol before an atom belongs to that atom; '(' and its ')' belong to the first atom
+ *  inside.
+ * What the writer promises.  For a written row whose unbracketed atoms pass mdt_smiles_check's valence rule, mdt_mol_graph of the
+ * written tokens has status 0; its atom words equal the input's, in the order the atoms first appear in token_atom; its bonds are
+ * the input's under that renumbering; hence it has the same mdt_mol_key.  With mdt_mol_rank's priority the row depends on the
+ * numbering only through ties of priority that the index then breaks: on the 2,000 random spellings of the tests every graph got one
+ * row, and so did every molecule of a table of symmetric ones (cubane, adamantane, pyrene, two cubanes in one row) under 24
+ * renumberings each.
+ * What it does NOT promise: a canonical form (ties are broken by index, not by search); RDKit's canonical SMILES; stereo; a
+ * preferred Kekule structure; rows wider than 128 tokens.
+ * Every loop of the kernel is bounded by natoms, nbonds or W (n compares, three passes over the entries, two scalar walks of at
+ * most 2 natoms and natoms + nbonds steps), so there is no step cap.  R == 0 launches nothing and reads nothing.  The cost is in
+ * DESIGN.md section 6. */
+enum mdt_molw_flag { MDT_MOLW_WRITTEN = 1, MDT_MOLW_NO_FIT = 2, MDT_MOLW_NO_VOCABULARY = 4, MDT_MOLW_NOT_WRITABLE = 8 };
+enum { MDT_MOLW_MAX_WIDTH = 128 };
+int mdt_mol_rank(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+                 uint64_t *priority, void *stream);
+int mdt_mol_write(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds,
+                  const uint64_t *priority, int32_t L, int32_t R, const uint8_t *class_id, int32_t W, int32_t *tokens,
+                  int32_t *length, uint8_t *token_atom, uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */
 /* ------------------------------------------------------------------ */
 typedef struct mdt_timer mdt_timer;

@@ -872,6 +872,7 @@ MAX_SCREEN_PROPERTIES = 64
 MAX_EDIT_LENGTH = 64            # the edit distance (csrc/k_edit.hip): one 64-bit word per row, one mask per id
 MAX_EDIT_ID = 64
 MAX_MOL_LENGTH = 64             # the molecular graph and its key (csrc/k_molgraph.hip): at most 64 atoms, one root per lane
+MAX_WRITE_WIDTH = rt.MOLW_MAX_WIDTH    # the SMILES writer (csrc/k_molwrite.hip): written rows of at most 128 tokens
 IDENTITIES = ("string", "graph")
 FP_SIM_DEN = 65536              # a similarity threshold crosses into the kernels as sim_num / 65536 (MDT_FP_SIM_DEN)
 MAX_SUB_PATTERNS = 32           # the substructure match (csrc/k_molsub.hip): patterns a call, one bit of a 32-bit word each
@@ -1478,7 +1479,9 @@ class SmilesVocabulary:
     ``max_valence``: overrides of the default maxima B 3, C 4, N 3, O 2, P 5, S 6, F 1, Cl 1, Br 1, I 1, e.g. ``{"N": 5}``; other
     keys, or values outside 0..8, are refused.
     ``classes`` uint8 (256), ``max_valence`` uint8 (10), ``elements`` int32 (26): numpy, the tables of mdt_smiles_check
-    (include/mdt_hip.h).  The device copy is made on first use and cached, one per device."""
+    (include/mdt_hip.h).  ``class_id`` uint8 (128): the other way round for mol_write() -- the id that encodes each class of
+    ``classes``, 0 where no character of the vocabulary has it; of two ids for one character the lower one encodes, as in encode().
+    The device copies are made on first use and cached, one per device."""
 
     def __init__(self, chars, max_valence=None):
         import numpy as np
@@ -1514,7 +1517,12 @@ class SmilesVocabulary:
         self._ids = {}
         for i in sorted(self.chars):
             self._ids.setdefault(self.chars[i], i)                         # (of two ids for one character the lower encodes)
+        self.class_id = np.zeros(128, np.uint8)
+        for i in sorted(self.chars, reverse=True):
+            if self.classes[i]:
+                self.class_id[self.classes[i]] = i
         self._on = {}
+        self._class_id_on = {}
 
     def __len__(self) -> int:
         return len(self.chars)
@@ -1556,6 +1564,15 @@ class SmilesVocabulary:
         if device not in self._on:
             self._on[device] = tuple(torch.from_numpy(a).to(device) for a in (self.classes, self.max_valence, self.elements))
         return self._on[device]
+
+    def class_id_on(self, device):
+        """``class_id`` uint8 (128) on ``device``."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._class_id_on:
+            self._class_id_on[device] = torch.from_numpy(self.class_id).to(device)
+        return self._class_id_on[device]
 
 
 def _vocabulary_arg(vocabulary, length: int) -> None:
@@ -2292,6 +2309,142 @@ def scaffold_key(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: b
     Sequence: mol_scaffold()'s, then mdt::mol_key."""
     out, status, position = _scaffold_of(tokens, vocabulary, device, normalize, exocyclic, generic)
     return torch.ops.mdt.mol_key(*out[:4]), out[5].long(), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# graph rows back to token rows: the SMILES writer (csrc/k_molwrite.hip): rows of at most 64 atoms, written rows of at most 128 tokens
+# ----------------------------------------------------------------------------------------------------------------------
+def _width_arg(width, default: int) -> int:
+    """The refusals of ``width=`` -> the width of the written rows."""
+    if width is None:
+        return default
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= MAX_WRITE_WIDTH:
+        raise ValueError(f"width must be an int in 1..{MAX_WRITE_WIDTH} or None, got {width!r} (wider rows are out of scope)")
+    return width
+
+
+def _invariant_arg(invariant) -> None:
+    if not isinstance(invariant, bool):
+        raise ValueError(f"invariant must be True or False, got {invariant!r}")
+
+
+def _write(graph, vocabulary, device, width, invariant):
+    """mdt::mol_rank (only with ``invariant``) -> mdt::mol_write on device graph arrays"""
+    priority = torch.ops.mdt.mol_rank(*graph) if invariant else None
+    return torch.ops.mdt.mol_write(*graph, priority, vocabulary.class_id_on(torch.device(device)), width)
+
+
+def mol_write(natoms, atoms, nbonds, bonds, vocabulary: "SmilesVocabulary", device, *, width: int, invariant: bool = True):
+    """Graph arrays back to SMILES token rows -> (tokens int64 (R, width), length int64 (R,), token_atom int64 (R, width), flags
+    int64 (R,)).  The four graph arrays may come from any producer -- mol_graph(), mol_normalize(), mol_scaffold(), the ops behind
+    them, or your own -- as integer tensors in mol_graph()'s format, (R,) counts and (R, L) words, L <= 64.
+
+    ``tokens[r, :length[r]]`` spells row r in the ids of ``vocabulary`` (``vocabulary.decode`` gives the string), zero after;
+    ``token_atom`` is 1 + the atom each token belongs to (an atom's text and its ring numbers; a bond symbol, '(' and ')' go with
+    the atom they lead to), 0 for '.' and for padding.  ``flags``: 1 written; 2 the row needs ``length`` > ``width`` tokens; 4 the
+    vocabulary lacks a character the row needs ('%' for a tenth open ring, '[' for a bracket atom, ...); 8 the arrays are not
+    writable (an entry (a, a), a pair of atoms named by two entries, an order outside 1..5, an atom word no scan writes); 0 no
+    molecule.  With anything but 1 the tokens are all zero.
+    The walk is a depth-first one that takes start atoms and neighbours in ascending (priority, index), ring numbers from the
+    lowest free one, bond symbols only where mol_graph() would read another order; mdt_mol_write in include/mdt_hip.h has every
+    rule.  ``invariant=True`` takes the priority from the refinement behind mol_key() (one root per dotted component), so that
+    the row depends on the numbering of the atoms only through ties the index then breaks: the four random spellings of each of
+    the 500 graphs of the tests come out as one row.  ``invariant=False`` visits the atoms as numbered: a row written this way
+    reads back to the same numbering.
+    What it promises: mol_graph() of a written row whose unbracketed atoms pass smiles_check()'s valence rule has status 0, the
+    same atom words in the order the atoms appear, the same bonds, hence the same mol_key().
+    What it is NOT: NOT RDKit's canonical SMILES and not a canonical form at all -- ties are broken by index, not by search, so
+    two numberings of a symmetric molecule CAN give two rows (coronene does; none of the 30 molecules of the tests' symmetric
+    table did).  No stereo (the graph
+    has none), no preferred Kekule structure (orders are written as handed in), no rows wider than 128 tokens.
+    Refused with ValueError before anything is launched: arrays that are not integer (R,) / (R, L) tensors of matching shapes,
+    L > 64, ``width`` outside 1..128.  Sequence: mdt::mol_rank (only with ``invariant=True``) -> mdt::mol_write."""
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    _invariant_arg(invariant)
+    if width is None:
+        raise ValueError("width must be given: the graph arrays do not say how wide the rows were")
+    width = _width_arg(width, 0)
+    arrays = []
+    for name, t in (("natoms", natoms), ("atoms", atoms), ("nbonds", nbonds), ("bonds", bonds)):
+        if not isinstance(t, Tensor) or t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"{name} must be an integer tensor")
+        arrays.append(t)
+    natoms, atoms, nbonds, bonds = arrays
+    if atoms.dim() != 2 or bonds.shape != atoms.shape or natoms.shape != atoms.shape[:1] or nbonds.shape != atoms.shape[:1]:
+        raise ValueError("atoms and bonds must be (R, L) with one natoms and one nbonds per row")
+    if not 1 <= atoms.shape[1] <= MAX_MOL_LENGTH:
+        raise ValueError(f"atoms has rows of {atoms.shape[1]} positions; the writer takes 1 to {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
+    device = torch.device(device)
+    graph = tuple(t.to(device).to(torch.int32) for t in (natoms, atoms, nbonds, bonds))   # (the low 32 bits: the words as written)
+    tokens, length, token_atom, flags = _write(graph, vocabulary, device, width, invariant)
+    return tokens.long(), length.long(), token_atom.long(), flags.long()
+
+
+def mol_respell(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, invariant: bool = True, width=None):
+    """One spelling per molecule -> (tokens int64 (R, width), flags int64 (R,), status int64 (R,), position int64 (R,)) for raw
+    (R, L) ids of any integer dtype, zeros anywhere: the graph behind each row (mol_graph()), written again by mol_write().  With
+    ``invariant=True`` two rows that spell one graph -- another start atom, branch order, ring numbers, %nn, an explicit '-', the
+    order of dotted components -- come back as the same row, so generated molecules can be stored and deduplicated as strings.
+    ``normalize=True`` spells the normal form of mol_normalize(): every atom in brackets with its hydrogens, aromaticity as
+    perceived there, so that [CH4] and C, c1ccccc1 and C1=CC=CC=C1 come back as one row (a much longer one).
+    ``status`` / ``position`` are smiles_check()'s; ``flags`` are mol_write()'s: 1 written, 2 too long for ``width`` (default: the
+    input's L), 4 the vocabulary lacks a character, 0 no molecule (status != 0 or empty); rows of flags != 1 are all zero.  108 of
+    the 2,000 random spellings of the tests come back longer than they went in, none beyond 55 tokens.
+    NOT RDKit's canonical SMILES and not a canonical form: see mol_write() for what is promised and what is not.
+    L <= 64; the refusals are mol_key()'s and ``width`` outside 1..128, with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_rank (only with ``invariant=True``) -> mdt::mol_write; with
+    ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize go after mdt::mol_graph."""
+    _normalize_arg(normalize)
+    _invariant_arg(invariant)
+    tok = _integer_ids(tokens, "tokens")
+    width = _width_arg(width, tok.shape[1])
+    packed, n = _mol_rows(tok, vocabulary, device)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    out, _, _, flags = _write(graph, vocabulary, device, width, invariant)
+    return out.long(), flags.long(), status.long(), position.long()
+
+
+def scaffold_tokens(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True,
+                    generic: bool = False, width=None):
+    """The scaffold of each row as a row the model and a chemist can read -> (tokens int64 (R, width), flags int64 (R,),
+    scaffold_flags int64 (R,), status int64 (R,), position int64 (R,)): mol_scaffold() (whose keywords this takes; see there for
+    what a scaffold is and is not -- not RDKit's MurckoScaffold), written by mol_write() with ``invariant=True``, so that two
+    decorations of one ring system give the same row.  ``flags`` are mol_write()'s (1 written; 0 for a row without a scaffold,
+    whose tokens are all zero), ``scaffold_flags`` mol_scaffold()'s, ``status`` / ``position`` smiles_check()'s.  ``width``
+    defaults to the input's L.  The spelling is NOT RDKit's canonical SMILES and not a canonical form (mol_write()).
+    Sequence: mol_scaffold()'s, then mdt::mol_rank -> mdt::mol_write."""
+    tok = _integer_ids(tokens, "tokens")
+    width = _width_arg(width, tok.shape[1])
+    out, status, position = _scaffold_of(tok, vocabulary, device, normalize, exocyclic, generic)
+    written, _, _, flags = _write(out[:4], vocabulary, device, width, True)
+    return written.long(), flags.long(), out[5].long(), status.long(), position.long()
+
+
+def scaffold_keep(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True, width=None):
+    """A lead respelled, and the mask of its scaffold's tokens -> (tokens int64 (R, width), keep_mask bool (R, width), flags int64
+    (R,), status int64 (R,), position int64 (R,)).  ``tokens`` is mol_respell()'s row (``invariant=True``; with ``normalize`` the
+    normal form); ``keep_mask`` is True exactly at the tokens that belong to an atom of the scaffold (mol_scaffold() with the same
+    ``normalize`` / ``exocyclic``): the atom's text, its ring numbers, and the bond symbol and parentheses that lead to it.  This is
+    the mask refine_keep_tokens(keep_mask=) takes: refine a lead around its kept ring system.  A row without a scaffold, or one
+    that was not written (``flags`` != 1), has an all-False mask.  What leads from a kept atom to a pruned one -- '(' , a bond
+    symbol, ')' -- goes with the pruned atom and is not kept.
+    The limits are mol_write()'s (NOT RDKit's canonical SMILES) and mol_scaffold()'s (not RDKit's MurckoScaffold).
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_scaffold -> mdt::mol_rank -> mdt::mol_write, with
+    ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize after mdt::mol_graph; the mask is torch on the
+    two ops' outputs, no kernel of its own."""
+    _normalize_arg(normalize)
+    mode = _scaffold_mode(exocyclic, False)
+    tok = _integer_ids(tokens, "tokens")
+    width = _width_arg(width, tok.shape[1])
+    packed, n = _mol_rows(tok, vocabulary, device)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    atom_map = torch.ops.mdt.mol_scaffold(*graph, mode)[4]
+    written, _, token_atom, flags = _write(graph, vocabulary, device, width, True)
+    kept = torch.cat([torch.zeros_like(atom_map[:, :1]), atom_map], dim=1) != 0          # (R, 1 + L): column 0 is "no atom"
+    keep_mask = torch.gather(kept, 1, token_atom.long())
+    return written.long(), keep_mask, flags.long(), status.long(), position.long()
 
 
 # ----------------------------------------------------------------------------------------------------------------------

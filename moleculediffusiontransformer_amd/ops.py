@@ -21,6 +21,8 @@ fake / meta tensors).
     smiles_check        well-formedness and valence of compacted id rows: status 0 / 32 / 64 and a position (csrc/k_smiles.hip)
     mol_graph / mol_key / key_flags   the molecular graph behind a row, its spelling-invariant 64-bit key, and the duplicate / known
                         flags by that key (csrc/k_molgraph.hip)
+    mol_rank / mol_write   graph arrays back to token rows: a numbering-invariant visiting priority per atom, and the SMILES writer
+                        that walks in its order (csrc/k_molwrite.hip)
     edit_distance       Levenshtein distance between compacted id rows, row by row (csrc/k_edit.hip)
     edit_nearest        per row the nearest row of a known set: its distance and its (lowest) index
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
@@ -1111,6 +1113,86 @@ def _(natoms, atoms, nbonds, bonds, mode):
     R, L = atoms.shape
     return (atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, dtype=torch.int32),
             atoms.new_empty(R, L, dtype=torch.int32), atoms.new_empty(R, L, dtype=torch.uint8), atoms.new_empty(R, dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# graph rows back to token rows (csrc/k_molwrite.hip): rows of at most 64 positions, written rows of at most 128 tokens
+def _graph_arrays(op, natoms, atoms, nbonds, bonds, what):
+    if atoms.dim() != 2 or tuple(bonds.shape) != tuple(atoms.shape) or any(t.dtype != torch.int32 for t in (natoms, atoms, nbonds, bonds)):
+        raise RuntimeError(f"{op}: atoms and bonds must be int32 (R, L), natoms and nbonds int32 (as mdt::mol_graph returns them)")
+    R, L = atoms.shape
+    if natoms.numel() != R or nbonds.numel() != R:
+        raise RuntimeError(f"{op}: natoms and nbonds must hold one value per row of atoms")
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, {what} takes 1 to {rt.MOL_MAX_LENGTH}")
+    return R, L
+
+
+@custom_op("mdt::mol_rank", mutates_args=())
+def mol_rank(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor) -> Tensor:
+    """-> priority int64 (R, L): the uint64 bits of mdt_mol_rank (include/mdt_hip.h) for graph arrays in mdt::mol_graph's format --
+    per atom the label it has in mdt::mol_key's refinement under the root of its component whose rooted hash is the smallest (ties:
+    the lowest index): a visiting priority that does not depend on the numbering.  0 beyond natoms and for a row that is no
+    molecule."""
+    dev = _hip(natoms, atoms, nbonds, bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_rank"
+    R, L = _graph_arrays(op, natoms, atoms, nbonds, bonds, "the priority")
+    natoms, atoms, nbonds, bonds = (t.contiguous() for t in (natoms, atoms, nbonds, bonds))
+    priority = torch.zeros(R, L, dtype=torch.int64, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_rank(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, rt.ptr(priority),
+                                      rt.current_stream()))
+    return priority
+
+
+@mol_rank.register_fake
+def _(natoms, atoms, nbonds, bonds):
+    return atoms.new_empty(atoms.shape, dtype=torch.int64)
+
+
+@custom_op("mdt::mol_write", mutates_args=())
+def mol_write(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, priority: Optional[Tensor], class_id: Tensor,
+              width: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (tokens int32 (R, W), length int32 (R,), token_atom uint8 (R, W), flags uint8 (R,)) of mdt_mol_write (include/mdt_hip.h):
+    graph arrays in mdt::mol_graph's format spelled as SMILES token rows of ``width`` = W positions, zero after the ``length``
+    tokens.  priority: int64 (R, L) as mdt::mol_rank returns it, or None: the atoms are visited as numbered.  class_id: uint8
+    (128,), the token id of every class of mdt::smiles_check's class table, 0 for none.  token_atom: 1 + the atom a token belongs
+    to, 0 for a dot.  flags: 1 written; 2 length > W; 4 the vocabulary lacks a class the row needs; 8 not writable (an entry
+    (a, a), a pair named twice, an order outside 1..5, an atom word mdt::mol_graph cannot have written); with 2, 4 and 8 the tokens
+    are all zero.  Not a canonical form and not RDKit's canonical SMILES."""
+    dev = _hip(natoms, atoms, nbonds, bonds, priority, class_id)
+    lib = rt.load_library()
+    op = "mdt::mol_write"
+    R, L = _graph_arrays(op, natoms, atoms, nbonds, bonds, "the writer")
+    if not 1 <= width <= rt.MOLW_MAX_WIDTH:
+        raise RuntimeError(f"{op}: width = {width}, the writer writes rows of 1 to {rt.MOLW_MAX_WIDTH} tokens")
+    if priority is not None and (priority.dtype != torch.int64 or tuple(priority.shape) != (R, L)):
+        raise RuntimeError(f"{op}: priority must be int64 (R, L) (as mdt::mol_rank returns it) or None")
+    if class_id.dtype != torch.uint8 or tuple(class_id.shape) != (128,):
+        raise RuntimeError(f"{op}: class_id must be uint8 (128,)")
+    natoms, atoms, nbonds, bonds = (t.contiguous() for t in (natoms, atoms, nbonds, bonds))
+    priority = None if priority is None else priority.contiguous()
+    class_id = class_id.contiguous()
+    W = int(width)
+    tokens = torch.zeros(R, W, dtype=torch.int32, device=dev)
+    length = torch.zeros(R, dtype=torch.int32, device=dev)
+    token_atom = torch.zeros(R, W, dtype=torch.uint8, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_write(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), rt.ptr(priority), L, R,
+                                       rt.ptr(class_id), W, rt.ptr(tokens), rt.ptr(length), rt.ptr(token_atom), rt.ptr(flags),
+                                       rt.current_stream()))
+    return tokens, length, token_atom, flags
+
+
+@mol_write.register_fake
+def _(natoms, atoms, nbonds, bonds, priority, class_id, width):
+    R = atoms.shape[0]
+    return (atoms.new_empty(R, width, dtype=torch.int32), atoms.new_empty(R, dtype=torch.int32),
+            atoms.new_empty(R, width, dtype=torch.uint8), atoms.new_empty(R, dtype=torch.uint8))
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -60,6 +60,8 @@ MOLR_DESC = 16                               # mdt_mol_rings: words of a descrip
 MOLN_NORMALIZED, MOLN_AROMATIC, MOLN_CHANGED = 1, 2, 4    # enum mdt_moln_flag: the flags of mdt_mol_normalize
 MOLS_EXOCYCLIC, MOLS_GENERIC = 1, 2          # enum mdt_mols_mode: the mode bits of mdt_mol_scaffold
 MOLS_MOLECULE, MOLS_SCAFFOLD, MOLS_WHOLE = 1, 2, 4        # enum mdt_mols_flag: its flags
+MOLW_WRITTEN, MOLW_NO_FIT, MOLW_NO_VOCABULARY, MOLW_NOT_WRITABLE = 1, 2, 4, 8    # enum mdt_molw_flag: the flags of mdt_mol_write
+MOLW_MAX_WIDTH = 128             # MDT_MOLW_MAX_WIDTH: mdt_mol_write writes rows of at most 128 tokens
 FP_KNOWN_CHUNK = 512             # MDT_FP_KNOWN_CHUNK: known rows of one workgroup of mdt_fp_nearest
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
@@ -142,6 +144,8 @@ SYMBOLS = {
     "mdt_mol_rings": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_normalize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mdt_mol_scaffold": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mdt_mol_rank": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "mdt_mol_write": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "mdt_screen_select_classes": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P,
                                        _P]),
     "mdt_edit_distance_rows": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
