@@ -1185,7 +1185,8 @@ int mdt_screen_select_classes(const float *score, const uint64_t *key, const int
  * numbering only through ties of priority that the index then breaks: on the 2,000 random spellings of the tests every graph got one
  * row, and so did every molecule of a table of symmetric ones (cubane, adamantane, pyrene, two cubanes in one row) under 24
  * renumberings each.
- * What it does NOT promise: a canonical form (ties are broken by index, not by search); RDKit's canonical SMILES; stereo; a
+ * What it does NOT promise: with mdt_mol_rank's priority, a canonical form (ties are broken by index, not by search -- with
+ * mdt_mol_canon's priority, below, a decided row has ONE spelling under every numbering); RDKit's canonical SMILES; stereo; a
  * preferred Kekule structure; rows wider than 128 tokens.
  * Every loop of the kernel is bounded by natoms, nbonds or W (n compares, three passes over the entries, two scalar walks of at
  * most 2 natoms and natoms + nbonds steps), so there is no step cap.  R == 0 launches nothing and reads nothing.  The cost is in
@@ -1197,6 +1198,55 @@ int mdt_mol_rank(const int32_t *natoms, const uint32_t *atoms, const int32_t *nb
 int mdt_mol_write(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds,
                   const uint64_t *priority, int32_t L, int32_t R, const uint8_t *class_id, int32_t W, int32_t *tokens,
                   int32_t *length, uint8_t *token_atom, uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* The canonical atom order (csrc/k_molcanon.hip, csrc/mdt_molcanon.h); an addition inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* mdt_mol_key is a hash and mdt_mol_rank breaks its ties by index; this entry SEARCHES: an individualisation-refinement tree over
+ * the refinement of mdt_mol_key, the smallest relabelled graph as the answer.  Two rows are the same molecular graph exactly when
+ * their canon_atoms and canon_bonds (and counts) are equal, and mdt_mol_write with this priority spells a row the same way under
+ * every numbering.
+ *
+ * Inputs (device pointers), R rows of width 1 <= L <= 64: the four graph arrays.  A row that is no molecule by the rule of
+ * mdt_mol_key has every output 0.  n = natoms, mix, ROOT and the rounds are mdt_mol_key's.
+ * Refinement with marks m_0 .. m_{k-1} (distinct atoms): lab[a] = mix(atoms[a]); then lab[m_j] = mix(mix(atoms[m_j]) ^ (ROOT + j));
+ *  then the n rounds of mdt_mol_key, unchanged.  With k = 1 these are the labels behind H_root.
+ * Components are mdt_mol_rank's: pairs a != b named by an entry.  The search runs once per component C; all marks lie in C, and
+ *  the labels come from refining the whole row.
+ * A node is a mark list; the root's is empty.  The unmarked atoms of C are grouped by their label after the node's refinement (a
+ *  marked atom stands alone, so a path never marks an atom twice and is at most |C| - 1 marks long).  A class is a TWIN CLASS when
+ *  every member is named by exactly one entry of the row (an entry (a, a) names a twice), all those entries lead to the same other
+ *  atom with the same order, and all members have the same atom word: swapping twins is an automorphism, so twin classes are never
+ *  searched.  The node's TARGET is the class with the smallest label value among the classes of at least 2 members that are not
+ *  twin classes.  With no target the node is a LEAF; otherwise it has one child per member of the target, the mark list extended
+ *  by that member.
+ * The certificate of a leaf: the atoms of C in ascending (label, index) -- only twins can tie -- take the positions 0..|C|-1; the
+ *  certificate is the integer sequence |C|, the atom words in position order, the number of entries inside C, those entries as
+ *  (lo position, hi position, order) in ascending order.  Certificates compare lexicographically, and the compare is on the
+ *  certificates themselves, never on a hash of them: that is what makes the identity exact.
+ * The canonical order of C is the position assignment of a leaf with the smallest certificate; all such leaves give the same
+ *  relabelled graph, and of several the one whose positions, read in ascending atom index, are the smallest sequence is taken, so
+ *  that the answer does not depend on the order in which the leaves are met.  The components are placed in ascending
+ *  (certificate, lowest atom index); the canonical position of an atom is the number of atoms of the components before its own plus
+ *  its position.  Every quantity in this rule is a sum or a label value that cannot depend on the numbering; ties by index happen
+ *  only between twins, between leaves of one certificate and between components of one certificate, where they cannot change the
+ *  relabelled graph.
+ * The cap.  nodes is the number of nodes over the row's components, roots included; there is no pruning, so it is exact.  A row
+ *  with nodes <= MDT_MOLC_MAX_NODES (4096, the step cap of the other searches) is decided.  Every node that is no leaf has at least
+ *  2 children, so nodes < 2 x leaves: a row of at most 2,048 leaves is always decided, whatever the hash values.
+ * Outputs, every word defined: priority uint64 (R,L), 1 + the canonical position, 0 beyond natoms -- mdt_mol_write's type, so that
+ *  it is handed to mdt_mol_write as it is; canon_atoms uint32 (R,L), the atom words in canonical position, 0 beyond natoms;
+ *  canon_bonds uint32 (R,L), the entries lo | hi << 8 | order << 16 in canonical positions, ascending in (lo, hi, order), 0 beyond
+ *  nbonds; nodes int32 (R); flags uint8 (R): MDT_MOLC_CANONICAL (1); MDT_MOLC_UNDECIDED (2), the cap was passed: priority,
+ *  canon_atoms and canon_bonds are all 0 and nodes is some value above the cap; 0, no molecule.
+ * What it does NOT promise: RDKit's canonical SMILES or its atom order; stereo; a preferred Kekule structure (orders are compared as
+ * handed in); anything for an undecided row; automorphism pruning (hexaphenylethane, 4,608 leaves, is undecided).
+ * Every loop of the kernel is bounded by natoms, nbonds, 64 or the cap.  R == 0 launches nothing and reads nothing.  The cost is in
+ * DESIGN.md section 6. */
+enum mdt_molc_flag { MDT_MOLC_CANONICAL = 1, MDT_MOLC_UNDECIDED = 2 };
+enum { MDT_MOLC_MAX_NODES = 4096 };
+int mdt_mol_canon(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+                  uint64_t *priority, uint32_t *canon_atoms, uint32_t *canon_bonds, int32_t *nodes, uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */

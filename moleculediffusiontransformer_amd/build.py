@@ -51,6 +51,7 @@ SOURCES = [
     ("k_molnorm.hip", []),
     ("k_molscaf.hip", []),
     ("k_molwrite.hip", []),
+    ("k_molcanon.hip", []),
     ("mdt_api.cpp", ["-x", "hip"]),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

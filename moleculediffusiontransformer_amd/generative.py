@@ -2328,13 +2328,25 @@ def _invariant_arg(invariant) -> None:
         raise ValueError(f"invariant must be True or False, got {invariant!r}")
 
 
-def _write(graph, vocabulary, device, width, invariant):
-    """mdt::mol_rank (only with ``invariant``) -> mdt::mol_write on device graph arrays"""
+def _canonical_arg(canonical, invariant) -> None:
+    if not isinstance(canonical, bool):
+        raise ValueError(f"canonical must be True or False, got {canonical!r}")
+    if canonical and not invariant:
+        raise ValueError("canonical=True needs invariant=True: the canonical order is a priority, invariant=False writes as numbered")
+
+
+def _write(graph, vocabulary, device, width, invariant, canonical=False):
+    """mdt::mol_rank (only with ``invariant``) -> mdt::mol_write on device graph arrays; with ``canonical`` mdt::mol_canon goes
+    between the two and its priority is taken wherever the row is decided (a torch.where on the flag: no synchronisation)"""
     priority = torch.ops.mdt.mol_rank(*graph) if invariant else None
+    if canonical:
+        searched, _, _, _, canon_flags = torch.ops.mdt.mol_canon(*graph)
+        priority = torch.where((canon_flags == rt.MOLC_CANONICAL)[:, None], searched, priority)
     return torch.ops.mdt.mol_write(*graph, priority, vocabulary.class_id_on(torch.device(device)), width)
 
 
-def mol_write(natoms, atoms, nbonds, bonds, vocabulary: "SmilesVocabulary", device, *, width: int, invariant: bool = True):
+def mol_write(natoms, atoms, nbonds, bonds, vocabulary: "SmilesVocabulary", device, *, width: int, invariant: bool = True,
+              canonical: bool = False):
     """Graph arrays back to SMILES token rows -> (tokens int64 (R, width), length int64 (R,), token_atom int64 (R, width), flags
     int64 (R,)).  The four graph arrays may come from any producer -- mol_graph(), mol_normalize(), mol_scaffold(), the ops behind
     them, or your own -- as integer tensors in mol_graph()'s format, (R,) counts and (R, L) words, L <= 64.
@@ -2353,15 +2365,23 @@ def mol_write(natoms, atoms, nbonds, bonds, vocabulary: "SmilesVocabulary", devi
     reads back to the same numbering.
     What it promises: mol_graph() of a written row whose unbracketed atoms pass smiles_check()'s valence rule has status 0, the
     same atom words in the order the atoms appear, the same bonds, hence the same mol_key().
-    What it is NOT: NOT RDKit's canonical SMILES and not a canonical form at all -- ties are broken by index, not by search, so
-    two numberings of a symmetric molecule CAN give two rows (coronene does; none of the 30 molecules of the tests' symmetric
-    table did).  No stereo (the graph
-    has none), no preferred Kekule structure (orders are written as handed in), no rows wider than 128 tokens.
+    What it is NOT: NOT RDKit's canonical SMILES, and with ``canonical=False`` not a canonical form at all -- ties are broken by
+    index, not by search, so two numberings of a symmetric molecule CAN give two rows (coronene does; none of the 30 molecules of
+    the tests' symmetric table did).  ``canonical=True`` (needs ``invariant=True``) takes the priority from the search of
+    mol_canon() instead: every row the search DECIDES is written the same way under every numbering of its atoms -- coronene gives
+    one row.  A row the search leaves undecided (more than 4,096 nodes: hexaphenylethane) is written with the priority of
+    ``canonical=False``; mol_canon() tells which rows those are.  THE COST: the search runs for every row, one wave a row, and
+    has no automorphism pruning -- about 1.6 passes of mdt::mol_rank on rows of ordinary generated molecules, but a row that runs
+    to the cap (hexaphenylethane) keeps its wave busy for about a second, alone on its compute unit, and a batch with many
+    such cage-like rows has not been measured: ask mol_canon() for ``nodes`` on a sample first.  Still not promised: RDKit's canonical SMILES, stereo (the graph
+    has none), a preferred Kekule structure (orders are written as handed in), undecided rows, rows wider than 128 tokens.
     Refused with ValueError before anything is launched: arrays that are not integer (R,) / (R, L) tensors of matching shapes,
-    L > 64, ``width`` outside 1..128.  Sequence: mdt::mol_rank (only with ``invariant=True``) -> mdt::mol_write."""
+    L > 64, ``width`` outside 1..128, ``canonical=True`` with ``invariant=False``.  Sequence: mdt::mol_rank (only with
+    ``invariant=True``) -> mdt::mol_canon (only with ``canonical=True``) -> mdt::mol_write."""
     if not isinstance(vocabulary, SmilesVocabulary):
         raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
     _invariant_arg(invariant)
+    _canonical_arg(canonical, invariant)
     if width is None:
         raise ValueError("width must be given: the graph arrays do not say how wide the rows were")
     width = _width_arg(width, 0)
@@ -2378,11 +2398,12 @@ def mol_write(natoms, atoms, nbonds, bonds, vocabulary: "SmilesVocabulary", devi
                          "(wider rows are out of scope)")
     device = torch.device(device)
     graph = tuple(t.to(device).to(torch.int32) for t in (natoms, atoms, nbonds, bonds))   # (the low 32 bits: the words as written)
-    tokens, length, token_atom, flags = _write(graph, vocabulary, device, width, invariant)
+    tokens, length, token_atom, flags = _write(graph, vocabulary, device, width, invariant, canonical)
     return tokens.long(), length.long(), token_atom.long(), flags.long()
 
 
-def mol_respell(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, invariant: bool = True, width=None):
+def mol_respell(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, invariant: bool = True, width=None,
+                canonical: bool = False):
     """One spelling per molecule -> (tokens int64 (R, width), flags int64 (R,), status int64 (R,), position int64 (R,)) for raw
     (R, L) ids of any integer dtype, zeros anywhere: the graph behind each row (mol_graph()), written again by mol_write().  With
     ``invariant=True`` two rows that spell one graph -- another start atom, branch order, ring numbers, %nn, an explicit '-', the
@@ -2392,37 +2413,49 @@ def mol_respell(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bo
     ``status`` / ``position`` are smiles_check()'s; ``flags`` are mol_write()'s: 1 written, 2 too long for ``width`` (default: the
     input's L), 4 the vocabulary lacks a character, 0 no molecule (status != 0 or empty); rows of flags != 1 are all zero.  108 of
     the 2,000 random spellings of the tests come back longer than they went in, none beyond 55 tokens.
-    NOT RDKit's canonical SMILES and not a canonical form: see mol_write() for what is promised and what is not.
-    L <= 64; the refusals are mol_key()'s and ``width`` outside 1..128, with ValueError before anything is launched.
-    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_rank (only with ``invariant=True``) -> mdt::mol_write; with
-    ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize go after mdt::mol_graph."""
+    NOT RDKit's canonical SMILES, and by default not a canonical form: two numberings of a symmetric molecule can come back as two
+    rows (coronene).  ``canonical=True`` (needs ``invariant=True``) takes the visiting order from the search of mol_canon(): every
+    row the search decides comes back as ONE row under every numbering; an undecided row (more than 4,096 nodes) comes back as
+    with ``canonical=False``.  The search costs about 1.6 passes of mdt::mol_rank on ordinary rows and up to about a second for
+    ONE row that runs to the cap (no automorphism pruning; many such rows in a batch are unmeasured): see mol_write().  Not
+    promised either way: RDKit's canonical SMILES, stereo, a preferred Kekule structure, undecided
+    rows; see mol_write().
+    L <= 64; the refusals are mol_key()'s, ``width`` outside 1..128 and ``canonical=True`` with ``invariant=False``, with
+    ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_rank (only with ``invariant=True``) -> mdt::mol_canon (only with
+    ``canonical=True``) -> mdt::mol_write; with ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize go
+    after mdt::mol_graph."""
     _normalize_arg(normalize)
     _invariant_arg(invariant)
+    _canonical_arg(canonical, invariant)
     tok = _integer_ids(tokens, "tokens")
     width = _width_arg(width, tok.shape[1])
     packed, n = _mol_rows(tok, vocabulary, device)
     graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
-    out, _, _, flags = _write(graph, vocabulary, device, width, invariant)
+    out, _, _, flags = _write(graph, vocabulary, device, width, invariant, canonical)
     return out.long(), flags.long(), status.long(), position.long()
 
 
 def scaffold_tokens(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True,
-                    generic: bool = False, width=None):
+                    generic: bool = False, width=None, canonical: bool = False):
     """The scaffold of each row as a row the model and a chemist can read -> (tokens int64 (R, width), flags int64 (R,),
     scaffold_flags int64 (R,), status int64 (R,), position int64 (R,)): mol_scaffold() (whose keywords this takes; see there for
     what a scaffold is and is not -- not RDKit's MurckoScaffold), written by mol_write() with ``invariant=True``, so that two
     decorations of one ring system give the same row.  ``flags`` are mol_write()'s (1 written; 0 for a row without a scaffold,
     whose tokens are all zero), ``scaffold_flags`` mol_scaffold()'s, ``status`` / ``position`` smiles_check()'s.  ``width``
-    defaults to the input's L.  The spelling is NOT RDKit's canonical SMILES and not a canonical form (mol_write()).
-    Sequence: mol_scaffold()'s, then mdt::mol_rank -> mdt::mol_write."""
+    defaults to the input's L.  The spelling is NOT RDKit's canonical SMILES and by default not a canonical form; with
+    ``canonical=True`` a scaffold whose search is decided has one row under every numbering (mol_write()).
+    Sequence: mol_scaffold()'s, then mdt::mol_rank -> mdt::mol_canon (only with ``canonical=True``) -> mdt::mol_write."""
+    _canonical_arg(canonical, True)
     tok = _integer_ids(tokens, "tokens")
     width = _width_arg(width, tok.shape[1])
     out, status, position = _scaffold_of(tok, vocabulary, device, normalize, exocyclic, generic)
-    written, _, _, flags = _write(out[:4], vocabulary, device, width, True)
+    written, _, _, flags = _write(out[:4], vocabulary, device, width, True, canonical)
     return written.long(), flags.long(), out[5].long(), status.long(), position.long()
 
 
-def scaffold_keep(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True, width=None):
+def scaffold_keep(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, exocyclic: bool = True, width=None,
+                  canonical: bool = False):
     """A lead respelled, and the mask of its scaffold's tokens -> (tokens int64 (R, width), keep_mask bool (R, width), flags int64
     (R,), status int64 (R,), position int64 (R,)).  ``tokens`` is mol_respell()'s row (``invariant=True``; with ``normalize`` the
     normal form); ``keep_mask`` is True exactly at the tokens that belong to an atom of the scaffold (mol_scaffold() with the same
@@ -2430,21 +2463,82 @@ def scaffold_keep(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: 
     the mask refine_keep_tokens(keep_mask=) takes: refine a lead around its kept ring system.  A row without a scaffold, or one
     that was not written (``flags`` != 1), has an all-False mask.  What leads from a kept atom to a pruned one -- '(' , a bond
     symbol, ')' -- goes with the pruned atom and is not kept.
-    The limits are mol_write()'s (NOT RDKit's canonical SMILES) and mol_scaffold()'s (not RDKit's MurckoScaffold).
-    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_scaffold -> mdt::mol_rank -> mdt::mol_write, with
+    The limits are mol_write()'s (NOT RDKit's canonical SMILES; ``canonical=True`` makes the respelled lead, and with it the mask,
+    the same under every numbering of a lead whose search is decided) and mol_scaffold()'s (not RDKit's MurckoScaffold).
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_scaffold -> mdt::mol_rank -> mdt::mol_canon (only with
+    ``canonical=True``) -> mdt::mol_write, with
     ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize after mdt::mol_graph; the mask is torch on the
     two ops' outputs, no kernel of its own."""
     _normalize_arg(normalize)
+    _canonical_arg(canonical, True)
     mode = _scaffold_mode(exocyclic, False)
     tok = _integer_ids(tokens, "tokens")
     width = _width_arg(width, tok.shape[1])
     packed, n = _mol_rows(tok, vocabulary, device)
     graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
     atom_map = torch.ops.mdt.mol_scaffold(*graph, mode)[4]
-    written, _, token_atom, flags = _write(graph, vocabulary, device, width, True)
+    written, _, token_atom, flags = _write(graph, vocabulary, device, width, True, canonical)
     kept = torch.cat([torch.zeros_like(atom_map[:, :1]), atom_map], dim=1) != 0          # (R, 1 + L): column 0 is "no atom"
     keep_mask = torch.gather(kept, 1, token_atom.long())
     return written.long(), keep_mask, flags.long(), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the canonical atom order (csrc/k_molcanon.hip): rows of at most 64 atoms, search trees of at most 4,096 nodes
+# ----------------------------------------------------------------------------------------------------------------------
+def _canon_rows(tokens, vocabulary, device, normalize):
+    """mol_canon()'s launches on raw ids -> (the op's five outputs, the graph arrays, status, position)"""
+    _normalize_arg(normalize)
+    packed, n = _mol_rows(tokens, vocabulary, device)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    return torch.ops.mdt.mol_canon(*graph), graph, status, position
+
+
+def mol_canon(tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False):
+    """The canonical atom order of each row -> (rank int64 (R, L), canon_atoms int64 (R, L), canon_bonds int64 (R, L), natoms int64
+    (R,), nbonds int64 (R,), flags int64 (R,), nodes int64 (R,), status int64 (R,), position int64 (R,)) for raw (R, L) ids of any
+    integer dtype, zeros anywhere: the graph behind each row (mol_graph(); with ``normalize=True`` its normal form,
+    mol_normalize()) relabelled by an individualisation-refinement SEARCH over mol_key()'s refinement, the smallest relabelled graph
+    as the answer.  ``rank[r, a]`` is 1 + the canonical position of atom a (0 beyond ``natoms``); ``canon_atoms`` are the atom words
+    in canonical position, ``canon_bonds`` the entries lo | hi << 8 | order << 16 in canonical positions, ascending, zero beyond the
+    counts.  ``flags``: 1 canonical; 2 undecided -- the search trees have more than 4,096 nodes (``nodes`` is then some value above
+    that), the three arrays are all zero; 0 no molecule (status != 0 or empty).  Two rows of flags 1 are the same molecular graph
+    EXACTLY when their counts, ``canon_atoms`` and ``canon_bonds`` are equal: the compare is on the relabelled graph itself, not on a
+    hash (mol_same() does it).  There is no automorphism pruning: cubane takes 81 nodes, dodecahedrane 201, hexaphenylbenzene 1,531;
+    hexaphenylethane (4,608 leaves) is undecided.  Not RDKit's canonical atom order; no stereo; orders are compared as written
+    (c1ccccc1 and C1=CC=CC=C1 differ unless ``normalize=True``).
+    L <= 64; the refusals are mol_key()'s, with ValueError before anything is launched.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::mol_canon; with ``normalize=True`` mdt::mol_hydrogens ->
+    mdt::mol_rings -> mdt::mol_normalize go after mdt::mol_graph."""
+    (rank, canon_atoms, canon_bonds, nodes, flags), graph, status, position = _canon_rows(tokens, vocabulary, device, normalize)
+    return (rank, canon_atoms.long() & 0xFFFFFFFF, canon_bonds.long() & 0xFFFFFFFF, graph[0].long(), graph[2].long(), flags.long(), nodes.long(),
+            status.long(), position.long())
+
+
+def mol_same(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False):
+    """Are row r of ``a_tokens`` and row r of ``b_tokens`` the same molecular graph, exactly?  -> (same bool (R,), undecided bool
+    (R,)) for raw ids of any integer dtype with the same number of rows (the widths may differ).  ``same`` compares the counts and
+    the canonical arrays of mol_canon(), so it is an identity test, not a hash compare.  A pair with an undecided side is
+    ``same = False, undecided = True``; two rows that are no molecule are not the same.
+    The refusals are mol_canon()'s and a different number of rows, with ValueError before anything is launched.
+    Sequence: mol_canon()'s for ``a_tokens``, then for ``b_tokens``; the compare is torch on the ops' outputs."""
+    _normalize_arg(normalize)
+    a, b = _integer_ids(a_tokens, "a_tokens"), _integer_ids(b_tokens, "b_tokens")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"a_tokens has {a.shape[0]} rows and b_tokens {b.shape[0]}: they are compared row by row")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    for name, t in (("a_tokens", a), ("b_tokens", b)):           # (both are refused before the first launch)
+        if not 1 <= t.shape[1] <= MAX_MOL_LENGTH:
+            raise ValueError(f"{name} has rows of {t.shape[1]} positions; the canonical order takes 1 to {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+    (_, xa, xb, _, fa), ga, _, _ = _canon_rows(a, vocabulary, device, normalize)
+    (_, ya, yb, _, fb), gb, _, _ = _canon_rows(b, vocabulary, device, normalize)
+    width = max(xa.shape[1], ya.shape[1])
+    pad = lambda t: torch.nn.functional.pad(t, (0, width - t.shape[1]))  # noqa: E731
+    decided = (fa == rt.MOLC_CANONICAL) & (fb == rt.MOLC_CANONICAL)
+    same = (decided & (ga[0] == gb[0]) & (ga[2] == gb[2]) & (pad(xa) == pad(ya)).all(dim=1) & (pad(xb) == pad(yb)).all(dim=1))
+    return same, (fa == rt.MOLC_UNDECIDED) | (fb == rt.MOLC_UNDECIDED)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

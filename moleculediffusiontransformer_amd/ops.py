@@ -23,6 +23,8 @@ fake / meta tensors).
                         flags by that key (csrc/k_molgraph.hip)
     mol_rank / mol_write   graph arrays back to token rows: a numbering-invariant visiting priority per atom, and the SMILES writer
                         that walks in its order (csrc/k_molwrite.hip)
+    mol_canon           the canonical atom order of graph arrays by an individualisation-refinement search: the priority that
+                        makes mol_write's row the same under every numbering, and the relabelled arrays (csrc/k_molcanon.hip)
     edit_distance       Levenshtein distance between compacted id rows, row by row (csrc/k_edit.hip)
     edit_nearest        per row the nearest row of a known set: its distance and its (lowest) index
     unet_eval           UNetCFG1d.forward: net(x, time, embedding=, embedding_scale=) (modules.py:1228-1255)
@@ -1150,6 +1152,38 @@ def mol_rank(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor) -> Te
 @mol_rank.register_fake
 def _(natoms, atoms, nbonds, bonds):
     return atoms.new_empty(atoms.shape, dtype=torch.int64)
+
+
+@custom_op("mdt::mol_canon", mutates_args=())
+def mol_canon(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (priority int64 (R, L), canon_atoms int32 (R, L), canon_bonds int32 (R, L), nodes int32 (R,), flags uint8 (R,)) of
+    mdt_mol_canon (include/mdt_hip.h) for graph arrays in mdt::mol_graph's format: 1 + the canonical position of every atom (what
+    mdt::mol_write takes as its priority), the row relabelled -- the atom words in canonical position and the entries lo | hi << 8 |
+    order << 16 in ascending (lo, hi, order), zero beyond the counts -- the nodes of the search trees, and flags: 1 canonical; 2
+    undecided, the search passed 4,096 nodes: the three arrays are all zero; 0 no molecule.  Two decided rows are the same
+    molecular graph exactly when their counts and relabelled arrays are equal."""
+    dev = _hip(natoms, atoms, nbonds, bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_canon"
+    R, L = _graph_arrays(op, natoms, atoms, nbonds, bonds, "the canonical order")
+    natoms, atoms, nbonds, bonds = (t.contiguous() for t in (natoms, atoms, nbonds, bonds))
+    priority = torch.empty(R, L, dtype=torch.int64, device=dev)           # (the kernel defines every word: no fill launches)
+    canon_atoms = torch.empty(R, L, dtype=torch.int32, device=dev)
+    canon_bonds = torch.empty(R, L, dtype=torch.int32, device=dev)
+    nodes = torch.empty(R, dtype=torch.int32, device=dev)
+    flags = torch.empty(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_canon(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, rt.ptr(priority),
+                                       rt.ptr(canon_atoms), rt.ptr(canon_bonds), rt.ptr(nodes), rt.ptr(flags), rt.current_stream()))
+    return priority, canon_atoms, canon_bonds, nodes, flags
+
+
+@mol_canon.register_fake
+def _(natoms, atoms, nbonds, bonds):
+    R = atoms.shape[0]
+    return (atoms.new_empty(atoms.shape, dtype=torch.int64), atoms.new_empty(atoms.shape, dtype=torch.int32),
+            atoms.new_empty(atoms.shape, dtype=torch.int32), atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, dtype=torch.uint8))
 
 
 @custom_op("mdt::mol_write", mutates_args=())

@@ -62,6 +62,8 @@ MOLS_EXOCYCLIC, MOLS_GENERIC = 1, 2          # enum mdt_mols_mode: the mode bits
 MOLS_MOLECULE, MOLS_SCAFFOLD, MOLS_WHOLE = 1, 2, 4        # enum mdt_mols_flag: its flags
 MOLW_WRITTEN, MOLW_NO_FIT, MOLW_NO_VOCABULARY, MOLW_NOT_WRITABLE = 1, 2, 4, 8    # enum mdt_molw_flag: the flags of mdt_mol_write
 MOLW_MAX_WIDTH = 128             # MDT_MOLW_MAX_WIDTH: mdt_mol_write writes rows of at most 128 tokens
+MOLC_CANONICAL, MOLC_UNDECIDED = 1, 2    # enum mdt_molc_flag: the flags of mdt_mol_canon
+MOLC_MAX_NODES = 4096            # MDT_MOLC_MAX_NODES: the node cap of mdt_mol_canon's search
 FP_KNOWN_CHUNK = 512             # MDT_FP_KNOWN_CHUNK: known rows of one workgroup of mdt_fp_nearest
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
@@ -145,6 +147,7 @@ SYMBOLS = {
     "mdt_mol_normalize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mdt_mol_scaffold": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_rank": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "mdt_mol_canon": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_write": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "mdt_screen_select_classes": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P,
                                        _P]),
