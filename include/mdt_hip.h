@@ -885,6 +885,41 @@ int mdt_sub_match(const int32_t *natoms, const uint32_t *atoms, const int32_t *n
                   int32_t LP, int32_t P, uint32_t need, uint32_t ban,
                   uint32_t *match, uint32_t *undecided, uint8_t *flags, void *stream);
 
+/* Which atoms match, and how often?  (mdt_sub_match returns no mapping; this call does.  An addition inside ABI version 5.)
+ * Everything up to the search is mdt_sub_match's, word for word: the inputs, the atom rule, the bond rule, the back-bonds, the
+ * candidates in ascending target index, and what is decided before any search.  It is as little SMARTS or RDKit's
+ * GetSubstructMatches as that call is, with the same limits (no implicit hydrogens, no aromaticity perception, no stereo).
+ * The enumeration.  Every root r in compat[0] runs the depth-first search of mdt_sub_match with f(0) = r to the END of its tree:
+ * when atom m - 1 is assigned the full map f is an EMBEDDING, it is counted, and the walk goes on at the same depth with the
+ * candidates above the one just taken.  Steps are counted as there, one per assignment f(p) = t, p >= 1, and the root is abandoned
+ * (capped) when step MDT_SUB_MAX_STEPS + 1 would be made.  A root ends with the number of embeddings it saw, and capped or not.  Up
+ * to its first success the walk and the step count are mdt_sub_match's, so "saw at least one embedding" is that call's success of
+ * the root and "capped and saw none" its abandoned root: bit q of match[r] is found[r][q] != 0, bit q of undecided[r] is
+ * found[r][q] == 0 && capped[r][q] != 0.  No root stops for another, so every root's end is defined whatever the scheduling.
+ * Outputs per (row r, pattern q), every word written, all zero for a pair decided "no match" before the search:
+ *  found uint64 (R,P)       bit t: root t saw an embedding -- the set of target atoms that can play pattern atom 0.
+ *  capped uint64 (R,P)      bit t: root t was abandoned.  A root can have both bits.
+ *  embeddings uint32 (R,P)  the maps seen over all roots; exact when capped == 0.
+ *  cover uint64 (R,P)       every target atom that lies in some embedding seen; exact when capped == 0.
+ *  map uint8 (R,P,LP)       1 + f(p) for the FIRST map of the LOWEST found root, 0 elsewhere and beyond m.  When no root below that
+ *                           one is capped it is the lexicographically smallest of all embeddings.
+ * A pattern of one atom: found = cover = compat[0], embeddings = popcount, map[0] = 1 + the lowest accepted atom.
+ * The count is of ANCHORS, not atom sets: popcount(found), the target atoms that can play pattern atom 0.  C(F)(F)F counts CF3
+ * carbons (6 embeddings each, one anchor); [N+](=O)[O-] counts nitro nitrogens; CC counts every carbon with a carbon neighbour, not
+ * the C-C bonds.  Write the fragment with its distinctive atom first.
+ * flags uint8 (R) or NULL, from count_lo / count_hi uint8 (P), both NULL or both given (flags needs them): with c =
+ * popcount(found) and u = popcount(capped & ~found), the flag is MDT_SCREEN_SUBSTRUCTURE unless for every q count_lo[q] <= c and
+ * c + u <= count_hi[q] -- conservative both ways: an abandoned root that saw nothing may be an anchor (it counts against the upper
+ * bound) or none (it does not count towards the lower).  c + u <= 64, so a count_hi of 64 or more is no upper bound.
+ * The refusals before any launch are mdt_sub_match's, and the two about count_lo / count_hi / flags.  R == 0 launches nothing.  The
+ * worst case is 64 roots of MDT_SUB_MAX_STEPS steps per pair, and once more for one of them (the first map is found by running the
+ * lowest found root's walk again, csrc/k_molsub.hip). */
+int mdt_sub_map(const int32_t *natoms, const uint32_t *atoms, const int32_t *nbonds, const uint32_t *bonds, int32_t L, int32_t R,
+                const int32_t *p_natoms, const uint32_t *p_atoms, const int32_t *p_nbonds, const uint32_t *p_bonds,
+                int32_t LP, int32_t P, const uint8_t *count_lo, const uint8_t *count_hi,
+                uint64_t *found, uint64_t *capped, uint32_t *embeddings, uint64_t *cover, uint8_t *map, uint8_t *flags,
+                void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Implicit hydrogens and a Kekule check (csrc/k_molh.hip, csrc/mdt_molh.h); additions inside ABI version 5 */
 /* ------------------------------------------------------------------ */

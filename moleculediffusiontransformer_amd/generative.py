@@ -1175,11 +1175,12 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
             forward_timesteps=100, X_norm_factor=1.0, forward_noise=None, sampler=None, sigma_schedule=None, min_distance=1,
             min_novelty=1, vocabulary=None, identity="string", max_similarity=None, max_known_similarity=None,
             fingerprint_radius=2, require=None, forbid=None, kekulize=False, limits=None, max_per_scaffold=None,
-            novel_scaffold=False, scaffold_exocyclic=True, scaffold_generic=False, normalize=False) -> Screened:
+            novel_scaffold=False, scaffold_exocyclic=True, scaffold_generic=False, normalize=False, counts=None) -> Screened:
     """screen_tokens and screen_tokens_diverse; with both filters at 1 this is screen_tokens' sequence, launch for launch.  With a
     ``vocabulary`` one mdt::smiles_check over the N * G rows goes in front of the selection, which takes its status as `reject`;
     with ``identity="graph"`` mdt::mol_graph -> mdt::mol_key -> mdt::key_flags follow it and their bits 4 / 8 are OR-ed into `reject`;
-    with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in; with ``kekulize`` one mdt::mol_hydrogens on the
+    with ``require`` / ``forbid`` one mdt::sub_match on the same graph ORs bit 128 in, and with ``counts`` one mdt::sub_map after it does;
+    with ``kekulize`` one mdt::mol_hydrogens on the
     same graph, right after mdt::mol_graph, ORs bit 64 in where its verdict is not 0; with ``limits`` one mdt::mol_rings after that
     mdt::mol_hydrogens (made once when both are asked for) ORs bit 128 in where a descriptor lies outside its bounds; with
     ``normalize`` one mdt::mol_normalize follows those two launches (made for it where nobody else asked) and mdt::mol_key,
@@ -1196,8 +1197,9 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
     _kekulize_arg(kekulize, vocabulary, width)
     _limits_arg(limits, vocabulary, width)
     scaffold_mode = _scaffold_args(max_per_scaffold, novel_scaffold, scaffold_exocyclic, scaffold_generic, vocabulary, known, width)
+    _counts_arg(counts, vocabulary, width)
     _screen_normalize_arg(normalize, vocabulary, width, identity == "graph" or sim_num is not None or known_sim_num is not None or
-                          fragments is not None or scaffold_mode is not None)
+                          fragments is not None or scaffold_mode is not None or counts is not None)
     device = torch.device(device)
     N, K = candidates, keep
     G, n = conditioning.shape
@@ -1236,6 +1238,10 @@ def _screen(model_forward, tokens, conditioning, device, candidates, keep, *, kn
         if graph is None:
             graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
         reject = reject | torch.ops.mdt.sub_match(*graph, *_joined_patterns(fragments[0], device), fragments[1], fragments[2])[2]
+    if counts is not None:                                       # how often does it contain the fragment?  bit 128, never kept
+        if graph is None:
+            graph = torch.ops.mdt.mol_graph(packed, length, *vocabulary.on(device))[:4]
+        reject = reject | torch.ops.mdt.sub_map(*graph, *counts.set.on(device), *counts.on(device))[5]
     fp = fp_count = None
     if sim_num is not None or known_sim_num is not None:         # how similar is it?  fingerprints of the graph, computed once
         if graph is None:
@@ -1315,7 +1321,7 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
                           keep: int, *, min_distance: int = 1, min_novelty: int = 1, vocabulary=None, identity: str = "string",
                           max_similarity=None, max_known_similarity=None, fingerprint_radius: int = 2, require=None, forbid=None,
                           kekulize: bool = False, limits=None, max_per_scaffold: Optional[int] = None, novel_scaffold: bool = False,
-                          scaffold_exocyclic: bool = True, scaffold_generic: bool = False, normalize: bool = False,
+                          scaffold_exocyclic: bool = True, scaffold_generic: bool = False, counts=None, normalize: bool = False,
                           **screen_tokens_kwargs) -> Screened:
     """screen_tokens (whose keyword arguments this takes) with "distinct" and "novel" measured in edits: the Levenshtein distance
     (insert, delete, substitute: 1 each) between the compacted id rows, i.e. between the molecules' strings -- and, with
@@ -1421,12 +1427,21 @@ def screen_tokens_diverse(model_forward: "QMDiffusionForward", tokens: Tensor, c
     into `reject` where the scaffold key is found in KnownSet.scaffold_keys() (computed once), so a new decoration of a known ring
     system counts as known.  Refusals come with ValueError before anything is launched.  With both at their defaults the call
     makes exactly the launches it makes without the keywords, in the same order.
+
+    ``counts``: a SubstructureCounts (None: not asked) -- how OFTEN a kept candidate may contain fragments: "at most one nitro
+    group", "at least two ring nitrogens".  What is counted is substructure_map()'s ``count`` (see there for the definition and
+    its limits: anchors, not atom sets -- the atoms that can play the pattern's first atom; not SMARTS, a step cap, no stereo).
+    It needs a ``vocabulary`` and rows of at most 64 positions, and counts as a consumer of ``normalize``.  One mdt::sub_map runs
+    over the N * G rows on the graph the other filters read (after mdt::sub_match when ``require`` / ``forbid`` are given too) and
+    ORs status bit 128 (runtime.SCREEN_SUBSTRUCTURE) into `reject` where a pattern's count lies outside its bounds; a start atom
+    abandoned at the step cap counts against the candidate both ways.  Such a candidate is never kept and pushes nothing out.  With
+    None the call makes exactly the launches it makes without the keyword, in the same order.
     Returns Screened, its six fields as screen_tokens'."""
     return _screen(model_forward, tokens, conditioning, device, candidates, keep, min_distance=min_distance, min_novelty=min_novelty,
                    vocabulary=vocabulary, identity=identity, max_similarity=max_similarity,
                    max_known_similarity=max_known_similarity, fingerprint_radius=fingerprint_radius, require=require, forbid=forbid,
                    kekulize=kekulize, limits=limits, max_per_scaffold=max_per_scaffold, novel_scaffold=novel_scaffold,
-                   scaffold_exocyclic=scaffold_exocyclic, scaffold_generic=scaffold_generic, normalize=normalize,
+                   scaffold_exocyclic=scaffold_exocyclic, scaffold_generic=scaffold_generic, normalize=normalize, counts=counts,
                    **screen_tokens_kwargs)
 
 
@@ -1923,7 +1938,7 @@ def has_substructure(tokens, patterns, vocabulary: "SmilesVocabulary", device):
     of small patterns and random molecules of up to 20 atoms; ``C.C.C.C.C.C.CN`` against 62 carbons and a lone N is.
     What it is NOT: not SMARTS and not RDKit's HasSubstructMatch.  There are no implicit hydrogens, so [CH4] does not accept C; no
     aromaticity perception, so c1ccccc1 is not found in C1=CC=CC=C1; no stereo, no recursive or logical atom expressions, and no
-    mapping is returned.  (has_substructure_normalized() matches against the normal form of the rows, which lifts the first two.)
+    mapping is returned (substructure_map() returns one, and counts).  (has_substructure_normalized() matches against the normal form of the rows, which lifts the first two.)
     The fingerprint of mol_fingerprint() is no pre-filter for this: an atom's degree enters its first
     round, so a fragment's bits are not a subset of its host's.
     L <= 64; non-integer ids, L < 1, L > 64, a vocabulary that is no SmilesVocabulary and patterns that SubstructureSet refuses
@@ -1946,7 +1961,10 @@ def has_substructure_normalized(tokens, patterns, vocabulary: "SmilesVocabulary"
     return _has_substructure(tokens, patterns, vocabulary, device, True)
 
 
-def _has_substructure(tokens, patterns, vocabulary, device, normalize):
+def _map_rows(tokens, patterns, vocabulary, normalize):
+    """The refusals of has_substructure(), substructure_map() and substructure_keep(), before anything is launched -> (ids, the
+    SubstructureSet)."""
+    _normalize_arg(normalize)
     tok = _integer_ids(tokens, "tokens")
     if not isinstance(vocabulary, SmilesVocabulary):
         raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
@@ -1955,13 +1973,169 @@ def _has_substructure(tokens, patterns, vocabulary, device, normalize):
     if tok.shape[1] > MAX_MOL_LENGTH:
         raise ValueError(f"tokens has rows of {tok.shape[1]} positions; the substructure match takes at most {MAX_MOL_LENGTH} "
                          "(wider rows are out of scope)")
-    fragments = _substructure_set(patterns, vocabulary, "patterns")
+    return tok, _substructure_set(patterns, vocabulary, "patterns")
+
+
+def _has_substructure(tokens, patterns, vocabulary, device, normalize):
+    tok, fragments = _map_rows(tokens, patterns, vocabulary, normalize)
     packed, n = _mol_rows(tok, vocabulary, device)
     graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
     match, undecided, _ = torch.ops.mdt.sub_match(*graph, *fragments.on(device), 0, 0)
     bit = torch.arange(len(fragments), device=match.device)
     spread = lambda word: ((word.long().unsqueeze(1) >> bit) & 1).bool()  # noqa: E731
     return spread(match), spread(undecided), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# which atoms match, and how often?  the enumeration behind the match (csrc/k_molsub.hip, k_sub_map)
+# ----------------------------------------------------------------------------------------------------------------------
+class SubstructureMap(NamedTuple):
+    """What substructure_map() returns."""
+    atom_map: Tensor      # (R, P, LP) int64: 1 + the row atom that pattern atom p maps to, 0 = none
+    count: Tensor         # (R, P) int64: the anchors, popcount of ``found``
+    found: Tensor         # (R, P, L) bool: the row atoms that can play pattern atom 0
+    cover: Tensor         # (R, P, L) bool: the row atoms that lie in some embedding seen
+    embeddings: Tensor    # (R, P) int64: the maps seen
+    undecided: Tensor     # (R, P) bool: some root ran into the step cap
+    status: Tensor        # (R,) int64, smiles_check()'s
+    position: Tensor      # (R,) int64, smiles_check()'s
+
+
+def _atom_bits(word, width: int):
+    """(..., ) int64 words, the uint64 bits -> (..., width) bool, bit t at position t"""
+    return ((word.unsqueeze(-1) >> torch.arange(width, device=word.device)) & 1).bool()
+
+
+def substructure_map(tokens, patterns, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False) -> SubstructureMap:
+    """Which atoms of each row match each fragment, and how often?  -> SubstructureMap(atom_map int64 (R, P, LP), count int64 (R, P),
+    found bool (R, P, L), cover bool (R, P, L), embeddings int64 (R, P), undecided bool (R, P), status int64 (R,), position int64
+    (R,)) for raw (R, L) ids and ``patterns`` as has_substructure() takes them (LP: the widest pattern's characters).
+
+    The definition is has_substructure()'s -- subgraph monomorphism on the graph of mol_graph(), pattern atoms in order of
+    appearance, candidates in ascending atom index -- but every start atom (root) runs its depth-first search to the END instead of
+    stopping at its first success; every full map met is an embedding.  mdt_sub_map in include/mdt_hip.h has every step.
+    ``found[r, q, t]``: atom t of row r can play the FIRST atom of pattern q.  ``count`` is how many atoms can: it counts
+    anchors, not atom sets.  C(F)(F)F counts CF3 carbons (each has 6 embeddings and is one anchor), [N+](=O)[O-] counts nitro
+    nitrogens, and CC counts the carbons with a carbon neighbour, not the C-C bonds: WRITE THE FRAGMENT WITH ITS DISTINCTIVE ATOM
+    FIRST.  ``embeddings`` is the number of maps seen (symmetric fragments are seen once per symmetry), ``cover`` the atoms in any of
+    them.  ``atom_map[r, q, p]`` is 1 + the atom that pattern atom p maps to in the first map of the lowest found root (0: the
+    pattern does not occur, or p is beyond its atoms), the lexicographically smallest embedding unless a lower root was capped.
+    ``undecided[r, q]``: a root was abandoned after 4096 steps, so ``count`` may miss anchors, and ``embeddings`` / ``cover`` are
+    lower bounds; where it is False all of them are exact and do not depend on how row or pattern is spelled (``atom_map`` names
+    atoms in the row's own order of appearance, which does).  ``count > 0`` is has_substructure()'s ``match``; its ``undecided`` is
+    ``count == 0`` and ``undecided`` here.  Enumeration runs into the cap more easily than the first-success search: a pattern of k
+    equal dotted parts against n such atoms has n!/(n-k)! maps.
+    ``normalize=True`` matches against the normal form of the rows (mol_normalize(), which keeps the atom numbering; the patterns
+    are matched as written, see has_substructure_normalized()).
+    What it is NOT: not SMARTS and not RDKit's GetSubstructMatches -- no implicit hydrogens, no aromaticity perception (without
+    ``normalize``), no stereo, no uniquified atom sets.  A row that is no molecule has all-zero results.  The refusals are
+    has_substructure()'s.  Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::sub_map, with ``normalize=True``
+    mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize after mdt::mol_graph."""
+    tok, fragments = _map_rows(tokens, patterns, vocabulary, normalize)
+    packed, n = _mol_rows(tok, vocabulary, device)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device, normalize)
+    found, capped, embeddings, cover, atom_map, _ = torch.ops.mdt.sub_map(*graph, *fragments.on(device), None, None)
+    found = _atom_bits(found, tok.shape[1])
+    return SubstructureMap(atom_map.long(), found.sum(2), found, _atom_bits(cover, tok.shape[1]), embeddings.long(), capped != 0,
+                           status.long(), position.long())
+
+
+OCCURRENCES = ("all", "first")
+
+
+def substructure_keep(tokens, patterns, vocabulary: "SmilesVocabulary", device, *, occurrences: str = "all", normalize: bool = False,
+                      width=None, canonical: bool = False):
+    """A lead respelled, and the mask of the tokens of its matched fragments -> (tokens int64 (R, width), keep_mask bool (R, width),
+    matched bool (R, P), complete bool (R,), flags int64 (R,), status int64 (R,), position int64 (R,)): "keep this amide, vary
+    the rest".  ``tokens`` is the lead respelled as scaffold_keep() does it (mol_write() with ``invariant=True``, ``width`` default
+    the input's L, ``canonical`` as there); ``keep_mask`` is True exactly at the tokens that belong to an atom matched by ANY of
+    the patterns -- the atom's text, its ring numbers, and the bond symbol and parentheses that lead to it -- and is the mask
+    refine_keep_tokens(keep_mask=) takes.  ``occurrences="all"``: every atom in any embedding (substructure_map()'s ``cover``);
+    ``"first"``: the atoms of the one returned map per pattern (``atom_map``, the first map of the lowest found root).
+    ``matched[r, q]``: pattern q occurs in row r.  ``complete[r]`` is False where a root of that row ran into the step cap: atoms
+    may be missing from the mask.  A row that was not written (``flags`` != 1, mol_write()'s) has an all-False mask.
+    ``normalize=True``: the match reads the normal form (aromatic fragments in lower case, see has_substructure_normalized()), but
+    the lead is written from the graph AS WRITTEN -- the model was trained on ordinary SMILES, and an all-bracket row is long and
+    out of distribution; mol_normalize() keeps the atom numbering, so the matched atoms name the same tokens.
+    The limits are substructure_map()'s (anchors, not atom sets; not SMARTS, a step cap, no stereo) and mol_write()'s (NOT RDKit's
+    canonical SMILES).  The refusals are has_substructure()'s, ``occurrences`` outside ("all", "first"), ``width`` outside 1..128.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph -> mdt::sub_map -> mdt::mol_rank -> mdt::mol_canon (only with
+    ``canonical=True``) -> mdt::mol_write, with ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize
+    after mdt::mol_graph; the mask is torch on the ops' outputs, no kernel of its own."""
+    if occurrences not in OCCURRENCES:
+        raise ValueError(f"occurrences must be one of {OCCURRENCES}, got {occurrences!r}")
+    _canonical_arg(canonical, True)
+    tok, fragments = _map_rows(tokens, patterns, vocabulary, normalize)
+    width = _width_arg(width, tok.shape[1])
+    packed, n = _mol_rows(tok, vocabulary, device)
+    graph, status, position = _graph_rows(packed, n, vocabulary, device)
+    found, capped, _, cover, atom_map, _ = torch.ops.mdt.sub_map(*(_normal_form(*graph)[0] if normalize else graph),
+                                                                 *fragments.on(device), None, None)
+    written, _, token_atom, flags = _write(graph, vocabulary, device, width, True, canonical)
+    R, L = tok.shape
+    if occurrences == "all":
+        kept = torch.cat([torch.zeros(R, 1, dtype=torch.bool, device=cover.device), _atom_bits(cover, L).any(1)], dim=1)
+    else:
+        kept = torch.zeros(R, 1 + L, dtype=torch.bool, device=cover.device).scatter_(1, atom_map.long().view(R, -1), True)
+        kept[:, 0] = False                                                   # (R, 1 + L): column 0 is "no atom"
+    keep_mask = torch.gather(kept, 1, token_atom.long())
+    return written.long(), keep_mask, found != 0, (capped == 0).all(1), flags.long(), status.long(), position.long()
+
+
+class SubstructureCounts:
+    """How often fragments may occur (``counts=`` of the screening calls): ``patterns`` as SubstructureSet takes them (or a
+    SubstructureSet), with one lower bound ``at_least[q]`` and one upper bound ``at_most[q]`` per pattern, each an int >= 0 or None
+    (no bound); ``at_least`` / ``at_most`` None: no such bound at all.  "At most one nitro group" is
+    ``SubstructureCounts(["[N+](=O)[O-]"], v, at_most=[1])``, "at least two ring nitrogens" ``(["n"], v, at_least=[2])``.
+    What is counted is substructure_map()'s ``count``: anchors, not atom sets -- the atoms that can play the pattern's FIRST atom,
+    so write the fragment with its distinctive atom first; not SMARTS.  A start atom whose search was abandoned at the step cap
+    counts against the row both ways.  ``set`` is the SubstructureSet, ``at_least`` / ``at_most`` tuples of ints (64 and more: no
+    upper bound).  Bounds that are no ints >= 0, not one per pattern, or a lower bound above its upper one or above 64 raise
+    ValueError here."""
+
+    def __init__(self, patterns, vocabulary: "SmilesVocabulary", at_least=None, at_most=None):
+        self.set = _substructure_set(patterns, vocabulary, "patterns")
+        P = len(self.set)
+        bounds = []
+        for name, given, default in (("at_least", at_least, 0), ("at_most", at_most, 255)):
+            given = [None] * P if given is None else given
+            if isinstance(given, (str, int)) or not hasattr(given, "__len__") or len(given) != P:
+                raise ValueError(f"{name} must be None or hold one bound per pattern ({P}), got {given!r}")
+            for b in given:
+                if b is not None and (isinstance(b, bool) or not isinstance(b, int) or b < 0):
+                    raise ValueError(f"{name} holds {b!r}: every bound is an int >= 0 or None")
+            bounds.append(tuple(default if b is None else min(b, 255) for b in given))
+        self.at_least, self.at_most = bounds
+        for q, (lo, hi) in enumerate(zip(*bounds)):
+            if lo > hi or lo > MAX_MOL_LENGTH:
+                raise ValueError(f"pattern {q} {self.set.patterns[q]!r}: no row has at least {lo} and at most {hi} of its "
+                                 f"{MAX_MOL_LENGTH} atoms as anchors")
+        self._on = {}
+
+    def __len__(self) -> int:
+        return len(self.set)
+
+    def on(self, device):
+        """(count_lo uint8 (P,), count_hi uint8 (P,)) on ``device``, made once per device"""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = tuple(torch.tensor(b, dtype=torch.uint8).to(device) for b in (self.at_least, self.at_most))
+        return self._on[device]
+
+
+def _counts_arg(counts, vocabulary, length: int) -> None:
+    """The refusals of ``counts=``, before anything is launched."""
+    if counts is None:
+        return
+    if not isinstance(counts, SubstructureCounts):
+        raise ValueError(f"counts must be a SubstructureCounts or None, got {type(counts).__name__}")
+    if vocabulary is None:
+        raise ValueError("counts reads the rows as strings: give a vocabulary")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    if length > MAX_MOL_LENGTH:
+        raise ValueError(f"tokens has rows of {length} positions; the substructure match takes at most {MAX_MOL_LENGTH} "
+                         "(wider rows are out of scope)")
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -2593,7 +2767,7 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     of the G targets in one fused sampling call of N * G rows -- then screen_tokens (whose keyword arguments this takes, and
     ``min_distance`` / ``min_novelty`` / ``vocabulary`` / ``identity`` / ``max_similarity`` / ``max_known_similarity`` /
     ``fingerprint_radius`` / ``require`` / ``forbid`` / ``kekulize`` / ``limits`` / ``normalize`` / ``max_per_scaffold`` /
-    ``novel_scaffold`` / ``scaffold_exocyclic`` / ``scaffold_generic``, with which the tokens go to screen_tokens_diverse instead;
+    ``novel_scaffold`` / ``scaffold_exocyclic`` / ``scaffold_generic`` / ``counts``, with which the tokens go to screen_tokens_diverse instead;
     ``sampler`` / ``sigma_schedule`` go to both models, as in generate_and_validate).  ``cond_scale``: one float, or N values, one per
     candidate block (expanded with repeat_interleave(G) into the per-sample guidance).  ``noise``: as sample_tokens; with
     ``noise=NoiseSource(seed=..., sample0=s)`` candidate block c is the scalar call whose sample0 is s + c * G (bit for bit under a
@@ -2601,7 +2775,7 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     extra = set(screen_tokens_kwargs) - {"known_tokens", "weights", "forward_timesteps", "X_norm_factor", "forward_noise", "sampler",
                                          "sigma_schedule", "min_distance", "min_novelty", "vocabulary", "identity", "max_similarity",
                                          "max_known_similarity", "fingerprint_radius", "require", "forbid", "kekulize", "limits", "normalize",
-                                         "max_per_scaffold", "novel_scaffold", "scaffold_exocyclic", "scaffold_generic"}
+                                         "max_per_scaffold", "novel_scaffold", "scaffold_exocyclic", "scaffold_generic", "counts"}
     if extra:
         raise TypeError(f"screen_candidates got unexpected keyword arguments {sorted(extra)}")
     _, known = _screen_args(conditioning, candidates, keep, screen_tokens_kwargs.get("known_tokens"),
@@ -2647,8 +2821,13 @@ def screen_candidates(model: "QMDiffusion", model_forward: "QMDiffusionForward",
     if scaffold_on:                                              # (None and False: the calls made without the keywords)
         diverse = True
         filters.update(scaffold)
+    counts = screen_tokens_kwargs.pop("counts", None)
+    _counts_arg(counts, vocabulary, model.max_length)
+    if counts is not None:                                       # (None: the calls made without the keyword)
+        diverse, filters["counts"] = True, counts
     normalize = screen_tokens_kwargs.pop("normalize", False)
-    _screen_normalize_arg(normalize, vocabulary, model.max_length, identity == "graph" or bool(fragments) or scaffold_on or any(
+    _screen_normalize_arg(normalize, vocabulary, model.max_length, identity == "graph" or bool(fragments) or scaffold_on or
+                          counts is not None or any(
         similar.get(k) is not None for k in ("max_similarity", "max_known_similarity")))
     if normalize:                                                # (False: the calls made without the keyword)
         diverse, filters["normalize"] = True, True

@@ -936,6 +936,63 @@ def _(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds, need, 
     return (atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, dtype=torch.int32), atoms.new_empty(R, dtype=torch.uint8))
 
 
+@custom_op("mdt::sub_map", mutates_args=())
+def sub_map(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, p_natoms: Tensor, p_atoms: Tensor, p_nbonds: Tensor,
+            p_bonds: Tensor, count_lo: Optional[Tensor], count_hi: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (found int64 (R, P), capped int64 (R, P): the uint64 bits, bit t = root t saw an embedding / was abandoned; embeddings
+    int32 (R, P); cover int64 (R, P): the uint64 bits, the target atoms in some embedding seen; map uint8 (R, P, LP): 1 + f(p) of
+    the first map of the lowest found root; flags uint8 (R,)) of mdt_sub_map (include/mdt_hip.h) on the graph arrays of
+    mdt::mol_graph -- targets (R, L <= 64), patterns (P <= 32, LP <= 32).  ``count_lo`` / ``count_hi``: uint8 (P,), both or neither;
+    with them flags is 128 where the number of anchors of some pattern lies outside its bounds (abandoned roots count against the
+    row both ways), without them all zero.  The enumeration of mdt::sub_match's search under its step cap; anchors, not atom sets;
+    not SMARTS, not RDKit's GetSubstructMatches."""
+    dev = _hip(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds)
+    lib = rt.load_library()
+    op = "mdt::sub_map"
+    for what, n_, a_, nb_, b_ in (("", natoms, atoms, nbonds, bonds), ("p_", p_natoms, p_atoms, p_nbonds, p_bonds)):
+        if a_.dim() != 2 or tuple(b_.shape) != tuple(a_.shape) or any(t.dtype != torch.int32 for t in (n_, a_, nb_, b_)):
+            raise RuntimeError(f"{op}: {what}atoms and {what}bonds must be int32 (rows, width), {what}natoms and {what}nbonds int32 "
+                               "(as mdt::mol_graph returns them)")
+        if n_.numel() != a_.shape[0] or nb_.numel() != a_.shape[0]:
+            raise RuntimeError(f"{op}: {what}natoms and {what}nbonds must hold one value per row of {what}atoms")
+    (R, L), (P, LP) = atoms.shape, p_atoms.shape
+    if not 1 <= L <= rt.MOL_MAX_LENGTH:
+        raise RuntimeError(f"{op}: atoms has {L} positions per row, the match takes 1 to {rt.MOL_MAX_LENGTH}")
+    if not 1 <= LP <= rt.SUB_MAX_WIDTH:
+        raise RuntimeError(f"{op}: p_atoms has {LP} positions per pattern, the match takes 1 to {rt.SUB_MAX_WIDTH}")
+    if not 1 <= P <= rt.SUB_MAX_PATTERNS:
+        raise RuntimeError(f"{op}: {P} patterns, the match takes 1 to {rt.SUB_MAX_PATTERNS} a call")
+    if (count_lo is None) != (count_hi is None):
+        raise RuntimeError(f"{op}: count_lo and count_hi must be given together or not at all")
+    for name, t in (("count_lo", count_lo), ("count_hi", count_hi)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (P,)):
+            raise RuntimeError(f"{op}: {name} must be uint8 with one bound per pattern, ({P},)")
+    natoms, atoms, nbonds, bonds = natoms.contiguous(), atoms.contiguous(), nbonds.contiguous(), bonds.contiguous()
+    p_natoms, p_atoms, p_nbonds, p_bonds = p_natoms.contiguous(), p_atoms.contiguous(), p_nbonds.contiguous(), p_bonds.contiguous()
+    found = torch.zeros(R, P, dtype=torch.int64, device=dev)
+    capped = torch.zeros(R, P, dtype=torch.int64, device=dev)
+    embeddings = torch.zeros(R, P, dtype=torch.int32, device=dev)
+    cover = torch.zeros(R, P, dtype=torch.int64, device=dev)
+    fmap = torch.zeros(R, P, LP, dtype=torch.uint8, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        bounds = (None, None, None) if count_lo is None else (count_lo.contiguous(), count_hi.contiguous(), flags)
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_sub_map(rt.ptr(natoms), rt.ptr(atoms), rt.ptr(nbonds), rt.ptr(bonds), L, R, rt.ptr(p_natoms),
+                                     rt.ptr(p_atoms), rt.ptr(p_nbonds), rt.ptr(p_bonds), LP, P, rt.ptr(bounds[0]), rt.ptr(bounds[1]),
+                                     rt.ptr(found), rt.ptr(capped), rt.ptr(embeddings), rt.ptr(cover), rt.ptr(fmap),
+                                     rt.ptr(bounds[2]), rt.current_stream()))
+    return found, capped, embeddings, cover, fmap, flags
+
+
+@sub_map.register_fake
+def _(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds, count_lo, count_hi):
+    (R, L), (P, LP) = atoms.shape, p_atoms.shape
+    return (atoms.new_empty((R, P), dtype=torch.int64), atoms.new_empty((R, P), dtype=torch.int64),
+            atoms.new_empty((R, P), dtype=torch.int32), atoms.new_empty((R, P), dtype=torch.int64),
+            atoms.new_empty((R, P, LP), dtype=torch.uint8), atoms.new_empty(R, dtype=torch.uint8))
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # implicit hydrogens, the Kekule check and the formula (csrc/k_molh.hip): rows of at most 64 positions
 @custom_op("mdt::mol_hydrogens", mutates_args=())

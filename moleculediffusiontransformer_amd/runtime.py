@@ -142,6 +142,7 @@ SYMBOLS = {
     "mdt_fp_nearest": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "mdt_screen_select_similar": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mdt_sub_match": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _U32, _U32, _P, _P, _P, _P]),
+    "mdt_sub_map": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_hydrogens": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_rings": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_normalize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
