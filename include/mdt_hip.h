@@ -1284,6 +1284,80 @@ int mdt_mol_canon(const int32_t *natoms, const uint32_t *atoms, const int32_t *n
                   uint64_t *priority, uint32_t *canon_atoms, uint32_t *canon_bonds, int32_t *nodes, uint8_t *flags, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* Maximum common substructure of row pairs (csrc/k_molmcs.hip, csrc/mdt_molmcs.h); an addition inside ABI version 5 */
+/* ------------------------------------------------------------------ */
+/* What do these two molecules share, and where do they differ?  mdt_mol_key says same or not, mdt_mol_fp gives one number,
+ * mdt_sub_map needs a fragment that is already known; this call finds the greatest connected common subgraph of two rows.
+ * Inputs: the graph arrays of mdt_mol_graph (or of mdt_mol_normalize) for side A, R rows of width 1 <= LA <= 64, and for side B, RB
+ * rows of width 1 <= LB <= 64, with RB == R (row by row) or RB == 1 (every A row against the one B row).  mode: bit 0
+ * MDT_MCS_EXACT_ATOMS; any other bit is refused before any launch, as are widths outside 1..64, R < 0 and any other RB.  R == 0
+ * launches nothing and reads nothing.
+ * Usable entries.  A bond entry is USABLE when its ends differ and its order is 1..5.  A's usable entries are counted each for
+ * itself, in list order (an entry listed twice counts twice).  B is read as a set: per order o an adjacency word adj_o[u] per atom.
+ * A pair in which either row is no molecule -- natoms == 0, a count outside [0, width], a bond naming an atom >= natoms (the rule of
+ * mdt_mol_key) -- has every output word 0.
+ * Atom rule.  A atom a and B atom b are COMPATIBLE when ((atoms_a[a] ^ atoms_b[b]) & 0x7FF) == 0: symbol and aromatic bit, the mask
+ * mdt_sub_match uses for an unbracketed atom.  With MDT_MCS_EXACT_ATOMS the whole words must be equal.
+ * Bond rule.  Equal order.
+ * Common substructure.  An injective partial map M from A atoms to B atoms of compatible pairs, and a set E of usable A entries
+ * with both ends in M, each of whose images (M(a), M(b)) is a B bond of the same order; the A atoms of M must be connected through
+ * E.  Its size is (|E|, |M|), compared lexicographically: bonds first.  It is the edge kind, not the induced kind: C1CC1 and CCC
+ * share 2 bonds and 3 atoms.
+ * Roots.  Every compatible pair (a0, b0) is a root, in ascending (a0, b0).  Root (a0, b0) searches only the A atoms >= a0, with
+ * M(a0) = b0; hence every common substructure belongs to exactly one a0.
+ * The walk of a root.  State: M, the used B atoms, a set X of excluded A entries, and cur, the matched entries so far.  At a node:
+ *  1. If (cur, |M|) is greater than the root's best, record it (size and map).  The first record is (0, 1).
+ *  2. The bound.  ub_bonds = cur + the sum over the orders o of min(ra(o), rb(o)), where ra(o) is the usable A entries of order o
+ *     with both ends >= a0, not in X and not with both ends mapped, and rb(o) the B bonds of order o with not both ends used;
+ *     ub_atoms = |M| + min(the unmapped A atoms >= a0, nb - |M|).  If (ub_bonds, ub_atoms) <= the root's best, or < the floor
+ *     (below), return.
+ *  3. Take the lowest usable A entry e = (x, y, o) in list order with both ends >= a0, e not in X, exactly one end mapped (say x)
+ *     and a non-zero candidate word c = adj_o[M(x)] & compat(y) & ~used.  If there is none, return.
+ *  4. For each t in c, ascending: count one STEP; set M(y) = t; cur += the usable A entries at y not in X whose other end z is
+ *     mapped and whose image (M(z), t) is a B bond of their order (e itself and every closure); descend; undo.
+ *  5. Then count one step, put e in X, and descend; afterwards take it out again.
+ * A root about to make step MDT_MCS_MAX_STEPS + 1 is abandoned (CAPPED) and keeps its best so far.  Excluded entries are never
+ * counted.  The enumeration is complete: follow any optimal (M, E), take the include branch where e is matched in it and the
+ * exclude branch otherwise.
+ * The floor.  Before the walks every root makes a GREEDY DESCENT: the walk above, always taking the lowest candidate of step 3,
+ * never excluding and never pruning, until step 3 finds nothing; its steps are not counted.  The floor is the greatest size any
+ * descent reached.  It is part of the definition, because it decides which roots reach the cap.
+ * Result of a pair.  The greatest best over the roots, ties to the lowest root; the winning M is the one recorded at that best.
+ * The bond mask and the bond count are then RECOUNTED from M: every usable A entry between mapped atoms whose image is a B bond of
+ * its order.  For a pair with no capped root the recount equals the search's count.  No root stops or prunes because of another
+ * root's progress, only because of the floor, so every word is the same under any scheduling.
+ * Outputs, every word written:
+ *  size int32 (R,2)        bonds, atoms.
+ *  map_a uint8 (R,LA)      1 + the partner of each A atom, 0 for none and beyond natoms.
+ *  bond_a uint64 (R)       bit e set for each matched A entry.
+ *  steps int32 (R)         the sum over the roots, at most 4096 x 4096.
+ *  out_natoms int32 (R), out_atoms uint32 (R,LA), out_nbonds int32 (R), out_bonds uint32 (R,LA), atom_map uint8 (R,LA): the
+ *   common substructure as graph arrays of its own in mdt_mol_scaffold's output format, so that mdt_mol_key and mdt_mol_write take
+ *   them unchanged: the kept A atoms with A's words in ascending A index, the matched entries in their order and orientation,
+ *   renumbered (x' = the kept atoms below x), atom_map[x] = 1 + x' for a kept atom and 0 otherwise; words beyond the counts are 0.
+ *  flags uint8 (R)         MDT_MCS_PAIR (1) both rows are molecules; MDT_MCS_COMMON (2) the result is non-empty; MDT_MCS_UNDECIDED
+ *   (4) some root was capped: the result is a valid common substructure and a lower bound, like FindMCS's `canceled`;
+ *   MDT_MCS_WHOLE_A (8) every atom and every usable entry of A is in the result; MDT_MCS_WHOLE_B (16) the same for B (a usable
+ *   B entry is in the result when it is the image of a matched A entry).
+ * What this is NOT.  Not RDKit's FindMCS: there are no ring-matches-ring options, no complete-rings option, no SMARTS result.
+ * Charges, hydrogens and isotopes are ignored unless MDT_MCS_EXACT_ATOMS.  No stereo.  The result is connected, so it is ONE
+ * fragment.  Aromaticity is as handed in: compare normal forms to compare molecules and not spellings.
+ * A limit of the bound.  A's entries count each for itself while B is a set, so for an A row that names one pair of atoms by
+ * several entries of one order (a row mdt_mol_write calls not writable; no molecule is written that way) the bound of step 2 can lie
+ * under what the walk could still count, and the result, always a valid common substructure, can be smaller than the greatest one
+ * without MDT_MCS_UNDECIDED.  For rows without such entries the bound is a true upper bound and a decided result is the maximum.
+ * Worst case: 4,096 roots of 4,096 steps a pair, and once more for one of them (the winning map is found by running that root's
+ * walk again up to the step at which its best was recorded, csrc/k_molmcs.hip). */
+#define MDT_MCS_MAX_STEPS 4096
+enum mdt_mcs_mode { MDT_MCS_EXACT_ATOMS = 1 };
+enum mdt_mcs_flag { MDT_MCS_PAIR = 1, MDT_MCS_COMMON = 2, MDT_MCS_UNDECIDED = 4, MDT_MCS_WHOLE_A = 8, MDT_MCS_WHOLE_B = 16 };
+int mdt_mol_mcs(const int32_t *a_natoms, const uint32_t *a_atoms, const int32_t *a_nbonds, const uint32_t *a_bonds, int32_t LA,
+                int32_t R, const int32_t *b_natoms, const uint32_t *b_atoms, const int32_t *b_nbonds, const uint32_t *b_bonds,
+                int32_t LB, int32_t RB, int32_t mode, int32_t *size, uint8_t *map_a, uint64_t *bond_a, int32_t *steps,
+                int32_t *out_natoms, uint32_t *out_atoms, int32_t *out_nbonds, uint32_t *out_bonds, uint8_t *atom_map,
+                uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* measurement helpers (HIP events on the caller's stream)             */
 /* ------------------------------------------------------------------ */
 typedef struct mdt_timer mdt_timer;

@@ -15,7 +15,8 @@ from .generative import (DESCRIPTOR_NAMES, DescriptorLimits, KDiffusion_mod, Kno
                          has_substructure, has_substructure_normalized, mol_fingerprint, mol_descriptors, mol_formula, mol_graph, mol_hydrogens, mol_key, mol_normalize, mol_rings, mol_weight, nearest_known, nearest_known_tanimoto, one_hot_draft, predict_properties_from_tokens, refine_and_validate, screen_candidates,
                          mol_canon, mol_respell, mol_same, mol_scaffold, mol_write, scaffold_keep, scaffold_key, scaffold_tokens, screen_tokens,
                          screen_tokens_diverse, smiles_check, strength_sweep, tanimoto, tokens_to_forward_input,
-                         SubstructureCounts, substructure_keep, substructure_map)
+                         SubstructureCounts, substructure_keep, substructure_map,
+                         McsResult, mcs_keep, mcs_tokens, mol_difference, mol_mcs)
 from .graphmodel import AnalogDiffusionFull, AnalogDiffusionSparse  # noqa: F401
 from .modules import PositionalEncoding1D, UNetCFG1d  # noqa: F401
 from .netspec import UNetConfig, forward_unet_config, inverse_unet_config  # noqa: F401

@@ -46,6 +46,7 @@ SOURCES = [
     ("k_molgraph.hip", []),
     ("k_molfp.hip", []),
     ("k_molsub.hip", []),
+    ("k_molmcs.hip", []),
     ("k_molh.hip", []),
     ("k_molring.hip", []),
     ("k_molnorm.hip", []),

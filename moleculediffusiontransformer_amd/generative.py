@@ -2716,6 +2716,183 @@ def mol_same(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, *, norm
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# what do two molecules share?  maximum common substructure of row pairs (csrc/k_molmcs.hip): rows of at most 64 atoms a side
+# ----------------------------------------------------------------------------------------------------------------------
+MCS_ATOMS = ("element", "exact")
+
+
+class McsResult(NamedTuple):
+    """What mol_mcs() returns."""
+    bonds: Tensor         # (R,) int64: the matched bonds
+    atoms: Tensor         # (R,) int64: the matched atoms
+    map_a: Tensor         # (R, LA) int64: 1 + the b atom that a atom x is matched with, 0 = none
+    in_a: Tensor          # (R, LA) bool: a atom x is in the common substructure
+    in_b: Tensor          # (R, LB) bool: b atom t is
+    similarity: Tensor    # (R,) float64: shared atoms and bonds over the union of both sides' atoms and bonds
+    undecided: Tensor     # (R,) bool: some root ran into the step cap: the result is a lower bound
+    whole_a: Tensor       # (R,) bool: all of a is in it (a is a substructure of b; a row with a doubled bond: see mol_mcs())
+    whole_b: Tensor       # (R,) bool: all of b is
+    steps: Tensor         # (R,) int64: the steps of the search
+    natoms: Tensor        # (R,) int64  \
+    graph_atoms: Tensor   # (R, LA) int64  the common substructure as graph arrays of its own, mol_graph()'s format:
+    nbonds: Tensor        # (R,) int64     what mol_write() and the ops behind mol_key() take
+    graph_bonds: Tensor   # (R, LA) int64 /
+    atom_map: Tensor      # (R, LA) int64: 1 + the index in those arrays of a atom x, 0 = not kept
+    pair: Tensor          # (R,) bool: both rows are molecules
+    a_status: Tensor      # (R,) int64, smiles_check()'s, of a_tokens
+    a_position: Tensor    # (R,) int64
+    b_status: Tensor      # (R or 1,) int64, of b_tokens
+    b_position: Tensor    # (R or 1,) int64
+
+
+def _mcs_rows(a_tokens, b_tokens, vocabulary, normalize, atoms, names=("a_tokens", "b_tokens")):
+    """The refusals of the mol_mcs() family, before anything is launched -> (a ids, b ids, the mode of mdt::mol_mcs)"""
+    _normalize_arg(normalize)
+    if atoms not in MCS_ATOMS:
+        raise ValueError(f"atoms must be one of {MCS_ATOMS}, got {atoms!r}")
+    a, b = _integer_ids(a_tokens, names[0]), _integer_ids(b_tokens, names[1])
+    if b.shape[0] != a.shape[0] and b.shape[0] != 1:
+        raise ValueError(f"{names[0]} has {a.shape[0]} rows and {names[1]} {b.shape[0]}: they are compared row by row, or every "
+                         f"row of {names[0]} against ONE row of {names[1]}")
+    if not isinstance(vocabulary, SmilesVocabulary):
+        raise ValueError(f"vocabulary must be a SmilesVocabulary, got {type(vocabulary).__name__}")
+    for name, t in zip(names, (a, b)):                           # (both are refused before the first launch)
+        if not 1 <= t.shape[1] <= MAX_MOL_LENGTH:
+            raise ValueError(f"{name} has rows of {t.shape[1]} positions; the common substructure takes 1 to {MAX_MOL_LENGTH} "
+                             "(wider rows are out of scope)")
+    return a, b, rt.MCS_EXACT_ATOMS if atoms == "exact" else 0
+
+
+def _mcs_of(a, b, vocabulary, device, normalize, mode):
+    """The launches up to mdt::mol_mcs -> (its ten outputs, a's graph AS WRITTEN, a's and b's graphs as matched, both sides' status
+    and position)"""
+    packed, n = _mol_rows(a, vocabulary, device)
+    written, a_status, a_position = _graph_rows(packed, n, vocabulary, device)
+    ga = _normal_form(*written)[0] if normalize else written
+    packed, n = _mol_rows(b, vocabulary, device)
+    gb, b_status, b_position = _graph_rows(packed, n, vocabulary, device, normalize)
+    return torch.ops.mdt.mol_mcs(*ga, *gb, mode), written, ga, gb, (a_status, a_position, b_status, b_position)
+
+
+def _usable_entries(graph):
+    """(R,) int64: the bond entries of each row whose ends differ and whose order is 1..5"""
+    _, _, nbonds, bonds = graph
+    w = bonds.long() & 0xFFFFFFFF
+    listed = torch.arange(w.shape[1], device=w.device)[None, :] < nbonds.long()[:, None]
+    order = w >> 16
+    return (listed & ((w & 255) != ((w >> 8) & 255)) & (order >= 1) & (order <= 5)).sum(1)
+
+
+def _mcs_in_b(map_a, LB: int):
+    """(R, LA) int64 1 + partner -> (R, LB) bool: the b atoms that are some a atom's partner"""
+    return torch.zeros(map_a.shape[0], 1 + LB, dtype=torch.bool, device=map_a.device).scatter_(1, map_a, True)[:, 1:]   # column 0: none
+
+
+def mol_mcs(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, atoms: str = "element") -> McsResult:
+    """What do row r of ``a_tokens`` and row r of ``b_tokens`` share, and where do they differ?  -> McsResult (see its fields) for
+    raw ids of any integer dtype, zeros anywhere; ``b_tokens`` has as many rows as ``a_tokens`` or ONE row, against which every row
+    of ``a_tokens`` is then held (a batch of candidates and their target).  The widths LA, LB <= 64 may differ.
+
+    The answer is the MAXIMUM COMMON SUBSTRUCTURE of the two graphs of mol_graph(): the greatest connected subgraph of a that also
+    lies in b, compared by (bonds, atoms), bonds first, as RDKit's FindMCS does by default -- the edge kind, not the induced kind:
+    C1CC1 and CCC share 2 bonds and 3 atoms.  ``atoms="element"`` pairs atoms of the same symbol and aromatic bit (charges,
+    hydrogens and isotopes are ignored); ``"exact"`` wants the whole atom word equal.  Bonds pair when their order is equal.
+    ``map_a`` / ``in_a`` / ``in_b`` name the atoms in each row's own order of appearance; ``similarity`` is (atoms + bonds) / (a's
+    atoms + bonds + b's atoms + bonds - atoms - bonds) from the exact integer counts, 1.0 exactly when each is all of the other, 0
+    where the pair is no pair (``pair`` False: a row is no molecule; everything is then zero).  ``undecided``: a root of the search
+    ran into its cap of 4096 steps, and the result is a valid common substructure and a LOWER bound, like FindMCS's ``canceled``.
+    ``whole_a``: a is a substructure of b.  The graph arrays are the common substructure as a molecule of its own, a's atoms in a's
+    order: mol_write() and the ops behind mol_key() take them as they are (mcs_tokens() writes them).
+    The search -- roots, bound, greedy floor, cap -- is part of the definition; mdt_mol_mcs in include/mdt_hip.h has every step.
+    What it is NOT: not RDKit's FindMCS -- no ring-matches-ring or complete-rings options, no SMARTS result, no stereo; the result is
+    connected, so it is ONE fragment; aromaticity is as written unless ``normalize=True``, which compares the normal forms
+    (mol_normalize()) and so molecules, not spellings.  Where ``undecided`` is False, sizes, ``similarity`` and the whole flags
+    do not depend on how either row is spelled; which atoms are named can.  ONE EXCEPTION: a row that names one pair of atoms by
+    two bonds (two ring closures between the same atoms, C12CC12: a row mol_write() calls not writable, about 1 % of mutated
+    rows).  As ``a_tokens`` such a row can get a SMALLER common substructure than the greatest one without ``undecided``, and
+    ``whole_a`` can then be False although a lies in b: the search's bound reads b's bonds as a set and a's one by one.
+    The refusals are mol_same()'s, a ``b_tokens`` of neither R rows nor one, and ``atoms`` outside ("element", "exact"), with
+    ValueError before anything is launched.  Sequence: mdt::tokens_compact -> mdt::mol_graph for ``a_tokens``, the same for
+    ``b_tokens``, then mdt::mol_mcs; with ``normalize=True`` mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize go after
+    each mdt::mol_graph.  The rest is torch on the op's outputs."""
+    a, b, mode = _mcs_rows(a_tokens, b_tokens, vocabulary, normalize, atoms)
+    out, _, ga, gb, (a_status, a_position, b_status, b_position) = _mcs_of(a, b, vocabulary, device, normalize, mode)
+    size, map_a, _, steps, natoms, graph_atoms, nbonds, graph_bonds, atom_map, flags = out
+    map_a, flags = map_a.long(), flags.long()
+    in_b = _mcs_in_b(map_a, b.shape[1])
+    pair = (flags & rt.MCS_PAIR) != 0
+    common = size.long().sum(1)
+    union = ga[0].long() + _usable_entries(ga) + gb[0].long() + _usable_entries(gb) - common
+    similarity = torch.where(pair, common.double() / union.clamp(min=1).double(), torch.zeros_like(common, dtype=torch.float64))
+    return McsResult(size[:, 0].long(), size[:, 1].long(), map_a, map_a != 0, in_b, similarity, (flags & rt.MCS_UNDECIDED) != 0,
+                     (flags & rt.MCS_WHOLE_A) != 0, (flags & rt.MCS_WHOLE_B) != 0, steps.long(), natoms.long(),
+                     graph_atoms.long() & 0xFFFFFFFF, nbonds.long(), graph_bonds.long(), atom_map.long(), pair, a_status.long(),
+                     a_position.long(), b_status.long(), b_position.long())
+
+
+def mol_difference(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, atoms: str = "element"):
+    """Where do two molecules differ?  -> (only_a bool (R, LA), only_b bool (R, LB), undecided bool (R,)): the atoms of each row
+    OUTSIDE the maximum common substructure of mol_mcs() (whose arguments and limits this takes), in each row's own order of
+    appearance -- the two highlight lists of the reference's view_difference(), as masks.  Positions beyond a row's atoms are
+    False, as is everything in a pair that is no pair.  Sequence: mol_mcs()'s."""
+    a, b, mode = _mcs_rows(a_tokens, b_tokens, vocabulary, normalize, atoms)
+    out, _, ga, gb, _ = _mcs_of(a, b, vocabulary, device, normalize, mode)
+    map_a, flags = out[1].long(), out[9].long()
+    in_b = _mcs_in_b(map_a, b.shape[1])
+    pair = ((flags & rt.MCS_PAIR) != 0)[:, None]
+    inside_a = torch.arange(a.shape[1], device=map_a.device)[None, :] < ga[0].long()[:, None]
+    inside_b = torch.arange(b.shape[1], device=map_a.device)[None, :] < gb[0].long()[:, None]       # (R or 1, LB)
+    return inside_a & (map_a == 0) & pair, inside_b & ~in_b & pair, (flags & rt.MCS_UNDECIDED) != 0
+
+
+def mcs_tokens(a_tokens, b_tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, atoms: str = "element",
+               width=None, canonical: bool = False):
+    """The maximum common substructure of each pair as a row the model and a chemist can read -> (tokens int64 (R, width), flags
+    int64 (R,), undecided bool (R,), a_status int64 (R,), b_status int64 (R or 1,)): the graph arrays of mol_mcs() (whose
+    arguments and limits this takes) written by mol_write() with ``invariant=True``.  ``flags`` are mol_write()'s (1 written; 0
+    where nothing is shared, the tokens are then all zero).  ``width`` defaults to the LA of ``a_tokens``; ``canonical`` as on
+    scaffold_tokens().  The atoms are a's, with a's words: a bracket atom keeps its H count, an unbracketed atom that lost a
+    neighbour reads as carrying more implicit hydrogens -- the row is a fragment to look at, not a reaction product.  mol_key() of
+    the written row is mdt::mol_key of the graph arrays.  NOT RDKit's canonical SMILES and not FindMCS's SMARTS.
+    Sequence: mol_mcs()'s, then mdt::mol_rank -> mdt::mol_canon (only with ``canonical=True``) -> mdt::mol_write."""
+    _canonical_arg(canonical, True)
+    a, b, mode = _mcs_rows(a_tokens, b_tokens, vocabulary, normalize, atoms)
+    width = _width_arg(width, a.shape[1])
+    out, _, _, _, (a_status, _, b_status, _) = _mcs_of(a, b, vocabulary, device, normalize, mode)
+    written, _, _, flags = _write(out[4:8], vocabulary, device, width, True, canonical)
+    return written.long(), flags.long(), (out[9].long() & rt.MCS_UNDECIDED) != 0, a_status.long(), b_status.long()
+
+
+def mcs_keep(lead_tokens, other_tokens, vocabulary: "SmilesVocabulary", device, *, normalize: bool = False, atoms: str = "element",
+             width=None, canonical: bool = False):
+    """A lead respelled, and the mask of the tokens it shares with another molecule -> (tokens int64 (R, width), keep_mask bool (R,
+    width), complete bool (R,), flags int64 (R,), status int64 (R,), position int64 (R,)): "keep what this lead has in common with
+    that molecule, vary the rest".  Shaped like substructure_keep(): ``tokens`` is the lead respelled (mol_write() with
+    ``invariant=True``, ``width`` default the lead's L, ``canonical`` as there); ``keep_mask`` is True exactly at the tokens that
+    belong to a lead atom inside the maximum common substructure of mol_mcs() with ``other_tokens`` (R rows, or one row for every
+    lead) -- the atom's text, its ring numbers, and the bond symbol and parentheses that lead to it -- and is the mask
+    refine_keep_tokens(keep_mask=) takes.  ``complete[r]`` is False where a root ran into the step cap: the kept part is a common
+    substructure, but a greater one may exist.  A row that was not written (``flags`` != 1, mol_write()'s) or a pair that is no
+    pair has an all-False mask; ``status`` / ``position`` are the lead's.
+    ``normalize=True``: the match reads the normal forms of both sides, but the lead is written from the graph AS WRITTEN, as
+    substructure_keep() does -- mol_normalize() keeps the atom numbering, so the matched atoms name the same tokens.
+    The limits are mol_mcs()'s (not RDKit's FindMCS; connected; a step cap; no stereo) and mol_write()'s (NOT RDKit's canonical
+    SMILES).  The refusals are mol_mcs()'s and ``width`` outside 1..128.
+    Sequence: mdt::tokens_compact -> mdt::mol_graph for the lead, the same for the other, mdt::mol_mcs, then mdt::mol_rank ->
+    mdt::mol_canon (only with ``canonical=True``) -> mdt::mol_write on the lead's graph; with ``normalize=True``
+    mdt::mol_hydrogens -> mdt::mol_rings -> mdt::mol_normalize go after each mdt::mol_graph; the mask is torch on the ops' outputs,
+    no kernel of its own."""
+    _canonical_arg(canonical, True)
+    a, b, mode = _mcs_rows(lead_tokens, other_tokens, vocabulary, normalize, atoms, ("lead_tokens", "other_tokens"))
+    width = _width_arg(width, a.shape[1])
+    out, lead, _, _, (status, position, _, _) = _mcs_of(a, b, vocabulary, device, normalize, mode)
+    written, _, token_atom, flags = _write(lead, vocabulary, device, width, True, canonical)
+    kept = torch.cat([torch.zeros_like(out[1][:, :1]), out[1]], dim=1) != 0              # (R, 1 + L): column 0 is "no atom"
+    keep_mask = torch.gather(kept, 1, token_atom.long())
+    return written.long(), keep_mask, (out[9].long() & rt.MCS_UNDECIDED) == 0, flags.long(), status.long(), position.long()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # edit distance between molecules (csrc/k_edit.hip): rows of at most 64 positions, ids in [0, 64)
 # ----------------------------------------------------------------------------------------------------------------------
 def edit_distance(a_tokens, b_tokens, device) -> Tensor:

@@ -994,6 +994,65 @@ def _(natoms, atoms, nbonds, bonds, p_natoms, p_atoms, p_nbonds, p_bonds, count_
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# maximum common substructure of row pairs (csrc/k_molmcs.hip): rows of at most 64 positions on either side
+@custom_op("mdt::mol_mcs", mutates_args=())
+def mol_mcs(a_natoms: Tensor, a_atoms: Tensor, a_nbonds: Tensor, a_bonds: Tensor, b_natoms: Tensor, b_atoms: Tensor, b_nbonds: Tensor,
+            b_bonds: Tensor, mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (size int32 (R, 2): bonds, atoms; map_a uint8 (R, LA): 1 + the partner of each A atom; bond_a int64 (R,): the uint64 bits,
+    bit e = A entry e is matched; steps int32 (R,); natoms int32 (R,), atoms int32 (R, LA), nbonds int32 (R,), bonds int32 (R, LA),
+    atom_map uint8 (R, LA): the common substructure as graph arrays in mdt::mol_scaffold's format; flags uint8 (R,): 1 a pair of
+    molecules, 2 something in common, 4 undecided (a root was capped: a lower bound), 8 all of A, 16 all of B) of mdt_mol_mcs
+    (include/mdt_hip.h) on the graph arrays of mdt::mol_graph or mdt::mol_normalize -- A (R, LA <= 64) against B (R or 1, LB <= 64).
+    mode bit 0 (runtime.MCS_EXACT_ATOMS): whole atom words must be equal, not only symbol and aromatic bit.  The greatest CONNECTED
+    common subgraph by (bonds, atoms), edge kind, under a step cap per root; not RDKit's FindMCS."""
+    dev = _hip(a_natoms, a_atoms, a_nbonds, a_bonds, b_natoms, b_atoms, b_nbonds, b_bonds)
+    lib = rt.load_library()
+    op = "mdt::mol_mcs"
+    for what, n_, a_, nb_, b_ in (("a_", a_natoms, a_atoms, a_nbonds, a_bonds), ("b_", b_natoms, b_atoms, b_nbonds, b_bonds)):
+        if a_.dim() != 2 or tuple(b_.shape) != tuple(a_.shape) or any(t.dtype != torch.int32 for t in (n_, a_, nb_, b_)):
+            raise RuntimeError(f"{op}: {what}atoms and {what}bonds must be int32 (rows, width), {what}natoms and {what}nbonds int32 "
+                               "(as mdt::mol_graph returns them)")
+        if n_.numel() != a_.shape[0] or nb_.numel() != a_.shape[0]:
+            raise RuntimeError(f"{op}: {what}natoms and {what}nbonds must hold one value per row of {what}atoms")
+        if not 1 <= a_.shape[1] <= rt.MOL_MAX_LENGTH:
+            raise RuntimeError(f"{op}: {what}atoms has {a_.shape[1]} positions per row, the search takes 1 to {rt.MOL_MAX_LENGTH}")
+    (R, LA), (RB, LB) = a_atoms.shape, b_atoms.shape
+    if RB != R and RB != 1:
+        raise RuntimeError(f"{op}: b has {RB} rows; it takes {R} (row by row) or 1 (every a row against the one b row)")
+    if mode & ~rt.MCS_EXACT_ATOMS:
+        raise RuntimeError(f"{op}: mode = {mode} must be 0 or MCS_EXACT_ATOMS (1)")
+    a_natoms, a_atoms, a_nbonds, a_bonds = (t.contiguous() for t in (a_natoms, a_atoms, a_nbonds, a_bonds))
+    b_natoms, b_atoms, b_nbonds, b_bonds = (t.contiguous() for t in (b_natoms, b_atoms, b_nbonds, b_bonds))
+    size = torch.zeros(R, 2, dtype=torch.int32, device=dev)
+    map_a = torch.zeros(R, LA, dtype=torch.uint8, device=dev)
+    bond_a = torch.zeros(R, dtype=torch.int64, device=dev)
+    steps = torch.zeros(R, dtype=torch.int32, device=dev)
+    out_natoms = torch.zeros(R, dtype=torch.int32, device=dev)
+    out_atoms = torch.zeros(R, LA, dtype=torch.int32, device=dev)
+    out_nbonds = torch.zeros(R, dtype=torch.int32, device=dev)
+    out_bonds = torch.zeros(R, LA, dtype=torch.int32, device=dev)
+    atom_map = torch.zeros(R, LA, dtype=torch.uint8, device=dev)
+    flags = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if R:
+        with torch.cuda.device(dev):
+            rt.check(lib.mdt_mol_mcs(rt.ptr(a_natoms), rt.ptr(a_atoms), rt.ptr(a_nbonds), rt.ptr(a_bonds), LA, R, rt.ptr(b_natoms),
+                                     rt.ptr(b_atoms), rt.ptr(b_nbonds), rt.ptr(b_bonds), LB, RB, int(mode), rt.ptr(size),
+                                     rt.ptr(map_a), rt.ptr(bond_a), rt.ptr(steps), rt.ptr(out_natoms), rt.ptr(out_atoms),
+                                     rt.ptr(out_nbonds), rt.ptr(out_bonds), rt.ptr(atom_map), rt.ptr(flags), rt.current_stream()))
+    return size, map_a, bond_a, steps, out_natoms, out_atoms, out_nbonds, out_bonds, atom_map, flags
+
+
+@mol_mcs.register_fake
+def _(a_natoms, a_atoms, a_nbonds, a_bonds, b_natoms, b_atoms, b_nbonds, b_bonds, mode):
+    R, LA = a_atoms.shape
+    return (a_atoms.new_empty((R, 2), dtype=torch.int32), a_atoms.new_empty((R, LA), dtype=torch.uint8),
+            a_atoms.new_empty(R, dtype=torch.int64), a_atoms.new_empty(R, dtype=torch.int32), a_atoms.new_empty(R, dtype=torch.int32),
+            a_atoms.new_empty((R, LA), dtype=torch.int32), a_atoms.new_empty(R, dtype=torch.int32),
+            a_atoms.new_empty((R, LA), dtype=torch.int32), a_atoms.new_empty((R, LA), dtype=torch.uint8),
+            a_atoms.new_empty(R, dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # implicit hydrogens, the Kekule check and the formula (csrc/k_molh.hip): rows of at most 64 positions
 @custom_op("mdt::mol_hydrogens", mutates_args=())
 def mol_hydrogens(natoms: Tensor, atoms: Tensor, nbonds: Tensor, bonds: Tensor, max_steps: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:

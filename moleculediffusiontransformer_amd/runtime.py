@@ -64,6 +64,9 @@ MOLW_WRITTEN, MOLW_NO_FIT, MOLW_NO_VOCABULARY, MOLW_NOT_WRITABLE = 1, 2, 4, 8   
 MOLW_MAX_WIDTH = 128             # MDT_MOLW_MAX_WIDTH: mdt_mol_write writes rows of at most 128 tokens
 MOLC_CANONICAL, MOLC_UNDECIDED = 1, 2    # enum mdt_molc_flag: the flags of mdt_mol_canon
 MOLC_MAX_NODES = 4096            # MDT_MOLC_MAX_NODES: the node cap of mdt_mol_canon's search
+MCS_EXACT_ATOMS = 1              # enum mdt_mcs_mode: the mode bit of mdt_mol_mcs
+MCS_PAIR, MCS_COMMON, MCS_UNDECIDED, MCS_WHOLE_A, MCS_WHOLE_B = 1, 2, 4, 8, 16    # enum mdt_mcs_flag: its flags
+MCS_MAX_STEPS = 4096             # MDT_MCS_MAX_STEPS: the step cap of one root of mdt_mol_mcs
 FP_KNOWN_CHUNK = 512             # MDT_FP_KNOWN_CHUNK: known rows of one workgroup of mdt_fp_nearest
 EDIT_KNOWN_CHUNK = 512           # MDT_EDIT_KNOWN_CHUNK: known rows of one workgroup of mdt_edit_nearest
 EDIT_MAX_LENGTH = EDIT_MAX_ID = 64   # the edit distance takes rows of at most 64 positions, ids in [0, 64)
@@ -149,6 +152,7 @@ SYMBOLS = {
     "mdt_mol_scaffold": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_rank": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "mdt_mol_canon": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mdt_mol_mcs": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mdt_mol_write": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "mdt_screen_select_classes": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P,
                                        _P]),
