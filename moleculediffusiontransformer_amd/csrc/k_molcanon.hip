@@ -28,21 +28,6 @@ namespace mdt {
 static_assert(kMolcCanonical == MDT_MOLC_CANONICAL && kMolcUndecided == MDT_MOLC_UNDECIDED && kMolcMaxNodes == MDT_MOLC_MAX_NODES,
               "mdt_hip.h and mdt_molcanon.h agree");
 
-__device__ __forceinline__ uint64_t molc_readlane64(uint64_t v, int lane) {      // lane: wave-uniform
-  const int at = __builtin_amdgcn_readfirstlane(lane);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, at);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), at);
-  return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ int molc_readlane(int v, int lane) {                  // lane: wave-uniform
-  return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
-}
-__device__ __forceinline__ uint64_t molc_uniform64(uint64_t v) {                 // v: the same in every lane
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return (uint64_t)hi << 32 | lo;
-}
-
 // dynamic LDS of a row of width L: the lab and acc columns [L][L], the targets per level [L][L]
 __host__ __device__ inline size_t molc_lds_bytes(int L) { return (size_t)3 * L * L * sizeof(uint64_t); }
 
@@ -80,50 +65,46 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
   const bool here = lane < n;                                   // (n, nb <= L <= 64 from here on)
   const uint32_t d = here ? row_atoms[lane] : 0u;
   const uint32_t my_word = lane < nb ? row_bonds[lane] : 0u;
-  uint64_t adj = 0;
-  for (int e = 0; e < nb; ++e) {
+  uint64_t adj = 0;                                             // (mol_ring_adj_wave's loop, kept here: through the helper the
+  for (int e = 0; e < nb; ++e) {                                //  kernel came out with 60 VGPRs where this spelling gives 56)
     const uint32_t w = row_bonds[e];                            // the same word in every lane
     const int a = mol_a(w), b = mol_b(w);
-    if (a != b) adj |= (a == lane ? (uint64_t)1 << b : 0) | (b == lane ? (uint64_t)1 << a : 0);
+    if (a != b) adj |= (a == lane ? mol_bit(b) : 0) | (b == lane ? mol_bit(a) : 0);
   }
   const uint64_t twin_key = here ? molc_twin_key(row_bonds, nb, lane) : 0;
   uint64_t twins = 0;
   for (int b = 0; b < n; ++b) {
-    const uint64_t kb = molc_readlane64(twin_key, b);
-    const uint32_t db = (uint32_t)molc_readlane((int)d, b);
+    const uint64_t kb = readlane_u64(twin_key, b);
+    const uint32_t db = (uint32_t)readlane_i32((int)d, b);
     twins |= (twin_key != 0 && kb == twin_key && db == d) ? (uint64_t)1 << b : 0;
   }
   s_twins[lane] = twins;
   wave_lds_sync();
   // ---- the components, one search each ----
-  const uint64_t all = molw_all(n);
+  const uint64_t all = mol_all(n);
   uint64_t seen = 0;
   int count = 0, used = 0, components = 0;                      // wave-uniform: the nodes, the words of s_best in use
   int my_pos = 0, my_component = 0;                             // lane = atom: its position in the best leaf; its component
   int c_start = 0, c_size = 0, c_inside = 0;                    // lane = component: its certificate in s_best, its atoms and entries
   while (seen != all) {                                         // at most n floods of at most n levels in all
-    uint64_t members = 0, frontier = (uint64_t)1 << molh_lowest(all & ~seen);
-    while (frontier) {
-      members |= frontier;
-      frontier = __ballot((adj & frontier) != 0) & ~members;
-    }
+    const uint64_t members = mol_component_wave(adj, all, seen);
     seen |= members;
-    const bool member = mols_in(members, lane);
-    const int size = molh_popc(members);
-    const bool mine_in = lane < nb && mols_in(members, mol_a(my_word));   // lane = entry: inside this component
+    const bool member = mol_in(members, lane);
+    const int size = mol_popc(members);
+    const bool mine_in = lane < nb && mol_in(members, mol_a(my_word));   // lane = entry: inside this component
     const uint64_t inside_mask = __ballot(mine_in);
-    const int inside = molh_popc(inside_mask), words = 2 + size + inside;
+    const int inside = mol_popc(inside_mask), words = 2 + size + inside;
     uint32_t* best = s_best + used;                             // (used + words <= kMolcCertAll: the sizes and the counts sum to <= 64 each)
     bool have = false;
     int level = 0;                                              // the batch in hand: nodes of `level` marks
     uint64_t kids = 1, marked = 0, my_pending = 0;              // its lanes (the root: lane 0); the marks of the path; lane = level
     for (;;) {                                                  // a turn counts at least one node: bounded by the node cap
-      count += molh_popc(kids);
+      count += mol_popc(kids);
       if (count > kMolcMaxNodes) {
         nothing(kMolcUndecided, count);
         return;
       }
-      const bool active = mols_in(kids, lane);
+      const bool active = mol_in(kids, lane);
       if (lane < L)
         molc_refine(row_atoms, row_bonds, n, nb, s_marks, level > 0 ? level - 1 : 0, (level > 0 && active) ? lane : kMolcNoMark, lab, acc, L);
       const uint64_t open = members & ~marked & ~(level > 0 ? (uint64_t)1 << lane : 0);
@@ -133,19 +114,19 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
       const uint64_t inner = __ballot(active && target != 0);
       // ---- the leaves of the batch, one after the other: lane = atom, lane = entry ----
       for (uint64_t left = kids & ~inner; left != 0; left &= left - 1) {
-        const int leaf = molh_lowest(left);
+        const int leaf = mol_lowest(left);
         const uint64_t key = here ? s_cols[(size_t)lane * L + leaf] : 0;
         int pos = 0;
         for (int x = 0; x < n; ++x) {
           const uint64_t kx = s_cols[(size_t)x * L + leaf];     // the same word in every lane
-          pos += (mols_in(members, x) && (kx < key || (kx == key && x < lane))) ? 1 : 0;
+          pos += (mol_in(members, x) && (kx < key || (kx == key && x < lane))) ? 1 : 0;
         }
         const int pa = __shfl(pos, mol_a(my_word), 64), pb = __shfl(pos, mol_b(my_word), 64);
         const uint32_t entry = molc_entry(pa, pb, mol_order(my_word));
         int rank = 0;
         for (int x = 0; x < nb; ++x) {
-          const uint32_t ex = (uint32_t)molc_readlane((int)entry, x);
-          rank += (mols_in(inside_mask, x) && (ex < entry || (ex == entry && x < lane))) ? 1 : 0;
+          const uint32_t ex = (uint32_t)readlane_i32((int)entry, x);
+          rank += (mol_in(inside_mask, x) && (ex < entry || (ex == entry && x < lane))) ? 1 : 0;
         }
         if (member) s_cand[1 + pos] = d;
         if (mine_in) s_cand[2 + size + rank] = entry;
@@ -156,14 +137,14 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
           const int i = base + lane;
           const uint64_t differ = __ballot(i < words && s_cand[i] != best[i]);
           if (differ != 0) {
-            const int first = base + molh_lowest(differ);
+            const int first = base + mol_lowest(differ);
             better = s_cand[first] < best[first];
             decided = true;
           }
         }
         if (!decided) {                                         // one certificate: the positions in ascending atom index decide
           const uint64_t differ = __ballot(member && pos != my_pos);
-          if (differ != 0) better = molc_readlane(pos, molh_lowest(differ)) < molc_readlane(my_pos, molh_lowest(differ));
+          if (differ != 0) better = readlane_i32(pos, mol_lowest(differ)) < readlane_i32(my_pos, mol_lowest(differ));
         }
         if (better) {
           for (int i = lane; i < words; i += 64) best[i] = s_cand[i];
@@ -177,13 +158,13 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
       while (pend == 0 && level > 0) {
         --level;
         if (level >= 1) marked &= ~((uint64_t)1 << __builtin_amdgcn_readfirstlane((int)s_marks[level - 1]));
-        pend = molc_readlane64(my_pending, level);
+        pend = readlane_u64(my_pending, level);
       }
       if (pend == 0) break;
-      const int child = molh_lowest(pend);
+      const int child = mol_lowest(pend);
       pend &= pend - 1;
       my_pending = lane == level ? pend : my_pending;
-      kids = molc_uniform64(s_target[level * L + child]);
+      kids = uniform_u64(s_target[level * L + child]);
       if (level >= 1) {
         if (lane == 0) s_marks[level - 1] = (uint8_t)child;
         marked |= (uint64_t)1 << child;
@@ -200,15 +181,15 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
   int c_rank = 0;
   for (int i = 0; i < components; ++i) {
     for (int j = i + 1; j < components; ++j) {                  // (bounded by 64 * 63 / 2)
-      const int si = molc_readlane(c_start, i), sj = molc_readlane(c_start, j);
-      const int wi = 2 + molc_readlane(c_size, i) + molc_readlane(c_inside, i), wj = 2 + molc_readlane(c_size, j) + molc_readlane(c_inside, j);
+      const int si = readlane_i32(c_start, i), sj = readlane_i32(c_start, j);
+      const int wi = 2 + readlane_i32(c_size, i) + readlane_i32(c_inside, i), wj = 2 + readlane_i32(c_size, j) + readlane_i32(c_inside, j);
       const int shorter = wi < wj ? wi : wj;                    // (equal up to the shorter one's end only if equally long: the sizes lead)
       bool j_first = false, decided = false;
       for (int base = 0; base < shorter && !decided; base += 64) {
         const int k = base + lane;
         const uint64_t differ = __ballot(k < shorter && s_best[si + k] != s_best[sj + k]);
         if (differ != 0) {
-          const int first = base + molh_lowest(differ);
+          const int first = base + mol_lowest(differ);
           j_first = s_best[sj + first] < s_best[si + first];
           decided = true;
         }
@@ -218,9 +199,9 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
   }
   int c_offset = 0, c_entries = 0;                              // the atoms and the entries of the components before it
   for (int x = 0; x < components; ++x) {
-    const bool before = molc_readlane(c_rank, x) < c_rank;
-    c_offset += before ? molc_readlane(c_size, x) : 0;
-    c_entries += before ? molc_readlane(c_inside, x) : 0;
+    const bool before = readlane_i32(c_rank, x) < c_rank;
+    c_offset += before ? readlane_i32(c_size, x) : 0;
+    c_entries += before ? readlane_i32(c_inside, x) : 0;
   }
   // ---- the row: lane = atom, then per component lane = entry; the lanes from the counts up to L write the zeros ----
   const int my_offset = __shfl(c_offset, my_component, 64);
@@ -228,8 +209,8 @@ __global__ __launch_bounds__(64) void k_mol_canon(const int32_t* __restrict__ na
   if (here) out_a[my_offset + my_pos] = d;                      // (a permutation of 0..n-1: every word is written once)
   else if (lane < L) out_a[lane] = 0;
   for (int c = 0; c < components; ++c) {
-    const int start = molc_readlane(c_start, c), size = molc_readlane(c_size, c), inside = molc_readlane(c_inside, c);
-    const int offset = molc_readlane(c_offset, c), entries = molc_readlane(c_entries, c);
+    const int start = readlane_i32(c_start, c), size = readlane_i32(c_size, c), inside = readlane_i32(c_inside, c);
+    const int offset = readlane_i32(c_offset, c), entries = readlane_i32(c_entries, c);
     if (lane < inside) out_b[entries + lane] = molc_bond_word(s_best[start + 2 + size + lane], offset);
   }
   if (lane >= nb && lane < L) out_b[lane] = 0;                  // (the entries of the components are the nb entries of the row)

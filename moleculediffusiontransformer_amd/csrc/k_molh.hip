@@ -25,12 +25,6 @@ static_assert(kMolhOk == MDT_MOLH_OK && kMolhAromaticOvervalent == MDT_MOLH_AROM
                   kMolhNoKekule == MDT_MOLH_NO_KEKULE && kMolhUndecided == MDT_MOLH_UNDECIDED,
               "mdt_hip.h and mdt_molh.h agree");
 
-__device__ __forceinline__ uint64_t molh_readlane64(uint64_t v, int lane) {      // lane: wave-uniform
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-  return (uint64_t)hi << 32 | lo;
-}
-
 __global__ __launch_bounds__(64 * kMolhRowsPerBlock) void k_mol_hydrogens(
     const int32_t* __restrict__ natoms, const uint32_t* __restrict__ atoms, const int32_t* __restrict__ nbonds,
     const uint32_t* __restrict__ bonds, int L, int R, int max_steps, uint8_t* __restrict__ hydrogens, uint8_t* __restrict__ partner,
@@ -73,7 +67,7 @@ __global__ __launch_bounds__(64 * kMolhRowsPerBlock) void k_mol_hydrogens(
   int mine = 0;
 #pragma unroll
   for (int k = 0; k < kMolhSlotCharge; ++k) {
-    const int c = molh_popc(__ballot(slot == k));
+    const int c = mol_popc(__ballot(slot == k));
     mine = lane == k ? c : mine;
   }
   int both = here ? (h | (molh_charge(desc) + 9) << 16) : 0;    // (h <= 15 and charge + 9 <= 31 for each of <= 64 atoms)
@@ -84,8 +78,8 @@ __global__ __launch_bounds__(64 * kMolhRowsPerBlock) void k_mol_hydrogens(
   int code, first_over = -1, my_depth = -1, my_partner = 0;
   if (overvalent) {
     code = kMolhAromaticOvervalent;
-    first_over = molh_lowest(overvalent);
-  } else if (molh_popc(W) & 1) {
+    first_over = mol_lowest(overvalent);
+  } else if (mol_popc(W) & 1) {
     code = kMolhNoKekule;
   } else {
     uint64_t M = W, back = 0;                                   // back: the pair a step back has just restored, else 0
@@ -93,15 +87,15 @@ __global__ __launch_bounds__(64 * kMolhRowsPerBlock) void k_mol_hydrogens(
     for (;;) {                                                  // bounded: at most max_steps tries, and as many taken back
       if (M == 0) { code = kMolhOk; break; }
       const bool in = (M >> lane) & 1u;
-      const int cnt = molh_popc(adj & M);
+      const int cnt = mol_popc(adj & M);
       int u = 0;
       for (int c = 0; c < n; ++c) {                             // bounded by n: some atom of M has c < n unmatched neighbours
         const uint64_t at = __ballot(in && cnt == c);
-        if (at) { u = molh_lowest(at); break; }
+        if (at) { u = mol_lowest(at); break; }
       }
       u = __builtin_amdgcn_readfirstlane(u);
-      const uint64_t allowed = back ? molh_above(molh_lowest(back & ~((uint64_t)1 << u))) : ~(uint64_t)0;
-      const uint64_t cand = molh_readlane64(adj, u) & M & allowed;
+      const uint64_t allowed = back ? mol_above(mol_lowest(back & ~((uint64_t)1 << u))) : ~(uint64_t)0;
+      const uint64_t cand = readlane_u64(adj, u) & M & allowed;
       if (cand == 0) {                                          // back: the last pair returns, u goes on above its partner
         if (depth == 0) { code = kMolhNoKekule; break; }
         --depth;
@@ -111,7 +105,7 @@ __global__ __launch_bounds__(64 * kMolhRowsPerBlock) void k_mol_hydrogens(
         continue;
       }
       if (made == max_steps) { code = kMolhUndecided; break; }
-      const int v = molh_lowest(cand);
+      const int v = mol_lowest(cand);
       ++made;
       if (lane == u || lane == v) my_depth = depth, my_partner = 1 + (lane == u ? v : u);
       ++depth;

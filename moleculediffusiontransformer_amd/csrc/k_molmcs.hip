@@ -100,7 +100,7 @@ __global__ __launch_bounds__(64 * kMcsRowsPerBlock) void k_mol_mcs(
       }
       s.low[lane] = below;
       for (int o = 0; o < kMcsOrders; ++o) {                    // B's bonds of each order as a set: every pair once, at its lower atom
-        const int mine = sub_popcount(s.adj_b[o * 64 + lane] & sub_above(lane));
+        const int mine = mol_popc(s.adj_b[o * 64 + lane] & mol_above(lane));
         if (mine) atomicAdd(&s.total_b, (unsigned long long)mine << (8 * o));
       }
       wave_lds_sync();
@@ -159,8 +159,8 @@ __global__ __launch_bounds__(64 * kMcsRowsPerBlock) void k_mol_mcs(
         uint8_t* inv = s.st + s.winner * kMcsLaneStride;        // ... and, in its stack bytes, the inverse of it
         const bool kept = (mapped >> lane) & 1ull;              // (only bits below na are ever set)
         image = kept ? 1 + wm[lane] : 0;
-        renum = kept ? 1 + sub_popcount(mapped & (mcs_bit(lane) - 1)) : 0;
-        o_atoms = sub_popcount(mapped);
+        renum = kept ? 1 + mol_popc(mapped & (mol_bit(lane) - 1)) : 0;   // (mol_index by the lane's own bit, here and below: through
+        o_atoms = mol_popc(mapped);                              //  the helper the compiler forms the lane's mask a second way)
         inv[lane] = 255;
         wave_lds_sync();
         if (kept) inv[image - 1] = (uint8_t)lane, s.row[renum - 1] = da;
@@ -170,16 +170,15 @@ __global__ __launch_bounds__(64 * kMcsRowsPerBlock) void k_mol_mcs(
         const bool in = use_a && ((mapped >> mol_a(wa)) & (mapped >> mol_b(wa)) & 1ull) &&
                         ((s.adj_b[(mol_order(wa) - 1) * 64 + wm[mol_a(wa)]] >> wm[mol_b(wa)]) & 1ull);
         matched = __ballot(in);
-        o_bonds = sub_popcount(matched);
+        o_bonds = mol_popc(matched);
         // B's side: a usable B entry is in the result when A has a usable entry of its order between the partners of its ends
         const int ua = use_b ? inv[mol_a(wb)] : 255, ub = use_b ? inv[mol_b(wb)] : 255;
         const bool b_out = use_b && (ua == 255 || ub == 255 || !((s.adj_a[(mol_order(wb) - 1) * 64 + (ua & 63)] >> (ub & 63)) & 1ull));
         const bool b_miss = __any(b_out);
         wave_lds_sync();                                        // (the atom words are read: the row takes the bond words)
         if (in)
-          s.row[sub_popcount(matched & (mcs_bit(lane) - 1))] = (uint32_t)(sub_popcount(mapped & (mcs_bit(mol_a(wa)) - 1))) |
-                                                               (uint32_t)(sub_popcount(mapped & (mcs_bit(mol_b(wa)) - 1))) << 8 |
-                                                               (uint32_t)mol_order(wa) << 16;
+          s.row[mol_popc(matched & (mol_bit(lane) - 1))] = (uint32_t)mol_index(mapped, mol_a(wa)) | (uint32_t)mol_index(mapped, mol_b(wa)) << 8 |
+                                            (uint32_t)mol_order(wa) << 16;
         wave_lds_sync();
         bond_word = lane < o_bonds ? s.row[lane] : 0u;
         o_flags |= kMcsCommon;

@@ -84,11 +84,11 @@ __global__ __launch_bounds__(64 * kMolnRowsPerBlock) void k_mol_normalize(
   uint64_t aromatic = 0;
   bool marked = false;
   for (uint64_t rest = __ballot(tried); rest; rest &= rest - 1) {   // at most nb searches; none in a row without an eligible ring bond
-    const uint32_t w = row_bonds[molh_lowest(rest)];
+    const uint32_t w = row_bonds[mol_lowest(rest)];
     const int a = mol_a(w), b = mol_b(w);
     const uint64_t bit_a = (uint64_t)1 << a, bit_b = (uint64_t)1 << b;
     const uint64_t own = adj & ~(lane == a ? bit_b : 0) & ~(lane == b ? bit_a : 0);
-    uint64_t visited = bit_a, frontier = bit_a;
+    uint64_t visited = bit_a, frontier = bit_a;                 // (mol_search by the wave; why it is written out: k_molring.hip)
     int my_level = 0, depth = 0;                                // (0: lane a, and every lane this search has not reached)
     bool found = false;
     for (;;) {                                                  // bounded by n: a level adds an atom to `visited` or ends the search
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64 * kMolnRowsPerBlock) void k_mol_normalize(
       for (int level = depth - 1; level >= 1; --level) {        // one ballot per level
         const uint64_t from = __ballot(my_level == level && ((own >> at) & 1u));
         if (from == 0) break;                                   // (cannot be: an atom of level k + 1 has a neighbour of level k)
-        at = pick ? moln_highest(from) : molh_lowest(from);
+        at = pick ? mol_highest(from) : mol_lowest(from);
         ring |= (uint64_t)1 << at;
       }
       if (pick && ring == first) break;                         // one smallest cycle through the entry: judged already

@@ -66,17 +66,17 @@ __global__ __launch_bounds__(64 * kMolrRowsPerBlock) void k_mol_rings(
   const bool here = lane < n;
   const uint32_t d = here ? atoms[row * L + lane] : 0u;
   const int h = here ? (int)hydrogens[row * L + lane] : 0;
-  const int degree = molh_popc(adj);                            // (0 in a lane beyond n: no entry names it)
+  const int degree = mol_popc(adj);                            // (0 in a lane beyond n: no entry names it)
   const bool heavy = here && molr_heavy(d), carbon = here && molr_carbon(d), n_or_o = here && molr_n_or_o(d);
   const bool aromatic = here && molr_aromatic(d);
   const uint64_t heavy_set = __ballot(heavy);
   // ---- the components: floods from the lowest atom not yet seen (bounded by n: every level reaches an atom) ----
-  const uint64_t all = n >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << n) - 1);
+  const uint64_t all = mol_all(n);
   uint64_t seen = 0;
   int components = 0;
-  while (seen != all) {
-    uint64_t frontier = (uint64_t)1 << molh_lowest(all & ~seen);
-    ++components;
+  while (seen != all) {                                         // (mol_component_wave's flood without its `members`: the row's
+    uint64_t frontier = mol_bit(mol_lowest(all & ~seen));       //  atoms are only counted here, and through the helper the two
+    ++components;                                               //  loops came out 4 scalar instructions a component longer)
     while (frontier) {
       seen |= frontier;
       frontier = __ballot((adj & frontier) != 0) & ~seen;
@@ -96,6 +96,8 @@ __global__ __launch_bounds__(64 * kMolrRowsPerBlock) void k_mol_rings(
       const uint32_t w = row_bonds[e];
       const int a = mol_a(w), b = mol_b(w);
       if (a == b || (((leaves >> a) | (leaves >> b)) & 1u)) continue;   // no edge; the only edge of one of its ends: a bridge
+      // mol_search by the wave, written out here and in k_mol_normalize: that one keeps every lane's level and asks "reached?" after
+      // "empty?", this one keeps nothing and asks in the other order; one form for both needs a flag or changes both kernels' code
       const uint64_t own = adj & ~(lane == a ? (uint64_t)1 << b : 0) & ~(lane == b ? (uint64_t)1 << a : 0);
       uint64_t visited = (uint64_t)1 << a, frontier = visited;
       int ring = 0;
@@ -115,21 +117,21 @@ __global__ __launch_bounds__(64 * kMolrRowsPerBlock) void k_mol_rings(
   }
   if (lane < L) out_b[lane] = (uint8_t)my_bond_ring, out_a[lane] = (uint8_t)my_atom_ring;
   // ---- the descriptors: ballots and popcounts ----
-  const uint64_t turns = __ballot(molh_popc(adj & heavy_set) >= 2 && !triple);   // atoms a rotatable bond may end at
+  const uint64_t turns = __ballot(mol_popc(adj & heavy_set) >= 2 && !triple);   // atoms a rotatable bond may end at
   const int ea = mol_a(my_word), eb = mol_b(my_word);
   const bool rotatable = lane < nb && mol_order(my_word) == 1 && my_bond_ring == 0 && ea != eb && ((turns >> ea) & 1u) &&
                          ((turns >> eb) & 1u);
   int weight = h_sum * molr_mass(kMolhSlotH);
   const int slot = here ? molh_slot(d) : -1;
 #pragma unroll
-  for (int k = 0; k < kMolhSlotOther; ++k) weight += molh_popc(__ballot(slot == k)) * molr_mass(k);
+  for (int k = 0; k < kMolhSlotOther; ++k) weight += mol_popc(__ballot(slot == k)) * molr_mass(k);
   // (every ballot is taken by the whole wave, outside the selects: inside `lane == k ? ... : ...` only lane k would vote)
-  const int n_heavy = molh_popc(heavy_set), n_hetero = molh_popc(__ballot(heavy && !carbon));
-  const int n_donors = molh_popc(__ballot(n_or_o && h >= 1)), n_acceptors = molh_popc(__ballot(n_or_o));
-  const int n_rotatable = molh_popc(__ballot(rotatable));
-  const int n_ring_atoms = molh_popc(__ballot(my_atom_ring > 0)), n_ring_bonds = molh_popc(__ballot(my_bond_ring > 0));
-  const int n_aromatic = molh_popc(__ballot(aromatic)), n_outside = molh_popc(__ballot(aromatic && my_atom_ring == 0));
-  const int n_sp3 = molh_popc(__ballot(carbon && !aromatic && !not_single)), n_carbons = molh_popc(__ballot(carbon));
+  const int n_heavy = mol_popc(heavy_set), n_hetero = mol_popc(__ballot(heavy && !carbon));
+  const int n_donors = mol_popc(__ballot(n_or_o && h >= 1)), n_acceptors = mol_popc(__ballot(n_or_o));
+  const int n_rotatable = mol_popc(__ballot(rotatable));
+  const int n_ring_atoms = mol_popc(__ballot(my_atom_ring > 0)), n_ring_bonds = mol_popc(__ballot(my_bond_ring > 0));
+  const int n_aromatic = mol_popc(__ballot(aromatic)), n_outside = mol_popc(__ballot(aromatic && my_atom_ring == 0));
+  const int n_sp3 = mol_popc(__ballot(carbon && !aromatic && !not_single)), n_carbons = mol_popc(__ballot(carbon));
   int mine = 0;
   mine = lane == kMolrHeavy ? n_heavy : mine;
   mine = lane == kMolrHetero ? n_hetero : mine;

@@ -60,31 +60,31 @@ __global__ __launch_bounds__(64 * kMolsRowsPerBlock) void k_mol_scaffold(
   // ---- the core: in rounds, every atom with at most one neighbour still present leaves (bounded by n) ----
   uint64_t alive = __ballot(here);
   for (;;) {
-    const uint64_t gone = __ballot(mols_in(alive, lane) && molh_popc(adj & alive) <= 1);
+    const uint64_t gone = __ballot(mol_in(alive, lane) && mol_popc(adj & alive) <= 1);
     if (gone == 0) break;
     alive &= ~gone;
   }
   // ---- the exocyclic atoms, the kept word, and what a kept bracket atom gains for the entries it loses ----
   uint64_t kept = alive;
-  if (alive != 0 && (mode & kMolsExocyclic)) kept |= __ballot(here && !mols_in(alive, lane) && (dbl & alive) != 0);
-  const int kept_atoms = molh_popc(kept);
+  if (alive != 0 && (mode & kMolsExocyclic)) kept |= __ballot(here && !mol_in(alive, lane) && (dbl & alive) != 0);
+  const int kept_atoms = mol_popc(kept);
   int gained = 0;
   if (kept_atoms != 0 && kept_atoms != n && !(mode & kMolsGeneric))
     for (int e = 0; e < nb; ++e) {
       const uint32_t w = row_bonds[e];
       const int a = mol_a(w), b = mol_b(w);
-      const bool lost = a != b && ((a == lane && !mols_in(kept, b)) || (b == lane && !mols_in(kept, a)));
+      const bool lost = a != b && ((a == lane && !mol_in(kept, b)) || (b == lane && !mol_in(kept, a)));
       gained += lost ? mols_weight(mol_order(w)) : 0;
     }
   // ---- the scaffold: kept atoms and entries at their new slots, zeros from the kept counts up to L ----
-  const bool mine = mols_in(kept, lane);
-  const int to = mols_index(kept, lane);                        // (< kept_atoms <= n <= L where `mine`)
+  const bool mine = mol_in(kept, lane);
+  const int to = mol_index(kept, lane);                        // (< kept_atoms <= n <= L where `mine`)
   const int ea = mol_a(my_word), eb = mol_b(my_word);
-  const bool stays = entry && ea != eb && mols_in(kept, ea) && mols_in(kept, eb);
+  const bool stays = entry && ea != eb && mol_in(kept, ea) && mol_in(kept, eb);
   const uint64_t kept_entries = __ballot(stays);
-  const int kept_bonds = molh_popc(kept_entries);
+  const int kept_bonds = mol_popc(kept_entries);
   if (mine) out_a[to] = mols_atom_word(d, gained, mode);
-  if (stays) out_b[mols_index(kept_entries, lane)] = mols_bond_word(kept, ea, eb, mol_order(my_word), mode);
+  if (stays) out_b[mol_index(kept_entries, lane)] = mols_bond_word(kept, ea, eb, mol_order(my_word), mode);
   if (lane < L) {
     if (lane >= kept_atoms) out_a[lane] = 0u;
     if (lane >= kept_bonds) out_b[lane] = 0u;

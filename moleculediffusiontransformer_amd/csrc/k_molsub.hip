@@ -243,8 +243,8 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_map(
       }
       if (search && m == 1) {                                   // every accepted atom is an anchor, a map and its own image
         fnd = cov = roots;
-        emb = (uint32_t)__popcll((unsigned long long)roots);
-        image = lane == 0 ? 1 + sub_lowest(roots) : 0;
+        emb = (uint32_t)mol_popc(roots);
+        image = lane == 0 ? 1 + mol_lowest(roots) : 0;
       } else if (search) {
         if (lane == 0) s_cover[wave] = 0, s_sum[wave] = 0;
         wave_lds_sync();
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(64 * kSubRowsPerBlock) void k_sub_map(
         }
         fnd = __ballot(seen != 0);
         cap = __ballot(cut);
-        const int low = fnd ? sub_lowest(fnd) : -1;             // (wave-uniform)
+        const int low = fnd ? mol_lowest(fnd) : -1;             // (wave-uniform)
         if (lane == low) {                                      // the first map of the lowest found root: its walk once more
           int steps;
           SubNoSignal alone;

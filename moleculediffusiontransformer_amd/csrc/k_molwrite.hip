@@ -35,15 +35,6 @@ static_assert(kMolwWritten == MDT_MOLW_WRITTEN && kMolwNoFit == MDT_MOLW_NO_FIT 
                   kMolwNotWritable == MDT_MOLW_NOT_WRITABLE && kMolwMaxW == MDT_MOLW_MAX_WIDTH,
               "mdt_hip.h and mdt_molwrite.h agree");
 
-__device__ __forceinline__ uint64_t molw_readlane64(uint64_t v, int lane) {      // lane: wave-uniform
-  const int at = __builtin_amdgcn_readfirstlane(lane);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, at);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), at);
-  return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ int molw_readlane(int v, int lane) {                  // lane: wave-uniform
-  return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
-}
 __device__ __forceinline__ uint64_t molw_shfl64(uint64_t v, int lane) {          // lane: any lane's own choice, 0..63
   const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
   const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane, 64);
@@ -69,28 +60,19 @@ __global__ __launch_bounds__(64) void k_mol_rank(const int32_t* __restrict__ nat
   const uint64_t h = mol_root_hash(row_atoms, row_bonds, n, nb, lane, lab, acc, 64);
   wave_lds_sync();                                              // the columns are read across lanes below
   // ---- lane = atom: its neighbours in the ring graph (bounded by nb <= L) ----
-  uint64_t adj = 0;
-  for (int e = 0; e < nb; ++e) {
-    const uint32_t w = row_bonds[e];                            // the same word in every lane
-    const int a = mol_a(w), b = mol_b(w);
-    if (a != b) adj |= (a == lane ? (uint64_t)1 << b : 0) | (b == lane ? (uint64_t)1 << a : 0);
-  }
+  const uint64_t adj = mol_ring_adj_wave(row_bonds, nb, lane);
   // ---- per component: the root with the smallest (H, index), and its column (at most n floods of at most n levels in all) ----
-  const uint64_t all = molw_all(n);
+  const uint64_t all = mol_all(n);
   uint64_t seen = 0, mine = 0;
   while (seen != all) {
-    uint64_t members = 0, frontier = (uint64_t)1 << molh_lowest(all & ~seen);
-    while (frontier) {
-      members |= frontier;
-      frontier = __ballot((adj & frontier) != 0) & ~members;
-    }
-    const bool member = mols_in(members, lane);
+    const uint64_t members = mol_component_wave(adj, all, seen);
+    const bool member = mol_in(members, lane);
     uint64_t least = member ? h : ~(uint64_t)0;
     for (int off = 32; off >= 1; off >>= 1) {
       const uint64_t other = shfl_xor_u64(least, off);
       least = other < least ? other : least;
     }
-    const int root = molh_lowest(__ballot(member && h == least));   // (not empty: some member has the minimum)
+    const int root = mol_lowest(__ballot(member && h == least));   // (not empty: some member has the minimum)
     if (member) mine = s_cols[(size_t)lane * 64 + root];       // lab_root[lane]
     seen |= members;
   }
@@ -146,7 +128,7 @@ __global__ __launch_bounds__(64 * kMolwRowsPerBlock) void k_mol_write(
   const uint64_t p = (priority != nullptr && here) ? priority[row * L + lane] : 0;
   int rank = 0;
   for (int x = 0; x < n; ++x) {
-    const uint64_t px = molw_readlane64(p, x);
+    const uint64_t px = readlane_u64(p, x);
     rank += (px < p || (px == p && x < lane)) ? 1 : 0;
   }
   rank = here ? rank : lane;                                    // (a permutation of all 64 lanes: the lanes beyond n stay)
@@ -154,23 +136,23 @@ __global__ __launch_bounds__(64 * kMolwRowsPerBlock) void k_mol_write(
   uint64_t adj_rank = 0;
   for (int e = 0; e < nb; ++e) {
     const uint32_t w = row_bonds[e];
-    const int ra = molw_readlane(rank, mol_a(w)), rb = molw_readlane(rank, mol_b(w));
+    const int ra = readlane_i32(rank, mol_a(w)), rb = readlane_i32(rank, mol_b(w));
     adj_rank |= (lane == ra ? (uint64_t)1 << rb : 0) | (lane == rb ? (uint64_t)1 << ra : 0);
   }
   // ---- pass 1: the scalar walk (at most 2 n steps: a step visits an atom or steps back) ----
-  const uint64_t all = molw_all(n);
+  const uint64_t all = mol_all(n);
   uint64_t visited = 0;
   int count = 0, my_seq = lane, my_par = kMolwRoot, my_par_rank = 0;           // (lane = rank; beyond n a lane keeps itself)
   while (visited != all) {
-    const int root = molh_lowest(all & ~visited);
+    const int root = mol_lowest(all & ~visited);
     int cur = root, cur_seq = count;
     if (lane == cur) my_seq = count, my_par = kMolwRoot;
     visited |= (uint64_t)1 << cur;
     ++count;
     for (;;) {
-      const uint64_t cand = molw_readlane64(adj_rank, cur) & ~visited;
+      const uint64_t cand = readlane_u64(adj_rank, cur) & ~visited;
       if (cand != 0) {
-        const int next = molh_lowest(cand);
+        const int next = mol_lowest(cand);
         if (lane == next) my_seq = count, my_par = cur_seq, my_par_rank = cur;
         visited |= (uint64_t)1 << next;
         cur = next, cur_seq = count;
@@ -178,8 +160,8 @@ __global__ __launch_bounds__(64 * kMolwRowsPerBlock) void k_mol_write(
       } else if (cur == root) {
         break;
       } else {
-        const int up = molw_readlane(my_par_rank, cur);
-        cur_seq = molw_readlane(my_par, cur);
+        const int up = readlane_i32(my_par_rank, cur);
+        cur_seq = readlane_i32(my_par, cur);
         cur = up;
       }
     }
@@ -196,33 +178,33 @@ __global__ __launch_bounds__(64 * kMolwRowsPerBlock) void k_mol_write(
   me.adj = me.o0 = me.o1 = me.o2 = me.child = 0;
   for (int e = 0; e < nb; ++e) {
     const uint32_t w = row_bonds[e];
-    const int sa = molw_readlane(seq_of_atom, mol_a(w)), sb = molw_readlane(seq_of_atom, mol_b(w)), o = mol_order(w);
+    const int sa = readlane_i32(seq_of_atom, mol_a(w)), sb = readlane_i32(seq_of_atom, mol_b(w)), o = mol_order(w);
     const uint64_t far = (lane == sa ? (uint64_t)1 << sb : 0) | (lane == sb ? (uint64_t)1 << sa : 0);
     me.adj |= far, me.o0 |= (o & 1) ? far : 0, me.o1 |= (o & 2) ? far : 0, me.o2 |= (o & 4) ? far : 0;
   }
   for (int t = 0; t < n; ++t)                                   // the children: every atom tells its parent
-    me.child |= molw_readlane(me.par, t) == lane ? (uint64_t)1 << t : 0;
+    me.child |= readlane_i32(me.par, t) == lane ? (uint64_t)1 << t : 0;
   const uint64_t aromatic = __ballot(here && (me.d & kMolAromatic) != 0);
   const uint64_t my_open = here ? me.opens(lane) : 0, my_close = here ? me.closes(lane) : 0;
-  int base = molh_popc(my_open);                                // -> the exclusive prefix sum over the lanes
+  int base = mol_popc(my_open);                                // -> the exclusive prefix sum over the lanes
   for (int off = 1; off < 64; off <<= 1) {
     const int below = __shfl_up(base, off, 64);
     base += lane >= off ? below : 0;
   }
-  base -= molh_popc(my_open);
+  base -= mol_popc(my_open);
   // ---- the ring numbers: the second scalar walk, over the atoms and their closures; lane k keeps the number of slot k ----
   uint64_t free_numbers = ~(uint64_t)0;                         // bit k: number k + 1 (at most 63 closures: never empty)
   int my_number = 0;
   for (int s = 0; s < n; ++s) {
     uint64_t closed = 0;
-    for (uint64_t left = molw_readlane64(my_close, s); left != 0; left &= left - 1) {
-      const int t = molh_lowest(left);
-      const int slot = molw_readlane(base, t) + molh_popc(molw_readlane64(my_open, t) & mols_below(s));
-      closed |= (uint64_t)1 << (molw_readlane(my_number, slot) - 1);
+    for (uint64_t left = readlane_u64(my_close, s); left != 0; left &= left - 1) {
+      const int t = mol_lowest(left);
+      const int slot = readlane_i32(base, t) + mol_popc(readlane_u64(my_open, t) & mol_below(s));
+      closed |= (uint64_t)1 << (readlane_i32(my_number, slot) - 1);
     }
-    int slot = molw_readlane(base, s);
-    for (uint64_t left = molw_readlane64(my_open, s); left != 0; left &= left - 1, ++slot) {
-      const int k = molh_lowest(free_numbers);
+    int slot = readlane_i32(base, s);
+    for (uint64_t left = readlane_u64(my_open, s); left != 0; left &= left - 1, ++slot) {
+      const int k = mol_lowest(free_numbers);
       free_numbers &= ~((uint64_t)1 << k);
       my_number = lane == slot ? k + 1 : my_number;
     }

@@ -1,7 +1,7 @@
 // Device primitives shared by the ring and block kernels (k_tblock_lw, k_tblock32, k_tf128, k_tf256, k_rconv, k_res256, k_proj,
 // k_resblock, k_attn): vector types, MFMA names, lane-group exchanges, operand splits, counted LDS reads and their waits; and by the
-// screening kernels (k_screen, k_edit, k_molgraph, k_molfp, k_molsub): the 64-bit shuffle, the edit-distance recurrence, the
-// wave-local LDS ordering.
+// screening and molecule kernels (k_screen, k_edit, k_mol*): the 64-bit shuffle and lane reads, the edit-distance recurrence, the
+// wave-local LDS ordering.  (What the molecule kernels share about the graph row itself is mdt_molrow.h's.)
 // Device code only; included by the .hip files that use it, never through mdt_kernels.h (mdt_api.cpp does not see it).
 // Everything is __forceinline__: a kernel's code object does not depend on whether a primitive is defined here or in its file.
 // The rule: a primitive used by two kernels lives here, once, with its rationale; what one kernel alone uses stays in its file.
@@ -203,6 +203,24 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
   const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, off, 64);
   const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off, 64);
   return ((unsigned long long)hi << 32) | lo;
+}
+
+// One lane's value as a wave-uniform (scalar) value (k_molwrite: the walks over rank and seq; k_molcanon: the twins, the entries, the
+// components).  lane: the same in every lane, though the compiler may not know it -- hence the readfirstlane.
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int lane) {
+  const int at = __builtin_amdgcn_readfirstlane(lane);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, at);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), at);
+  return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ int readlane_i32(int v, int lane) {
+  return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
+}
+// v is the same in every lane: tell the compiler so (a word read from LDS that steers wave-uniform control flow)
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return (uint64_t)hi << 32 | lo;
 }
 
 // Levenshtein distance by Hyyro's form of Myers' bit-vector recurrence (k_edit, k_screen): the pattern a[0:m], 1 <= m <= 64, is

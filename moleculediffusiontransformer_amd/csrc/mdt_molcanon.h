@@ -1,8 +1,8 @@
 // The canonical atom order of a graph row (mdt_hip.h, mdt_mol_canon): refinement with marks, the twin word, the target class of a
 // node, the certificate of a leaf, and the serial form of the entry point -- an individualisation-refinement search over the
-// refinement of mdt_mol_key, the smallest relabelled graph as the answer.  The rooted hash, the bond accessors and "is this a graph
-// row?" are mdt_smiles_scan.h's, the bit helpers mdt_molh.h's, mdt_molnorm.h's and mdt_molscaf.h's, molw_all mdt_molwrite.h's.  Like
-// those headers everything here is __host__ __device__ and touches only the arrays it is handed.  The kernel (k_molcanon.hip: one
+// refinement of mdt_mol_key, the smallest relabelled graph as the answer.  The mixing of the rooted hash is mdt_smiles_scan.h's; the
+// bond accessors, "is this a graph row?", the sets, the ring graph and its components are mdt_molrow.h's.  Like those headers
+// everything here is __host__ __device__ and touches only the arrays it is handed.  The kernel (k_molcanon.hip: one
 // wave per row, lane = child of the node, then lane = atom and lane = entry for a leaf) uses molc_refine, molc_twin_key and
 // molc_target as they stand and certifies a leaf with the whole wave where molc_certify walks arrays; a host program
 // (tools/molcanon_host_check.cpp: arrays of exactly their size) runs molc_row.
@@ -11,7 +11,8 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "mdt_molwrite.h"
+#include "mdt_molrow.h"
+#include "mdt_smiles_scan.h"
 
 namespace mdt {
 
@@ -80,10 +81,10 @@ __host__ __device__ inline uint64_t molc_target(const uint64_t* lab, int stride,
   uint64_t target = 0, least = 0;
   for (int a = 0; a < n; ++a) {
     const uint64_t la = lab[a * stride];
-    if (!mols_in(open, a) || (target != 0 && la >= least)) continue;   // (la == least: the class already taken)
+    if (!mol_in(open, a) || (target != 0 && la >= least)) continue;   // (la == least: the class already taken)
     uint64_t cls = 0;
     for (int b = 0; b < n; ++b)
-      if (mols_in(open, b) && lab[b * stride] == la) cls |= (uint64_t)1 << b;
+      if (mol_in(open, b) && lab[b * stride] == la) cls |= (uint64_t)1 << b;
     if ((cls & (cls - 1)) != 0 && (cls & ~twins[a]) != 0) target = cls, least = la;
   }
   return target;
@@ -92,22 +93,22 @@ __host__ __device__ inline uint64_t molc_target(const uint64_t* lab, int stride,
 // The certificate of a leaf of the component `members` from its labels lab[0:n]: pos[a] for its atoms, cert[0:words] -> words.
 __host__ __device__ inline int molc_certify(const uint64_t* lab, const uint32_t* atoms, const uint32_t* bonds, int n, int nb,
                                             uint64_t members, uint8_t* pos, uint32_t* cert) {
-  const int size = molh_popc(members);
+  const int size = mol_popc(members);
   cert[0] = (uint32_t)size;
   for (int a = 0; a < n; ++a) {
-    if (!mols_in(members, a)) continue;
+    if (!mol_in(members, a)) continue;
     int below = 0;
-    for (int x = 0; x < n; ++x) below += (mols_in(members, x) && (lab[x] < lab[a] || (lab[x] == lab[a] && x < a))) ? 1 : 0;
+    for (int x = 0; x < n; ++x) below += (mol_in(members, x) && (lab[x] < lab[a] || (lab[x] == lab[a] && x < a))) ? 1 : 0;
     pos[a] = (uint8_t)below;
     cert[1 + below] = atoms[a];
   }
   int inside = 0;
   for (int e = 0; e < nb; ++e) {
-    if (!mols_in(members, mol_a(bonds[e]))) continue;
+    if (!mol_in(members, mol_a(bonds[e]))) continue;
     const uint32_t mine = molc_entry(pos[mol_a(bonds[e])], pos[mol_b(bonds[e])], mol_order(bonds[e]));
     int below = 0;
     for (int x = 0; x < nb; ++x) {
-      if (!mols_in(members, mol_a(bonds[x]))) continue;
+      if (!mol_in(members, mol_a(bonds[x]))) continue;
       const uint32_t other = molc_entry(pos[mol_a(bonds[x])], pos[mol_b(bonds[x])], mol_order(bonds[x]));
       below += (other < mine || (other == mine && x < e)) ? 1 : 0;
     }
@@ -126,7 +127,7 @@ __host__ __device__ inline bool molc_better(const uint32_t* cert, const uint32_t
   for (int i = 0; i < words; ++i)
     if (cert[i] != best[i]) return cert[i] < best[i];
   for (int a = 0; a < n; ++a)
-    if (mols_in(members, a) && pos[a] != best_pos[a]) return pos[a] < best_pos[a];
+    if (mol_in(members, a) && pos[a] != best_pos[a]) return pos[a] < best_pos[a];
   return false;
 }
 
@@ -138,11 +139,8 @@ __host__ __device__ inline int molc_row(const uint32_t* atoms, const uint32_t* b
   nodes = 0;
   if (!mol_graph_ok(bonds, n, nb, L, false)) return 0;
   uint64_t lab[kMolMaxL], acc[kMolMaxL], adj[kMolMaxL], twin_key[kMolMaxL], twins[kMolMaxL];
-  for (int a = 0; a < n; ++a) adj[a] = 0, twin_key[a] = molc_twin_key(bonds, nb, a);
-  for (int e = 0; e < nb; ++e) {
-    const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
-    if (a != b) adj[a] |= (uint64_t)1 << b, adj[b] |= (uint64_t)1 << a;
-  }
+  mol_ring_adj(bonds, n, nb, adj);
+  for (int a = 0; a < n; ++a) twin_key[a] = molc_twin_key(bonds, nb, a);
   for (int a = 0; a < n; ++a) {
     twins[a] = 0;
     for (int b = 0; b < n; ++b)
@@ -153,15 +151,8 @@ __host__ __device__ inline int molc_row(const uint32_t* atoms, const uint32_t* b
   uint64_t pending[kMolMaxL];                                   // per level: the children of the node there that are still to visit
   int start[kMolMaxL], components = 0, used = 0, count = 0;
   uint64_t seen = 0, member_of[kMolMaxL];
-  while (seen != molw_all(n)) {                                 // one component a turn: a flood from the lowest atom not yet seen
-    uint64_t members = 0, frontier = (uint64_t)1 << molh_lowest(molw_all(n) & ~seen);
-    while (frontier) {
-      members |= frontier;
-      uint64_t next = 0;
-      for (int x = 0; x < n; ++x)
-        if ((adj[x] & frontier) != 0) next |= (uint64_t)1 << x;
-      frontier = next & ~members;
-    }
+  while (seen != mol_all(n)) {                                 // one component a turn
+    const uint64_t members = mol_component(adj, n, seen);
     seen |= members;
     uint32_t* best = certs + used;
     bool have = false;
@@ -179,7 +170,7 @@ __host__ __device__ inline int molc_row(const uint32_t* atoms, const uint32_t* b
         if (!have || molc_better(cert, best, words, pos, best_pos, n, members)) {
           for (int i = 0; i < words; ++i) best[i] = cert[i];
           for (int a = 0; a < n; ++a)
-            if (mols_in(members, a)) best_pos[a] = pos[a];
+            if (mol_in(members, a)) best_pos[a] = pos[a];
           have = true;
         }
       }
@@ -188,7 +179,7 @@ __host__ __device__ inline int molc_row(const uint32_t* atoms, const uint32_t* b
         if (level >= 0) marked &= ~((uint64_t)1 << marks[level]);
       }
       if (level < 0) break;
-      const int child = molh_lowest(pending[level]);
+      const int child = mol_lowest(pending[level]);
       pending[level] &= pending[level] - 1;
       marks[level] = (uint8_t)child, marked |= (uint64_t)1 << child;
       ++level;
@@ -217,7 +208,7 @@ __host__ __device__ inline int molc_row(const uint32_t* atoms, const uint32_t* b
     const uint32_t* x = certs + start[next];
     const int size = (int)x[0], inside = (int)x[1 + size];
     for (int a = 0; a < n; ++a)
-      if (mols_in(member_of[next], a)) priority[a] = (uint64_t)(1 + offset + best_pos[a]), canon_atoms[offset + best_pos[a]] = atoms[a];
+      if (mol_in(member_of[next], a)) priority[a] = (uint64_t)(1 + offset + best_pos[a]), canon_atoms[offset + best_pos[a]] = atoms[a];
     for (int r = 0; r < inside; ++r) canon_bonds[entry_offset + r] = molc_bond_word(x[2 + size + r], offset);
     offset += size, entry_offset += inside;
   }

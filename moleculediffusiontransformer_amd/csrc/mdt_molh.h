@@ -1,6 +1,6 @@
 // Implicit hydrogens and the Kekule check (mdt_hip.h, mdt_mol_hydrogens): the per-atom rule, the slot of an atom in the formula, the
-// pick of the search and the search itself with its step count; the bond word and the check made before anything else (mol_graph_ok)
-// are mdt_smiles_scan.h's.  Like that header everything here is __host__ __device__ and touches only the arrays it is handed.  The
+// pick of the search and the search itself with its step count; the bond word, the check made before anything else (mol_graph_ok)
+// and the sets are mdt_molrow.h's.  Like that header everything here is __host__ __device__ and touches only the arrays it is handed.  The
 // kernel (k_molh.hip: one wave per row, lane = atom, the sets as wave-uniform 64-bit words) uses the rule, the slot and the pick
 // key as they stand and runs the search's loop with ballots where molh_search walks arrays; a host program
 // (tools/molh_host_check.cpp: arrays of exactly their size) runs molh_row, which is the definition written down in order.
@@ -9,29 +9,13 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "mdt_smiles_scan.h"
+#include "mdt_molrow.h"
 
 namespace mdt {
 
 constexpr int kMolhMaxSteps = 4096, kMolhFormula = 13;
 enum { kMolhOk = 0, kMolhAromaticOvervalent = 1, kMolhNoKekule = 2, kMolhUndecided = 3 };
 enum { kMolhSlotH = 0, kMolhSlotOther = 11, kMolhSlotCharge = 12 };
-
-__host__ __device__ __forceinline__ int molh_popc(uint64_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __popcll((unsigned long long)w);
-#else
-  return __builtin_popcountll(w);
-#endif
-}
-__host__ __device__ __forceinline__ int molh_lowest(uint64_t w) {          // w != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __ffsll((unsigned long long)w) - 1;
-#else
-  return __builtin_ctzll(w);
-#endif
-}
-__host__ __device__ __forceinline__ uint64_t molh_above(int t) { return ~(((uint64_t)2 << t) - 1); }   // the bits above bit t
 
 __host__ __device__ __forceinline__ int molh_charge(uint32_t d) { return (int)((d >> 12) & 31u) - 9; }
 __host__ __device__ __forceinline__ int molh_bracket_h(uint32_t d) { return (int)((d >> 17) & 15u); }
@@ -68,7 +52,7 @@ __host__ __device__ __forceinline__ uint32_t molh_group_valences(uint32_t d) {
 __host__ __device__ __forceinline__ int molh_at_least(uint32_t set, int sum) {
   if (sum > 6) return -1;
   const uint32_t left = (set >> sum) << sum;
-  return left ? molh_lowest((uint64_t)left) : -1;
+  return left ? mol_lowest((uint64_t)left) : -1;
 }
 
 // The per-atom rule: the hydrogens atom d carries when its entries sum to sum1, whether it still wants a double bond, and whether
@@ -115,7 +99,7 @@ __host__ __device__ inline int molh_search(const uint64_t* adj, int n, uint64_t 
     int u = -1, fewest = 65;
     for (int a = 0; a < n; ++a) {                               // the unmatched atom with the fewest unmatched neighbours, lowest first
       if (!((M >> a) & 1u)) continue;
-      const int c = molh_popc(adj[a] & M);
+      const int c = mol_popc(adj[a] & M);
       if (c < fewest) fewest = c, u = a;
     }
     const uint64_t cand = adj[u] & M & allowed;
@@ -123,11 +107,11 @@ __host__ __device__ inline int molh_search(const uint64_t* adj, int n, uint64_t 
       if (depth == 0) { code = kMolhNoKekule; break; }
       --depth;
       M |= (uint64_t)1 << su[depth] | (uint64_t)1 << sv[depth];
-      allowed = molh_above(sv[depth]);
+      allowed = mol_above(sv[depth]);
       continue;
     }
     if (made == max_steps) { code = kMolhUndecided; break; }
-    const int v = molh_lowest(cand);
+    const int v = mol_lowest(cand);
     ++made;
     su[depth] = (uint8_t)u;
     sv[depth] = (uint8_t)v;
@@ -171,7 +155,7 @@ __host__ __device__ inline int molh_row(const uint32_t* atoms, const uint32_t* b
     formula[kMolhSlotCharge] += molh_charge(atoms[a]);
   }
   if (atom >= 0) return kMolhAromaticOvervalent;
-  if (molh_popc(W) & 1) return kMolhNoKekule;
+  if (mol_popc(W) & 1) return kMolhNoKekule;
   for (int a = 0; a < n; ++a) adj[a] = ((W >> a) & 1u) ? adj[a] & W : 0;
   uint8_t su[kMolMaxL / 2], sv[kMolMaxL / 2];
   return molh_search(adj, n, W, max_steps, su, sv, partner, steps);

@@ -1,7 +1,8 @@
 // Maximum common substructure of a row pair (mdt_hip.h, mdt_mol_mcs): the walk of one root with its step count, the greedy descent
-// behind the floor, and the whole pair root after root.  Like mdt_molsub.h everything here is __host__ __device__ and touches only
-// the arrays it is handed, so the kernel (k_molmcs.hip: tables in LDS, one root per lane) and a host program
-// (tools/molmcs_host_check.cpp: tables in arrays of exactly their size) run the same walk.
+// behind the floor, and the whole pair root after root.  The bond word, "is this a graph row?" and the sets are mdt_molrow.h's.
+// Like mdt_molsub.h everything here is __host__ __device__ and touches only the arrays it is handed, so the kernel (k_molmcs.hip:
+// tables in LDS, one root per lane) and a host program (tools/molmcs_host_check.cpp: tables in arrays of exactly their size) run
+// the same walk.
 //
 // All state of a root is 64-bit masks, popcounts and a few ints -- no array but the two it is handed: the map (a byte per A atom)
 // and the stack (a byte per level).  A level consumes one A entry for good -- included, it has both ends mapped below that level;
@@ -14,7 +15,7 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "mdt_molsub.h"
+#include "mdt_molrow.h"
 
 namespace mdt {
 
@@ -26,7 +27,6 @@ __host__ __device__ __forceinline__ bool mcs_usable(uint32_t w) { return mol_a(w
 __host__ __device__ __forceinline__ bool mcs_compatible(uint32_t a, uint32_t b, int mode) {
   return (mode & kMcsExactAtoms) ? a == b : ((a ^ b) & 0x7FFu) == 0;
 }
-__host__ __device__ __forceinline__ uint64_t mcs_bit(int i) { return (uint64_t)1 << i; }
 
 // The tables of one pair, wherever they live.
 //   adj_b[(o - 1) * 64 + u]   the B atoms joined to u by a usable entry of order o
@@ -61,7 +61,7 @@ struct McsState {
   int cur;                                                      // inb byte o - 1: the B bonds of order o with both ends used
 };
 
-__host__ __device__ __forceinline__ int mcs_size(const McsState& s) { return s.cur << 8 | sub_popcount(s.mapped); }
+__host__ __device__ __forceinline__ int mcs_size(const McsState& s) { return s.cur << 8 | mol_popc(s.mapped); }
 
 // what M(y) = at adds: the entries at y, not excluded, whose other end is mapped onto a neighbour of `at` by their order (counted),
 // and per order the B bonds from `at` into the used atoms (packed).  y is unmapped and `at` unused in s.  Bounded by the entries at y.
@@ -69,12 +69,12 @@ __host__ __device__ __forceinline__ void mcs_gain(const McsTables& t, const McsL
                                                   uint64_t& inb) {
   gain = 0;
   for (uint64_t e = t.at[y] & s.par & ~s.x; e; e &= e - 1) {
-    const uint32_t w = t.ent[sub_lowest(e)];
+    const uint32_t w = t.ent[mol_lowest(e)];
     const int z = mol_a(w) == y ? mol_b(w) : mol_a(w);
     gain += (int)((t.adj_b[(mol_order(w) - 1) * 64 + at] >> l.m[z * l.m_stride]) & 1u);
   }
   inb = 0;
-  for (int o = 0; o < kMcsOrders; ++o) inb |= (uint64_t)sub_popcount(t.adj_b[o * 64 + at] & s.used) << (8 * o);
+  for (int o = 0; o < kMcsOrders; ++o) inb |= (uint64_t)mol_popc(t.adj_b[o * 64 + at] & s.used) << (8 * o);
 }
 
 __host__ __device__ __forceinline__ void mcs_assign(const McsTables& t, const McsLane& l, McsState& s, int y, int at) {
@@ -85,14 +85,14 @@ __host__ __device__ __forceinline__ void mcs_assign(const McsTables& t, const Mc
   s.inb += inb;                                                 // (a byte holds at most 64: no carry)
   s.both |= t.at[y] & s.par;
   s.par ^= t.at[y];
-  s.mapped |= mcs_bit(y);
-  s.used |= mcs_bit(at);
+  s.mapped |= mol_bit(y);
+  s.used |= mol_bit(at);
   l.m[y * l.m_stride] = (uint8_t)at;
 }
 
 __host__ __device__ __forceinline__ void mcs_undo(const McsTables& t, const McsLane& l, McsState& s, int y, int at) {
-  s.mapped &= ~mcs_bit(y);
-  s.used &= ~mcs_bit(at);
+  s.mapped &= ~mol_bit(y);
+  s.used &= ~mol_bit(at);
   s.par ^= t.at[y];
   s.both &= ~t.at[y];
   int gain;
@@ -107,11 +107,11 @@ __host__ __device__ __forceinline__ int mcs_bound(const McsTables& t, const McsS
   const uint64_t rem = s.live & ~s.x & ~s.both;
   int ub = s.cur;
   for (int o = 0; o < kMcsOrders; ++o) {
-    const int ra = sub_popcount(t.ord[o] & rem);
+    const int ra = mol_popc(t.ord[o] & rem);
     const int rb = (int)((t.total_b >> (8 * o)) & 255u) - (int)((s.inb >> (8 * o)) & 255u);
     ub += ra < rb ? ra : rb;
   }
-  const int have = sub_popcount(s.mapped), free_a = sub_popcount(atoms_from & ~s.mapped), free_b = t.nb - have;
+  const int have = mol_popc(s.mapped), free_a = mol_popc(atoms_from & ~s.mapped), free_b = t.nb - have;
   return ub << 8 | (have + (free_a < free_b ? free_a : free_b));
 }
 
@@ -119,7 +119,7 @@ __host__ __device__ __forceinline__ int mcs_bound(const McsTables& t, const McsS
 // Bounded by the entries.
 __host__ __device__ __forceinline__ bool mcs_pick(const McsTables& t, const McsLane& l, const McsState& s, int& k, int& y, uint64_t& c) {
   for (uint64_t e = s.par & s.live & ~s.x; e; e &= e - 1) {
-    k = sub_lowest(e);
+    k = mol_lowest(e);
     const uint32_t w = t.ent[k];
     const bool a_mapped = (s.mapped >> mol_a(w)) & 1u;
     const int x = a_mapped ? mol_a(w) : mol_b(w);
@@ -131,8 +131,8 @@ __host__ __device__ __forceinline__ bool mcs_pick(const McsTables& t, const McsL
 }
 
 __host__ __device__ __forceinline__ void mcs_root_init(const McsTables& t, const McsLane& l, McsState& s, int a0, int b0) {
-  s.mapped = mcs_bit(a0);
-  s.used = mcs_bit(b0);
+  s.mapped = mol_bit(a0);
+  s.used = mol_bit(b0);
   s.par = t.at[a0];
   s.both = s.x = s.inb = 0;
   s.live = t.all & ~t.low[a0];
@@ -140,9 +140,9 @@ __host__ __device__ __forceinline__ void mcs_root_init(const McsTables& t, const
   l.m[a0 * l.m_stride] = (uint8_t)b0;
 }
 
-// the A atoms >= a0
+// the A atoms >= a0 (mol_all(na) with the test written as na == 64, na <= 64 here: k_mol_mcs's code as it has been measured)
 __host__ __device__ __forceinline__ uint64_t mcs_atoms_from(const McsTables& t, int a0) {
-  return (t.na == 64 ? ~(uint64_t)0 : mcs_bit(t.na) - 1) & ~(mcs_bit(a0) - 1);
+  return (t.na == 64 ? ~(uint64_t)0 : mol_below(t.na)) & ~mol_below(a0);
 }
 
 // The greedy descent of root (a0, b0): always the lowest candidate of step 3, no exclusion, no pruning -> the size it reaches.
@@ -152,7 +152,7 @@ __host__ __device__ inline int mcs_root_greedy(const McsTables& t, const McsLane
   mcs_root_init(t, l, s, a0, b0);
   int k, y;
   uint64_t c;
-  while (mcs_pick(t, l, s, k, y, c)) mcs_assign(t, l, s, y, sub_lowest(c));
+  while (mcs_pick(t, l, s, k, y, c)) mcs_assign(t, l, s, y, mol_lowest(c));
   return mcs_size(s);
 }
 
@@ -180,7 +180,7 @@ __host__ __device__ inline int mcs_root_walk(const McsTables& t, const McsLane& 
         ++made;
         l.st[sp * l.st_stride] = (uint8_t)(k | (y == mol_b(t.ent[k]) ? 0x80 : 0));   // (sp < the usable entries <= 64)
         ++sp;
-        mcs_assign(t, l, s, y, sub_lowest(c));
+        mcs_assign(t, l, s, y, mol_lowest(c));
         continue;
       }
       enter = false;
@@ -188,7 +188,7 @@ __host__ __device__ inline int mcs_root_walk(const McsTables& t, const McsLane& 
     if (sp == 0) break;
     const int top = l.st[(sp - 1) * l.st_stride], k = top & 63;
     if (top & 0x40) {                                           // the exclude branch is done: the level is
-      s.x &= ~mcs_bit(k);
+      s.x &= ~mol_bit(k);
       --sp;
       continue;
     }
@@ -196,14 +196,14 @@ __host__ __device__ inline int mcs_root_walk(const McsTables& t, const McsLane& 
     const int y = (top & 0x80) ? mol_b(w) : mol_a(w), x = (top & 0x80) ? mol_a(w) : mol_b(w);
     const int last = l.m[y * l.m_stride];
     mcs_undo(t, l, s, y, last);
-    const uint64_t c = t.adj_b[(mol_order(w) - 1) * 64 + l.m[x * l.m_stride]] & t.compat[y] & ~s.used & sub_above(last);
+    const uint64_t c = t.adj_b[(mol_order(w) - 1) * 64 + l.m[x * l.m_stride]] & t.compat[y] & ~s.used & mol_above(last);
     if (made == kMcsMaxSteps) { cut = true; break; }            // (the next candidate and the exclusion each count one step)
     ++made;
     if (c) {
-      mcs_assign(t, l, s, y, sub_lowest(c));
+      mcs_assign(t, l, s, y, mol_lowest(c));
     } else {
       l.st[(sp - 1) * l.st_stride] = (uint8_t)(top | 0x40);
-      s.x |= mcs_bit(k);
+      s.x |= mol_bit(k);
     }
     enter = true;
   }
@@ -231,27 +231,27 @@ __host__ __device__ inline void mcs_fill_tables(const uint32_t* a_atoms, const u
   for (int e = 0; e < nbb; ++e) {                               // bounded by nbb <= LB
     const uint32_t w = b_bonds[e];
     if (!mcs_usable(w)) continue;
-    adj_b[(mol_order(w) - 1) * 64 + mol_a(w)] |= mcs_bit(mol_b(w));
-    adj_b[(mol_order(w) - 1) * 64 + mol_b(w)] |= mcs_bit(mol_a(w));
+    adj_b[(mol_order(w) - 1) * 64 + mol_a(w)] |= mol_bit(mol_b(w));
+    adj_b[(mol_order(w) - 1) * 64 + mol_b(w)] |= mol_bit(mol_a(w));
   }
   uint64_t total = 0, all = 0;
   for (int o = 0; o < kMcsOrders; ++o) {
     int twice = 0;
-    for (int u = 0; u < nb; ++u) twice += sub_popcount(adj_b[o * 64 + u]);
+    for (int u = 0; u < nb; ++u) twice += mol_popc(adj_b[o * 64 + u]);
     total |= (uint64_t)(twice / 2) << (8 * o);
   }
   for (int e = 0; e < nba; ++e) {                               // bounded by nba <= LA
     const uint32_t w = a_bonds[e];
     if (!mcs_usable(w)) continue;
-    all |= mcs_bit(e);
-    at[mol_a(w)] |= mcs_bit(e);
-    at[mol_b(w)] |= mcs_bit(e);
-    ord[mol_order(w) - 1] |= mcs_bit(e);
+    all |= mol_bit(e);
+    at[mol_a(w)] |= mol_bit(e);
+    at[mol_b(w)] |= mol_bit(e);
+    ord[mol_order(w) - 1] |= mol_bit(e);
   }
   for (int a = 1; a < na; ++a) low[a] = low[a - 1] | at[a - 1];
   for (int a = 0; a < na; ++a)
     for (int b = 0; b < nb; ++b)
-      if (mcs_compatible(a_atoms[a], b_atoms[b], mode)) compat[a] |= mcs_bit(b);
+      if (mcs_compatible(a_atoms[a], b_atoms[b], mode)) compat[a] |= mol_bit(b);
   t = McsTables{adj_b, compat, at, low, ord, a_bonds, total, all, na, nb};
 }
 
@@ -322,7 +322,7 @@ __host__ __device__ inline void mcs_pair(const uint32_t* a_atoms, const uint32_t
     const uint32_t w = a_bonds[e];
     if (!mcs_usable(w) || !((mapped >> mol_a(w)) & (mapped >> mol_b(w)) & 1u)) continue;
     if (!((adj_b[(mol_order(w) - 1) * 64 + m[mol_a(w)]] >> m[mol_b(w)]) & 1u)) continue;
-    matched |= mcs_bit(e);
+    matched |= mol_bit(e);
     out_bonds[kb++] = (uint32_t)(atom_map[mol_a(w)] - 1) | (uint32_t)(atom_map[mol_b(w)] - 1) << 8 | (uint32_t)mol_order(w) << 16;
   }
   size[0] = kb;
@@ -339,9 +339,9 @@ __host__ __device__ inline void mcs_pair(const uint32_t* a_atoms, const uint32_t
     uint64_t img[64];
     for (int u = 0; u < nb; ++u) img[u] = 0;
     for (uint64_t e = matched & ord[o]; e; e &= e - 1) {
-      const uint32_t w = a_bonds[sub_lowest(e)];
-      img[m[mol_a(w)]] |= mcs_bit(m[mol_b(w)]);
-      img[m[mol_b(w)]] |= mcs_bit(m[mol_a(w)]);
+      const uint32_t w = a_bonds[mol_lowest(e)];
+      img[m[mol_a(w)]] |= mol_bit(m[mol_b(w)]);
+      img[m[mol_b(w)]] |= mol_bit(m[mol_a(w)]);
     }
     for (int u = 0; u < nb; ++u) whole_b = whole_b && img[u] == adj_b[o * 64 + u];
   }

@@ -1,8 +1,8 @@
 // The normal form of a graph row (mdt_hip.h, mdt_mol_normalize): the Kekule view of an entry, what an atom gives to a ring's pi
-// system, the two rings tried for an entry -- the breadth-first search of molr_search with every atom keeping its level, walked back
-// by the lowest and by the highest predecessor -- Hueckel's count, and the words of the normal form.  The symbol fields, the charge
-// and the popcount are mdt_molh.h's, the bond word and "is this a graph row?" are mdt_smiles_scan.h's.  Like those headers
-// everything here is __host__ __device__ and touches only the arrays it is handed.  The kernel (k_molnorm.hip: one wave per row,
+// system, the two rings tried for an entry -- the breadth-first search of mol_search with every atom keeping its level, walked back
+// by the lowest and by the highest predecessor -- Hueckel's count, and the words of the normal form.  The symbol fields and the
+// charge are mdt_molh.h's; the bond word, "is this a graph row?", the sets, the ring graph and the search are mdt_molrow.h's.  Like
+// those headers everything here is __host__ __device__ and touches only the arrays it is handed.  The kernel (k_molnorm.hip: one wave per row,
 // lane = atom and lane = entry, the sets as wave-uniform 64-bit words) uses the per-atom rule, the Hueckel test and the output words
 // as they stand and runs one level of the search and of the walk back as a ballot where moln_two_rings walks arrays; a host program
 // (tools/molnorm_host_check.cpp: arrays of exactly their size) runs moln_row, which is the definition written down in order.
@@ -12,20 +12,13 @@
 #include <hip/hip_runtime.h>
 
 #include "mdt_molh.h"
+#include "mdt_molrow.h"
 
 namespace mdt {
 
 enum { kMolnNormalized = 1, kMolnAromatic = 2, kMolnChanged = 4 };
 constexpr int kMolnIneligible = -1;
 constexpr uint32_t kMolnHField = 15u << 17;
-
-__host__ __device__ __forceinline__ int moln_highest(uint64_t w) {         // w != 0
-#if defined(__HIP_DEVICE_COMPILE__)
-  return 63 - __clzll((long long)w);
-#else
-  return 63 - __builtin_clzll(w);
-#endif
-}
 
 // The Kekule view: the order an entry has once the aromatic entries are told apart by `partner` of mdt_mol_hydrogens (pa, pb: the
 // partner words of its two ends).
@@ -62,7 +55,7 @@ __host__ __device__ __forceinline__ int moln_pi(uint32_t d, int dbl, bool high, 
 
 // Hueckel on one ring: every atom eligible and the electrons 2 mod 4 (ones / twos: the atoms that give 1 / 2).
 __host__ __device__ __forceinline__ bool moln_hueckel(uint64_t ring, uint64_t eligible, uint64_t ones, uint64_t twos) {
-  return (ring & ~eligible) == 0 && ((molh_popc(ring & ones) + 2 * molh_popc(ring & twos)) & 3) == 2;
+  return (ring & ~eligible) == 0 && ((mol_popc(ring & ones) + 2 * mol_popc(ring & twos)) & 3) == 2;
 }
 
 // the words of the normal form
@@ -73,38 +66,21 @@ __host__ __device__ __forceinline__ uint32_t moln_bond_word(int a, int b, int or
   return (uint32_t)a | (uint32_t)b << 8 | (uint32_t)order << 16;
 }
 
-// The two rings tried for the entry (a, b), a != b, on the words adj[0:n] of the ring graph (mdt_molring.h): breadth first from a
-// without the edge {a, b} until b is reached, every atom keeping the level at which it was reached (at_level[k]: the atoms of
-// level k), then back from b taking at every level the lowest-numbered neighbour of that level, and again the highest.  -> false
-// when b is not reached.  Every pass of the search adds an atom or ends it, every step of a walk goes down a level: all bounded by n.
+// The two rings tried for the entry (a, b), a != b, on the words adj[0:n] of the ring graph: mol_search from a to b, every atom
+// keeping the level at which it was reached (at_level[k]: the atoms of level k; n words), then back from b taking at every level
+// the lowest-numbered neighbour of that level, and again the highest.  -> false when b is not reached.  Every step of a walk goes
+// down a level: bounded by n.
 __host__ __device__ inline bool moln_two_rings(const uint64_t* adj, int n, int a, int b, uint64_t* at_level, uint64_t& lowest,
                                                uint64_t& highest) {
-  const uint64_t bit_a = (uint64_t)1 << a, bit_b = (uint64_t)1 << b;
-  uint64_t visited = bit_a, frontier = bit_a;
-  int depth = 0;
-  at_level[0] = bit_a;
-  for (;;) {                                                    // bounded by n
-    uint64_t next = 0;
-    for (int x = 0; x < n; ++x) {
-      uint64_t mine = adj[x];
-      if (x == a) mine &= ~bit_b;
-      if (x == b) mine &= ~bit_a;
-      if (mine & frontier) next |= (uint64_t)1 << x;
-    }
-    next &= ~visited;
-    if (next == 0) return false;
-    at_level[++depth] = next;                                   // (depth <= n - 1: every level holds an atom of its own)
-    if (next & bit_b) break;
-    visited |= next;
-    frontier = next;
-  }
+  const int depth = mol_search(adj, n, a, b, at_level);
+  if (depth == 0) return false;
   for (int pick = 0; pick < 2; ++pick) {
-    uint64_t ring = bit_a | bit_b;
+    uint64_t ring = mol_bit(a) | mol_bit(b);
     int at = b;
     for (int level = depth - 1; level >= 1; --level) {          // (an atom of level k + 1 has a neighbour of level k)
       const uint64_t from = adj[at] & at_level[level];
-      at = pick ? moln_highest(from) : molh_lowest(from);
-      ring |= (uint64_t)1 << at;
+      at = pick ? mol_highest(from) : mol_lowest(from);
+      ring |= mol_bit(at);
     }
     (pick ? highest : lowest) = ring;
   }
@@ -125,11 +101,10 @@ __host__ __device__ inline int moln_row(const uint32_t* atoms, const uint32_t* b
   }
   uint64_t adj[kMolMaxL], at_level[kMolMaxL], eligible = 0, ones = 0, twos = 0, aromatic = 0, marked = 0;
   int kekule[kMolMaxL];
-  for (int a = 0; a < n; ++a) adj[a] = 0;
+  mol_ring_adj(bonds, n, nb, adj);
   for (int e = 0; e < nb; ++e) {
     const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
     kekule[e] = moln_kekule(a, b, mol_order(bonds[e]), partner[a], partner[b]);
-    if (a != b) adj[a] |= (uint64_t)1 << b, adj[b] |= (uint64_t)1 << a;
   }
   for (int x = 0; x < n; ++x) {
     int dbl = 0, sigma = hydrogens[x];

@@ -1,9 +1,10 @@
 // Ring perception and the descriptors of a graph row (mdt_hip.h, mdt_mol_rings): the descriptor slots and the rules that fill them,
-// the integer masses, and the serial form of the per-bond search -- a breadth-first search over 64-bit adjacency words, bounded by
-// the row's atoms.  The symbol and formula-slot accessors are mdt_molh.h's, the bond word and "is this a graph row?" are
-// mdt_smiles_scan.h's.  Like those headers everything here is __host__ __device__ and touches only the arrays it is handed.  The
-// kernel (k_molring.hip: one wave per row, lane = atom, visited set and frontier as wave-uniform 64-bit words) uses the atom rules
-// and the masses as they stand and runs one level of the search as a ballot where molr_search walks the words; a host program
+// the integer masses, and the serial form of the row.  The symbol and formula-slot accessors are mdt_molh.h's; the bond word, "is
+// this a graph row?", the ring graph, its components and the per-bond search -- breadth first over 64-bit adjacency words, bounded
+// by the row's atoms -- are mdt_molrow.h's.  Like those headers everything here is __host__ __device__ and touches only the arrays
+// it is handed.  The kernel (k_molring.hip: one wave per row, lane = atom, visited set and frontier as wave-uniform 64-bit words)
+// uses the atom rules and the masses as they stand and runs one level of the search as a ballot where mol_search walks the words;
+// a host program
 // (tools/molring_host_check.cpp: arrays of exactly their size) runs molr_row, which is the definition written down in order.
 #pragma once
 
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mdt_molh.h"
+#include "mdt_molrow.h"
 
 namespace mdt {
 
@@ -34,44 +36,17 @@ __host__ __device__ __forceinline__ int molr_mass(int slot) {
          : slot == 6 ? 30974 : slot == 7 ? 32060 : slot == 8 ? 35450 : slot == 9 ? 79904 : slot == 10 ? 126904 : 0;
 }
 
-// The search of the definition for one entry (a, b), a != b, on the words adj[0:n] of the ring graph (bit c of adj[x]: {x, c} is an
-// edge; symmetric, no bit x): 1 + the length of a shortest path from a to b that does not use the edge {a, b}, 0 if there is
-// none.  Breadth first from a, one level a pass; a and b do not see each other.  Every pass adds an atom to `visited` or ends the
-// search: at most n - 1 passes.
+// The search of the definition for one entry (a, b), a != b: 1 + the length of a shortest path from a to b that does not use the
+// edge {a, b}, 0 if there is none.
 __host__ __device__ inline int molr_search(const uint64_t* adj, int n, int a, int b) {
-  uint64_t visited = (uint64_t)1 << a, frontier = visited;
-  for (int depth = 1;; ++depth) {                               // bounded by n
-    uint64_t next = 0;
-    for (int x = 0; x < n; ++x) {
-      uint64_t mine = adj[x];
-      if (x == a) mine &= ~((uint64_t)1 << b);
-      if (x == b) mine &= ~((uint64_t)1 << a);
-      if (mine & frontier) next |= (uint64_t)1 << x;
-    }
-    next &= ~visited;
-    if ((next >> b) & 1u) return depth + 1;
-    if (next == 0) return 0;
-    visited |= next;
-    frontier = next;
-  }
+  const int level = mol_search(adj, n, a, b, nullptr);
+  return level ? level + 1 : 0;
 }
 
-// The components of the ring graph: floods from the lowest atom not yet reached, one level a pass; at most n passes in all.
+// The components of the ring graph: one flood each; at most n passes in all.
 __host__ __device__ inline int molr_components(const uint64_t* adj, int n) {
-  const uint64_t all = n >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << n) - 1);
-  uint64_t seen = 0;
   int components = 0;
-  while (seen != all) {                                         // bounded by n: every pass reaches an atom
-    uint64_t frontier = (uint64_t)1 << molh_lowest(all & ~seen);
-    ++components;
-    while (frontier) {
-      seen |= frontier;
-      uint64_t next = 0;
-      for (int x = 0; x < n; ++x)
-        if (adj[x] & frontier) next |= (uint64_t)1 << x;
-      frontier = next & ~seen;
-    }
-  }
+  for (uint64_t seen = 0; seen != mol_all(n); seen |= mol_component(adj, n, seen)) ++components;
   return components;
 }
 
@@ -84,11 +59,10 @@ __host__ __device__ inline int molr_row(const uint32_t* atoms, const uint32_t* b
   for (int k = 0; k < kMolrDesc; ++k) desc[k] = 0;
   if (!mol_graph_ok(bonds, n, nb, L, false)) return 0;         // (n == 0 included: no molecule)
   uint64_t adj[kMolMaxL], heavy = 0, triple = 0, not_single = 0;
-  for (int a = 0; a < n; ++a) adj[a] = 0;
+  mol_ring_adj(bonds, n, nb, adj);
   for (int e = 0; e < nb; ++e) {
-    const int a = mol_a(bonds[e]), b = mol_b(bonds[e]), o = mol_order(bonds[e]);
-    const uint64_t ends = (uint64_t)1 << a | (uint64_t)1 << b;
-    if (a != b) adj[a] |= (uint64_t)1 << b, adj[b] |= (uint64_t)1 << a;
+    const int o = mol_order(bonds[e]);
+    const uint64_t ends = mol_bit(mol_a(bonds[e])) | mol_bit(mol_b(bonds[e]));
     if (o == 3 || o == 4) triple |= ends;
     if (o != 1) not_single |= ends;
   }
@@ -96,7 +70,7 @@ __host__ __device__ inline int molr_row(const uint32_t* atoms, const uint32_t* b
   for (int a = 0; a < n; ++a) {
     const uint32_t d = atoms[a];
     const int h = hydrogens[a];
-    edges2 += molh_popc(adj[a]);
+    edges2 += mol_popc(adj[a]);
     if (molr_heavy(d)) heavy |= (uint64_t)1 << a, ++desc[kMolrHeavy];
     if (molr_heavy(d) && !molr_carbon(d)) ++desc[kMolrHetero];
     if (molr_n_or_o(d)) ++desc[kMolrAcceptors];
@@ -125,7 +99,7 @@ __host__ __device__ inline int molr_row(const uint32_t* atoms, const uint32_t* b
   }
   for (int e = 0; e < nb; ++e) {
     const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
-    if (mol_order(bonds[e]) == 1 && bond_ring[e] == 0 && a != b && molh_popc(adj[a] & heavy) >= 2 && molh_popc(adj[b] & heavy) >= 2 &&
+    if (mol_order(bonds[e]) == 1 && bond_ring[e] == 0 && a != b && mol_popc(adj[a] & heavy) >= 2 && mol_popc(adj[b] & heavy) >= 2 &&
         !((triple >> a) & 1u) && !((triple >> b) & 1u))
       ++desc[kMolrRotatable];
   }

@@ -1,7 +1,7 @@
 // The scaffold of a graph row (mdt_hip.h, mdt_mol_scaffold): the 2-core of the ring graph, the atoms double-bonded to it, what a
-// kept bracket atom gains for the entries it loses, the renumbering and the words written.  The popcount is mdt_molh.h's, the H
-// field and the bond word are mdt_molnorm.h's, the descriptor, the bond accessors and "is this a graph row?" are
-// mdt_smiles_scan.h's.  Like those headers everything here is __host__ __device__ and touches only the arrays it is handed.  The
+// kept bracket atom gains for the entries it loses, the renumbering and the words written.  The bracket atom's H count is
+// mdt_molh.h's, the H field and the bond word are mdt_molnorm.h's, the descriptor, the bond accessors, "is this a graph row?" and
+// the sets are mdt_molrow.h's.  Like those headers everything here is __host__ __device__ and touches only the arrays it is handed.  The
 // kernel (k_molscaf.hip: one wave per row, lane = atom and lane = entry, the sets as wave-uniform 64-bit words) uses the per-word
 // helpers as they stand and runs one round of the peeling as a ballot where mols_row walks arrays; a host program
 // (tools/molscaf_host_check.cpp: arrays of exactly their size) runs mols_row, which is the definition written down in order.
@@ -10,7 +10,9 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "mdt_molh.h"
 #include "mdt_molnorm.h"
+#include "mdt_molrow.h"
 
 namespace mdt {
 
@@ -19,10 +21,6 @@ enum { kMolsMolecule = 1, kMolsScaffold = 2, kMolsWhole = 4 };              // t
 
 // what a kept bracket atom gains in hydrogens for an entry of this order whose other end is pruned
 __host__ __device__ __forceinline__ int mols_weight(int o) { return (o >= 1 && o <= 4) ? o : 1; }
-// the bits of w below bit x (x <= 63), and the new index of kept atom x: the kept atoms below it
-__host__ __device__ __forceinline__ uint64_t mols_below(int x) { return ((uint64_t)1 << x) - 1; }
-__host__ __device__ __forceinline__ int mols_index(uint64_t kept, int x) { return molh_popc(kept & mols_below(x)); }
-__host__ __device__ __forceinline__ bool mols_in(uint64_t set, int x) { return ((set >> x) & 1u) != 0; }
 
 // The word of a kept atom: with GENERIC the unbracketed C of mdt_mol_graph; otherwise as written, but for a bracket atom, whose H
 // field takes the entries it lost (clamped at 15).
@@ -34,7 +32,7 @@ __host__ __device__ __forceinline__ uint32_t mols_atom_word(uint32_t d, int gain
 }
 // the word of a kept entry (a, b, o) under the renumbering of `kept`
 __host__ __device__ __forceinline__ uint32_t mols_bond_word(uint64_t kept, int a, int b, int o, int mode) {
-  return moln_bond_word(mols_index(kept, a), mols_index(kept, b), (mode & kMolsGeneric) ? 1 : o);
+  return moln_bond_word(mol_index(kept, a), mol_index(kept, b), (mode & kMolsGeneric) ? 1 : o);
 }
 __host__ __device__ __forceinline__ int mols_flags(int kept_atoms, int n) {
   return kMolsMolecule | (kept_atoms > 0 ? kMolsScaffold : 0) | (kept_atoms == n ? kMolsWhole : 0);
@@ -56,11 +54,11 @@ __host__ __device__ inline int mols_row(const uint32_t* atoms, const uint32_t* b
     adj[a] |= (uint64_t)1 << b, adj[b] |= (uint64_t)1 << a;
     if (mol_order(bonds[e]) == 2) dbl[a] |= (uint64_t)1 << b, dbl[b] |= (uint64_t)1 << a;
   }
-  uint64_t alive = n == 64 ? ~(uint64_t)0 : mols_below(n);
+  uint64_t alive = mol_all(n);
   for (;;) {                                                    // bounded by n: a round removes an atom or is the last
     uint64_t gone = 0;
     for (int x = 0; x < n; ++x)
-      if (mols_in(alive, x) && molh_popc(adj[x] & alive) <= 1) gone |= (uint64_t)1 << x;
+      if (mol_in(alive, x) && mol_popc(adj[x] & alive) <= 1) gone |= (uint64_t)1 << x;
     if (gone == 0) break;
     alive &= ~gone;
     ++rounds;
@@ -68,23 +66,23 @@ __host__ __device__ inline int mols_row(const uint32_t* atoms, const uint32_t* b
   uint64_t kept = alive;
   if (alive != 0 && (mode & kMolsExocyclic))
     for (int x = 0; x < n; ++x)
-      if (!mols_in(alive, x) && (dbl[x] & alive) != 0) kept |= (uint64_t)1 << x;
+      if (!mol_in(alive, x) && (dbl[x] & alive) != 0) kept |= (uint64_t)1 << x;
   for (int x = 0; x < n; ++x) {
-    if (!mols_in(kept, x)) continue;
+    if (!mol_in(kept, x)) continue;
     int gained = 0;
     for (int e = 0; e < nb; ++e) {
       const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
-      if (a != b && ((a == x && !mols_in(kept, b)) || (b == x && !mols_in(kept, a)))) gained += mols_weight(mol_order(bonds[e]));
+      if (a != b && ((a == x && !mol_in(kept, b)) || (b == x && !mol_in(kept, a)))) gained += mols_weight(mol_order(bonds[e]));
     }
-    const int to = mols_index(kept, x);
+    const int to = mol_index(kept, x);
     out_atoms[to] = mols_atom_word(atoms[x], gained, mode);
     atom_map[x] = (uint8_t)(1 + to);
   }
   for (int e = 0; e < nb; ++e) {
     const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
-    if (a != b && mols_in(kept, a) && mols_in(kept, b)) out_bonds[out_nb++] = mols_bond_word(kept, a, b, mol_order(bonds[e]), mode);
+    if (a != b && mol_in(kept, a) && mol_in(kept, b)) out_bonds[out_nb++] = mols_bond_word(kept, a, b, mol_order(bonds[e]), mode);
   }
-  out_n = molh_popc(kept);
+  out_n = mol_popc(kept);
   return mols_flags(out_n, n);
 }
 

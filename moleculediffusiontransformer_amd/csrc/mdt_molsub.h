@@ -1,5 +1,5 @@
 // Graph substructure match (mdt_hip.h, mdt_sub_match): the atom rule and the depth-first search of one root with its step count;
-// the bond word and the check made before any search (mol_graph_ok) are mdt_smiles_scan.h's.  Like that header everything here is
+// the bond word, the check made before any search (mol_graph_ok) and the sets are mdt_molrow.h's.  Like that header everything here is
 // __host__ __device__ and touches only the arrays it is handed, so the kernel (k_molsub.hip: tables in LDS, one root per lane) and
 // a host program (tools/molsub_host_check.cpp: tables in arrays of exactly their size) run the same search.
 #pragma once
@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "mdt_smiles_scan.h"
+#include "mdt_molrow.h"
 
 namespace mdt {
 
@@ -20,15 +20,6 @@ __host__ __device__ __forceinline__ uint32_t sub_atom_mask(uint32_t p) {
   return ((p & kMolBracket) ? 0xFFFFF000u : 0u) | ((p & 31u) == (uint32_t)kMolStar ? 0u : 0x7FFu);
 }
 __host__ __device__ __forceinline__ bool sub_accepts(uint32_t p, uint32_t t) { return ((p ^ t) & sub_atom_mask(p)) == 0; }
-// the bits above bit t
-__host__ __device__ __forceinline__ uint64_t sub_above(int t) { return ~(((uint64_t)2 << t) - 1); }
-__host__ __device__ __forceinline__ int sub_lowest(uint64_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __ffsll((unsigned long long)w) - 1;
-#else
-  return __builtin_ctzll(w);
-#endif
-}
 
 // The tables of one (target row, pattern) pair, wherever they live.
 //   compat[p]                   the target atoms that pattern atom p accepts, p < m
@@ -73,11 +64,11 @@ __host__ __device__ inline int sub_root_search(const SubTables& t, int m, int ro
       if (p == 0) { code = kSubNone; break; }
       const int last = t.f[p * t.f_stride];
       used &= ~((uint64_t)1 << last);
-      cand = sub_candidates(t, p, used) & sub_above(last);
+      cand = sub_candidates(t, p, used) & mol_above(last);
       continue;
     }
     if (made == kSubMaxSteps) { code = kSubCapped; break; }
-    const int at = sub_lowest(cand);
+    const int at = mol_lowest(cand);
     t.f[p * t.f_stride] = (uint8_t)at;
     ++made;
     if (p == m - 1) { signal.found(); code = kSubFound; break; }
@@ -180,17 +171,17 @@ __host__ __device__ inline uint32_t sub_root_enumerate(const SubTables& t, int m
       if (p == 0) break;
       const int last = t.f[p * t.f_stride];
       used &= ~((uint64_t)1 << last);
-      cand = sub_candidates(t, p, used) & sub_above(last);
+      cand = sub_candidates(t, p, used) & mol_above(last);
       continue;
     }
     if (made == kSubMaxSteps) { cut = true; break; }
-    const int at = sub_lowest(cand);
+    const int at = mol_lowest(cand);
     t.f[p * t.f_stride] = (uint8_t)at;
     ++made;
     if (p == m - 1) {                                           // a full map: report it, stay at this depth
       ++seen;
       sink.embedding(used | (uint64_t)1 << at);
-      cand &= sub_above(at);
+      cand &= mol_above(at);
       continue;
     }
     used |= (uint64_t)1 << at;
@@ -208,19 +199,11 @@ struct SubCoverSink {
   __host__ __device__ __forceinline__ void embedding(uint64_t image) { cover |= image; }
 };
 
-__host__ __device__ __forceinline__ int sub_popcount(uint64_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __popcll((unsigned long long)w);
-#else
-  return __builtin_popcountll(w);
-#endif
-}
-
 // Is the number of anchors of one (row, pattern) outside [lo, hi]?  c anchors are certain (roots that saw an embedding), u more are
 // possible (roots abandoned before they saw one): outside unless lo <= c and c + u <= hi -- conservative both ways.  c + u <= 64,
 // so hi >= 64 is no upper bound.
 __host__ __device__ __forceinline__ bool sub_count_outside(uint64_t found, uint64_t capped, int lo, int hi) {
-  const int c = sub_popcount(found), u = sub_popcount(capped & ~found);
+  const int c = mol_popc(found), u = mol_popc(capped & ~found);
   return !(lo <= c && c + u <= hi);
 }
 
@@ -277,8 +260,8 @@ __host__ __device__ inline void sub_map_pair(const uint32_t* atoms, const uint32
   if (empty) return;
   if (m == 1) {                                                 // every accepted atom is an anchor, a map and its own image
     *found = *cover = compat[0];
-    *embeddings = (uint32_t)sub_popcount(compat[0]);
-    map[0] = (uint8_t)(1 + sub_lowest(compat[0]));
+    *embeddings = (uint32_t)mol_popc(compat[0]);
+    map[0] = (uint8_t)(1 + mol_lowest(compat[0]));
     return;
   }
   const SubTables t{compat, adj, back_start, back, f, 1};
@@ -297,7 +280,7 @@ __host__ __device__ inline void sub_map_pair(const uint32_t* atoms, const uint32
   if (*found) {
     int steps;
     SubNoSignal alone;
-    sub_root_search(t, m, sub_lowest(*found), steps, alone);    // (it succeeds: the enumeration of that root saw a map)
+    sub_root_search(t, m, mol_lowest(*found), steps, alone);    // (it succeeds: the enumeration of that root saw a map)
     for (int p = 0; p < m; ++p) map[p] = (uint8_t)(1 + f[p]);   // bounded by m <= LP
   }
 }

@@ -2,9 +2,9 @@
 // bond symbol, the ring numbers, the tokens that belong to one atom, and the serial forms of both entry points.  The walk is told in
 // SEQ SPACE: once pass 1 has numbered the atoms in the order it first reaches them, the emission of pass 2 is that very order, a child
 // is a neighbour above its parent, a closure that closes at s is a neighbour below s that is not its parent, one that opens at s a
-// neighbour above s that is not its child -- and "ascending seq of the other end" is "ascending bit" of a 64-bit word.  The popcount
-// and the lowest bit are mdt_molh.h's, the highest bit mdt_molnorm.h's, the bit helpers mdt_molscaf.h's, the descriptor, the classes,
-// the bond accessors, "is this a graph row?" and the rooted hash mdt_smiles_scan.h's.  Like those headers everything here is
+// neighbour above s that is not its child -- and "ascending seq of the other end" is "ascending bit" of a 64-bit word.  The
+// descriptor, the bond accessors, "is this a graph row?", the sets, the ring graph and its components are mdt_molrow.h's, the
+// classes and the rooted hash mdt_smiles_scan.h's.  Like those headers everything here is
 // __host__ __device__ and touches only the arrays it is handed.  The kernels (k_molwrite.hip: one wave per row, lane = atom, then
 // lane = rank, then lane = seq) use the per-word helpers and molw_atom_tokens as they stand and run the walks on wave-uniform words
 // where molw_row walks arrays; a host program (tools/molwrite_host_check.cpp: arrays of exactly their size) runs molw_rank_row and
@@ -14,7 +14,8 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
-#include "mdt_molscaf.h"
+#include "mdt_molrow.h"
+#include "mdt_smiles_scan.h"
 
 namespace mdt {
 
@@ -98,8 +99,8 @@ struct MolwAtom {
   int par, atom;
   __host__ __device__ __forceinline__ int order(int t) const { return (int)((o0 >> t) & 1u) | (int)((o1 >> t) & 1u) << 1 | (int)((o2 >> t) & 1u) << 2; }
   __host__ __device__ __forceinline__ uint64_t parent_bit() const { return par == kMolwRoot ? 0 : (uint64_t)1 << par; }
-  __host__ __device__ __forceinline__ uint64_t closes(int s) const { return adj & mols_below(s) & ~parent_bit(); }
-  __host__ __device__ __forceinline__ uint64_t opens(int s) const { return adj & molh_above(s) & ~child; }
+  __host__ __device__ __forceinline__ uint64_t closes(int s) const { return adj & mol_below(s) & ~parent_bit(); }
+  __host__ __device__ __forceinline__ uint64_t opens(int s) const { return adj & mol_above(s) & ~child; }
 };
 
 // The tokens of the atom with seq s, in order: what stands before it -- '.' before a later root; otherwise ')' when the atom before
@@ -111,58 +112,45 @@ __host__ __device__ inline void molw_atom_tokens(const MolwAtom& me, int s, uint
                                                  const uint64_t* open_of, const uint8_t* base_of, const uint8_t* number_of,
                                                  MolwSink& out) {
   const int owner = 1 + me.atom;
-  const bool arom = mols_in(aromatic, s);
+  const bool arom = mol_in(aromatic, s);
   if (me.par == kMolwRoot) {
     if (s > 0) out.put(kClsDot, 0);
   } else {
-    if (me.par != s - 1) out.put(kClsClose, 1 + atom_of[moln_highest(parent_child & mols_below(s))]);
-    if ((parent_child & molh_above(s)) != 0) out.put(kClsOpen, owner);
-    const int c = molw_bond_class(me.order(me.par), arom && mols_in(aromatic, me.par));
+    if (me.par != s - 1) out.put(kClsClose, 1 + atom_of[mol_highest(parent_child & mol_below(s))]);
+    if ((parent_child & mol_above(s)) != 0) out.put(kClsOpen, owner);
+    const int c = molw_bond_class(me.order(me.par), arom && mol_in(aromatic, me.par));
     if (c != 0) out.put(c, owner);
   }
   molw_atom_text(me.d, owner, out);
   for (uint64_t left = me.closes(s); left != 0; left &= left - 1) {           // bounded by n
-    const int t = molh_lowest(left);
-    molw_number(number_of[base_of[t] + molh_popc(open_of[t] & mols_below(s))], owner, out);
+    const int t = mol_lowest(left);
+    molw_number(number_of[base_of[t] + mol_popc(open_of[t] & mol_below(s))], owner, out);
   }
   int slot = base_of[s];
   for (uint64_t left = me.opens(s); left != 0; left &= left - 1, ++slot) {    // bounded by n
-    const int t = molh_lowest(left);
-    const int c = molw_bond_class(me.order(t), arom && mols_in(aromatic, t));
+    const int t = mol_lowest(left);
+    const int c = molw_bond_class(me.order(t), arom && mol_in(aromatic, t));
     if (c != 0) out.put(c, owner);
     molw_number(number_of[slot], owner, out);
   }
 }
-
-__host__ __device__ __forceinline__ uint64_t molw_all(int n) { return n >= 64 ? ~(uint64_t)0 : mols_below(n); }
 
 // mdt_mol_rank of one row.  Reads atoms[0:n], bonds[0:nb]; writes priority[0:L] and nothing beyond.
 __host__ __device__ inline void molw_rank_row(const uint32_t* atoms, const uint32_t* bonds, int n, int nb, int L, uint64_t* priority) {
   for (int a = 0; a < L; ++a) priority[a] = 0;
   if (!mol_graph_ok(bonds, n, nb, L, false)) return;
   uint64_t lab[kMolMaxL], acc[kMolMaxL], h[kMolMaxL], adj[kMolMaxL];
-  for (int a = 0; a < n; ++a) adj[a] = 0;
-  for (int e = 0; e < nb; ++e) {
-    const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
-    if (a != b) adj[a] |= (uint64_t)1 << b, adj[b] |= (uint64_t)1 << a;
-  }
+  mol_ring_adj(bonds, n, nb, adj);
   for (int r = 0; r < n; ++r) h[r] = mol_root_hash(atoms, bonds, n, nb, r, lab, acc, 1);
   uint64_t seen = 0;
-  while (seen != molw_all(n)) {                                 // one component a turn: a flood from the lowest atom not yet seen
-    uint64_t members = 0, frontier = (uint64_t)1 << molh_lowest(molw_all(n) & ~seen);
-    while (frontier) {
-      members |= frontier;
-      uint64_t next = 0;
-      for (int x = 0; x < n; ++x)
-        if ((adj[x] & frontier) != 0) next |= (uint64_t)1 << x;
-      frontier = next & ~members;
-    }
+  while (seen != mol_all(n)) {                                 // one component a turn
+    const uint64_t members = mol_component(adj, n, seen);
     int root = -1;
     for (int r = 0; r < n; ++r)
-      if (mols_in(members, r) && (root < 0 || h[r] < h[root])) root = r;
+      if (mol_in(members, r) && (root < 0 || h[r] < h[root])) root = r;
     mol_root_hash(atoms, bonds, n, nb, root, lab, acc, 1);
     for (int a = 0; a < n; ++a)
-      if (mols_in(members, a)) priority[a] = lab[a];
+      if (mol_in(members, a)) priority[a] = lab[a];
     seen |= members;
   }
 }
@@ -180,7 +168,7 @@ __host__ __device__ inline int molw_row(const uint32_t* atoms, const uint32_t* b
   for (int a = 0; a < n; ++a) bad = bad || !molw_atom_ok(atoms[a]);
   for (int e = 0; e < nb; ++e) {
     const int a = mol_a(bonds[e]), b = mol_b(bonds[e]);
-    bad = bad || a == b || mols_in(adj[a], b) || !mol_order_ok(mol_order(bonds[e]));
+    bad = bad || a == b || mol_in(adj[a], b) || !mol_order_ok(mol_order(bonds[e]));
     adj[a] |= (uint64_t)1 << b, adj[b] |= (uint64_t)1 << a;
   }
   if (bad) return kMolwNotWritable;
@@ -205,14 +193,14 @@ __host__ __device__ inline int molw_row(const uint32_t* atoms, const uint32_t* b
   uint8_t par_rank[kMolMaxL];
   uint64_t visited = 0;
   int count = 0;
-  while (visited != molw_all(n)) {                              // bounded by 2 n steps in all: a step visits an atom or steps back
-    const int root = molh_lowest(molw_all(n) & ~visited);
+  while (visited != mol_all(n)) {                              // bounded by 2 n steps in all: a step visits an atom or steps back
+    const int root = mol_lowest(mol_all(n) & ~visited);
     int cur = root;
     seq_of_rank[cur] = (uint8_t)count, at[count].par = kMolwRoot, ++count, visited |= (uint64_t)1 << cur;
     for (;;) {
       const uint64_t cand = adj_rank[cur] & ~visited;
       if (cand != 0) {
-        const int next = molh_lowest(cand);
+        const int next = mol_lowest(cand);
         seq_of_rank[next] = (uint8_t)count, at[count].par = seq_of_rank[cur], par_rank[next] = (uint8_t)cur, ++count;
         visited |= (uint64_t)1 << next;
         cur = next;
@@ -246,17 +234,17 @@ __host__ __device__ inline int molw_row(const uint32_t* atoms, const uint32_t* b
   // ---- the ring numbers: in seq order, the numbers that close at s are read, those that open at s take the lowest free one,
   //      and what closed at s is free from the next atom on (at most 63 closures: a number is at most 64) ----
   int slots = 0;
-  for (int s = 0; s < n; ++s) open_of[s] = at[s].opens(s), base_of[s] = (uint8_t)slots, slots += molh_popc(open_of[s]);
+  for (int s = 0; s < n; ++s) open_of[s] = at[s].opens(s), base_of[s] = (uint8_t)slots, slots += mol_popc(open_of[s]);
   uint64_t free_numbers = ~(uint64_t)0;                         // bit k: number k + 1
   for (int s = 0; s < n; ++s) {
     uint64_t closed = 0;
     for (uint64_t left = at[s].closes(s); left != 0; left &= left - 1) {
-      const int t = molh_lowest(left);
-      closed |= (uint64_t)1 << (number_of[base_of[t] + molh_popc(open_of[t] & mols_below(s))] - 1);
+      const int t = mol_lowest(left);
+      closed |= (uint64_t)1 << (number_of[base_of[t] + mol_popc(open_of[t] & mol_below(s))] - 1);
     }
     int slot = base_of[s];
     for (uint64_t left = open_of[s]; left != 0; left &= left - 1, ++slot) {
-      const int k = molh_lowest(free_numbers);
+      const int k = mol_lowest(free_numbers);
       free_numbers &= ~((uint64_t)1 << k);
       number_of[slot] = (uint8_t)(k + 1);
     }

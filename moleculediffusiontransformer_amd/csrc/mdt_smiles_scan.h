@@ -1,13 +1,15 @@
 // The single-pass scanner of SMILES token rows that k_smiles.hip (the verdict) and k_molgraph.hip (the verdict and the molecular
-// graph) share, the graph row itself -- the bond word's accessors and "is this a graph row?", for k_molgraph.hip, k_molfp.hip and
-// (through mdt_molsub.h) k_molsub.hip -- and the graph key's per-root hash.  The rules: include/mdt_hip.h, mdt_smiles_check and
-// mdt_mol_graph / mdt_mol_key.  Everything here but mol_graph_ok_wave is __host__ __device__ and touches only the arrays it is handed,
-// so the rules can be run, and their array bounds checked, in a host program without a device.  Included by .hip files only
-// (mdt_api.cpp does not see it).
+// graph) share -- tokens -> graph row -- the graph key's per-root hash and the graph fingerprint.  The graph row itself (the
+// descriptor, the bond word's accessors, "is this a graph row?") and the sets over it are mdt_molrow.h's.  The rules:
+// include/mdt_hip.h, mdt_smiles_check and mdt_mol_graph / mdt_mol_key.  Everything here is __host__ __device__ and touches only the
+// arrays it is handed, so the rules can be run, and their array bounds checked, in a host program without a device.  Included by
+// .hip files only (mdt_api.cpp does not see it).
 #pragma once
 
 #include <cstdint>
 #include <hip/hip_runtime.h>
+
+#include "mdt_molrow.h"
 
 namespace mdt {
 
@@ -48,48 +50,6 @@ __host__ __device__ inline int smiles_lane_stride(int L) {
   const int bytes = L + L + (L + 1) / 2 + 2 * kSmilesRings;
   const int words = (bytes + 3) / 4;
   return 4 * (words | 1);
-}
-
-// ---- the atom descriptor and the bond word of the molecular graph (mdt_hip.h, mdt_mol_graph) ----
-constexpr int kMolMaxL = 64;                                   // at most 64 tokens: at most 64 atoms, at most 63 bonds
-constexpr int kMolStar = 26;                                   // '*' in the first-letter field
-constexpr uint32_t kMolAromatic = 1u << 10, kMolBracket = 1u << 11;
-// first: letter 0..25 (either case) or kMolStar; second: 0 none, else 1 + (lowercase letter); charge in [-9, 9]; h in [0, 9];
-// isotope already reduced modulo 2048
-__host__ __device__ __forceinline__ uint32_t mol_descriptor(int first, int second, bool aromatic, bool bracket, int charge, int h,
-                                                            int isotope) {
-  return (uint32_t)first | (uint32_t)second << 5 | (aromatic ? kMolAromatic : 0u) | (bracket ? kMolBracket : 0u) |
-         (uint32_t)(charge + 9) << 12 | (uint32_t)h << 17 | (uint32_t)isotope << 21;
-}
-// bond code (0 none, 1..7 = - = # $ : / \) -> the graph's order: - / \ 1, = 2, # 3, $ 4, ':' 5, none: 5 between two aromatic atoms, else 1
-__host__ __device__ __forceinline__ int mol_bond_order(int code, bool both_aromatic) {
-  if (code == 0) return both_aromatic ? 5 : 1;
-  return code >= 2 && code <= 5 ? code : 1;
-}
-// the bond word a | b << 8 | order << 16, for every reader of the graph arrays
-constexpr int kMolOrders = 5;                                  // the orders mol_bond_order writes: 1..5
-__host__ __device__ __forceinline__ int mol_a(uint32_t w) { return (int)(w & 255u); }
-__host__ __device__ __forceinline__ int mol_b(uint32_t w) { return (int)((w >> 8) & 255u); }
-__host__ __device__ __forceinline__ int mol_order(uint32_t w) { return (int)(w >> 16); }
-__host__ __device__ __forceinline__ bool mol_order_ok(int o) { return (unsigned)(o - 1) < (unsigned)kMolOrders; }
-__host__ __device__ __forceinline__ bool mol_counts_ok(int n, int nb, int L) { return !(n < 1 || n > L || nb < 0 || nb > L); }
-// Is (n, nb, bonds[0:nb]) the graph of a row of width L?  Counts inside [1, L] x [0, L], every bond end below n; with `orders`, also
-// every order in 1..5 (asked of a substructure pattern: an entry of any other order, which mdt_mol_graph never writes, could not be
-// satisfied).  A row that fails has no key, no fingerprint and matches nothing.  Reads bonds[0:nb] and nothing beyond.
-__host__ __device__ inline bool mol_graph_ok(const uint32_t* bonds, int n, int nb, int L, bool orders) {
-  if (!mol_counts_ok(n, nb, L)) return false;
-  for (int e = 0; e < nb; ++e)
-    if (mol_a(bonds[e]) >= n || mol_b(bonds[e]) >= n || (orders && !mol_order_ok(mol_order(bonds[e])))) return false;
-  return true;
-}
-// mol_graph_ok (without `orders`) by one wave that looks at one row, lane e owning bond e (nb <= L <= 64): the wave-uniform
-// verdict of k_mol_key and k_mol_fp.  Nothing is read when the counts already fail.  (k_sub_match spells the same check out with
-// these accessors: it keeps the bond word, and through this helper its search came out 1-3 % slower on eight patterns.)
-__device__ __forceinline__ bool mol_graph_ok_wave(const uint32_t* __restrict__ bonds, int n, int nb, int L, int lane) {
-  const bool counts = mol_counts_ok(n, nb, L);
-  const bool mine = counts && lane < nb;
-  const uint32_t w = mine ? bonds[lane] : 0u;
-  return counts && !__any(mine && (mol_a(w) >= n || mol_b(w) >= n));
 }
 
 // The emitter of the scan that only judges: nothing is recorded, and what the scan computes for it alone is dead code.
@@ -378,13 +338,6 @@ __host__ __device__ __forceinline__ uint64_t fp_bond_term(uint64_t other, uint32
 }
 __host__ __device__ __forceinline__ uint64_t fp_next(uint64_t id, uint64_t acc) { return mol_mix(id ^ mol_mix(acc)); }
 __host__ __device__ __forceinline__ int fp_bit(uint64_t id) { return (int)(id & (uint64_t)(kFpBits - 1)); }
-__host__ __device__ __forceinline__ int fp_popc64(uint64_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __popcll(w);
-#else
-  return __builtin_popcountll(w);
-#endif
-}
 // The fingerprint of one row, atom after atom: fp[0:16], returns the number of set bits.  This is the definition in the order it is
 // written down; k_mol_fp computes the same with one atom per lane.  atoms[0:n], bonds[0:nb] are read, nothing beyond.
 __host__ __device__ inline int fp_row(const uint32_t* atoms, const uint32_t* bonds, int n, int nb, int L, int radius, uint64_t* fp) {
@@ -412,16 +365,16 @@ __host__ __device__ inline int fp_row(const uint32_t* atoms, const uint32_t* bon
     for (int a = 0; a < n; ++a) id[a] = fp_next(id[a], acc[a]);
   }
   int count = 0;
-  for (int w = 0; w < kFpWords; ++w) count += fp_popc64(fp[w]);
+  for (int w = 0; w < kFpWords; ++w) count += mol_popc(fp[w]);
   return count;
 }
 // inter = |A & B|, uni = |A| + |B| - inter for two fingerprints of 16 words
 __host__ __device__ inline void fp_counts(const uint64_t* a, const uint64_t* b, int& inter, int& uni) {
   int i = 0, ca = 0, cb = 0;
   for (int w = 0; w < kFpWords; ++w) {
-    i += fp_popc64(a[w] & b[w]);
-    ca += fp_popc64(a[w]);
-    cb += fp_popc64(b[w]);
+    i += mol_popc(a[w] & b[w]);
+    ca += mol_popc(a[w]);
+    cb += mol_popc(b[w]);
   }
   inter = i;
   uni = ca + cb - i;

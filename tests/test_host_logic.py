@@ -193,6 +193,22 @@ def test_no_cpu_fallback():
         ADPM2Sampler(rho=1).step(torch.randn(2, 16, 32), lambda x, sigma: x, 1.0, 0.5)
 
 
+def test_molecule_kernels_share_one_graph_row_header():
+    """The graph row and the sets over it are defined once, in csrc/mdt_molrow.h: no header and no molecule kernel keeps a copy."""
+    import glob
+    csrc = os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "k_mol*.hip")))
+    assert os.path.join(csrc, "mdt_molrow.h") in files and len(files) > 20
+    for path in files:
+        text, name = open(path).read(), os.path.basename(path)
+        for builtin in ("__builtin_popcountll", "__builtin_ctzll", "__builtin_clzll"):
+            assert (builtin in text) == (name == "mdt_molrow.h"), (name, builtin)
+        for helper in ("mol_popc", "mol_lowest", "mol_all", "mol_ring_adj"):
+            defined = re.search(r"\b(?:int|void|bool|uint64_t)\s+" + helper + r"\s*\(", text) is not None
+            assert defined == (name == "mdt_molrow.h"), (name, helper)
+    assert "int mol_a(" not in open(os.path.join(csrc, "mdt_smiles_scan.h")).read()
+
+
 def test_training_loss_matches_reference_formula():
     """QMDiffusion.forward (generative.py:812-833) -> KDiffusion_mod.forward (diffusion.py:820-844) as plain PyTorch with
     autograd (train.py): equal to the loss assembled from the pinned oracle's denoiser on the same sigmas / noise, and every

@@ -232,6 +232,9 @@ def test_header_declares_and_the_library_exports_the_new_symbol():
     assert "__shared__" not in src and "__syncthreads" not in src            # no LDS, no barrier
     shared = open(os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc", "mdt_molnorm.h")).read()
     assert "mdt_molh.h" in shared and "molh_charge(" in shared and "molh_charge(uint32_t" not in shared   # reused, not copied
+    assert "mdt_molrow.h" in shared and "int mol_search(" not in shared and "int mol_highest(" not in shared
+    for used in ("mol_search(", "mol_ring_adj(", "mol_highest(", "mol_lowest(", "mol_popc("):
+        assert used in shared, used
 
 
 def test_entry_point_refuses_bad_arguments_before_any_launch():

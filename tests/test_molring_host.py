@@ -182,6 +182,9 @@ def test_header_declares_and_the_library_exports_the_new_symbol():
     assert "molr_mass(" in src and "molh_slot(" in src and "mol_graph_ok_wave(" in src and "mdt_molring.h" in src and "mdt_finish(" in src
     shared = open(os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc", "mdt_molring.h")).read()
     assert "mdt_molh.h" in shared and "molh_slot(" in shared and "molh_slot(uint32_t" not in shared   # reused, not copied
+    assert "mdt_molrow.h" in shared and "int mol_search(" not in shared and "uint64_t mol_component(" not in shared
+    for used in ("mol_search(", "mol_component(", "mol_ring_adj(", "mol_popc("):
+        assert used in shared, used
 
 
 def test_entry_point_refuses_bad_arguments_before_any_launch():

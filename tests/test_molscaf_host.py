@@ -250,11 +250,13 @@ def test_header_declares_and_the_library_exports_the_new_symbols():
         assert phrase in flat, phrase
     assert "k_molscaf.hip" in [s for s, _ in __import__("moleculediffusiontransformer_amd.build", fromlist=["SOURCES"]).SOURCES]
     src = open(os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc", "k_molscaf.hip")).read()
-    for used in ("mols_atom_word(", "mols_bond_word(", "mols_index(", "mols_flags(", "mol_graph_ok_wave(", "mdt_molscaf.h", "mdt_finish(", "__ballot("):
+    for used in ("mols_atom_word(", "mols_bond_word(", "mol_index(", "mols_flags(", "mol_graph_ok_wave(", "mdt_molscaf.h", "mdt_finish(", "__ballot("):
         assert used in src, used
     assert "__shared__" not in src and "__syncthreads" not in src            # no LDS, no barrier
     shared = open(os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc", "mdt_molscaf.h")).read()
-    assert "mdt_molnorm.h" in shared and "molh_popc(" in shared and "molh_popc(uint64_t" not in shared     # reused, not copied
+    assert "mdt_molnorm.h" in shared and "mdt_molrow.h" in shared                                          # reused, not copied:
+    for helper in ("mol_popc", "mol_index", "mol_in", "mol_all"):                                          # the sets are the row header's
+        assert helper + "(" in shared and re.search(r"\b(int|bool|uint64_t) " + helper + r"\(", shared) is None, helper
     assert "moln_bond_word(" in shared and "moln_bond_word(int" not in shared and "mols_row(" in shared
     for phrase in ("not RDKit's MurckoScaffold", "Aromaticity and hydrogens are as handed in", "An acyclic molecule has NO scaffold"):
         assert phrase in " ".join(M.mol_scaffold.__doc__.split()), phrase

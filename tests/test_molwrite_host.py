@@ -258,7 +258,9 @@ def test_header_declares_and_the_library_exports_the_new_symbols():
     shared = open(os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc", "mdt_molwrite.h")).read()
     scan = open(os.path.join(ROOT, "moleculediffusiontransformer_amd", "csrc", "mdt_smiles_scan.h")).read()
     assert "uint64_t mol_root_hash(" not in src + shared and scan.count("uint64_t mol_root_hash(") == 1   # shared, not copied
-    assert "molw_row(" in shared and "molw_rank_row(" in shared and "molh_popc(uint64_t" not in shared
+    assert "molw_row(" in shared and "molw_rank_row(" in shared and "mdt_molrow.h" in shared
+    for helper in ("mol_popc", "mol_lowest", "mol_all", "mol_ring_adj", "mol_component"):                  # reused, not copied
+        assert helper + "(" in shared and re.search(r"\b(int|void|uint64_t) " + helper + r"\(", shared) is None, helper
     for f in (M.mol_write, M.mol_respell, M.scaffold_tokens, M.scaffold_keep):
         assert "NOT RDKit's canonical SMILES" in " ".join(f.__doc__.split()), f.__name__
     readme = " ".join(open(os.path.join(ROOT, "README.md")).read().split())

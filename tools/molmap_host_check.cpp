@@ -17,11 +17,7 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molsub.h"
-
-struct Graph {
-  int width, n, nb;
-  uint32_t *atoms, *bonds;
-};
+#include "mol_host_graph.h"
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
@@ -33,15 +29,8 @@ int main(int argc, char** argv) {
   while (fscanf(f, "%7s", tag) == 1) {
     if (!strcmp(tag, "T") || !strcmp(tag, "Q")) {
       Graph g;
-      int have_atoms, have_bonds;
-      if (fscanf(f, "%d %d %d %d %d", &g.width, &g.n, &g.nb, &have_atoms, &have_bonds) != 5) return 2;
-      g.atoms = new uint32_t[have_atoms];                         // exact sizes: a read past the counts is a report
-      g.bonds = new uint32_t[have_bonds];
-      for (int i = 0; i < have_atoms; ++i)
-        if (fscanf(f, "%u", &g.atoms[i]) != 1) return 2;
-      for (int i = 0; i < have_bonds; ++i)
-        if (fscanf(f, "%u", &g.bonds[i]) != 1) return 2;
-      (tag[0] == 'T' ? targets : patterns).push_back(g);
+      if (!read_graph(f, g)) return 2;                            // exact sizes: a read past the counts is a report
+      (tag[0] == 'T' ? targets : patterns).push_back(std::move(g));
     } else if (!strcmp(tag, "M")) {
       int t, q, count;
       unsigned long long want_found, want_capped, want_cover;
@@ -54,7 +43,7 @@ int main(int argc, char** argv) {
       for (int r = 0; r < a.width; ++r) steps[r] = 0, seen[r] = 0;
       uint64_t found, capped, cover;
       uint32_t emb;
-      mdt::sub_map_pair(a.atoms, a.bonds, a.n, a.nb, a.width, p.atoms, p.bonds, p.n, p.nb, p.width, &found, &capped, &emb, &cover, map,
+      mdt::sub_map_pair(a.atoms.get(), a.bonds.get(), a.n, a.nb, a.width, p.atoms.get(), p.bonds.get(), p.n, p.nb, p.width, &found, &capped, &emb, &cover, map,
                         steps, seen);
       bool bad = found != want_found || capped != want_capped || emb != want_emb || cover != want_cover;
       for (int i = 0; i < p.width; ++i) {
@@ -69,7 +58,7 @@ int main(int argc, char** argv) {
         bad = bad || root < 0 || root >= a.width || (int)seen[root] != its_seen || steps[root] != made;
         steps_max = made > steps_max ? made : steps_max;
       }
-      const int old = mdt::sub_match_pair(a.atoms, a.bonds, a.n, a.nb, a.width, p.atoms, p.bonds, p.n, p.nb, p.width, nullptr, nullptr);
+      const int old = mdt::sub_match_pair(a.atoms.get(), a.bonds.get(), a.n, a.nb, a.width, p.atoms.get(), p.bonds.get(), p.n, p.nb, p.width, nullptr, nullptr);
       bad = bad || (old == mdt::kSubFound) != (found != 0) || (old == mdt::kSubCapped) != (found == 0 && capped != 0);
       if (bad) {
         ++wrong;
@@ -89,8 +78,6 @@ int main(int argc, char** argv) {
     }
   }
   fclose(f);
-  for (Graph& g : targets) delete[] g.atoms, delete[] g.bonds;
-  for (Graph& g : patterns) delete[] g.atoms, delete[] g.bonds;
   printf("%zu targets, %zu patterns, %ld pairs (%ld with a capped root), %ld roots, %ld embeddings, most steps of a root %ld, %ld wrong\n",
          targets.size(), patterns.size(), pairs, with_cap, roots, maps, steps_max, wrong);
   return wrong ? 1 : 0;

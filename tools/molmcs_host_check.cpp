@@ -16,11 +16,7 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molmcs.h"
-
-struct Graph {
-  int width, n, nb;
-  uint32_t *atoms, *bonds;
-};
+#include "mol_host_graph.h"
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
@@ -32,15 +28,8 @@ int main(int argc, char** argv) {
   while (fscanf(f, "%7s", tag) == 1) {
     if (!strcmp(tag, "G")) {
       Graph g;
-      int have_atoms, have_bonds;
-      if (fscanf(f, "%d %d %d %d %d", &g.width, &g.n, &g.nb, &have_atoms, &have_bonds) != 5) return 2;
-      g.atoms = new uint32_t[have_atoms];                         // exact sizes: a read past the counts is a report
-      g.bonds = new uint32_t[have_bonds];
-      for (int i = 0; i < have_atoms; ++i)
-        if (fscanf(f, "%u", &g.atoms[i]) != 1) return 2;
-      for (int i = 0; i < have_bonds; ++i)
-        if (fscanf(f, "%u", &g.bonds[i]) != 1) return 2;
-      graphs.push_back(g);
+      if (!read_graph(f, g)) return 2;                            // exact sizes: a read past the counts is a report
+      graphs.push_back(std::move(g));
     } else if (!strcmp(tag, "P")) {
       int ia, ib, mode, want_bonds, want_atoms, want_steps, want_flags, want_natoms, want_nbonds, want_floor, count;
       unsigned long long want_mask;
@@ -58,7 +47,7 @@ int main(int argc, char** argv) {
       uint64_t bond_a;
       uint8_t flags;
       int floor;
-      mdt::mcs_pair(a.atoms, a.bonds, a.n, a.nb, LA, b.atoms, b.bonds, b.n, b.nb, b.width, mode, size, map_a, &bond_a, &steps,
+      mdt::mcs_pair(a.atoms.get(), a.bonds.get(), a.n, a.nb, LA, b.atoms.get(), b.bonds.get(), b.n, b.nb, b.width, mode, size, map_a, &bond_a, &steps,
                     &out_natoms, out_atoms, &out_nbonds, out_bonds, atom_map, &flags, root_size, root_steps, root_capped, &floor);
       bool bad = size[0] != want_bonds || size[1] != want_atoms || bond_a != want_mask || steps != want_steps || flags != want_flags ||
                  out_natoms != want_natoms || out_nbonds != want_nbonds || floor != want_floor;
@@ -102,7 +91,6 @@ int main(int argc, char** argv) {
     }
   }
   fclose(f);
-  for (Graph& g : graphs) delete[] g.atoms, delete[] g.bonds;
   printf("%zu graphs, %ld pairs (%ld with a capped root), %ld roots, %ld steps, most steps of a root %ld, %ld wrong\n", graphs.size(),
          pairs, with_cap, roots, steps_all, steps_max, wrong);
   return wrong ? 1 : 0;

@@ -17,10 +17,10 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molnorm.h"
+#include "mol_host_graph.h"
 
-struct Graph {
-  int width, n, nb, have_atoms, have_bonds, verdict;
-  std::vector<uint32_t> atoms, bonds;
+struct Row : Graph {
+  int verdict;
   std::vector<uint8_t> hydrogens, partner, bond_ring;
 };
 
@@ -37,28 +37,22 @@ int main(int argc, char** argv) {
   if (argc != 2) return 2;
   FILE* f = fopen(argv[1], "r");
   if (!f) return 2;
-  std::vector<Graph> rows;
+  std::vector<Row> rows;
   char tag[8];
   long asked = 0, wrong = 0, normalized = 0, aromatic = 0, changed = 0;
   while (fscanf(f, "%7s", tag) == 1) {
     if (!strcmp(tag, "T")) {
-      Graph g;
-      if (fscanf(f, "%d %d %d %d %d %d", &g.width, &g.n, &g.nb, &g.have_atoms, &g.have_bonds, &g.verdict) != 6) return 2;
-      g.atoms.resize(g.have_atoms);
-      g.bonds.resize(g.have_bonds);
+      Row g;
+      if (!read_graph(f, g, &g.verdict)) return 2;
       g.hydrogens.resize(g.have_atoms);
       g.partner.resize(g.have_atoms);
       g.bond_ring.resize(g.have_bonds);
-      for (uint32_t& w : g.atoms)
-        if (fscanf(f, "%u", &w) != 1) return 2;
-      for (uint32_t& w : g.bonds)
-        if (fscanf(f, "%u", &w) != 1) return 2;
       if (!bytes(f, g.hydrogens) || !bytes(f, g.partner) || !bytes(f, g.bond_ring)) return 2;
-      rows.push_back(g);
+      rows.push_back(std::move(g));
     } else if (!strcmp(tag, "A")) {
       int t, flags;
       if (fscanf(f, "%d %d", &t, &flags) != 2) return 2;
-      const Graph& g = rows[t];
+      const Row& g = rows[t];
       const int L = g.width;
       std::vector<unsigned> want(2 * L);
       for (unsigned& w : want)

@@ -17,10 +17,9 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molring.h"
+#include "mol_host_graph.h"
 
-struct Graph {
-  int width, n, nb, have_atoms, have_bonds;
-  std::vector<uint32_t> atoms, bonds;
+struct Row : Graph {
   std::vector<uint8_t> hydrogens;
 };
 
@@ -28,30 +27,24 @@ int main(int argc, char** argv) {
   if (argc != 2) return 2;
   FILE* f = fopen(argv[1], "r");
   if (!f) return 2;
-  std::vector<Graph> rows;
+  std::vector<Row> rows;
   char tag[8];
   long asked = 0, wrong = 0, flagged = 0, with_ring = 0, largest = 0;
   while (fscanf(f, "%7s", tag) == 1) {
     if (!strcmp(tag, "T")) {
-      Graph g;
-      if (fscanf(f, "%d %d %d %d %d", &g.width, &g.n, &g.nb, &g.have_atoms, &g.have_bonds) != 5) return 2;
-      g.atoms.resize(g.have_atoms);
-      g.bonds.resize(g.have_bonds);
+      Row g;
+      if (!read_graph(f, g)) return 2;
       g.hydrogens.resize(g.have_atoms);
-      for (int i = 0; i < g.have_atoms; ++i)
-        if (fscanf(f, "%u", &g.atoms[i]) != 1) return 2;
-      for (int i = 0; i < g.have_bonds; ++i)
-        if (fscanf(f, "%u", &g.bonds[i]) != 1) return 2;
       for (int i = 0; i < g.have_atoms; ++i) {
         unsigned h;
         if (fscanf(f, "%u", &h) != 1) return 2;
         g.hydrogens[i] = (uint8_t)h;
       }
-      rows.push_back(g);
+      rows.push_back(std::move(g));
     } else if (!strcmp(tag, "A")) {
       int t, bounded, flag;
       if (fscanf(f, "%d %d %d", &t, &bounded, &flag) != 3) return 2;
-      const Graph& g = rows[t];
+      const Row& g = rows[t];
       const int L = g.width, D = mdt::kMolrDesc;
       std::vector<long long> want(2 * D + 2 * L + D);
       for (long long& w : want)

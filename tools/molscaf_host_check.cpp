@@ -17,11 +17,7 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molscaf.h"
-
-struct Graph {
-  int width, n, nb, have_atoms, have_bonds;
-  std::vector<uint32_t> atoms, bonds;
-};
+#include "mol_host_graph.h"
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
@@ -33,14 +29,8 @@ int main(int argc, char** argv) {
   while (fscanf(f, "%7s", tag) == 1) {
     if (!strcmp(tag, "T")) {
       Graph g;
-      if (fscanf(f, "%d %d %d %d %d", &g.width, &g.n, &g.nb, &g.have_atoms, &g.have_bonds) != 5) return 2;
-      g.atoms.resize(g.have_atoms);
-      g.bonds.resize(g.have_bonds);
-      for (uint32_t& w : g.atoms)
-        if (fscanf(f, "%u", &w) != 1) return 2;
-      for (uint32_t& w : g.bonds)
-        if (fscanf(f, "%u", &w) != 1) return 2;
-      rows.push_back(g);
+      if (!read_graph(f, g)) return 2;
+      rows.push_back(std::move(g));
     } else if (!strcmp(tag, "A")) {
       int t, mode, want_n, want_nb, flags;
       if (fscanf(f, "%d %d %d %d %d", &t, &mode, &want_n, &want_nb, &flags) != 5) return 2;

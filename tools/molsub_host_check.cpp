@@ -17,11 +17,7 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molsub.h"
-
-struct Graph {
-  int width, n, nb;
-  uint32_t *atoms, *bonds;
-};
+#include "mol_host_graph.h"
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
@@ -33,15 +29,8 @@ int main(int argc, char** argv) {
   while (fscanf(f, "%7s", tag) == 1) {
     if (!strcmp(tag, "T") || !strcmp(tag, "Q")) {
       Graph g;
-      int have_atoms, have_bonds;
-      if (fscanf(f, "%d %d %d %d %d", &g.width, &g.n, &g.nb, &have_atoms, &have_bonds) != 5) return 2;
-      g.atoms = new uint32_t[have_atoms];                         // exact sizes: a read past the counts is a report
-      g.bonds = new uint32_t[have_bonds];
-      for (int i = 0; i < have_atoms; ++i)
-        if (fscanf(f, "%u", &g.atoms[i]) != 1) return 2;
-      for (int i = 0; i < have_bonds; ++i)
-        if (fscanf(f, "%u", &g.bonds[i]) != 1) return 2;
-      (tag[0] == 'T' ? targets : patterns).push_back(g);
+      if (!read_graph(f, g)) return 2;                            // exact sizes: a read past the counts is a report
+      (tag[0] == 'T' ? targets : patterns).push_back(std::move(g));
     } else if (!strcmp(tag, "M")) {
       int t, q, verdict, count;
       if (fscanf(f, "%d %d %d %d", &t, &q, &verdict, &count) != 4) return 2;
@@ -49,7 +38,7 @@ int main(int argc, char** argv) {
       int* code = new int[a.width];
       int* steps = new int[a.width];
       for (int r = 0; r < a.width; ++r) code[r] = -1, steps[r] = 0;
-      const int got = mdt::sub_match_pair(a.atoms, a.bonds, a.n, a.nb, a.width, p.atoms, p.bonds, p.n, p.nb, p.width, code, steps);
+      const int got = mdt::sub_match_pair(a.atoms.get(), a.bonds.get(), a.n, a.nb, a.width, p.atoms.get(), p.bonds.get(), p.n, p.nb, p.width, code, steps);
       bool bad = got != verdict;
       int searched = 0;
       for (int r = 0; r < a.width; ++r) searched += code[r] >= 0;
@@ -74,8 +63,6 @@ int main(int argc, char** argv) {
     }
   }
   fclose(f);
-  for (Graph& g : targets) delete[] g.atoms, delete[] g.bonds;
-  for (Graph& g : patterns) delete[] g.atoms, delete[] g.bonds;
   printf("%zu targets, %zu patterns, %ld pairs (%ld undecided), %ld roots, most steps of a root %ld, %ld wrong\n", targets.size(),
          patterns.size(), pairs, undecided, roots, steps_max, wrong);
   return wrong ? 1 : 0;

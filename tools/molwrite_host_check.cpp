@@ -18,10 +18,9 @@
 #include <vector>
 
 #include "../moleculediffusiontransformer_amd/csrc/mdt_molwrite.h"
+#include "mol_host_graph.h"
 
-struct Graph {
-  int width, n, nb, have_atoms, have_bonds;
-  std::vector<uint32_t> atoms, bonds;
+struct Row : Graph {
   std::vector<uint64_t> priority;
 };
 
@@ -29,7 +28,7 @@ int main(int argc, char** argv) {
   if (argc != 2) return 2;
   FILE* f = fopen(argv[1], "r");
   if (!f) return 2;
-  std::vector<Graph> rows;
+  std::vector<Row> rows;
   std::vector<std::vector<uint8_t>> tables;
   char tag[8];
   long ranked = 0, asked = 0, wrong = 0, by_flag[9] = {0}, longest = 0;
@@ -45,19 +44,13 @@ int main(int argc, char** argv) {
       }
       tables.push_back(table);
     } else if (!strcmp(tag, "T")) {
-      Graph g;
-      if (fscanf(f, "%d %d %d %d %d", &g.width, &g.n, &g.nb, &g.have_atoms, &g.have_bonds) != 5) return 2;
-      g.atoms.resize(g.have_atoms);
-      g.bonds.resize(g.have_bonds);
-      for (uint32_t& w : g.atoms)
-        if (fscanf(f, "%u", &w) != 1) return 2;
-      for (uint32_t& w : g.bonds)
-        if (fscanf(f, "%u", &w) != 1) return 2;
-      rows.push_back(g);
+      Row g;
+      if (!read_graph(f, g)) return 2;
+      rows.push_back(std::move(g));
     } else if (!strcmp(tag, "P")) {
       int t;
       if (fscanf(f, "%d", &t) != 1) return 2;
-      Graph& g = rows[t];
+      Row& g = rows[t];
       const int L = g.width;
       g.priority.resize(L);
       for (uint64_t& w : g.priority) {
@@ -88,7 +81,7 @@ int main(int argc, char** argv) {
     } else if (!strcmp(tag, "A")) {
       int t, v, invariant, W, want_length, want_flags;
       if (fscanf(f, "%d %d %d %d %d %d", &t, &v, &invariant, &W, &want_length, &want_flags) != 6) return 2;
-      const Graph& g = rows[t];
+      const Row& g = rows[t];
       const int L = g.width;
       std::vector<int> want(2 * W);
       for (int& w : want)
